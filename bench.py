@@ -2,11 +2,19 @@
 """bench.py -- 3-D R2C+C2R pairs/s of the slab transform on MI355X.
 
   python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W --full
+  python bench.py --gpus N --steps K --warmup W --dump-outputs DIR
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one fftn + one ifftn of a 1024^3 fp64 cube (BASELINE.json metric),
 inputs and outputs resident in HBM.  N ranks share ONE cube (strong scaling,
 slab decomposition, RCCL all-to-all over xGMI).  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full
+adds the secondary measurements (pencil class, dealiased transforms, pitched
+spectra, Taylor-Green RK4 steps: `extras`) and the host's `cpu_baseline`.
+--dump-outputs DIR writes what the last timed step computed as .npy files
+(see dump_sample).
 """
 import argparse
 import ctypes
@@ -42,6 +50,12 @@ def parse_args():
     ap.add_argument("--child-task", default="slab", choices=["slab", "pencil_relay"], help=argparse.SUPPRESS)
     ap.add_argument("--stage-timing", default="on", choices=["on", "off"],
                     help="HIP events around every stage inside the timed region (roofline numbers)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (extras: pencil class, dealiased transforms, pitched spectra, "
+                         "Taylor-Green RK4) and the CPU baseline; a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed (a fixed sample of the forward spectrum "
+                         "and of the inverse's real field) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     return ap.parse_args()
 
 
@@ -169,6 +183,33 @@ def pmc_traffic(n, precision, decomp, world):
         if vals:
             return sum(vals) / len(vals), "%s (kernel %s)" % (os.path.basename(path), k[2])
     return None, "no committed PMC profile of '%s'" % want.strip()
+
+
+DUMP_BYTES = 64 * 10 ** 6          # --dump-outputs: all files of one run together
+DUMP_SEED = 20240607               # which planes of a large output are written (the same for every run and build)
+
+
+def dump_sample(a, budget):
+    """Host copy of what a caller of the timed path receives in the DeviceArray `a`: the whole array when it fits `budget`
+    bytes, otherwise the planes (leading index) that a fixed seed picks, as many as fit, in increasing order (the leading
+    rows of one such plane when not even one fits).  Complex values become a trailing axis of two (real, imaginary), so
+    that the sample is float32 / float64."""
+    n0 = a.shape[0]
+    plane = a.nbytes // n0
+    k = min(n0, budget // max(plane, 1))
+    rng = np.random.default_rng(DUMP_SEED)
+    if k == n0:
+        x = a.get()
+    elif k >= 1:
+        idx = np.sort(rng.choice(n0, size=k, replace=False))
+        x = np.stack([a.component(int(i)).get() for i in idx])
+    else:
+        p = a.component(int(rng.integers(n0)))
+        rows = max(1, min(p.shape[0], budget // max(p.nbytes // p.shape[0], 1)))
+        x = p.leading(0, rows).get()[None]
+    if np.iscomplexobj(x):
+        x = np.stack([x.real, x.imag], axis=-1)
+    return np.ascontiguousarray(x)
 
 
 def cpu_baseline(n_full, seconds_budget=30.0):
@@ -529,8 +570,14 @@ def main():
         a0 = u.leading(0, k).get()
         b0 = u2.leading(0, k).get()
         rt_err = float(np.linalg.norm((a0 - b0).ravel()) / np.linalg.norm(a0.ravel()))
+        # --dump-outputs: what the last timed step handed back (a sample on the host; written once the run has chosen
+        # the measurement it reports)
+        dump = None
+        if args.dump_outputs:
+            share = DUMP_BYTES // (2 * world) - 4096          # two arrays per rank, room for the .npy headers
+            dump = {"fftn_out": dump_sample(fu, share), "ifftn_out": dump_sample(u2, share)}
         return {"dt": dt, "stages": stages, "rt_err": rt_err, "pipeline": pipeline, "comm_cus": comm_cus,
-                "transport": cand_name(comm, pull), "ranks": ranks_report(comm)}
+                "transport": cand_name(comm, pull), "ranks": ranks_report(comm), "dump": dump}
 
     def comm_name(c):
         return getattr(c, "transport_name", "rccl" if world > 1 else "none")
@@ -733,11 +780,16 @@ def main():
     else:
         mres = measure(args.pipeline)
     out = headline(mres, tuning) if rank == 0 else None
+    if mres["dump"] is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, x in mres["dump"].items():
+            np.save(os.path.join(args.dump_outputs, name + ("_rank%d" % rank if world > 1 else "") + ".npy"), x)
+        mres["dump"] = None
 
-    # ---- secondary measurement: the pencil path on the same cube (needs a P1 x P2 grid with
+    # ---- secondary measurement (--full): the pencil path on the same cube (needs a P1 x P2 grid with
     # even factors, i.e. 4 or 8 ranks, or the degenerate 1 x 1 grid as the 1-GPU denominator)
     extras = {}
-    want_pencil = args.pencil_extra == "on" or (args.pencil_extra == "auto" and args.decomp == "slab"
+    want_pencil = args.pencil_extra == "on" or (args.pencil_extra == "auto" and args.full and args.decomp == "slab"
                                                  and world in (1, 4, 8, 16))
     watchdog = None
     if want_pencil and world > 1:
@@ -795,9 +847,9 @@ def main():
     if watchdog is not None:
         watchdog.cancel()
 
-    # ---- secondary measurement (one GPU): the dealiased transforms of the same class on the same cube -- the inverse
+    # ---- secondary measurement (one GPU, --full): the dealiased transforms of the same class on the same cube -- the inverse
     # with the 2/3-rule (slab.py:237-245; here pruned passes) and the 3/2-rule ifftn + fftn pair (slab.py:247-346, 453-485)
-    if world == 1 and args.decomp == "slab" and args.pencil_extra != "off":
+    if args.full and world == 1 and args.decomp == "slab" and args.pencil_extra != "off":
         try:
             Fd = Slab_R2C(N, L, comm, args.precision)
             fud = DeviceArray.random(Fd.complex_shape(), Fd.complex, seed=5)
@@ -861,11 +913,12 @@ def main():
         except Exception as e:      # noqa: BLE001  - the headline (slab) line must survive
             extras["dealias"] = {"error": "%s: %s" % (type(e).__name__, e)}
 
-    # ---- secondary measurement (one GPU): the APPLICATION the transforms are for -- the reference demo's Taylor-Green RK4 loop
-    # (demo/spectral_dns_solver.py:83-98) with the state in HBM, 3/2-rule, double precision.  `fused`: the nonlinear term as one
-    # plan operation (mfft_nonlinear_cross, csrc/fft_nlz.h) + one sweep per Runge-Kutta stage; `composed`: rounds 3 - 5 (36
-    # transforms + element-wise kernels per step).  ms per RK4 step and the split by plan stage (HIP events).
-    if world == 1 and args.decomp == "slab" and args.pencil_extra != "off" and os.environ.get("MFFT_BENCH_DNS", "1") != "0":
+    # ---- secondary measurement (one GPU, --full): the APPLICATION the transforms are for -- the reference demo's Taylor-Green
+    # RK4 loop (demo/spectral_dns_solver.py:83-98) with the state in HBM, 3/2-rule, double precision.  `fused`: the nonlinear
+    # term as one plan operation (mfft_nonlinear_cross, csrc/fft_nlz.h) + one sweep per Runge-Kutta stage; `composed`: rounds
+    # 3 - 5 (36 transforms + element-wise kernels per step).  ms per RK4 step and the split by plan stage (HIP events).
+    if args.full and world == 1 and args.decomp == "slab" and args.pencil_extra != "off" \
+            and os.environ.get("MFFT_BENCH_DNS", "1") != "0":
         try:
             sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "examples"))
             import spectral_dns_device as dns
@@ -903,7 +956,7 @@ def main():
     failed = not (bad <= tol)              # also catches NaN
     if rank == 0:
         out["extras"] = extras
-        if args.cpu_baseline == "auto" and not failed:
+        if args.full and args.cpu_baseline == "auto" and not failed:
             out["cpu_baseline"] = cpu_baseline_cached(n, world)
         else:
             out["cpu_baseline"] = None

@@ -54,5 +54,48 @@ def load():
     return mod
 
 
+GOLDEN = os.path.join(HERE, "..", "tests", "golden", "ref_maths_loops.npz")
+
+
+def loop_cases():
+    """The seeded inputs of the tests that compare with the compiled loops (tests/test_oracle_golden.py: "cpu_*",
+    tests/test_gpu_stages.py: "gpu_*"), keyed <case>_<dtype>_<array>."""
+    import numpy as np
+    cases = {}
+    for tag, seed, P, Np0, Np1, Nf, fshape in (("cpu", 8, 4, 3, 5, 9, (6, 7, 5)), ("gpu", 12, 8, 4, 6, 33, (16, 8, 33))):
+        rng = np.random.default_rng(seed)
+        for dt in (np.complex128, np.complex64):
+            key = "%s_%s_" % (tag, np.dtype(dt).name)
+            cases[key + "U"] = (rng.random((P, Np0, Np1, Nf)) + 1j * rng.random((P, Np0, Np1, Nf))).astype(dt)
+            cases[key + "fu"] = (rng.random(fshape) + 1j * rng.random(fshape)).astype(dt)
+            cases[key + "mask"] = (rng.random(fshape) > 0.5).astype(np.uint8)
+    return cases
+
+
+def run_loops(ref, cases):
+    """What the compiled loops return for `cases`: <case>_<dtype>_T (transpose_Uc) and _filtered (dealias_filter)."""
+    import numpy as np
+    out = {}
+    for key in [k[:-1] for k in cases if k.endswith("_U")]:
+        U = cases[key + "U"]
+        P, Np0, Np1, Nf = U.shape
+        T = np.zeros((Np0, P * Np1, Nf), dtype=U.dtype)
+        ref.transpose_Uc(T, U, P, Np0, Np1, Nf)                      # maths.pyx:21-31
+        out[key + "T"] = T
+        out[key + "filtered"] = np.asarray(ref.dealias_filter(cases[key + "fu"].copy(), cases[key + "mask"]))   # maths.pyx:9-19
+    return out
+
+
+def write_golden():
+    """tests/golden/ref_maths_loops.npz: the inputs of loop_cases and the compiled loops' outputs for them, so that the
+    tests that compare with the loops also run where the reference is absent."""
+    import numpy as np
+    build()
+    ref = load()
+    cases = loop_cases()
+    np.savez_compressed(GOLDEN, **cases, **run_loops(ref, cases))
+    return os.path.abspath(GOLDEN)
+
+
 if __name__ == "__main__":
-    print(build(verbose=True))
+    print(write_golden() if sys.argv[1:] == ["golden"] else build(verbose=True))

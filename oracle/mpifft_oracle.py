@@ -1001,3 +1001,18 @@ def rel_l2(x, ref):
     d = np.linalg.norm((x - ref).ravel())
     n = np.linalg.norm(ref.ravel())
     return float(d / n) if n > 0 else float(d)
+
+
+def load_fixture(path):
+    """The arrays of a .npz fixture as one dict.  A fixture too large for one file is kept in parts: <stem>.npz, then
+    <stem>.part2.npz, <stem>.part3.npz, ... (oracle/refharness/make_golden.py writes them)."""
+    import os
+    out = {}
+    stem, k = path[:-len(".npz")], 1
+    while True:
+        with np.load(path) as g:
+            out.update((name, g[name]) for name in g.files)
+        k += 1
+        path = "%s.part%d.npz" % (stem, k)
+        if not os.path.exists(path):
+            return out

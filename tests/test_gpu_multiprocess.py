@@ -145,7 +145,7 @@ def test_bench_multi_rank_prints_one_json_line(world, launcher, transport):
     # "mock": --transport auto, i.e. the (mocked) RCCL path first and the IPC transport as the second candidate, the
     # way the driver's multi-GPU run goes; "ipc": the IPC transport alone (real RCCL would refuse the shared GPU)
     rc, out, err = run(world, [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--size", "128", "--steps", "3",
-                               "--warmup", "1", "--cpu-baseline", "off", "--transport", "ipc" if transport == "ipc" else "auto"],
+                               "--warmup", "1", "--cpu-baseline", "off", "--full", "--transport", "ipc" if transport == "ipc" else "auto"],
                        transport=transport)
     assert rc == 0, (out[-2000:], err[-4000:])
     lines = [l for l in out.splitlines() if l.strip()]
@@ -223,7 +223,7 @@ def test_bench_measures_relay_striping_in_children():
     env = {k: v for k, v in _env("ipc").items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env["MFFT_BENCH_RELAY"] = "force"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--size", "128", "--steps", "2",
-                        "--warmup", "1", "--cpu-baseline", "off", "--transport", "ipc", "--pipeline", "1"], env=env,
+                        "--warmup", "1", "--cpu-baseline", "off", "--full", "--transport", "ipc", "--pipeline", "1"], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=240, cwd=ROOT)
     out, err = p.stdout.decode(), p.stderr.decode()
     assert p.returncode == 0, (out[-2000:], err[-4000:])

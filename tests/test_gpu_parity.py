@@ -680,7 +680,7 @@ def test_two_thirds_rule(decomp, P, pipeline, prec):
 def test_golden_fixtures(prec, golden_dir):
     """Against the arrays the REAL reference produced (tests/golden, N = [8,16,32])."""
     from mpifft4py_amd import Pencil_R2C, Slab_C2C, Slab_R2C
-    g = np.load(os.path.join(golden_dir, "ref_8x16x32_%s.npz" % prec))
+    g = orc.load_fixture(os.path.join(golden_dir, "ref_8x16x32_%s.npz" % prec))
     N = [8, 16, 32]
     A = g["A"]
 
@@ -1121,7 +1121,7 @@ def test_slab_c2c_padded(P, prec, golden_dir):
         assert orc.rel_l2(ap, want_ap[r]) < 4 * TOL[prec]
         assert orc.rel_l2(cp, want_cp[r]) < 4 * TOL[prec]
     # the reference's arrays at N = [8, 16, 32]
-    g = np.load(os.path.join(golden_dir, "ref_8x16x32_%s.npz" % prec))
+    g = orc.load_fixture(os.path.join(golden_dir, "ref_8x16x32_%s.npz" % prec))
     if P <= 2:
         Ng = [8, 16, 32]
         Cc = g["Cc"]

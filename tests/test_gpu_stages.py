@@ -3,6 +3,7 @@ mpifft4py_amd.serialFFT, i.e. mfft_c2c_axis / mfft_r2c_last / mfft_c2r_last),
 slab pack/unpack and the dealias mask, against numpy.fft (the arithmetic the
 reference's numpy backend uses, numpy_fft.py:25-107)."""
 import ctypes
+import os
 
 import numpy as np
 import pytest
@@ -277,28 +278,30 @@ def test_rfft_irfft_arbitrary_length(n, prec):
     assert orc.rel_l2(back, a) < 4 * TOL[prec]
 
 
-def test_unpack_and_mask_vs_reference_compiled_loops():
-    """mfft_slab_unpack / mfft_dealias_filter against the reference's own compiled Cython loops
-    (oracle/_ref, built from /root/reference/mpiFFT4py/cython/maths.pyx in the dev container)."""
+def test_unpack_and_mask_vs_reference_compiled_loops(golden_dir):
+    """mfft_slab_unpack / mfft_dealias_filter against the reference's own compiled Cython loops (cython/maths.pyx): what
+    they returned for these inputs (tests/golden/ref_maths_loops.npz, written by `oracle/build_ref.py golden`), and
+    the same live from oracle/_ref where oracle/build_ref.py could compile them."""
     from oracle import build_ref
     from mpifft4py_amd import DeviceArray, _lib
+    g = orc.load_fixture(os.path.join(golden_dir, "ref_maths_loops.npz"))
     ref = build_ref.load()
-    if ref is None:
-        pytest.skip("oracle/_ref not present")
-    rng = np.random.default_rng(12)
+    if ref is not None:
+        cases = {k: v for k, v in g.items() if k.startswith("gpu_") and k.rsplit("_", 1)[1] in ("U", "fu", "mask")}
+        for k, v in build_ref.run_loops(ref, cases).items():
+            assert np.array_equal(v, g[k]), k
     for prec in ("double", "single"):
         dt = cdtype(prec)
-        P, Np0, Np1, Nf = 8, 4, 6, 33
-        U = (rng.random((P, Np0, Np1, Nf)) + 1j * rng.random((P, Np0, Np1, Nf))).astype(dt)
-        T = np.zeros((Np0, P * Np1, Nf), dtype=dt)
-        ref.transpose_Uc(T, U, P, Np0, Np1, Nf)
+        key = "gpu_%s_" % np.dtype(dt).name
+        U, T = g[key + "U"], g[key + "T"]
+        P, Np0, Np1, Nf = U.shape
+        assert U.dtype == dt and (P, Np0, Np1, Nf) == (8, 4, 6, 33) and T.shape == (Np0, P * Np1, Nf)
         dU = DeviceArray.from_numpy(U)
         dT = DeviceArray.zeros(T.shape, dt)
         _lib.call("mfft_slab_unpack", dU.ptr, dT.ptr, P, Np0, Np1, Nf, _lib.precision_code(prec))
         assert np.array_equal(dT.get(), T)
-        fu = (rng.random((16, 8, 33)) + 1j * rng.random((16, 8, 33))).astype(dt)
-        mask = (rng.random(fu.shape) > 0.5).astype(np.uint8)
-        want = ref.dealias_filter(fu.copy(), mask)
+        fu, mask, want = g[key + "fu"], g[key + "mask"], g[key + "filtered"]
+        assert fu.shape == (16, 8, 33) and want.dtype == dt
         d = DeviceArray.from_numpy(fu)
         dm = DeviceArray.from_numpy(mask)
         _lib.call("mfft_dealias_filter", d.ptr, dm.ptr, fu.size, _lib.precision_code(prec))

@@ -251,6 +251,48 @@ def test_bench_cpu_baseline_cache_is_private_dated_and_versioned(tmp_path, monke
     assert bench.cpu_baseline_cached(64, 8)["cached"] is True
 
 
+def test_bench_dump_sample_is_fixed_and_bounded():
+    """bench.py dump_sample (--dump-outputs): the whole array when it fits, otherwise the same planes on every call, never
+    more bytes than the budget; complex values as a trailing (real, imaginary) axis of the matching float type."""
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    import bench
+
+    class Host(object):                     # the part of DeviceArray that dump_sample uses, over a numpy array
+        def __init__(self, x):
+            self.x, self.shape, self.nbytes = x, x.shape, x.nbytes
+
+        def get(self):
+            return self.x.copy()
+
+        def component(self, i):
+            return Host(self.x[i])
+
+        def leading(self, i0, i1):
+            return Host(self.x[i0:i1])
+    r = np.random.default_rng(5)
+    for dt in (np.complex128, np.complex64):
+        x = cplx((40, 8, 5)).astype(dt)
+        ft = np.float64 if dt == np.complex128 else np.float32
+        whole = bench.dump_sample(Host(x), x.nbytes)
+        assert whole.dtype == ft and whole.shape == (40, 8, 5, 2)
+        assert np.array_equal(whole[..., 0] + 1j * whole[..., 1], x)
+        plane = x.nbytes // 40
+        s1 = bench.dump_sample(Host(x), 10 * plane + plane // 2)
+        s2 = bench.dump_sample(Host(x), 10 * plane + plane // 2)
+        assert s1.shape == (10, 8, 5, 2) and s1.nbytes <= 10 * plane and np.array_equal(s1, s2)
+        c1 = s1[..., 0] + 1j * s1[..., 1]
+        hits = [i for i in range(40) if any(np.array_equal(x[i], c) for c in c1)]
+        assert len(hits) == 10              # ten distinct planes of the array, in increasing order
+        assert all(np.array_equal(x[i], c) for i, c in zip(hits, c1))
+        rows = bench.dump_sample(Host(x), plane // 2)
+        assert rows.shape == (1, 4, 5, 2) and rows.nbytes <= plane // 2
+    y = r.random((6, 4, 4))
+    assert np.array_equal(bench.dump_sample(Host(y), y.nbytes), y) and bench.dump_sample(Host(y), y.nbytes).dtype == np.float64
+
+
 @pytest.mark.parametrize("prec,line", [("double", 8), ("single", 16)])
 def test_complex_pitch_layout_is_device_free(prec, line):
     """The pitched device spectrum (mfft_plan_desc::complex_pitch): what a caller must allocate is host arithmetic

@@ -16,7 +16,7 @@ TOL = {"double": 1e-13, "single": 2e-5}
 
 @pytest.fixture(scope="module", params=["double", "single"])
 def gold(request, golden_dir):
-    return request.param, np.load(os.path.join(golden_dir, "ref_8x16x32_%s.npz" % request.param))
+    return request.param, orc.load_fixture(os.path.join(golden_dir, "ref_8x16x32_%s.npz" % request.param))
 
 
 def test_layout_tables(golden_dir):
@@ -155,26 +155,27 @@ def test_slab_c2c_padded(gold, P):
         assert orc.rel_l2(AP, g["slabc2c_P2_pad_bwd"]) < TOL[prec]
 
 
-def test_oracle_vs_reference_compiled_helpers():
-    """oracle/_ref/ref_maths = the reference's own Cython loops (cython/maths.pyx), compiled by
-    oracle/build_ref.py from /root/reference.  Bit-exact comparison of the oracle's restatements."""
+def test_oracle_vs_reference_compiled_helpers(golden_dir):
+    """The reference's own Cython loops (cython/maths.pyx: transpose_Uc, dealias_filter) against the oracle's restatements,
+    bit-exact: live from oracle/_ref/ref_maths where oracle/build_ref.py could compile them, and always from what they
+    returned for the same inputs (tests/golden/ref_maths_loops.npz, written by `oracle/build_ref.py golden`)."""
     from oracle import build_ref
+    g = orc.load_fixture(os.path.join(golden_dir, "ref_maths_loops.npz"))
+    cases = {k: v for k, v in g.items() if k.startswith("cpu_") and k.rsplit("_", 1)[1] in ("U", "fu", "mask")}
+    assert all(np.array_equal(cases[k], v) for k, v in build_ref.loop_cases().items() if k in cases)
     ref = build_ref.load()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (reference not mounted)")
-    rng = np.random.default_rng(8)
+    live = build_ref.run_loops(ref, cases) if ref is not None else {}
     for dt in (np.complex128, np.complex64):
-        P, Np0, Np1, Nf = 4, 3, 5, 9
-        U = (rng.random((P, Np0, Np1, Nf)) + 1j * rng.random((P, Np0, Np1, Nf))).astype(dt)
-        T = np.zeros((Np0, P * Np1, Nf), dtype=dt)
-        ref.transpose_Uc(T, U, P, Np0, Np1, Nf)                      # maths.pyx:21-31
-        assert np.array_equal(T, orc.slab_unpack(U))
-        assert np.array_equal(orc.slab_pack(T, P), U)
-        fu = (rng.random((6, 7, 5)) + 1j * rng.random((6, 7, 5))).astype(dt)
-        mask = (rng.random(fu.shape) > 0.5).astype(np.uint8)
-        want = orc.apply_mask(fu, mask).astype(dt)
-        got = ref.dealias_filter(fu.copy(), mask)                     # maths.pyx:9-19
-        assert np.array_equal(got, want)
+        key = "cpu_%s_" % np.dtype(dt).name
+        U, fu, mask = g[key + "U"], g[key + "fu"], g[key + "mask"]
+        assert U.dtype == dt and U.shape == (4, 3, 5, 9) and fu.shape == (6, 7, 5)
+        for out in [g] + ([live] if live else []):
+            T = out[key + "T"]
+            assert np.array_equal(T, orc.slab_unpack(U))
+            assert np.array_equal(orc.slab_pack(T, 4), U)
+            want = orc.apply_mask(fu, mask).astype(dt)
+            got = out[key + "filtered"]
+            assert got.dtype == dt and np.array_equal(got, want)
 
 
 @pytest.mark.parametrize("prec", ["double", "single"])
