@@ -1,6 +1,6 @@
 """Host-side (numpy) spectrum padding helpers with the names the reference's classes carry
 (slab.py:516-536, 803-825; pencil.py:351-379; line.py:164-175).  The device path never uses them -- the
-3/2-rule copies are fused into the transforms (csrc/plan.hip) -- they exist for callers of the
+3/2-rule copies are fused into the transforms (csrc/plan_dealias.hip) -- they exist for callers of the
 reference's helper API.  Written once, generically: a spectrum axis of n modes sits in a padded axis of
 m >= n modes with its non-negative frequencies at the front and its negative ones at the back."""
 import numpy as np

@@ -267,7 +267,7 @@ int scratch_for(hipStream_t s, size_t bytes, void** p) {
   return 0;
 }
 
-}  // namespace (the release hook below is called from plan.hip)
+}  // namespace (the release hook below is called from plan_create.hip)
 // A plan's stream is going away: its scratch buffer (up to 256 MiB) goes with it instead of staying for the life of the process.
 void big_release_stream(hipStream_t s) {
   int dev = 0;

@@ -1,5 +1,5 @@
 // capi.hip -- the extern "C" surface of libmpifft4py_amd.so that is not the plan
-// executor (plan.hip): device/memory helpers, communicators, the stage-level
+// executor (plan_*.hip): device/memory helpers, communicators, the stage-level
 // "serialFFT seam" entry points and HIP-event timers.
 #include <cstring>
 #include "comm.h"

@@ -2,7 +2,7 @@
 // buffers through IPC-mapped device memory.  Three ways to pull (MFFT_IPC_PULL, mfft_comm_set_option "ipc_pull"):
 //   kernel  (default) ONE launch of ipc_pull_kernel (ipc_pull.h) reads from all peers' mappings at once, a few
 //           workgroups per peer: every xGMI link of the fully connected node carries data at the same time; the launch
-//           runs on the plan's communication stream, which plan.hip confines to a handful of CUs (MFFT_COMM_CUS);
+//           runs on the plan's communication stream, which plan_create.hip confines to a handful of CUs (MFFT_COMM_CUS);
 //   streams one hipMemcpyAsync per peer, each on a stream of its own (fork / join events around them): the copy
 //           engines of several links at once, no CU at all;
 //   copy    round 2's path: the hipMemcpyAsync's one after the other on the issuing stream (one link at a time).
@@ -15,7 +15,7 @@
 // on a single-GPU box.
 //
 // Design, each point decided by a measurement on this pool (tools/ipc_probe.hip, tests/test_gpu_multiprocess.py):
-//  * Only plan work buffers are ever the SOURCE of an exchange (plan.hip), and they come from an arena this
+//  * Only plan work buffers are ever the SOURCE of an exchange (plan_*.hip), and they come from an arena this
 //    communicator owns (work_alloc): segments of device memory that are exported once, when they are created, and
 //    live as long as the communicator.  Exporting arbitrary buffers on demand does not survive long runs: after a
 //    process has closed imported mappings (of buffers their owners had freed), hipIpcGetMemHandle of a NEW allocation

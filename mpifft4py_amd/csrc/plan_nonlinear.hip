@@ -1,0 +1,278 @@
+// plan_nonlinear.hip -- the nonlinear term of a pseudo-spectral step as one plan-level operation.
+#include "plan_impl.h"
+
+using namespace mfft;
+
+// ===========================================================================
+// Round 6: the nonlinear term of a pseudo-spectral step, out = fftn(ifftn(a) x ifftn(b)), as ONE plan-level operation
+// (what demo/spectral_dns_solver.py:53-71 composes from six ifftn, a cross product in real space and three fftn).
+// ===========================================================================
+extern "C" int mfft_ew_cross(mfft_plan_t plan, const void* a, const void* b, void* out, size_t n, int precision);
+
+int64_t mfft_plan_s::local_real_count(bool padded) const {
+  if (d.line2d) return 0;
+  if (d.decomp == MFFT_SLAB) return padded ? (int64_t)(d.padsize * Np0) * M1 * M2 : Np0 * N1 * N2;
+  return padded ? (int64_t)(d.padsize * N1_0) * (int64_t)(d.padsize * N2_1) * M2 : N1_0 * N2_1 * N2;
+}
+
+// Composed route (every decomposition and length): the transforms the caller would run, on nine work arrays of the plan.
+int mfft_plan_s::nonlinear_cross_composed(const void* a, const void* b, void* out, int dealias) {
+  const bool pad = dealias == MFFT_DEALIAS_3_2, masked = dealias == MFFT_DEALIAS_2_3;
+  const int64_t nr = local_real_count(pad), nc = local_complex_alloc();       // (pitched arrays: a component is that much larger)
+  if (nr <= 0 || !r2c) return set_error(MFFT_ERR_UNSUPPORTED, "nonlinear_cross needs a 3-D real-to-complex plan");
+  MFFT_TRY(ensure(nlr, (size_t)(9 * nr) * rs));
+  char* R = static_cast<char*>(nlr.p);
+  auto back = [&](const void* in, void* o) { return exec(false, in, o, dealias); };
+  auto fwd = [&](const void* in, void* o) { return exec(true, in, o, masked ? (int)MFFT_DEALIAS_NONE : dealias); };
+  for (int f = 0; f < 3; ++f) {
+    MFFT_TRY(back(static_cast<const char*>(a) + (size_t)(f * nc) * es, R + (size_t)(f * nr) * rs));
+    MFFT_TRY(back(static_cast<const char*>(b) + (size_t)(f * nc) * es, R + (size_t)((3 + f) * nr) * rs));
+  }
+  MFFT_TRY(stage("nl_cross", 9.0 * (double)nr * rs, [&] {
+    return mfft_ew_cross(this, R, R + (size_t)(3 * nr) * rs, R + (size_t)(6 * nr) * rs, (size_t)nr, prec);
+  }));
+  for (int f = 0; f < 3; ++f) MFFT_TRY(fwd(R + (size_t)((6 + f) * nr) * rs, static_cast<char*>(out) + (size_t)(f * nc) * es));
+  return 0;
+}
+
+// x planes per batch of the fused routes: `planes` planes whose six y-pass outputs take plane6 bytes each, cut into
+// equal batches of at most MFFT_NLZ_BATCH_MB (read once per process; default 16 GiB, see nonlinear_cross_fused)
+static int64_t nlz_batch_planes(size_t plane6, int64_t planes) {
+  static const long batch_mb = env_int("MFFT_NLZ_BATCH_MB", 16384);
+  const int64_t nbat = (int64_t)((plane6 * (size_t)planes + ((size_t)batch_mb << 20) - 1) / ((size_t)batch_mb << 20));
+  return (planes + std::max<int64_t>(nbat, 1) - 1) / std::max<int64_t>(nbat, 1);
+}
+
+// the fused z stage on a batch: rows of the six fields in Y (yelems apart, pitch Za) in, the three rows of the cross product
+// out, in place on the first three
+static int nlz_rows(mfft_plan_s* p, char* Y, size_t yelems, int64_t L2, int64_t Za, int64_t nrows, int valid_in) {
+  NlzArgs z;
+  for (int f = 0; f < 3; ++f) {
+    z.a[f] = Y + (size_t)f * yelems * p->es;
+    z.b[f] = Y + (size_t)(3 + f) * yelems * p->es;
+    z.out[f] = Y + (size_t)f * yelems * p->es;
+  }
+  z.n = (int)L2; z.prec = p->prec; z.in_stride = Za; z.out_stride = Za; z.nrows = nrows; z.valid = (int)p->Nf;
+  z.valid_in = valid_in;
+  z.scale = 1.0 / ((double)L2 * (double)L2);
+  return launch_nlz(z, p->stream);
+}
+
+// Fused route: one rank, slab, real data, radix kernels on every axis.
+bool mfft_plan_s::nonlinear_fusable(int dealias) const {
+  static const bool off = env_on("MFFT_NO_NLZ"), ranks_off = env_on("MFFT_NO_NLZ_RANKS");      // read once per process
+  if (off || d.decomp != MFFT_SLAB || !r2c || d.line2d || d.drop_nyquist || N0 < 2 || N1 < 2 || N2 < 2) return false;
+  if (P > 1 && (ranks_off || pitched() || (dealias == MFFT_DEALIAS_3_2 && P > N0 / 2))) return false;
+  if (dealias == MFFT_DEALIAS_3_2) return can_fuse_pad() && nlz_supported(M2, prec);
+  auto plain_ok = [&](int64_t n) {
+    return n < 65536 && find_kernel(FAM_COL, (int)n, prec, 0) && find_kernel(FAM_COL, (int)n, prec, 1);
+  };
+  if (!plain_ok(N0) || !plain_ok(N1) || !nlz_supported(N2, prec)) return false;
+  if (dealias == MFFT_DEALIAS_2_3) return mask_set() && mask_fusable(N0, prec);
+  return dealias == MFFT_DEALIAS_NONE;
+}
+
+// The six spectra go through their inverse x passes into (L0, N1, Za) buffers of the plan (L = the padded mesh under the
+// 3/2-rule; Za = the row pitch, whole cache lines where rows are long).  Everything after that is local to an x plane, so
+// batches of x planes then run: inverse y pass of the six fields -> NlzFft (six z rows in, the three rows of the cross
+// product out, in place on the first three) -> forward y pass of the three results back into the x-pass buffers, whose
+// planes of that batch are free by then.  Three forward x passes finish.  The real-space arrays never exist; the batch
+// buffers are at most 16 GiB (1024^3 with the 3/2-rule: 6 x 13.1 GB of x-pass buffers + 14.7 GB of batch buffers, where the
+// composed route needs 9 x 29 GB of real work arrays).
+int mfft_plan_s::nonlinear_cross_fused(const void* a, const void* b, void* out, int dealias) {
+  const bool pad = dealias == MFFT_DEALIAS_3_2, masked = dealias == MFFT_DEALIAS_2_3;
+  const int64_t L0 = pad ? M0 : N0, L1 = pad ? M1 : N1, L2 = pad ? M2 : N2;
+  const int64_t line = (int64_t)(128 / es);
+  static const int align_mode = (int)env_int("MFFT_NLZ_ALIGN", -1);     // 0 compact rows, 1 aligned, unset: rows of 2 KiB and more
+  const bool aligned = align_mode > 0 || (align_mode < 0 && Nf * (int64_t)es >= 2048);
+  const int64_t Zi = Zc();                         // row pitch of the caller's arrays
+  const int64_t Za = nat_pitch() ? Zp : aligned ? (Nf + line - 1) / line * line : Nf;
+  const int64_t C = N0 * N1 * Zi;                  // elements of one component of the caller's arrays
+  const size_t xelems = (size_t)(L0 * N1 * Za);    // ... of one x-pass buffer
+  // Batch of x planes.  Large batches win (512^3 with the 3/2-rule, ms per Runge-Kutta step against the MiB of a batch's six
+  // y-pass outputs: 80: 181, 160: 157, 320: 143, 640: 130, 1536: 117, 6000: 111 -- batches that would fit the 256 MB Infinity Cache
+  // gain nothing from it and pay for their short launches: profiles/r06_dns_batch.txt), so: batches of 16 GiB -- ONE batch up to
+  // 512^3 with the 3/2-rule (14.9 GB), four at 768^3, eight at 1024^3 (14.7 GB of batch buffers beside 78.5 GB of x-pass
+  // buffers).  MFFT_NLZ_BATCH_MB overrides.
+  const size_t plane6 = (size_t)(6 * L1 * Za) * es;
+  const int64_t mb = std::min(std::max<int64_t>(nlz_batch_planes(plane6, L0), 1), L0);
+  MFFT_TRY(ensure(nlx, 6 * xelems * es));
+  MFFT_TRY(ensure(nly, (size_t)mb * plane6));
+  char* X = static_cast<char*>(nlx.p);
+  char* Y = static_cast<char*>(nly.p);
+  const size_t yelems = (size_t)(mb * L1 * Za);
+  const double sc3 = pad ? padscale() : 1.0;
+  const double Cb = (double)C * es, Xb = (double)(L0 * N1 * Nf) * es, Yb = (double)(L0 * L1 * Nf) * es;
+  MaskScope mask_scope{this};
+  lband_use = false;
+  // 2/3-rule with the reference's own filter (detect_band): the six inverse transforms are PRUNED as in slab_backward -- the x
+  // pass neither loads the removed kx rows nor touches the removed ky and kz columns, the y pass works on the kept kz columns
+  // and does not load the removed ky rows, the fused z kernel reads ba2 bins per row (NlzParams::valid_in) and stores all Nf.
+  // 512^3, per Taylor-Green step: nl_x_inv 12.9 -> 5.9 ms, nl_y_inv 9.3 -> 5.2, nl_z 8.2 -> 7.1; step 60.3 -> 45.5 ms
+  // (profiles/r06_dns_23rule.txt).  MFFT_NO_PRUNE=1: the masked loads below.
+  const bool pruned = masked && band_ok && prune_enabled();
+  double keep0 = 1.0, keep1 = 1.0, keep2 = 1.0;
+  if (pruned) band_keep(&keep0, &keep1, &keep2);
+  MFFT_TRY(stage("nl_x_inv", 6 * (Cb * keep0 + Xb) * keep1 * keep2, [&] {
+    for (int f = 0; f < 6; ++f) {
+      const void* src = static_cast<const char*>(f < 3 ? a : b) + (size_t)((f % 3) * C) * es;
+      void* dst = X + (size_t)f * xelems * es;
+      if (pruned) {                                // one outer batch per ky, the kept kz columns of it
+        ColArgs::Band bx;
+        bx.row_lo = ba0; bx.row_hi = bb0; bx.g_off = 0; bx.g_step = 1; bx.g_lo = ba1; bx.g_hi = bb1;
+        MFFT_TRY(col_band(src, dst, N0, N1, ba2, Zi, plain(N1 * Zi), Za, plain(N1 * Za), bx));
+      } else if (masked) {                                // `fu * dealias` (slab.py:237-245) applied while the spectrum is loaded
+        mask_src = src;
+        MFFT_TRY(col(src, dst, N0, true, N1, Nf, Zi, plain(N1 * Zi), Za, plain(N1 * Za)));
+        mask_src = nullptr;
+      } else if (Zi == Za && Za != Nf) {           // pitched caller rows: whole planes of N1 * Za columns
+        MFFT_TRY(col_pad(src, dst, L0, true, pad ? 1 : 0, false, 1, N1 * Za, 0, plain(N1 * Za), 0, plain(N1 * Za), sc3 / (double)L0));
+      } else if (Za != Nf) {                       // one outer batch per y row: compact rows in, pitched rows out
+        MFFT_TRY(col_pad(src, dst, L0, true, pad ? 1 : 0, false, N1, Nf, Nf, plain(N1 * Nf), Za, plain(N1 * Za), sc3 / (double)L0,
+                         0, 0, 1));
+      } else {
+        MFFT_TRY(col_pad(src, dst, L0, true, pad ? 1 : 0, false, 1, N1 * Nf, 0, plain(N1 * Nf), 0, plain(N1 * Nf), sc3 / (double)L0));
+      }
+    }
+    return 0;
+  }));
+  for (int64_t i0 = 0; i0 < L0; i0 += mb) {
+    const int64_t m = std::min(mb, L0 - i0);
+    const double frac = (double)m / (double)L0;
+    MFFT_TRY(stage("nl_y_inv", 6 * (Xb * keep1 + Yb) * keep2 * frac, [&] {
+      for (int f = 0; f < 6; ++f) {
+        const void* src = X + ((size_t)f * xelems + (size_t)(i0 * N1 * Za)) * es;
+        void* dst = Y + (size_t)f * yelems * es;
+        if (pruned) {
+          ColArgs::Band by;
+          by.row_lo = ba1; by.row_hi = bb1; by.c_lim = ba2;
+          MFFT_TRY(col_band(src, dst, N1, m, ba2, N1 * Za, plain(Za), L1 * Za, plain(Za), by));
+        } else {
+          MFFT_TRY(col_pad(src, dst, L1, true, pad ? 1 : 0, false, m, Nf, N1 * Za, plain(Za), L1 * Za, plain(Za), 1.0 / (double)L1));
+        }
+      }
+      return 0;
+    }));
+    MFFT_TRY(stage("nl_z", (6 * keep2 + 3) * Yb * frac, [&] {
+      return nlz_rows(this, Y, yelems, L2, Za, m * L1, pruned ? ba2 : 0);
+    }));
+    MFFT_TRY(stage("nl_y_fwd", 3 * (Xb + Yb) * frac, [&] {
+      for (int f = 0; f < 3; ++f)
+        MFFT_TRY(col_pad(Y + (size_t)f * yelems * es, X + ((size_t)f * xelems + (size_t)(i0 * N1 * Za)) * es, L1, false, pad ? 2 : 0,
+                         pad, m, Nf, L1 * Za, plain(Za), N1 * Za, plain(Za), 1.0));
+      return 0;
+    }));
+  }
+  MFFT_TRY(stage("nl_x_fwd", 3 * (Cb + Xb), [&] {
+    for (int f = 0; f < 3; ++f) {
+      const void* src = X + (size_t)f * xelems * es;
+      void* dst = static_cast<char*>(out) + (size_t)(f * C) * es;
+      if (Zi == Za && Za != Nf)                    // pitched result
+        MFFT_TRY(col_pad(src, dst, L0, false, pad ? 2 : 0, pad, 1, N1 * Za, 0, plain(N1 * Za), 0, plain(N1 * Za), 1.0 / sc3));
+      else if (Za != Nf)                           // tiles of the compact result; input column (y, z) sits at y * Za + z
+        MFFT_TRY(col_pad(src, dst, L0, false, pad ? 2 : 0, pad, 1, N1 * Nf, 0, plain(N1 * Za), 0, plain(N1 * Nf), 1.0 / sc3, Nf, Za - Nf));
+      else
+        MFFT_TRY(col_pad(src, dst, L0, false, pad ? 2 : 0, pad, 1, N1 * Nf, 0, plain(N1 * Nf), 0, plain(N1 * Nf), 1.0 / sc3));
+    }
+    return 0;
+  }));
+  return 0;
+}
+
+// The same over several ranks of a slab plan (blocking exchanges, whatever pipeline the plan's transforms use): six inverse x
+// passes, six all-to-alls, then batches of the rank's x planes -- inverse y passes reading the receive layout through the
+// two-level row map (transpose_Uc fused, maths.pyx:21-31), the fused z kernel, forward y passes writing the packed send
+// layout (slab.py:403) -- three all-to-alls, three forward x passes.  Nine exchanges as in the composition, no real arrays.
+int mfft_plan_s::nonlinear_cross_fused_ranks(const void* a, const void* b, void* out, int dealias) {
+  const bool pad = dealias == MFFT_DEALIAS_3_2, masked = dealias == MFFT_DEALIAS_2_3;
+  const int64_t L0 = pad ? M0 : N0, L1 = pad ? M1 : N1, L2 = pad ? M2 : N2, Lp0 = L0 / P;
+  const int64_t line = (int64_t)(128 / es);
+  const int64_t Za = Nf * (int64_t)es >= 2048 ? (Nf + line - 1) / line * line : Nf;        // batch buffers: line-aligned rows
+  const int64_t S = Np1 * Nf + (pad ? 0 : xplane_pad(true));      // x-row pitch of the forward exchange's layout (sched())
+  const int64_t C = N0 * Np1 * Nf;                                 // one component of the caller's arrays
+  const size_t xelems = (size_t)(L0 * S);                          // one field in any of the exchanged layouts
+  const size_t plane6 = (size_t)(6 * L1 * Za) * es;
+  const int64_t mb = nlz_batch_planes(plane6, Lp0);
+  MFFT_TRY(ensure(nlw[0], 6 * xelems * es));
+  MFFT_TRY(ensure(nlw[1], 6 * xelems * es));
+  MFFT_TRY(ensure(nly, (size_t)mb * plane6));
+  char *X = static_cast<char*>(nlw[0].p), *R = static_cast<char*>(nlw[1].p), *Y = static_cast<char*>(nly.p);
+  const size_t yelems = (size_t)(mb * L1 * Za);
+  const double sc3 = pad ? padscale() : 1.0;
+  MaskScope mask_scope{this};
+  lband_use = false;
+  // 2/3-rule with the reference's own filter: the six inverse transforms pruned as in slab_backward's blocking route -- the x
+  // pass reads the kept kx rows and writes (N0, Np1, ap) with the kept kz only (zeros for the ky this rank's mask removes), the
+  // six inverse exchanges carry ap / Nf of the bytes, the y pass and the fused z kernel work on a2 bins per row
+  const int64_t a2 = ba2, ap = (a2 + line - 1) / line * line;      // rows of the pruned layout start on cache lines
+  const bool pruned = masked && band_ok && ap <= Nf && prune_enabled();
+  MFFT_TRY(stage("nl_x_inv", 0, [&] {
+    for (int f = 0; f < 6; ++f) {
+      const void* src = static_cast<const char*>(f < 3 ? a : b) + (size_t)((f % 3) * C) * es;
+      void* dst = X + (size_t)f * xelems * es;
+      if (pruned) {
+        if (band_allzero) {                        // nothing of this rank's spectrum survives the mask
+          MFFT_TRY(zero(dst, (size_t)(N0 * Np1 * ap) * es));
+        } else {
+          ColArgs::Band bx;
+          bx.row_lo = ba0; bx.row_hi = bb0; bx.g_off = 0; bx.g_step = 1; bx.g_lo = ba1; bx.g_hi = bb1; bx.g_zero = 1;
+          MFFT_TRY(col_band(src, dst, N0, Np1, a2, Nf, plain(Np1 * Nf), ap, plain(Np1 * ap), bx));
+        }
+      } else if (masked) {
+        mask_src = src;
+        MFFT_TRY(col(src, dst, N0, true, 1, Np1 * Nf, 0, plain(Np1 * Nf), 0, plain(Np1 * Nf)));
+        mask_src = nullptr;
+      } else {
+        MFFT_TRY(col_pad(src, dst, L0, true, pad ? 1 : 0, false, 1, Np1 * Nf, 0, plain(Np1 * Nf), 0, plain(Np1 * Nf), sc3 / (double)L0));
+      }
+    }
+    return 0;
+  }));
+  MFFT_TRY(stage("nl_a2a_inv", 0, [&] {
+    for (int f = 0; f < 6; ++f) {
+      if (pruned) MFFT_TRY(exchange_equal(world, X + (size_t)f * xelems * es, R + (size_t)f * xelems * es, (size_t)(Np0 * Np1 * ap) * es));
+      else MFFT_TRY(xchg(0, false, pad, X + (size_t)f * xelems * es, R + (size_t)f * xelems * es));
+    }
+    return 0;
+  }));
+  for (int64_t i0 = 0; i0 < Lp0; i0 += mb) {
+    const int64_t m = std::min(mb, Lp0 - i0);
+    MFFT_TRY(stage("nl_y_inv", 0, [&] {
+      for (int f = 0; f < 6; ++f) {
+        if (pruned)
+          MFFT_TRY(col(R + ((size_t)f * xelems + (size_t)(i0 * Np1 * ap)) * es, Y + (size_t)f * yelems * es, N1, true, m, a2, Np1 * ap,
+                       two_level(Np1, Np0 * Np1 * ap, ap), L1 * Za, plain(Za)));
+        else
+          MFFT_TRY(col_pad(R + ((size_t)f * xelems + (size_t)(i0 * Np1 * Nf)) * es, Y + (size_t)f * yelems * es, L1, true, pad ? 1 : 0,
+                           false, m, Nf, Np1 * Nf, two_level(Np1, Lp0 * Np1 * Nf, Nf), L1 * Za, plain(Za), 1.0 / (double)L1));
+      }
+      return 0;
+    }));
+    MFFT_TRY(stage("nl_z", 0, [&] {
+      return nlz_rows(this, Y, yelems, L2, Za, m * L1, pruned ? (int)a2 : 0);
+    }));
+    MFFT_TRY(stage("nl_y_fwd", 0, [&] {      // truncate + fold in y, straight into the packed (P, Lp0, S) send layout
+      for (int f = 0; f < 3; ++f)
+        MFFT_TRY(col_pad(Y + (size_t)f * yelems * es, X + ((size_t)f * xelems + (size_t)(i0 * S)) * es, L1, false, pad ? 2 : 0, pad, m,
+                         Nf, L1 * Za, plain(Za), S, two_level(Np1, Lp0 * S, Nf), 1.0));
+      return 0;
+    }));
+  }
+  MFFT_TRY(stage("nl_a2a_fwd", 0, [&] {
+    for (int f = 0; f < 3; ++f) MFFT_TRY(xchg(0, true, pad, X + (size_t)f * xelems * es, R + (size_t)f * xelems * es));
+    return 0;
+  }));
+  MFFT_TRY(stage("nl_x_fwd", 0, [&] {
+    for (int f = 0; f < 3; ++f)
+      MFFT_TRY(col_pad(R + (size_t)f * xelems * es, static_cast<char*>(out) + (size_t)(f * C) * es, L0, false, pad ? 2 : 0, pad, 1,
+                       Np1 * Nf, 0, plain(S), 0, plain(Np1 * Nf), 1.0 / sc3));
+    return 0;
+  }));
+  return 0;
+}
+
+int mfft_plan_s::nonlinear_cross(const void* a, const void* b, void* out, int dealias) {
+  if (dealias == MFFT_DEALIAS_2_3) MFFT_TRY(require_mask());
+  if (nonlinear_fusable(dealias)) return P == 1 ? nonlinear_cross_fused(a, b, out, dealias) : nonlinear_cross_fused_ranks(a, b, out, dealias);
+  return nonlinear_cross_composed(a, b, out, dealias);
+}

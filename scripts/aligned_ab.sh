@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of the one-rank real transform's line-aligned intermediate (plan.hip aligned_route; developer tool, round 4)
+# A/B of the one-rank real transform's line-aligned intermediate (plan_slab.hip aligned_route; developer tool, round 4)
 out=gpurun_out/r04_aligned_ab.txt
 : > $out
 for rep in 1 2; do

@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of the one-rank padded-plane route for real data (plan.hip p1_plane_pad; MFFT_P1_XPAD = cache lines, 0 = off).  Round 4.
+# A/B of the one-rank padded-plane route for real data (plan_sched.hip p1_plane_pad; MFFT_P1_XPAD = cache lines, 0 = off).  Round 4.
 out=gpurun_out/r04_p1_xpad_ab.txt
 : > $out
 timeout 600 python3 -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "one_rank_padded_planes or mask_on_load or two_thirds_rule_pruned" 2>&1 | tail -3 >> $out

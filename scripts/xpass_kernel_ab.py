@@ -2,7 +2,7 @@
 forms (developer tool; round 4):
   (a) in place on a compact (N0, cols) array                      rounds 1 - 3
   (b) out of place, compact -> compact                            MFFT_NO_XPAD=1
-  (c) out of place, rows one cache line further apart -> the same pitch   (the read side of plan.hip xplane_pad; the store
+  (c) out of place, rows one cache line further apart -> the same pitch   (the read side of plan_sched.hip xplane_pad; the store
       side of the real pass is compact, which costs nothing: profiles/r02_power_of_two_stride.txt)
 through the stage-level entry point mfft_c2c_axis (serialFFT.fft's seam), timed with HIP events.
 python scripts/xpass_kernel_ab.py"""

@@ -1,4 +1,4 @@
-"""The y pass of a Nyquist-holding rank with compact and with line-aligned INPUT rows (plan.hip zrow_pitch), output compact
+"""The y pass of a Nyquist-holding rank with compact and with line-aligned INPUT rows (plan_sched.hip zrow_pitch), output compact
 as the plan needs it; alone on the device (developer tool, round 4).  python scripts/ypass_pitch_ab.py"""
 import ctypes, os, sys
 import numpy as np

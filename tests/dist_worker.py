@@ -226,7 +226,7 @@ def pencil(rank, P, N, A, align, P1=None, pipeline=1, relay=False):
     s0 = _lib.exchange_schedule(N, P, rank, dec, 0, True, p1=P1 or 0)
     assert s0["peers"] == (lay.comm1_members(rank) if align == "X" else lay.comm0_members(rank))
     # z chunks: the pencils' rule (N2 / Pz / 2 columns each, the Nyquist column on the last rank: pencil.py:197, 908); in
-    # the FORWARD exchange the rows of a block of 64 columns and more lie a whole number of cache lines apart (plan.hip
+    # the FORWARD exchange the rows of a block of 64 columns and more lie a whole number of cache lines apart (plan_sched.hip
     # zrow_pitch: y-aligned plans; the byte counts say how far), the rest of the row is unused
     Pz = len(s0["peers"])
     lens = [N[2] // Pz // 2] * Pz
@@ -234,7 +234,7 @@ def pencil(rank, P, N, A, align, P1=None, pipeline=1, relay=False):
     starts = np.concatenate([[0], np.cumsum(lens)[:-1]])
     pitch = [c // (m * n * ES) for c in s0["scount"]]
 
-    def zpitch(ln):       # plan.hip zrow_pitch: y-aligned: whole lines; x-aligned (round 5): one more line for rows of k * 8 KiB
+    def zpitch(ln):       # plan_sched.hip zrow_pitch: y-aligned: whole lines; x-aligned (round 5): one more line for rows of k * 8 KiB
         if ln < 64:
             return ln
         if align == "Y":
@@ -257,7 +257,7 @@ def pencil(rank, P, N, A, align, P1=None, pipeline=1, relay=False):
     if align == "X":
         b = np.fft.fft(np.concatenate(list(blocks[..., :q]), axis=1), axis=1)     # (m, N1, q): the y pass reads the pitched rows
         assert s1["peers"] == lay.comm0_members(rank)
-        SX = s1["scount"][0] // (m * ES)                      # x-row pitch of the blocks: N1_1 * q (+ a line: plan.hip xplane_pad)
+        SX = s1["scount"][0] // (m * ES)                      # x-row pitch of the blocks: N1_1 * q (+ a line: plan_sched.hip xplane_pad)
         assert SX in (N1_1 * q, N1_1 * q + 8)
         blk = np.zeros((lay.P1, m, SX), dtype=complex)
         for l in range(lay.P1):
@@ -300,7 +300,7 @@ def pencil(rank, P, N, A, align, P1=None, pipeline=1, relay=False):
 def c2c_plane_padded_exchanges(rank, P):
     """Round 4: complex data on power-of-two meshes.  The x rows of the exchange that feeds the strided x pass would lie
     a multiple of 64 KiB apart; the plan then leaves one cache line (8 complex128) between them INSIDE the exchanged
-    chunks (plan.hip xplane_pad) and the schedule says so.  Here: the slab C2C forward exchange (slab.py:759-766), the
+    chunks (plan_sched.hip xplane_pad) and the schedule says so.  Here: the slab C2C forward exchange (slab.py:759-766), the
     second forward exchange of the x-aligned pencil and the second inverse exchange of the y-aligned one, each executed
     over gloo with the library's byte counts on buffers laid out the way the kernels write / read them; the opposite
     directions (whose x pass reads the caller's array) must stay compact."""
@@ -381,7 +381,7 @@ def c2c_plane_padded_exchanges(rank, P):
 
 def slab_c2c_kz_slices_padded(rank, P):
     """The slab's DEFAULT multi-rank path (4 kz slices) on complex data: every slice's x rows lie N1/P * kz elements apart --
-    a power of two here -- so each slice is exchanged with one cache line between its x rows (plan.hip slice_pitch); the
+    a power of two here -- so each slice is exchanged with one cache line between its x rows (plan_sched.hip slice_pitch); the
     piece schedules say where."""
     N = [8, 256, 512]
     A = np.random.default_rng(2030).random(N) + 1j * np.random.default_rng(2031).random(N)

@@ -44,7 +44,7 @@ def test_schedules_over_gloo(world):
 def test_schedule_matches_reference_message_sizes():
     """Per-peer chunk sizes at 1024^3 fp64 from SURVEY.md section 2.1 (derived from the reference's Alltoall / Alltoallw
     call sites).  The exchanges whose receiver runs a strided x pass out of the chunks carry one cache line (8 complex128)
-    between x rows where the compact pitch reads slowly (plan.hip xplane_pad, round 4): 128 * 513 elements (slab over 8
+    between x rows where the compact pitch reads slowly (plan_sched.hip xplane_pad, round 4): 128 * 513 elements (slab over 8
     ranks, forward), 256 * 257 (x-aligned pencil, forward, the ranks that hold the Nyquist column), 512 * 128 / 512 * 129
     (y-aligned pencil, inverse); the forward z-splitting exchange of the y-aligned pencil carries the rows of the
     Nyquist-holding rank's chunk (129 columns) a whole number of cache lines apart (zrow_pitch: 136); the opposite

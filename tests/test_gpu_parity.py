@@ -137,7 +137,7 @@ def test_slab_padded(P, prec):
 @pytest.mark.parametrize("N", [[32, 64, 128], [64, 32, 1024], [16, 1024, 16], [1024, 8, 48], [20, 12, 44]])
 def test_slab_padded_one_rank_line_aligned_intermediates(N, prec, monkeypatch):
     """One rank, fused 3/2-rule transforms (slab.py:250-268, 372-386): the plan's two intermediates keep their z rows on
-    cache lines (plan.hip pad_pitch: 513 -> 520 bins), the inverse x pass writes pitched rows per y row, the forward x pass
+    cache lines (plan_dealias.hip pad_pitch: 513 -> 520 bins), the inverse x pass writes pitched rows per y row, the forward x pass
     tiles the compact result and wraps its input columns (ColParams::in_wrap; [64,32,1024] and [1024,8,48] through the
     three-sub-transform kernels of 1536 in single precision).  Against the oracle, and bit for bit against the compact
     route (MFFT_PAD_ALIGN=0): same arithmetic per column, other addresses."""
@@ -292,7 +292,7 @@ def test_padded_long_axes(N, prec):
 @pytest.mark.parametrize("N", [[16, 256, 256], [12, 512, 512]])
 def test_one_rank_padded_planes(N, prec, monkeypatch):
     """One rank, real data, a mesh whose own plane pitch N1 * (N2/2 + 1) elements is one the strided x pass reads slowly
-    (2^a + 2^(a-7), 2^a + 2^(a-8): the power-of-two meshes 256 and 512; plan.hip p1_plane_pad, a switch: MFFT_P1_XPAD): the
+    (2^a + 2^(a-7), 2^a + 2^(a-8): the power-of-two meshes 256 and 512; plan_sched.hip p1_plane_pad, a switch: MFFT_P1_XPAD): the
     intermediate's planes lie some cache lines further apart, the forward x pass reads them out of place, the inverse starts with the y pass.
     Route asserted, results against numpy.fft (slab.py:366-370, 247-249), the 2/3-rule with the reference's filter
     (pruned passes) and with an arbitrary one (mask applied by the y pass, now the first one)."""
@@ -330,7 +330,7 @@ def test_one_rank_padded_planes(N, prec, monkeypatch):
 @pytest.mark.parametrize("decomp,P,pipeline", [("slab", 1, 0), ("slab", 2, 1), ("slab", 4, 2), ("slab", 4, -2), ("pencilX", 4, 1),
                                                ("pencilX", 8, 2), ("pencilY", 4, 1), ("pencilY", 8, 2), ("c2c", 1, 0), ("c2c", 2, 1)])
 def test_two_thirds_rule_mask_on_load(decomp, P, pipeline, prec, fused, monkeypatch):
-    """The dealias mask applied by the first inverse pass while it reads the spectrum (ColFft PAD == 3, plan.hip
+    """The dealias mask applied by the first inverse pass while it reads the spectrum (ColFft PAD == 3, plan_dealias.hip
     fuse_mask) against the masked-copy path (MFFT_NO_MASK_FUSION=1) and against ifftn(fu * mask): blocking and
     pipelined exchanges (the kz-slice and row-batch pipelines read the caller's array at offsets), both precisions, the
     C2C class (on one GPU its inverse starts with the y pass).  The mask here is a random one: nothing in the kernels
@@ -390,7 +390,7 @@ def _pruned_cases():
 def test_two_thirds_rule_pruned(N, P, pipeline, prec, monkeypatch):
     """Real data, the reference's own dealias filter (three 1-D band conditions).  One GPU: the inverse does not load
     the removed rows, skips the tiles of removed columns and reads only the kept bins of every z row; P ranks: the x pass
-    writes the kept kz bins only (zeros for removed ky), the exchange carries a2 / Nf of the bytes (plan.hip detect_band,
+    writes the kept kz bins only (zeros for removed ky), the exchange carries a2 / Nf of the bytes (plan_dealias.hip detect_band,
     ColFft PAD == 4).  Against ifftn(fu * dealias) through the plain kernels and against the same call with
     MFFT_NO_PRUNE=1 (the general masked-load path); the input spectrum stays untouched.  Over 8 ranks some ranks own
     nothing but removed ky ([32,32,32]: ranks 3 and 4, as ranks 3 and 4 of the 1024^3 BASELINE mesh do): they vote
@@ -645,7 +645,7 @@ def test_two_thirds_rule_one_element_of_a_large_filter(mode, P):
 def test_two_thirds_rule(decomp, P, pipeline, prec):
     """ifftn(dealias='2/3-rule') == ifftn of the masked spectrum (slab.py:237-245, pencil.py:455-462).  With the reference's
     own filter the pencils' first inverse pass takes the band kernel (three 1-D conditions instead of one mask byte per
-    element; plan.hip detect_band_local): asserted through mfft_plan_get_info, result against the oracle's arithmetic."""
+    element; plan_dealias.hip detect_band_local): asserted through mfft_plan_get_info, result against the oracle's arithmetic."""
     from mpifft4py_amd import Pencil_R2C, Slab_R2C
     rng = np.random.default_rng(600)
     N = NREF
@@ -863,7 +863,7 @@ def test_pencil_c2c_extension(P, P1, align, prec):
 @pytest.mark.parametrize("cls,P,pipeline", [("slab", 2, 1), ("slab", 2, 0), ("slab", 4, 0), ("pencilX", 4, 1), ("pencilX", 4, 0),
                                             ("pencilY", 4, 1), ("pencilY", 4, 0)])
 def test_exchanged_layouts_with_padded_x_rows(cls, P, pipeline, kind, N):
-    """Round 4: where the x rows of an exchanged layout lie a slow pitch apart (a power of two, 2^a + 2^(a-7..9): plan.hip
+    """Round 4: where the x rows of an exchanged layout lie a slow pitch apart (a power of two, 2^a + 2^(a-7..9): plan_sched.hip
     xplane_pad / slice_pitch) the chunks carry one cache line between x rows and the x pass reads them out of place.
     Meshes on which that is the case for the slab (un-pipelined and kz slices), the x-aligned pencil (forward) and the
     y-aligned one (inverse), un-pipelined and pipelined, complex and real data -- asserted through the device-free
@@ -917,7 +917,7 @@ def test_exchanged_layouts_with_padded_x_rows(cls, P, pipeline, kind, N):
                                                  ("Y", 4, None, 1), ("Y", 4, None, 0), ("Y", 8, None, 0), ("Y", 8, 2, 1)])
 def test_pencil_forward_z_blocks_with_line_aligned_rows(align, P, P1, pipeline, prec):
     """Round 4: in the forward z-splitting exchange the rows of a chunk of 64 columns and more lie a whole number of cache
-    lines apart in the y-aligned plans (plan.hip zrow_pitch, fft_kernels.h ZSplit pitch): the rank that holds the Nyquist
+    lines apart in the y-aligned plans (plan_sched.hip zrow_pitch, fft_kernels.h ZSplit pitch): the rank that holds the Nyquist
     column (129 / 65 columns here) runs its x pass off the 2^a + 2^(a-7) pitch and carries the row pitch through the second
     exchange; the x-aligned plans keep compact rows (same test, same meshes).  [32, 64, 512]: Nf = 257; asserted through the schedule query; against numpy.fft."""
     from mpifft4py_amd import Pencil_R2C, _lib
@@ -929,7 +929,7 @@ def test_pencil_forward_z_blocks_with_line_aligned_rows(align, P, P1, pipeline, 
     es = 16 if prec == "double" else 8
     q_last = lay.complex_shape(P - 1)[2]
     per_line = 128 // es
-    want_pitch = -(-q_last // per_line) * per_line if align == "Y" else q_last      # y-aligned plans only (plan.hip zrow_pitch)
+    want_pitch = -(-q_last // per_line) * per_line if align == "Y" else q_last      # y-aligned plans only (plan_sched.hip zrow_pitch)
     assert q_last % 2 == 1 and s0["rcount"][0] == m * n * want_pitch * es, (q_last, s0)
     rng = np.random.default_rng(31 + P)
     A = rng.random(N).astype(rdtype(prec))
@@ -950,7 +950,7 @@ def test_pencil_forward_z_blocks_with_line_aligned_rows(align, P, P1, pipeline, 
 @pytest.mark.parametrize("align,P1,pipeline", [("X", 4, 1), ("X", 4, 0), ("X", 1, 1), ("X", 1, 0), ("Y", 1, 1), ("Y", 1, 0), ("Y", 4, 1), ("Y", 4, 0)])
 def test_one_dimensional_process_grids_with_padded_layouts(align, P1, pipeline, kind):
     """P x 1 and 1 x P grids (the C ABI takes them; bench.py times them) on meshes where the padded exchange layouts of
-    round 4 are active: a group of one rank exchanges nothing, so the buffers change roles differently (plan.hip:
+    round 4 are active: a group of one rank exchanges nothing, so the buffers change roles differently (plan_pencil.hip:
     zsolo / g2solo) -- x-aligned 4 x 1: no z exchange but a padded second one; y-aligned 1 x 4: a z exchange with pitched
     rows and no second one; and the two grids on which neither pad applies."""
     from mpifft4py_amd import Pencil_C2C, Pencil_R2C
@@ -982,7 +982,7 @@ def test_one_dimensional_process_grids_with_padded_layouts(align, P1, pipeline, 
 
 @pytest.mark.parametrize("pipeline", [1, 0])
 def test_pencil_c2c_y_with_pitched_z_chunks(pipeline):
-    """The y-aligned pencil's row pitch (plan.hip zrow_pitch) on COMPLEX data: chunks of 72 complex64 columns (576 bytes)
+    """The y-aligned pencil's row pitch (plan_sched.hip zrow_pitch) on COMPLEX data: chunks of 72 complex64 columns (576 bytes)
     travel 80 apart; the contiguous-axis c2c kernel writes them (RowFft CHUNK through ZSplit)."""
     from mpifft4py_amd import Pencil_C2C, _lib
     N, P = [32, 64, 144], 4
@@ -1512,7 +1512,7 @@ def test_slab_c2c_arbitrary_lengths(N, P, prec):
 @pytest.mark.parametrize("N", [[64, 64, 64], [24, 128, 64], [40, 32, 256], [16, 4096, 2], [12, 64, 2048]])
 def test_slab_c2c_power_of_two_planes(N, prec):
     """One GPU, complex data whose y-z planes are a multiple of 64 KiB: the transforms go through an intermediate with
-    padded planes (plan.hip plane_pad), the inverse in the order y, x, z.  The 2/3-rule inverse and the input's
+    padded planes (plan_sched.hip plane_pad), the inverse in the order y, x, z.  The 2/3-rule inverse and the input's
     preservation ride along."""
     from mpifft4py_amd.slab import C2C
     rng = np.random.default_rng(sum(N) + 13)
