@@ -347,7 +347,7 @@ bool big_length_ok(int64_t n) { return n >= 2 && n <= MFFT_BIG_MAX_LENGTH; }
 // chunks of the strided form must end on column-group boundaries: process one outer batch (or a run of whole ones) per
 // chunk by letting run_big_t's chunk be a multiple of ncols -- done here by splitting the call per group of outer batches
 int big_col(const ColArgs& a, hipStream_t s) {
-  if (a.pad || a.mask || a.band.on || a.in_wrap)
+  if (a.pad != Op::Plain || a.mask || a.band.on || a.in_wrap)
     return set_error(MFFT_ERR_UNSUPPORTED, "length %d has no radix plan: the fused 3/2-rule / 2/3-rule passes are not available for it", a.n);
   BigTables tb;
   MFFT_TRY(tables_for(a.n, a.prec, &tb));

@@ -171,9 +171,9 @@ int mfft_length_route_precision(int64_t n, int real_transform, int precision) {
 
 int mfft_kernel_name(int family, int64_t n, int precision, int inverse, int nt, char* buf, size_t buflen) {
   if (!buf || buflen == 0 || family < FAM_COL || family > FAM_C2R) return set_error(MFFT_ERR_INVALID, "bad argument");
-  const KernelEntry* e = find_kernel(family, (int)n, precision, family == FAM_C2R ? 1 : (inverse ? 1 : 0), nt ? 1 : 0);
+  const KernelEntry* e = find_kernel(family, (int)n, precision, family == FAM_C2R ? 1 : (inverse ? 1 : 0), Op::Plain, nt ? Build::NonTemporal : Build::Default);
   if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no radix kernel of family %d for length %lld", family, (long long)n);
-  snprintf(buf, buflen, "%s tile=%d threads=%d lds=%d%s", e->name, e->tile, e->threads, e->lds_bytes, e->nt ? " nt" : "");
+  snprintf(buf, buflen, "%s tile=%d threads=%d lds=%d%s", e->name, e->tile, e->threads, e->lds_bytes, e->build == Build::NonTemporal ? " nt" : "");
   return 0;
 }
 

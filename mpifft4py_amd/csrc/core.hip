@@ -35,26 +35,39 @@ std::vector<KernelEntry>& kernel_registry() {
 
 // The registry is complete once the static initialisers of the kernels_*.hip units have run; lookups go
 // through hash maps built on first use (a linear scan of ~2000 entries per launch costs ~0.3 us, visible at 32^3).
-static uint64_t kernel_key(int family, int n, int prec, int inv, int nt, int pad) {
-  // pad codes run to 18 (registry.h: 16 + pad for the ColFft3 kernels): six bits
-  return ((uint64_t)(unsigned)n << 16) | ((uint64_t)family << 10) | ((uint64_t)(pad & 63) << 4) | ((uint64_t)nt << 2) |
-         ((uint64_t)inv << 1) | (uint64_t)prec;
+constexpr int OP_BITS = 5, BUILD_BITS = 3, FAMILY_BITS = 6;
+static_assert(2 * (unsigned)Op::TopFlag <= (1u << OP_BITS) && (unsigned)Op::Band < (unsigned)Op::Limited, "Op does not fit its key field");
+static_assert((unsigned)Build::Last < (1u << BUILD_BITS), "Build does not fit its key field");
+static_assert((unsigned)FAM_NLZ < (1u << FAMILY_BITS), "Family does not fit its key field");
+static uint64_t kernel_key(int family, int n, int prec, int inv, Op op, Build build) {
+  uint64_t k = (unsigned)n;
+  k = k << FAMILY_BITS | (uint64_t)family;
+  k = k << OP_BITS | (uint64_t)op;
+  k = k << BUILD_BITS | (uint64_t)build;
+  return k << 2 | (uint64_t)(inv << 1 | prec);
 }
 
-const KernelEntry* find_kernel(int family, int n, int prec, int inv, int nt, int pad) {
+const KernelEntry* find_kernel(int family, int n, int prec, int inv, Op op, Build build) {
   static std::unordered_map<uint64_t, const KernelEntry*> index;
   static std::once_flag once;
   std::call_once(once, [] {
-    for (const KernelEntry& e : kernel_registry()) index.emplace(kernel_key(e.family, e.n, e.prec, e.inv, e.nt, e.pad), &e);
+    for (const KernelEntry& e : kernel_registry()) {
+      auto ins = index.emplace(kernel_key(e.family, e.n, e.prec, e.inv, e.op, e.build), &e);
+      if (!ins.second) {      // two entries under one key: a registration error, which of them ran would depend on link order
+        fprintf(stderr, "mpifft4py_amd: kernel registry holds '%s' and '%s' under one key (family %d, n %d, prec %d, inv %d, op %u, build %u)\n",
+                ins.first->second->name, e.name, e.family, e.n, e.prec, e.inv, (unsigned)e.op, (unsigned)e.build);
+        abort();
+      }
+    }
   });
-  auto it = index.find(kernel_key(family, n, prec, inv, nt, pad));
+  auto it = index.find(kernel_key(family, n, prec, inv, op, build));
   return it == index.end() ? nullptr : it->second;
 }
 
 const KernelEntry* find_chirpz(int family, int n, int prec, int inv) {
   static std::unordered_map<uint64_t, const KernelEntry*> cache;
   static std::mutex mu;
-  const uint64_t key = kernel_key(family, n, prec, inv, 0, 0);
+  const uint64_t key = kernel_key(family, n, prec, inv, Op::Plain, Build::Default);
   std::lock_guard<std::mutex> lk(mu);
   auto it = cache.find(key);
   if (it != cache.end()) return it->second;
@@ -98,110 +111,74 @@ struct DevCache {
   std::map<const KernelEntry*, void*> tw;
   std::map<std::pair<int, int>, void*> rtw;
   std::map<const void*, bool> attr_done;
-  std::map<std::tuple<int, int, int>, std::pair<void*, void*>> ztab;   // (n, M, prec) -> (chirp, bhat)
+  std::map<std::tuple<int, int, int>, void*> zchirp, zbhat;            // (n, M, prec) -> chirp, filter of the chirp-z kernels
   std::map<std::pair<int, int>, void*> rt3;                            // (L, prec) -> twiddles of the pruned nonlinear z stage
 };
 static std::mutex g_cache_mu;
 static std::map<int, DevCache> g_cache;
 
-static int prepare_kernel(const KernelEntry* e, void** tw_out) {
+template <class F> static auto by_prec(int prec, F f) { return prec == MFFT_DOUBLE ? f(double{}) : f(float{}); }
+template <class V> static std::vector<char> bytes_of(const V& v) {
+  const char* p = reinterpret_cast<const char*>(v.data());
+  return std::vector<char>(p, p + v.size() * sizeof(v[0]));
+}
+// One table of the current device's cache (a member of DevCache): built on the host and uploaded the first time its key is
+// asked for, remembered after.  `before` runs under the same lock on every call.
+template <class Key, class Fill, class Before>
+static int device_table(std::map<Key, void*> DevCache::*table, Key key, Fill fill, void** out, Before before) {
   int dev = 0;
   MFFT_HIP(hipGetDevice(&dev));
   std::lock_guard<std::mutex> lk(g_cache_mu);
   DevCache& c = g_cache[dev];
-  if (!c.attr_done[e->func]) {
-    if (e->lds_bytes > 65536)
-      MFFT_HIP(hipFuncSetAttribute(e->func, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
-    c.attr_done[e->func] = true;
-  }
-  auto it = c.tw.find(e);
-  if (it == c.tw.end()) {
-    const size_t bytes = (size_t)e->tw_count * elem_bytes(e->prec, true);
-    std::vector<char> host(bytes);
-    e->build_tw(host.data());
+  MFFT_TRY(before(c));
+  auto& m = c.*table;
+  auto it = m.find(key);
+  if (it == m.end()) {
+    const std::vector<char> host = fill();
     void* d = nullptr;
-    MFFT_HIP(hipMalloc(&d, bytes));
-    MFFT_HIP(hipMemcpy(d, host.data(), bytes, hipMemcpyHostToDevice));
-    it = c.tw.emplace(e, d).first;
+    MFFT_HIP(hipMalloc(&d, host.size()));
+    MFFT_HIP(hipMemcpy(d, host.data(), host.size(), hipMemcpyHostToDevice));
+    it = m.emplace(key, d).first;
   }
-  *tw_out = it->second;
+  *out = it->second;
   return 0;
+}
+template <class Key, class Fill>
+static int device_table(std::map<Key, void*> DevCache::*table, Key key, Fill fill, void** out) {
+  return device_table(table, key, fill, out, [](DevCache&) { return 0; });
+}
+
+static int prepare_kernel(const KernelEntry* e, void** tw_out) {
+  auto fill = [&] {
+    std::vector<char> host((size_t)e->tw_count * elem_bytes(e->prec, true));
+    e->build_tw(host.data());
+    return host;
+  };
+  return device_table(&DevCache::tw, e, fill, tw_out, [&](DevCache& c) {
+    if (!c.attr_done[e->func]) {
+      if (e->lds_bytes > 65536)
+        MFFT_HIP(hipFuncSetAttribute(e->func, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
+      c.attr_done[e->func] = true;
+    }
+    return 0;
+  });
 }
 
 static int real_twiddles(int n, int prec, void** out) {
-  int dev = 0;
-  MFFT_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(g_cache_mu);
-  DevCache& c = g_cache[dev];
-  auto key = std::make_pair(n, prec);
-  auto it = c.rtw.find(key);
-  if (it == c.rtw.end()) {
-    void* d = nullptr;
-    if (prec == MFFT_DOUBLE) {
-      auto v = build_real_twiddles<double>(n);
-      MFFT_HIP(hipMalloc(&d, v.size() * sizeof(v[0])));
-      MFFT_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
-    } else {
-      auto v = build_real_twiddles<float>(n);
-      MFFT_HIP(hipMalloc(&d, v.size() * sizeof(v[0])));
-      MFFT_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
-    }
-    it = c.rtw.emplace(key, d).first;
-  }
-  *out = it->second;
-  return 0;
+  return device_table(&DevCache::rtw, std::make_pair(n, prec),
+                      [&] { return by_prec(prec, [&](auto t) { return bytes_of(build_real_twiddles<decltype(t)>(n)); }); }, out);
 }
 
 static int nlz3_twiddles(int L, int prec, void** out) {
-  int dev = 0;
-  MFFT_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(g_cache_mu);
-  DevCache& c = g_cache[dev];
-  auto key = std::make_pair(L, prec);
-  auto it = c.rt3.find(key);
-  if (it == c.rt3.end()) {
-    void* d = nullptr;
-    if (prec == MFFT_DOUBLE) {
-      auto v = build_nlz3_twiddles<double>(L);
-      MFFT_HIP(hipMalloc(&d, v.size() * sizeof(v[0])));
-      MFFT_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
-    } else {
-      auto v = build_nlz3_twiddles<float>(L);
-      MFFT_HIP(hipMalloc(&d, v.size() * sizeof(v[0])));
-      MFFT_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
-    }
-    it = c.rt3.emplace(key, d).first;
-  }
-  *out = it->second;
-  return 0;
+  return device_table(&DevCache::rt3, std::make_pair(L, prec),
+                      [&] { return by_prec(prec, [&](auto t) { return bytes_of(build_nlz3_twiddles<decltype(t)>(L)); }); }, out);
 }
 
 // chirp-z tables of logical length n on convolution length M (fft_chirpz.h)
-template <typename T>
-static int upload_chirpz(int n, int M, void** chirp, void** bhat) {
-  auto c = build_chirp<T>(n);
-  auto b = build_chirp_filter<T>(n, M);
-  MFFT_HIP(hipMalloc(chirp, c.size() * sizeof(c[0])));
-  MFFT_HIP(hipMemcpy(*chirp, c.data(), c.size() * sizeof(c[0]), hipMemcpyHostToDevice));
-  MFFT_HIP(hipMalloc(bhat, b.size() * sizeof(b[0])));
-  MFFT_HIP(hipMemcpy(*bhat, b.data(), b.size() * sizeof(b[0]), hipMemcpyHostToDevice));
-  return 0;
-}
 static int chirpz_tables(int n, int M, int prec, void** chirp, void** bhat) {
-  int dev = 0;
-  MFFT_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(g_cache_mu);
-  DevCache& c = g_cache[dev];
-  auto key = std::make_tuple(n, M, prec);
-  auto it = c.ztab.find(key);
-  if (it == c.ztab.end()) {
-    void *ch = nullptr, *bh = nullptr;
-    MFFT_TRY(prec == MFFT_DOUBLE ? upload_chirpz<double>(n, M, &ch, &bh) : upload_chirpz<float>(n, M, &ch, &bh));
-    it = c.ztab.emplace(key, std::make_pair(ch, bh)).first;
-  }
-  *chirp = it->second.first;
-  *bhat = it->second.second;
-  return 0;
+  const auto key = std::make_tuple(n, M, prec);
+  MFFT_TRY(device_table(&DevCache::zchirp, key, [&] { return by_prec(prec, [&](auto t) { return bytes_of(build_chirp<decltype(t)>(n)); }); }, chirp));
+  return device_table(&DevCache::zbhat, key, [&] { return by_prec(prec, [&](auto t) { return bytes_of(build_chirp_filter<decltype(t)>(n, M)); }); }, bhat);
 }
 
 static RowMap to_map(const RowSpec& r, int n) { return make_rowmap(r.hi, r.lo, r.split, n); }
@@ -254,6 +231,82 @@ static int launch_col_t(const KernelEntry* e, const ColArgs& a, void* tw, hipStr
 #ifndef MFFT_COL3S_DEFAULT
 #define MFFT_COL3S_DEFAULT 1
 #endif
+// Which kernel runs the strided pass `a` (2 <= n < 65536): a radix entry, a chirp-z entry (family FAM_COLZ), or none where the
+// scratch-buffer fallback of bigfft.hip serves the length.
+static int select_col(const ColArgs& a, const KernelEntry** out) {
+  const int inv = a.inverse ? 1 : 0;
+  // non-temporal variant only when every row segment of the tile is a whole, private L2 line
+  const int64_t per_line = 128 / (int64_t)elem_bytes(a.prec, true);
+  auto aligned = [&](const void* p, int64_t outer, const RowSpec& r) {
+    return ((uintptr_t)p % 128 == 0) && outer % per_line == 0 && r.lo % per_line == 0 && r.hi % per_line == 0;
+  };
+  // Out of place the NT variant is always ahead (1024^3 x pass 3.70 -> 3.63 ms at one workgroup per CU, 3.24 -> 3.19 ms at
+  // two); in place only the kernels that run two workgroups per CU gain from it (3.42 -> 3.35 ms; one per CU: 3.57 -> 3.84 ms)
+  static const int nt_mode = getenv("MFFT_NT") ? atoi(getenv("MFFT_NT")) : 1;   // 0 never, 1 by that rule, 2 always
+  auto find_nt = [&](Op op) {
+    const KernelEntry* k = find_kernel(FAM_COL, a.n, a.prec, inv, op, Build::NonTemporal);
+    return k && a.in == a.out && !(k->nt_inplace || nt_mode == 2) ? nullptr : k;
+  };
+  const bool nt_ok = a.allow_nt && nt_mode > 0 && a.pad == Op::Plain && aligned(a.in, a.in_outer, a.in_rows) && aligned(a.out, a.out_outer, a.out_rows);
+  const KernelEntry* ent = nt_ok ? find_nt(Op::Plain) : nullptr;
+  const KernelEntry* e = nullptr;
+  if (a.mask || a.band.on) {
+    const Op op = a.band.on ? Op::Band : Op::MaskLoad;
+    if (!a.inverse || a.pad != Op::Plain || (a.mask && a.band.on)) return set_error(MFFT_ERR_INVALID, "a dealias mask is applied by inverse, un-padded transforms only");
+    if (ent) e = find_nt(op);      // the same alignment rule picks the non-temporal build
+    if (!e) e = find_kernel(FAM_COL, a.n, a.prec, 1, op);
+    if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no masked-load kernel for length %d", a.n);
+    ent = nullptr;
+  }
+  if (a.pad != Op::Plain) {
+    if ((a.pad == Op::PadLoad) != a.inverse) return set_error(MFFT_ERR_INVALID, "pad-on-load is an inverse-transform mode, truncate-on-store a forward one");
+    e = find_kernel(FAM_COL, a.n, a.prec, inv, a.pad);
+    if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused 3/2-rule kernel for length %d", a.n);
+  }
+  // N = 3 L as three sub-transforms per workgroup (fft_col3.h; Build::Col3), plain and 3/2-rule passes.  Measured at
+  // 1536 (profiles/r04_col3_1536.txt): even with the ColFft plan in double precision (1536^3 pair 75.1 - 81.0 against 76.9 -
+  // 78.1 ms, 3/2-rule pair of 1024^3 45.5 - 47.7 against 47.9 - 48.1), ahead in single precision on the x passes (rows a whole
+  // plane apart: 9.0 -> 7.3 ms inverse, 7.5 -> 6.8 forward) and behind on the y passes (6.9 -> 7.7 - 8.1).  Default: single
+  // precision, passes without an outer batch (the x passes); MFFT_COL3=1 always, MFFT_COL3=0 never.
+  static const int col3_mode = getenv("MFFT_COL3") ? atoi(getenv("MFFT_COL3")) : -1;
+  const bool col3_on = col3_mode > 0 || (col3_mode < 0 && a.prec == MFFT_SINGLE && (a.nouter == 1 || a.thirds > 0));
+  if (col3_on && !a.mask && !a.band.on) {
+    const KernelEntry* e3 = nullptr;
+    if (nt_ok) e3 = find_kernel(FAM_COL, a.n, a.prec, inv, Op::Plain, Build::Col3NT);      // same alignment rule, NT build
+    if (!e3) e3 = find_kernel(FAM_COL, a.n, a.prec, inv, a.pad, Build::Col3);
+    if (e3) e = e3;
+  }
+  // The pad-on-load inverse with one third of a tile's transform per workgroup (fft_col3.h ColFft3S, Build::Col3Thirds): out of
+  // place only (its passes are).  3/2-rule ifftn + fftn pair of 1024^3 (profiles/r04_col3s_ab.txt): double precision x pass
+  // 5.31 -> 5.16 ms, y pass 8.47 -> 9.17 (not taken); single precision x 2.99 -> 2.54, y 4.98 -> 4.35.  Default on; MFFT_COL3S=0 never.
+  static const int col3s_mode = getenv("MFFT_COL3S") ? atoi(getenv("MFFT_COL3S")) : MFFT_COL3S_DEFAULT;
+  // double precision: the passes without an outer batch only (y pass 8.4 -> 9.1 ms with it); MFFT_COL3S=2: every pass
+  if (col3s_mode > 0 && a.thirds != 0 && a.pad == Op::PadLoad && a.inverse && a.in != a.out && !a.mask && !a.band.on &&
+      (col3s_mode > 1 || a.thirds > 0 || a.prec == MFFT_SINGLE || a.nouter == 1)) {
+    if (const KernelEntry* es = find_kernel(FAM_COL, a.n, a.prec, 1, Op::PadLoad, Build::Col3Thirds)) e = es;
+  }
+  if (!e && ent) e = ent;
+  if (!e) e = find_kernel(FAM_COL, a.n, a.prec, inv);
+  // Round 5: the y-pass builds (registry.h register_col_ytile, Build::YTile: 64-byte tiles, LDS twiddles, two workgroups per
+  // CU) where the rows of a tile lie at most 64 KB apart on both sides -- the y passes of every decomposition; the x passes,
+  // rows a plane apart, lose with them (1440 / 1536 fp64: y 12.95 -> 9.62 / 13.74 -> 11.55 ms, x 12.85 -> 14.49 / 12.56 -> 14.41).  Not for the
+  // pruned 2/3-rule passes (their tile lists are built for the width of the general kernel).  MFFT_YTILE=0 never, 2 always.
+  static const int ytile_mode = getenv("MFFT_YTILE") ? atoi(getenv("MFFT_YTILE")) : 1;
+  if (ytile_mode > 0 && e && !a.band.on && (e->build == Build::Default || e->build == Build::NonTemporal) &&
+      (e->op == Op::Plain || e->op == Op::PadLoad || e->op == Op::TruncStore || e->op == Op::MaskLoad)) {
+    const int64_t es = (int64_t)elem_bytes(a.prec, true);
+    const bool near_rows = std::llabs(a.in_rows.lo) * es <= 65536 && std::llabs(a.out_rows.lo) * es <= 65536;
+    if (near_rows || ytile_mode > 1)
+      if (const KernelEntry* ey = find_kernel(FAM_COL, a.n, a.prec, inv, e->op, Build::YTile)) e = ey;
+  }
+  if (!e) {   // no radix plan for this length: chirp-z on the next compiled length >= 2n-1
+    e = find_chirpz(FAM_COLZ, a.n, a.prec, inv);
+    if (!e && !big_length_ok(a.n)) return set_error(MFFT_ERR_UNSUPPORTED, "no kernel for a complex transform of length %d", a.n);
+  }
+  *out = e;
+  return 0;
+}
+
 int launch_col(const ColArgs& a, hipStream_t s) {
   if (a.n == 1) {   // a length-1 transform is a (scaled) copy of its single row
     if (a.in == a.out && a.in_outer == a.out_outer && a.scale == 1.0) return 0;
@@ -265,85 +318,32 @@ int launch_col(const ColArgs& a, hipStream_t s) {
   if (a.n >= 65536)      // beyond the radix kernels' 16-bit row arithmetic: the scratch-buffer fallback or nothing
     return big_length_ok(a.n) ? big_col(a, s) : set_error(MFFT_ERR_UNSUPPORTED, "transform length %d too large", a.n);
   if (a.ncols >= (1ll << 31)) return set_error(MFFT_ERR_UNSUPPORTED, "too many columns");
-  // non-temporal variant only when every row segment of the tile is a whole, private L2 line
-  const int64_t per_line = 128 / (int64_t)elem_bytes(a.prec, true);
-  auto aligned = [&](const void* p, int64_t outer, const RowSpec& r) {
-    return ((uintptr_t)p % 128 == 0) && outer % per_line == 0 && r.lo % per_line == 0 && r.hi % per_line == 0;
-  };
-  // Out of place the NT variant is always ahead (1024^3 x pass 3.70 -> 3.63 ms at one workgroup per CU, 3.24 -> 3.19 ms at
-  // two); in place only the kernels that run two workgroups per CU gain from it (3.42 -> 3.35 ms; one per CU: 3.57 -> 3.84 ms)
-  static const int nt_mode = getenv("MFFT_NT") ? atoi(getenv("MFFT_NT")) : 1;   // 0 never, 1 by that rule, 2 always
-  const KernelEntry* ent = nullptr;
-  const bool nt_ok = a.allow_nt && nt_mode > 0 && !a.pad && aligned(a.in, a.in_outer, a.in_rows) && aligned(a.out, a.out_outer, a.out_rows);
-  if (nt_ok) {
-    ent = find_kernel(FAM_COL, a.n, a.prec, a.inverse ? 1 : 0, 1);
-    if (ent && a.in == a.out && !(ent->nt_inplace || nt_mode == 2)) ent = nullptr;
-  }
   const KernelEntry* e = nullptr;
-  if (a.mask || a.band.on) {
-    const int code = a.band.on ? 6 : 5;
-    if (!a.inverse || a.pad || (a.mask && a.band.on)) return set_error(MFFT_ERR_INVALID, "a dealias mask is applied by inverse, un-padded transforms only");
-    if (ent) {      // the same alignment rule picks the non-temporal build
-      e = find_kernel(FAM_COL, a.n, a.prec, 1, 1, code);
-      if (e && a.in == a.out && !(e->nt_inplace || nt_mode == 2)) e = nullptr;
-    }
-    if (!e) e = find_kernel(FAM_COL, a.n, a.prec, 1, 0, code);
-    if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no masked-load kernel for length %d", a.n);
-    ent = nullptr;
-  }
-  if (a.pad) {
-    if ((a.pad == 1) != a.inverse) return set_error(MFFT_ERR_INVALID, "pad-on-load is an inverse-transform mode, truncate-on-store a forward one");
-    e = find_kernel(FAM_COL, a.n, a.prec, a.inverse ? 1 : 0, 0, a.pad);
-    if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused 3/2-rule kernel for length %d", a.n);
-  }
-  // N = 3 L as three sub-transforms per workgroup (fft_col3.h; pad codes 16 + pad), plain and 3/2-rule passes.  Measured at
-  // 1536 (profiles/r04_col3_1536.txt): even with the ColFft plan in double precision (1536^3 pair 75.1 - 81.0 against 76.9 -
-  // 78.1 ms, 3/2-rule pair of 1024^3 45.5 - 47.7 against 47.9 - 48.1), ahead in single precision on the x passes (rows a whole
-  // plane apart: 9.0 -> 7.3 ms inverse, 7.5 -> 6.8 forward) and behind on the y passes (6.9 -> 7.7 - 8.1).  Default: single
-  // precision, passes without an outer batch (the x passes); MFFT_COL3=1 always, MFFT_COL3=0 never.
-  static const int col3_mode = getenv("MFFT_COL3") ? atoi(getenv("MFFT_COL3")) : -1;
-  const bool col3_on = col3_mode > 0 || (col3_mode < 0 && a.prec == MFFT_SINGLE && (a.nouter == 1 || a.thirds > 0));
-  if (col3_on && !a.mask && !a.band.on) {
-    const KernelEntry* e3 = nullptr;
-    if (nt_ok) e3 = find_kernel(FAM_COL, a.n, a.prec, a.inverse ? 1 : 0, 1, 16);              // same alignment rule, NT build
-    if (!e3) e3 = find_kernel(FAM_COL, a.n, a.prec, a.inverse ? 1 : 0, 0, 16 + a.pad);
-    if (e3) e = e3;
-  }
-  // The pad-on-load inverse with one third of a tile's transform per workgroup (fft_col3.h ColFft3S, pad code 33): out of
-  // place only (its passes are).  3/2-rule ifftn + fftn pair of 1024^3 (profiles/r04_col3s_ab.txt): double precision x pass
-  // 5.31 -> 5.16 ms, y pass 8.47 -> 9.17 (not taken); single precision x 2.99 -> 2.54, y 4.98 -> 4.35.  Default on; MFFT_COL3S=0 never.
-  static const int col3s_mode = getenv("MFFT_COL3S") ? atoi(getenv("MFFT_COL3S")) : MFFT_COL3S_DEFAULT;
-  // double precision: the passes without an outer batch only (y pass 8.4 -> 9.1 ms with it); MFFT_COL3S=2: every pass
-  if (col3s_mode > 0 && a.thirds != 0 && a.pad == 1 && a.inverse && a.in != a.out && !a.mask && !a.band.on &&
-      (col3s_mode > 1 || a.thirds > 0 || a.prec == MFFT_SINGLE || a.nouter == 1)) {
-    if (const KernelEntry* es = find_kernel(FAM_COL, a.n, a.prec, 1, 0, 33)) e = es;
-  }
-  if (!e && ent) e = ent;
-  if (!e) e = find_kernel(FAM_COL, a.n, a.prec, a.inverse ? 1 : 0, 0);
-  // Round 5: the y-pass builds (registry.h register_col_ytile, nt code 2: 64-byte tiles, LDS twiddles, two workgroups per
-  // CU) where the rows of a tile lie at most 64 KB apart on both sides -- the y passes of every decomposition; the x passes,
-  // rows a plane apart, lose with them (1440 / 1536 fp64: y 12.95 -> 9.62 / 13.74 -> 11.55 ms, x 12.85 -> 14.49 / 12.56 -> 14.41).  Not for the
-  // pruned 2/3-rule passes (their tile lists are built for the width of the general kernel).  MFFT_YTILE=0 never, 2 always.
-  static const int ytile_mode = getenv("MFFT_YTILE") ? atoi(getenv("MFFT_YTILE")) : 1;
-  if (ytile_mode > 0 && e && !a.band.on && e->family == FAM_COL && e->pad <= 5 && e->nt != 2) {
-    const int64_t es = (int64_t)elem_bytes(a.prec, true);
-    const bool near_rows = std::llabs(a.in_rows.lo) * es <= 65536 && std::llabs(a.out_rows.lo) * es <= 65536;
-    if (near_rows || ytile_mode > 1)
-      if (const KernelEntry* ey = find_kernel(FAM_COL, a.n, a.prec, a.inverse ? 1 : 0, 2, e->pad)) e = ey;
-  }
-  void* tw = nullptr;
-  if (!e) {   // no radix plan for this length: chirp-z on the next compiled length >= 2n-1
-    e = find_chirpz(FAM_COLZ, a.n, a.prec, a.inverse ? 1 : 0);
-    if (!e && big_length_ok(a.n)) return big_col(a, s);
-    if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no kernel for a complex transform of length %d", a.n);
-    void *chirp = nullptr, *bhat = nullptr;
-    MFFT_TRY(prepare_kernel(e, &tw));
-    MFFT_TRY(chirpz_tables(a.n, e->n, a.prec, &chirp, &bhat));
-    return a.prec == MFFT_DOUBLE ? launch_col_t<double, ColParamsZ<double>>(e, a, tw, s, chirp, bhat)
-                                 : launch_col_t<float, ColParamsZ<float>>(e, a, tw, s, chirp, bhat);
-  }
+  MFFT_TRY(select_col(a, &e));
+  if (!e) return big_col(a, s);
+  void *tw = nullptr, *chirp = nullptr, *bhat = nullptr;
   MFFT_TRY(prepare_kernel(e, &tw));
-  return a.prec == MFFT_DOUBLE ? launch_col_t<double>(e, a, tw, s) : launch_col_t<float>(e, a, tw, s);
+  if (e->family == FAM_COLZ) {
+    MFFT_TRY(chirpz_tables(a.n, e->n, a.prec, &chirp, &bhat));
+    return by_prec(a.prec, [&](auto t) { return launch_col_t<decltype(t), ColParamsZ<decltype(t)>>(e, a, tw, s, chirp, bhat); });
+  }
+  return by_prec(a.prec, [&](auto t) { return launch_col_t<decltype(t)>(e, a, tw, s); });
+}
+
+// ---- contiguous-axis kernels: shared pieces of their parameter blocks and launches ----
+template <class P>
+static void set_zsplit(P& p, const ZSplitArgs& zs) {
+  p.zs = zs.nchunk ? make_zsplit(zs.q, zs.nchunk, zs.last_len, zs.rows_total, zs.pitch, zs.last_pitch) : ZSplit{1, 1, 0, 0, 0, 1, 0};
+  p.row0 = zs.row0;
+}
+template <class P>
+static int launch_rows(const KernelEntry* e, const P& p, int64_t nrows, int rows_per_wg, hipStream_t s) {
+  const int64_t grid = (nrows + rows_per_wg - 1) / rows_per_wg;
+  if (grid <= 0) return 0;
+  if (grid > 0x7FFFFFFF) return set_error(MFFT_ERR_UNSUPPORTED, "grid too large");
+  e->launch(&p, (int)grid, s);
+  MFFT_HIP(hipGetLastError());
+  return 0;
 }
 
 template <typename T, class PT = RowParams<T>>
@@ -362,58 +362,43 @@ static int launch_row_t(const KernelEntry* e, const RowArgs& a, void* tw, hipStr
   P.out_stride = a.out_stride;
   P.nrows = a.nrows;
   P.scale = (T)a.scale;
-  if constexpr (std::is_same<PT, RowParams<T>>::value) {
-    P.zs = a.zs.nchunk ? make_zsplit(a.zs.q, a.zs.nchunk, a.zs.last_len, a.zs.rows_total, a.zs.pitch, a.zs.last_pitch) : ZSplit{1, 1, 0, 0, 0, 1, 0};
-    P.row0 = a.zs.row0;
-  }
-  const int64_t grid = (a.nrows + e->tile - 1) / e->tile;
-  if (grid <= 0) return 0;
-  if (grid > 0x7FFFFFFF) return set_error(MFFT_ERR_UNSUPPORTED, "grid too large");
-  e->launch(&P, (int)grid, s);
-  MFFT_HIP(hipGetLastError());
-  return 0;
+  if constexpr (std::is_same<PT, RowParams<T>>::value) set_zsplit(P, a.zs);
+  return launch_rows(e, P, a.nrows, e->tile, s);
 }
 
-int col_tile_width(int64_t n, int prec, bool inverse, int pad_code) {
-  const KernelEntry* e = find_kernel(FAM_COL, (int)n, prec, inverse ? 1 : 0, 0, pad_code);
+int col_tile_width(int64_t n, int prec, bool inverse, Op op) {
+  const KernelEntry* e = find_kernel(FAM_COL, (int)n, prec, inverse ? 1 : 0, op);
   return e ? e->tile : 0;
 }
-bool c2r_limit_supported(int64_t n, int prec) { return n >= 4 && n < 65536 && find_kernel(FAM_C2R, (int)n, prec, 1, 0, 3) != nullptr; }
-bool band_fusable(int64_t n, int prec) { return n >= 2 && n < 65536 && find_kernel(FAM_COL, (int)n, prec, 1, 0, 6) != nullptr; }
-bool mask_fusable(int64_t n, int prec) { return n >= 2 && n < 65536 && find_kernel(FAM_COL, (int)n, prec, 1, 0, 5) != nullptr; }
+bool c2r_limit_supported(int64_t n, int prec) { return n >= 4 && n < 65536 && find_kernel(FAM_C2R, (int)n, prec, 1, Op::Limited) != nullptr; }
+bool band_fusable(int64_t n, int prec) { return n >= 2 && n < 65536 && find_kernel(FAM_COL, (int)n, prec, 1, Op::Band) != nullptr; }
+bool mask_fusable(int64_t n, int prec) { return n >= 2 && n < 65536 && find_kernel(FAM_COL, (int)n, prec, 1, Op::MaskLoad) != nullptr; }
 
 bool zsplit_limit_supported(int64_t n, int prec) {
-  return n >= 2 && n < 65536 && find_kernel(FAM_R2C, (int)n, prec, 0, 0, 7) && find_kernel(FAM_C2R, (int)n, prec, 1, 0, 7);
+  return n >= 2 && n < 65536 && find_kernel(FAM_R2C, (int)n, prec, 0, Op::Limited | Op::ZChunk) && find_kernel(FAM_C2R, (int)n, prec, 1, Op::Limited | Op::ZChunk);
 }
 
 bool zsplit_supported(int64_t n, int prec, bool real_transform) {
   if (n < 2 || n > 65536) return false;
-  if (real_transform) return find_kernel(FAM_R2C, (int)n, prec, 0, 0, 4) && find_kernel(FAM_C2R, (int)n, prec, 1, 0, 4);
-  return find_kernel(FAM_ROW, (int)n, prec, 0, 0, 4) && find_kernel(FAM_ROW, (int)n, prec, 1, 0, 4);
+  if (real_transform) return find_kernel(FAM_R2C, (int)n, prec, 0, Op::ZChunk) && find_kernel(FAM_C2R, (int)n, prec, 1, Op::ZChunk);
+  return find_kernel(FAM_ROW, (int)n, prec, 0, Op::ZChunk) && find_kernel(FAM_ROW, (int)n, prec, 1, Op::ZChunk);
 }
 
 int launch_row(const RowArgs& a, hipStream_t s) {
-  if (a.zs.nchunk) {
-    const KernelEntry* ec = find_kernel(FAM_ROW, a.n, a.prec, a.inverse ? 1 : 0, 0, 4);
-    if (!ec) return set_error(MFFT_ERR_UNSUPPORTED, "no z-chunked row kernel of length %d", a.n);
-    void* twc = nullptr;
-    MFFT_TRY(prepare_kernel(ec, &twc));
-    return a.prec == MFFT_DOUBLE ? launch_row_t<double>(ec, a, twc, s) : launch_row_t<float>(ec, a, twc, s);
-  }
-  const KernelEntry* e = find_kernel(FAM_ROW, a.n, a.prec, a.inverse ? 1 : 0);
-  void* tw = nullptr;
+  const int inv = a.inverse ? 1 : 0;
+  const KernelEntry* e = find_kernel(FAM_ROW, a.n, a.prec, inv, a.zs.nchunk ? Op::ZChunk : Op::Plain);
+  if (!e && a.zs.nchunk) return set_error(MFFT_ERR_UNSUPPORTED, "no z-chunked row kernel of length %d", a.n);
+  void *tw = nullptr, *chirp = nullptr, *bhat = nullptr;
   if (!e) {
-    e = find_chirpz(FAM_ROWZ, a.n, a.prec, a.inverse ? 1 : 0);
+    e = find_chirpz(FAM_ROWZ, a.n, a.prec, inv);
     if (!e && big_length_ok(a.n)) return big_row(a, s);
     if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no kernel for a complex transform of length %d", a.n);
-    void *chirp = nullptr, *bhat = nullptr;
     MFFT_TRY(prepare_kernel(e, &tw));
     MFFT_TRY(chirpz_tables(a.n, e->n, a.prec, &chirp, &bhat));
-    return a.prec == MFFT_DOUBLE ? launch_row_t<double, RowParamsZ<double>>(e, a, tw, s, chirp, bhat)
-                                 : launch_row_t<float, RowParamsZ<float>>(e, a, tw, s, chirp, bhat);
+    return by_prec(a.prec, [&](auto t) { return launch_row_t<decltype(t), RowParamsZ<decltype(t)>>(e, a, tw, s, chirp, bhat); });
   }
   MFFT_TRY(prepare_kernel(e, &tw));
-  return a.prec == MFFT_DOUBLE ? launch_row_t<double>(e, a, tw, s) : launch_row_t<float>(e, a, tw, s);
+  return by_prec(a.prec, [&](auto t) { return launch_row_t<decltype(t)>(e, a, tw, s); });
 }
 
 template <typename T, class PT = RealParams<T>>
@@ -434,16 +419,8 @@ static int launch_real_t(const KernelEntry* e, const RealArgs& a, void* tw, void
   P.nrows = a.nrows;
   P.valid = a.valid > 0 ? a.valid : a.n / 2 + 1;
   P.scale = (T)a.scale;
-  if constexpr (std::is_same<PT, RealParams<T>>::value) {
-    P.zs = a.zs.nchunk ? make_zsplit(a.zs.q, a.zs.nchunk, a.zs.last_len, a.zs.rows_total, a.zs.pitch, a.zs.last_pitch) : ZSplit{1, 1, 0, 0, 0, 1, 0};
-    P.row0 = a.zs.row0;
-  }
-  const int64_t grid = (a.nrows + e->tile - 1) / e->tile;
-  if (grid <= 0) return 0;
-  if (grid > 0x7FFFFFFF) return set_error(MFFT_ERR_UNSUPPORTED, "grid too large");
-  e->launch(&P, (int)grid, s);
-  MFFT_HIP(hipGetLastError());
-  return 0;
+  if constexpr (std::is_same<PT, RealParams<T>>::value) set_zsplit(P, a.zs);
+  return launch_rows(e, P, a.nrows, e->tile, s);
 }
 
 // c2r kernels with the mirrors through LDS (registry.h c2r_mlds_candidate: built where they were measured ahead): taken where
@@ -470,50 +447,45 @@ static bool c2r_mlds_take(int n, int prec, bool limited) {
   if (c == 2048) return !limited && prec == MFFT_DOUBLE;
   return true;
 }
-static int launch_real(int fam, const RealArgs& a, hipStream_t s) {
-  if (a.zs.nchunk) {
-    // column-limited as well (3/2-rule: only the first `valid` of the n/2+1 bins exist, and those are what is chunked)
-    const bool lim = a.valid > 0 && a.valid < a.n / 2 + 1;
-    const KernelEntry* ec = find_kernel(fam, a.n, a.prec, fam == FAM_C2R ? 1 : 0, 0, lim ? 7 : 4);
-    if (fam == FAM_C2R && c2r_mlds_take(a.n, a.prec, lim))
-      if (const KernelEntry* em = find_kernel(fam, a.n, a.prec, 1, 1, lim ? 7 : 4)) ec = em;
-    const int64_t real_stride_c = fam == FAM_R2C ? a.in_stride : a.out_stride;
-    if (!ec || real_stride_c % 2 != 0) return set_error(MFFT_ERR_UNSUPPORTED, "no z-chunked real kernel of length %d", a.n);
-    void *twc = nullptr, *rtwc = nullptr;
-    MFFT_TRY(prepare_kernel(ec, &twc));
-    MFFT_TRY(real_twiddles(a.n, a.prec, &rtwc));
-    return a.prec == MFFT_DOUBLE ? launch_real_t<double>(ec, a, twc, rtwc, s) : launch_real_t<float>(ec, a, twc, rtwc, s);
-  }
+// Which kernel runs the real transform `a`: a radix entry of family `fam`, an entry of one of the chirp-z families, or none
+// where the scratch-buffer fallback of bigfft.hip serves the length.
+static int select_real(int fam, const RealArgs& a, const KernelEntry** out) {
+  // column-limited (3/2-rule: only the first `valid` of the n/2+1 bins exist; z-chunked, those are what is chunked)
   const bool limited = a.valid > 0 && a.valid < a.n / 2 + 1;
-  const KernelEntry* e = find_kernel(fam, a.n, a.prec, fam == FAM_C2R ? 1 : 0, 0, limited ? 3 : 0);
+  const Op op = (limited ? Op::Limited : Op::Plain) | (a.zs.nchunk ? Op::ZChunk : Op::Plain);
+  const KernelEntry* e = find_kernel(fam, a.n, a.prec, fam == FAM_C2R ? 1 : 0, op);
   if (fam == FAM_C2R && c2r_mlds_take(a.n, a.prec, limited))
-    if (const KernelEntry* em = find_kernel(fam, a.n, a.prec, 1, 1, limited ? 3 : 0)) e = em;
-  if (!e && limited) return set_error(MFFT_ERR_UNSUPPORTED, "no column-limited real kernel of length %d", a.n);
+    if (const KernelEntry* em = find_kernel(fam, a.n, a.prec, 1, op, Build::LdsMirrors)) e = em;
   // the radix kernels read a real row as (n/2) complex values: rows must stay 2-element aligned
   const int64_t real_stride = fam == FAM_R2C ? a.in_stride : a.out_stride;
-  void *tw = nullptr, *rtw = nullptr;
+  if (a.zs.nchunk && (!e || real_stride % 2 != 0)) return set_error(MFFT_ERR_UNSUPPORTED, "no z-chunked real kernel of length %d", a.n);
+  if (!e && limited) return set_error(MFFT_ERR_UNSUPPORTED, "no column-limited real kernel of length %d", a.n);
   if (!e || (real_stride % 2 != 0 && !limited)) {   // no radix plan (or an odd pitch): chirp-z on the real row
     const bool r2c = fam == FAM_R2C;
     // even length and pitch: n/2 complex values + split pass (half the convolution length); else full length
     const bool half = a.n % 2 == 0 && a.n >= 4 && real_stride % 2 == 0;
-    const int nz = half ? a.n / 2 : a.n;
-    e = find_chirpz(half ? (r2c ? FAM_R2CZH : FAM_C2RZH) : (r2c ? FAM_R2CZ : FAM_C2RZ), nz, a.prec, r2c ? 0 : 1);
-    if (!e && big_length_ok(a.n)) return big_real(!r2c, a, s);
-    if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no kernel for a real transform of length %d", a.n);
-    void *chirp = nullptr, *bhat = nullptr;
-    MFFT_TRY(prepare_kernel(e, &tw));
-    MFFT_TRY(chirpz_tables(nz, e->n, a.prec, &chirp, &bhat));
-    if (half) MFFT_TRY(real_twiddles(a.n, a.prec, &rtw));
-    RealArgs az = a;
-    az.n = a.n;
-    return a.prec == MFFT_DOUBLE ? launch_real_t<double, RealParamsZ<double>>(e, az, tw, rtw, s, chirp, bhat)
-                                 : launch_real_t<float, RealParamsZ<float>>(e, az, tw, rtw, s, chirp, bhat);
-  }
-  if (real_stride % 2 != 0)
+    e = find_chirpz(half ? (r2c ? FAM_R2CZH : FAM_C2RZH) : (r2c ? FAM_R2CZ : FAM_C2RZ), half ? a.n / 2 : a.n, a.prec, r2c ? 0 : 1);
+    if (!e && !big_length_ok(a.n)) return set_error(MFFT_ERR_UNSUPPORTED, "no kernel for a real transform of length %d", a.n);
+  } else if (real_stride % 2 != 0) {
     return set_error(MFFT_ERR_UNSUPPORTED, "real row stride %lld must be even", (long long)real_stride);
+  }
+  *out = e;
+  return 0;
+}
+static int launch_real(int fam, const RealArgs& a, hipStream_t s) {
+  const KernelEntry* e = nullptr;
+  MFFT_TRY(select_real(fam, a, &e));
+  if (!e) return big_real(fam == FAM_C2R, a, s);
+  void *tw = nullptr, *rtw = nullptr, *chirp = nullptr, *bhat = nullptr;
   MFFT_TRY(prepare_kernel(e, &tw));
+  if (e->family != fam) {
+    const bool half = e->family == FAM_R2CZH || e->family == FAM_C2RZH;
+    MFFT_TRY(chirpz_tables(half ? a.n / 2 : a.n, e->n, a.prec, &chirp, &bhat));
+    if (half) MFFT_TRY(real_twiddles(a.n, a.prec, &rtw));
+    return by_prec(a.prec, [&](auto t) { return launch_real_t<decltype(t), RealParamsZ<decltype(t)>>(e, a, tw, rtw, s, chirp, bhat); });
+  }
   MFFT_TRY(real_twiddles(a.n, a.prec, &rtw));
-  return a.prec == MFFT_DOUBLE ? launch_real_t<double>(e, a, tw, rtw, s) : launch_real_t<float>(e, a, tw, rtw, s);
+  return by_prec(a.prec, [&](auto t) { return launch_real_t<decltype(t)>(e, a, tw, rtw, s); });
 }
 
 int launch_r2c(const RealArgs& a, hipStream_t s) { return launch_real(FAM_R2C, a, s); }
@@ -521,7 +493,7 @@ int launch_c2r(const RealArgs& a, hipStream_t s) { return launch_real(FAM_C2R, a
 
 // fused nonlinear z stage (fft_nlz.h): out_f = rfft((irfft(a) x irfft(b))_f) along the contiguous axis, row by row
 bool nlz_supported(int64_t n, int prec) {
-  return n >= 2 && n < 65536 && (find_kernel(FAM_NLZ, (int)n, prec, 0) != nullptr || find_kernel(FAM_NLZ, (int)n, prec, 0, 0, 3) != nullptr);
+  return n >= 2 && n < 65536 && (find_kernel(FAM_NLZ, (int)n, prec, 0) != nullptr || find_kernel(FAM_NLZ, (int)n, prec, 0, Op::Plain, Build::Nlz3) != nullptr);
 }
 template <typename T>
 static int launch_nlz_t(const KernelEntry* e, const NlzArgs& a, void* tw, void* rt3, hipStream_t s) {
@@ -539,12 +511,7 @@ static int launch_nlz_t(const KernelEntry* e, const NlzArgs& a, void* tw, void* 
   P.valid = a.valid > 0 && a.valid < a.n / 2 + 1 ? a.valid : a.n / 2 + 1;
   P.valid_in = a.valid_in > 0 && a.valid_in < P.valid ? a.valid_in : P.valid;
   P.scale = (T)a.scale;
-  const int64_t grid = (a.nrows + 2 * e->tile - 1) / (2 * e->tile);      // a thread group works through a PAIR of rows
-  if (grid <= 0) return 0;
-  if (grid > 0x7FFFFFFF) return set_error(MFFT_ERR_UNSUPPORTED, "grid too large");
-  e->launch(&P, (int)grid, s);
-  MFFT_HIP(hipGetLastError());
-  return 0;
+  return launch_rows(e, P, a.nrows, 2 * e->tile, s);      // a thread group works through a PAIR of rows
 }
 int launch_nlz(const NlzArgs& a, hipStream_t s) {
   const KernelEntry* e = a.n < 65536 ? find_kernel(FAM_NLZ, a.n, a.prec, 0) : nullptr;
@@ -555,14 +522,14 @@ int launch_nlz(const NlzArgs& a, hipStream_t s) {
   static const int nlz3_on = getenv("MFFT_NLZ3") ? atoi(getenv("MFFT_NLZ3")) : 0;
   const bool rows3 = a.n % 3 == 0 && a.valid == a.n / 3 + 1 && a.n < 65536;
   if ((nlz3_on || !e) && rows3)
-    if (const KernelEntry* e3 = find_kernel(FAM_NLZ, a.n, a.prec, 0, 0, 3)) e = e3;
+    if (const KernelEntry* e3 = find_kernel(FAM_NLZ, a.n, a.prec, 0, Op::Plain, Build::Nlz3)) e = e3;
   if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused nonlinear z-stage kernel of length %d", a.n);
   for (int f = 0; f < 3; ++f)
     if (!a.a[f] || !a.b[f] || !a.out[f]) return set_error(MFFT_ERR_INVALID, "null argument");
   void *tw = nullptr, *rt3 = nullptr;
   MFFT_TRY(prepare_kernel(e, &tw));
-  if (e->pad == 3) MFFT_TRY(nlz3_twiddles(a.n / 3, a.prec, &rt3));
-  return a.prec == MFFT_DOUBLE ? launch_nlz_t<double>(e, a, tw, rt3, s) : launch_nlz_t<float>(e, a, tw, rt3, s);
+  if (e->build == Build::Nlz3) MFFT_TRY(nlz3_twiddles(a.n / 3, a.prec, &rt3));
+  return by_prec(a.prec, [&](auto t) { return launch_nlz_t<decltype(t)>(e, a, tw, rt3, s); });
 }
 
 // ---------------------------------------------------------------------------

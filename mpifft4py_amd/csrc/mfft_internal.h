@@ -47,11 +47,12 @@ struct ColArgs {
   double scale = 1.0;
   int remap = 1;         // XCD-aware tile order
   bool allow_nt = true;  // use the non-temporal variant when the layout is 128-byte aligned
-  int pad = 0;           // 1: input has 2n/3 physical rows (zero band skipped); 2: output truncated to 2n/3 rows
-  bool fold = false;     // pad == 2: sum the two Nyquist rows (R2C convention)
+  Op pad = Op::Plain;    // PadLoad: input has 2n/3 physical rows (zero band skipped); TruncStore: output truncated to 2n/3 rows
+                         // (mask-on-load and band-pruned passes are asked for through `mask` and `band` below)
+  bool fold = false;     // TruncStore: sum the two Nyquist rows (R2C convention)
   int64_t in_wrap = 0, in_wrap_gap = 0;   // wrapped input columns (fft_kernels.h ColParams::in_wrap): column c is read from
                                           // c + (c / in_wrap) * in_wrap_gap; radix kernels only
-  int thirds = -1;       // pad == 1 inverse: one third of a tile's transform per workgroup (ColFft3S)?  -1: launch_col's rule
+  int thirds = -1;       // PadLoad inverse: one third of a tile's transform per workgroup (ColFft3S)?  -1: launch_col's rule
                          // (single precision, or a pass without an outer batch), 1: yes where the kernel exists, 0: no
   const uint8_t* mask = nullptr;   // inverse transforms: one byte per element of `in` (same element offsets), 0 = reads as zero
                                    // (the 2/3-rule `fu * dealias` of slab.py:237-245 without a masked copy of the spectrum)
@@ -67,8 +68,8 @@ struct ColArgs {
   } band;
 };
 bool c2r_limit_supported(int64_t n, int prec);   // a c2r kernel of real length n that reads only the first `valid` bins exists
-bool band_fusable(int64_t n, int prec);
-int col_tile_width(int64_t n, int prec, bool inverse, int pad_code);   // columns per tile of the strided kernel that would run   // a pruned (band) strided inverse kernel of length n exists
+bool band_fusable(int64_t n, int prec);          // a pruned (band) strided inverse kernel of length n exists
+int col_tile_width(int64_t n, int prec, bool inverse, Op op);   // columns per tile of the default build of that strided kernel, 0: none
 int launch_col(const ColArgs& a, hipStream_t s);
 bool mask_fusable(int64_t n, int prec);   // a strided inverse kernel of length n that applies a mask on load exists
 

@@ -92,7 +92,7 @@ int mfft_plan_s::analyse_band(const uint8_t* m, int* a0, int* b0, int* a1, int* 
   if (!zero_run(f[0], a0, b0) || *a0 < 1 || !zero_run(f[1], a1, b1) || !zero_run(f[2], &z0, &z1) || z1 != (int)Nf || z0 < 1) return 0;
   *a2 = z0;
   if (P == 1) {      // x pass: tiles of the flattened (ky, kz) columns that hold a kept column, in memory order
-    const int w = col_tile_width(N0, prec, true, 6);
+    const int w = col_tile_width(N0, prec, true, Op::Band);
     if (w <= 0) return 0;
     const int64_t ncols = Np1 * Nf, ntile = (ncols + w - 1) / w;
     for (int64_t t = 0; t < ntile; ++t) {
@@ -222,9 +222,9 @@ int64_t mfft_plan_s::pad_pitch() const {
 bool mfft_plan_s::can_fuse_pad() const {
   if (!r2c || d.padsize != 1.5 || d.drop_nyquist || d.line2d) return false;
   if (N0 % 2 || N1 % 2 || 2 * M0 != 3 * N0 || 2 * M1 != 3 * N1 || 2 * M2 != 3 * N2) return false;
-  return find_kernel(FAM_COL, (int)M0, prec, 1, 0, 1) && find_kernel(FAM_COL, (int)M0, prec, 0, 0, 2) &&
-         find_kernel(FAM_COL, (int)M1, prec, 1, 0, 1) && find_kernel(FAM_COL, (int)M1, prec, 0, 0, 2) &&
-         find_kernel(FAM_R2C, (int)M2, prec, 0, 0, 3) && find_kernel(FAM_C2R, (int)M2, prec, 1, 0, 3) &&
+  return find_kernel(FAM_COL, (int)M0, prec, 1, Op::PadLoad) && find_kernel(FAM_COL, (int)M0, prec, 0, Op::TruncStore) &&
+         find_kernel(FAM_COL, (int)M1, prec, 1, Op::PadLoad) && find_kernel(FAM_COL, (int)M1, prec, 0, Op::TruncStore) &&
+         find_kernel(FAM_R2C, (int)M2, prec, 0, Op::Limited) && find_kernel(FAM_C2R, (int)M2, prec, 1, Op::Limited) &&
          getenv("MFFT_NO_PAD_FUSION") == nullptr;
 }
 
@@ -242,12 +242,12 @@ int mfft_plan_s::slab_backward_padded_fused(const void* fu, void* u) {
     const int64_t Zx = (nat_pitch() || xconv) ? Za : Nf;       // row pitch of the x pass's output
     MFFT_TRY(stage("bwd_x", 0, [&] {
       if (xconv)
-        return col_pad(fu, W0, M0, true, 1, false, N1, Nf, Nf, plain(N1 * Nf), Za, plain(N1 * Za), sc3 / (double)M0, 0, 0,
+        return col_pad(fu, W0, M0, true, Op::PadLoad, false, N1, Nf, Nf, plain(N1 * Nf), Za, plain(N1 * Za), sc3 / (double)M0, 0, 0,
                        pad_align_inv == 2 ? -1 : 1);
-      return col_pad(fu, W0, M0, true, 1, false, 1, N1 * Zx, 0, plain(N1 * Zx), 0, plain(N1 * Zx), sc3 / (double)M0);
+      return col_pad(fu, W0, M0, true, Op::PadLoad, false, 1, N1 * Zx, 0, plain(N1 * Zx), 0, plain(N1 * Zx), sc3 / (double)M0);
     }));
     MFFT_TRY(stage("bwd_y", 0, [&] {
-      return col_pad(W0, W2, M1, true, 1, false, M0, Nf, N1 * Zx, plain(Zx), M1 * Za, plain(Za), 1.0 / (double)M1);
+      return col_pad(W0, W2, M1, true, Op::PadLoad, false, M0, Nf, N1 * Zx, plain(Zx), M1 * Za, plain(Za), 1.0 / (double)M1);
     }));
     MFFT_TRY(stage("bwd_z", 0, [&] { return c2r_rows(W2, u, M0 * M1, M2, Za, M2, 1.0 / (double)M2, (int)Nf); }));
     return 0;
@@ -257,7 +257,7 @@ int mfft_plan_s::slab_backward_padded_fused(const void* fu, void* u) {
   MFFT_TRY(ensure(work[2], (size_t)(Mp0 * M1 * Nf) * es));
   void *W0 = work[0].p, *W1 = work[1].p, *W2 = work[2].p;
   MFFT_TRY(stage("bwd_x", 0, [&] {
-    return col_pad(fu, W0, M0, true, 1, false, 1, Np1 * Nf, 0, plain(Np1 * Nf), 0, plain(Np1 * Nf), sc3 / (double)M0);
+    return col_pad(fu, W0, M0, true, Op::PadLoad, false, 1, Np1 * Nf, 0, plain(Np1 * Nf), 0, plain(Np1 * Nf), sc3 / (double)M0);
   }));
   const void* yin = W0;
   RowSpec yrows = plain(Nf);
@@ -267,7 +267,7 @@ int mfft_plan_s::slab_backward_padded_fused(const void* fu, void* u) {
     yrows = two_level(Np1, Mp0 * Np1 * Nf, Nf);
   }
   MFFT_TRY(stage("bwd_y", 0, [&] {
-    return col_pad(yin, W2, M1, true, 1, false, Mp0, Nf, Np1 * Nf, yrows, M1 * Nf, plain(Nf), 1.0 / (double)M1);
+    return col_pad(yin, W2, M1, true, Op::PadLoad, false, Mp0, Nf, Np1 * Nf, yrows, M1 * Nf, plain(Nf), 1.0 / (double)M1);
   }));
   MFFT_TRY(stage("bwd_z", 0, [&] { return c2r_rows(W2, u, Mp0 * M1, M2, Nf, M2, 1.0 / (double)M2, (int)Nf); }));
   return 0;
@@ -282,13 +282,13 @@ int mfft_plan_s::slab_forward_padded_fused(const void* u, void* fu) {
     void *W0 = work[0].p, *W2 = work[2].p;
     MFFT_TRY(stage("fwd_z", 0, [&] { return r2c_rows(u, W2, M0 * M1, M2, M2, Za, 1.0, (int)Nf); }));
     MFFT_TRY(stage("fwd_y", 0, [&] {
-      return col_pad(W2, W0, M1, false, 2, true, M0, Nf, M1 * Za, plain(Za), N1 * Za, plain(Za), 1.0);
+      return col_pad(W2, W0, M1, false, Op::TruncStore, true, M0, Nf, M1 * Za, plain(Za), N1 * Za, plain(Za), 1.0);
     }));
     // pitched result (nat_pitch): whole planes of N1 * Za columns, no conversion.  Compact result: its tiles, the input
     // column c = (y, z) sits at y * Za + z (ColParams::in_wrap)
     const int64_t Zo = nat_pitch() ? Za : Nf;
     MFFT_TRY(stage("fwd_x", 0, [&] {
-      return col_pad(W0, fu, M0, false, 2, true, 1, N1 * Zo, 0, plain(N1 * Za), 0, plain(N1 * Zo), isc3, Zo == Za ? 0 : Nf, Za - Zo);
+      return col_pad(W0, fu, M0, false, Op::TruncStore, true, 1, N1 * Zo, 0, plain(N1 * Za), 0, plain(N1 * Zo), isc3, Zo == Za ? 0 : Nf, Za - Zo);
     }));
     return 0;
   }
@@ -299,7 +299,7 @@ int mfft_plan_s::slab_forward_padded_fused(const void* u, void* fu) {
   MFFT_TRY(stage("fwd_z", 0, [&] { return r2c_rows(u, W2, Mp0 * M1, M2, M2, Nf, 1.0, (int)Nf); }));
   // truncate + fold in y; P > 1: written straight into the packed (P, Mp0, Np1, Nf) send layout
   MFFT_TRY(stage("fwd_y", 0, [&] {
-    return col_pad(W2, W0, M1, false, 2, true, Mp0, Nf, M1 * Nf, plain(Nf), Np1 * Nf,
+    return col_pad(W2, W0, M1, false, Op::TruncStore, true, Mp0, Nf, M1 * Nf, plain(Nf), Np1 * Nf,
                    P > 1 ? two_level(Np1, Mp0 * Np1 * Nf, Nf) : plain(Nf), 1.0);
   }));
   void* xin = W0;
@@ -308,7 +308,7 @@ int mfft_plan_s::slab_forward_padded_fused(const void* u, void* fu) {
     xin = W1;
   }
   MFFT_TRY(stage("fwd_x", 0, [&] {
-    return col_pad(xin, fu, M0, false, 2, true, 1, Np1 * Nf, 0, plain(Np1 * Nf), 0, plain(Np1 * Nf), isc3);
+    return col_pad(xin, fu, M0, false, Op::TruncStore, true, 1, Np1 * Nf, 0, plain(Np1 * Nf), 0, plain(Np1 * Nf), isc3);
   }));
   return 0;
 }
@@ -420,7 +420,7 @@ int mfft_plan_s::pencil_backward_padded_fused(const void* fu, void* u) {
   if (X) {
     // fu (N0, N1_1, q) -> ifft x over M0 rows, the zero band never read
     MFFT_TRY(stage("bwd_x", 0, [&] {
-      return col_pad(fu, W0, M0, true, 1, false, 1, N1_1 * q, 0, plain(N1_1 * q), 0, plain(N1_1 * q), sc3 / (double)M0);
+      return col_pad(fu, W0, M0, true, Op::PadLoad, false, 1, N1_1 * q, 0, plain(N1_1 * q), 0, plain(N1_1 * q), sc3 / (double)M0);
     }));
     if (!g2solo) {
       MFFT_TRY(stage("bwd_a2a_2", 0, [&] { return xchg(1, false, true, W0, W1); }));
@@ -429,14 +429,14 @@ int mfft_plan_s::pencil_backward_padded_fused(const void* fu, void* u) {
     // cur = P1 blocks (mp, N1_1, q): gather y through the input row map, pad on load, write P2 blocks (mp, np, q)
     void* dst = other(cur);
     MFFT_TRY(stage("bwd_y", 0, [&] {
-      return col_pad(cur, dst, M1, true, 1, false, mp, q, N1_1 * q, two_level(N1_1, mp * N1_1 * q, q), np * q,
+      return col_pad(cur, dst, M1, true, Op::PadLoad, false, mp, q, N1_1 * q, two_level(N1_1, mp * N1_1 * q, q), np * q,
                      two_level(np, mp * np * q, q), 1.0 / (double)M1);
     }));
     cur = dst;
   } else {
     // fu (N2_0, N1, q) -> ifft y over M1 rows, written as P2 blocks (N2_0, np, q)
     MFFT_TRY(stage("bwd_y", 0, [&] {
-      return col_pad(fu, W0, M1, true, 1, false, N2_0, q, N1 * q, plain(q), np * q, two_level(np, N2_0 * np * q, q),
+      return col_pad(fu, W0, M1, true, Op::PadLoad, false, N2_0, q, N1 * q, plain(q), np * q, two_level(np, N2_0 * np * q, q),
                      sc3 / (double)M1);
     }));
     if (!g2solo) {
@@ -446,7 +446,7 @@ int mfft_plan_s::pencil_backward_padded_fused(const void* fu, void* u) {
     // cur = (N0, np, q) -> ifft x over M0 rows; its x chunks (mp rows) are the blocks of the next exchange
     void* dst = other(cur);
     MFFT_TRY(stage("bwd_x", 0, [&] {
-      return col_pad(cur, dst, M0, true, 1, false, 1, np * q, 0, plain(np * q), 0, plain(np * q), 1.0 / (double)M0);
+      return col_pad(cur, dst, M0, true, Op::PadLoad, false, 1, np * q, 0, plain(np * q), 0, plain(np * q), 1.0 / (double)M0);
     }));
     cur = dst;
   }
@@ -499,7 +499,7 @@ int mfft_plan_s::pencil_forward_padded_fused(const void* u, void* fu) {
     // the P1 blocks (mp, N1_1, q) of the next exchange
     void* dst = other(cur);
     MFFT_TRY(stage("fwd_y", 0, [&] {
-      return col_pad(cur, dst, M1, false, 2, true, mp, q, np * q, two_level(np, mp * np * q, q), N1_1 * q,
+      return col_pad(cur, dst, M1, false, Op::TruncStore, true, mp, q, np * q, two_level(np, mp * np * q, q), N1_1 * q,
                      two_level(N1_1, mp * N1_1 * q, q), 1.0);
     }));
     cur = dst;
@@ -509,13 +509,13 @@ int mfft_plan_s::pencil_forward_padded_fused(const void* u, void* fu) {
       cur = dst;
     }
     MFFT_TRY(stage("fwd_x", 0, [&] {
-      return col_pad(cur, fu, M0, false, 2, true, 1, N1_1 * q, 0, plain(N1_1 * q), 0, plain(N1_1 * q), isc3);
+      return col_pad(cur, fu, M0, false, Op::TruncStore, true, 1, N1_1 * q, 0, plain(N1_1 * q), 0, plain(N1_1 * q), isc3);
     }));
   } else {
     // cur = (M0, np, q): fft x, truncate + fold to (N0, np, q)
     void* dst = other(cur);
     MFFT_TRY(stage("fwd_x", 0, [&] {
-      return col_pad(cur, dst, M0, false, 2, true, 1, np * q, 0, plain(np * q), 0, plain(np * q), 1.0);
+      return col_pad(cur, dst, M0, false, Op::TruncStore, true, 1, np * q, 0, plain(np * q), 0, plain(np * q), 1.0);
     }));
     cur = dst;
     if (!g2solo) {
@@ -525,7 +525,7 @@ int mfft_plan_s::pencil_forward_padded_fused(const void* u, void* fu) {
     }
     // cur = P2 blocks (N2_0, np, q): fft y gathering over M1 rows, truncate + fold into fu (N2_0, N1, q)
     MFFT_TRY(stage("fwd_y", 0, [&] {
-      return col_pad(cur, fu, M1, false, 2, true, N2_0, q, np * q, two_level(np, N2_0 * np * q, q), N1 * q, plain(q), isc3);
+      return col_pad(cur, fu, M1, false, Op::TruncStore, true, N2_0, q, np * q, two_level(np, N2_0 * np * q, q), N1 * q, plain(q), isc3);
     }));
   }
   return 0;

@@ -85,6 +85,7 @@ struct mfft_plan_s {
   using Buf = mfft::Buf;
   using RowSpec = mfft::RowSpec;
   using ColArgs = mfft::ColArgs;
+  using Op = mfft::Op;
   using RealArgs = mfft::RealArgs;
   using RowArgs = mfft::RowArgs;
 
@@ -270,7 +271,7 @@ struct mfft_plan_s {
     a.band.on = true;
     return mfft::launch_col(a, stream);
   }
-  int col_pad(const void* in, void* out, int64_t n, bool inv, int pad, bool fold, int64_t nouter, int64_t ncols,
+  int col_pad(const void* in, void* out, int64_t n, bool inv, Op pad, bool fold, int64_t nouter, int64_t ncols,
               int64_t in_outer, RowSpec in_rows, int64_t out_outer, RowSpec out_rows, double scale, int64_t in_wrap = 0,
               int64_t in_wrap_gap = 0, int thirds = -1) {
     ColArgs a = col_args(in, out, n, inv, nouter, ncols, in_outer, in_rows, out_outer, out_rows, scale);

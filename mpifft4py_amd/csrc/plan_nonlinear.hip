@@ -126,12 +126,12 @@ int mfft_plan_s::nonlinear_cross_fused(const void* a, const void* b, void* out, 
         MFFT_TRY(col(src, dst, N0, true, N1, Nf, Zi, plain(N1 * Zi), Za, plain(N1 * Za)));
         mask_src = nullptr;
       } else if (Zi == Za && Za != Nf) {           // pitched caller rows: whole planes of N1 * Za columns
-        MFFT_TRY(col_pad(src, dst, L0, true, pad ? 1 : 0, false, 1, N1 * Za, 0, plain(N1 * Za), 0, plain(N1 * Za), sc3 / (double)L0));
+        MFFT_TRY(col_pad(src, dst, L0, true, pad ? Op::PadLoad : Op::Plain, false, 1, N1 * Za, 0, plain(N1 * Za), 0, plain(N1 * Za), sc3 / (double)L0));
       } else if (Za != Nf) {                       // one outer batch per y row: compact rows in, pitched rows out
-        MFFT_TRY(col_pad(src, dst, L0, true, pad ? 1 : 0, false, N1, Nf, Nf, plain(N1 * Nf), Za, plain(N1 * Za), sc3 / (double)L0,
+        MFFT_TRY(col_pad(src, dst, L0, true, pad ? Op::PadLoad : Op::Plain, false, N1, Nf, Nf, plain(N1 * Nf), Za, plain(N1 * Za), sc3 / (double)L0,
                          0, 0, 1));
       } else {
-        MFFT_TRY(col_pad(src, dst, L0, true, pad ? 1 : 0, false, 1, N1 * Nf, 0, plain(N1 * Nf), 0, plain(N1 * Nf), sc3 / (double)L0));
+        MFFT_TRY(col_pad(src, dst, L0, true, pad ? Op::PadLoad : Op::Plain, false, 1, N1 * Nf, 0, plain(N1 * Nf), 0, plain(N1 * Nf), sc3 / (double)L0));
       }
     }
     return 0;
@@ -148,7 +148,7 @@ int mfft_plan_s::nonlinear_cross_fused(const void* a, const void* b, void* out, 
           by.row_lo = ba1; by.row_hi = bb1; by.c_lim = ba2;
           MFFT_TRY(col_band(src, dst, N1, m, ba2, N1 * Za, plain(Za), L1 * Za, plain(Za), by));
         } else {
-          MFFT_TRY(col_pad(src, dst, L1, true, pad ? 1 : 0, false, m, Nf, N1 * Za, plain(Za), L1 * Za, plain(Za), 1.0 / (double)L1));
+          MFFT_TRY(col_pad(src, dst, L1, true, pad ? Op::PadLoad : Op::Plain, false, m, Nf, N1 * Za, plain(Za), L1 * Za, plain(Za), 1.0 / (double)L1));
         }
       }
       return 0;
@@ -158,7 +158,7 @@ int mfft_plan_s::nonlinear_cross_fused(const void* a, const void* b, void* out, 
     }));
     MFFT_TRY(stage("nl_y_fwd", 3 * (Xb + Yb) * frac, [&] {
       for (int f = 0; f < 3; ++f)
-        MFFT_TRY(col_pad(Y + (size_t)f * yelems * es, X + ((size_t)f * xelems + (size_t)(i0 * N1 * Za)) * es, L1, false, pad ? 2 : 0,
+        MFFT_TRY(col_pad(Y + (size_t)f * yelems * es, X + ((size_t)f * xelems + (size_t)(i0 * N1 * Za)) * es, L1, false, pad ? Op::TruncStore : Op::Plain,
                          pad, m, Nf, L1 * Za, plain(Za), N1 * Za, plain(Za), 1.0));
       return 0;
     }));
@@ -168,11 +168,11 @@ int mfft_plan_s::nonlinear_cross_fused(const void* a, const void* b, void* out, 
       const void* src = X + (size_t)f * xelems * es;
       void* dst = static_cast<char*>(out) + (size_t)(f * C) * es;
       if (Zi == Za && Za != Nf)                    // pitched result
-        MFFT_TRY(col_pad(src, dst, L0, false, pad ? 2 : 0, pad, 1, N1 * Za, 0, plain(N1 * Za), 0, plain(N1 * Za), 1.0 / sc3));
+        MFFT_TRY(col_pad(src, dst, L0, false, pad ? Op::TruncStore : Op::Plain, pad, 1, N1 * Za, 0, plain(N1 * Za), 0, plain(N1 * Za), 1.0 / sc3));
       else if (Za != Nf)                           // tiles of the compact result; input column (y, z) sits at y * Za + z
-        MFFT_TRY(col_pad(src, dst, L0, false, pad ? 2 : 0, pad, 1, N1 * Nf, 0, plain(N1 * Za), 0, plain(N1 * Nf), 1.0 / sc3, Nf, Za - Nf));
+        MFFT_TRY(col_pad(src, dst, L0, false, pad ? Op::TruncStore : Op::Plain, pad, 1, N1 * Nf, 0, plain(N1 * Za), 0, plain(N1 * Nf), 1.0 / sc3, Nf, Za - Nf));
       else
-        MFFT_TRY(col_pad(src, dst, L0, false, pad ? 2 : 0, pad, 1, N1 * Nf, 0, plain(N1 * Nf), 0, plain(N1 * Nf), 1.0 / sc3));
+        MFFT_TRY(col_pad(src, dst, L0, false, pad ? Op::TruncStore : Op::Plain, pad, 1, N1 * Nf, 0, plain(N1 * Nf), 0, plain(N1 * Nf), 1.0 / sc3));
     }
     return 0;
   }));
@@ -223,7 +223,7 @@ int mfft_plan_s::nonlinear_cross_fused_ranks(const void* a, const void* b, void*
         MFFT_TRY(col(src, dst, N0, true, 1, Np1 * Nf, 0, plain(Np1 * Nf), 0, plain(Np1 * Nf)));
         mask_src = nullptr;
       } else {
-        MFFT_TRY(col_pad(src, dst, L0, true, pad ? 1 : 0, false, 1, Np1 * Nf, 0, plain(Np1 * Nf), 0, plain(Np1 * Nf), sc3 / (double)L0));
+        MFFT_TRY(col_pad(src, dst, L0, true, pad ? Op::PadLoad : Op::Plain, false, 1, Np1 * Nf, 0, plain(Np1 * Nf), 0, plain(Np1 * Nf), sc3 / (double)L0));
       }
     }
     return 0;
@@ -243,7 +243,7 @@ int mfft_plan_s::nonlinear_cross_fused_ranks(const void* a, const void* b, void*
           MFFT_TRY(col(R + ((size_t)f * xelems + (size_t)(i0 * Np1 * ap)) * es, Y + (size_t)f * yelems * es, N1, true, m, a2, Np1 * ap,
                        two_level(Np1, Np0 * Np1 * ap, ap), L1 * Za, plain(Za)));
         else
-          MFFT_TRY(col_pad(R + ((size_t)f * xelems + (size_t)(i0 * Np1 * Nf)) * es, Y + (size_t)f * yelems * es, L1, true, pad ? 1 : 0,
+          MFFT_TRY(col_pad(R + ((size_t)f * xelems + (size_t)(i0 * Np1 * Nf)) * es, Y + (size_t)f * yelems * es, L1, true, pad ? Op::PadLoad : Op::Plain,
                            false, m, Nf, Np1 * Nf, two_level(Np1, Lp0 * Np1 * Nf, Nf), L1 * Za, plain(Za), 1.0 / (double)L1));
       }
       return 0;
@@ -253,7 +253,7 @@ int mfft_plan_s::nonlinear_cross_fused_ranks(const void* a, const void* b, void*
     }));
     MFFT_TRY(stage("nl_y_fwd", 0, [&] {      // truncate + fold in y, straight into the packed (P, Lp0, S) send layout
       for (int f = 0; f < 3; ++f)
-        MFFT_TRY(col_pad(Y + (size_t)f * yelems * es, X + ((size_t)f * xelems + (size_t)(i0 * S)) * es, L1, false, pad ? 2 : 0, pad, m,
+        MFFT_TRY(col_pad(Y + (size_t)f * yelems * es, X + ((size_t)f * xelems + (size_t)(i0 * S)) * es, L1, false, pad ? Op::TruncStore : Op::Plain, pad, m,
                          Nf, L1 * Za, plain(Za), S, two_level(Np1, Lp0 * S, Nf), 1.0));
       return 0;
     }));
@@ -264,7 +264,7 @@ int mfft_plan_s::nonlinear_cross_fused_ranks(const void* a, const void* b, void*
   }));
   MFFT_TRY(stage("nl_x_fwd", 0, [&] {
     for (int f = 0; f < 3; ++f)
-      MFFT_TRY(col_pad(R + (size_t)f * xelems * es, static_cast<char*>(out) + (size_t)(f * C) * es, L0, false, pad ? 2 : 0, pad, 1,
+      MFFT_TRY(col_pad(R + (size_t)f * xelems * es, static_cast<char*>(out) + (size_t)(f * C) * es, L0, false, pad ? Op::TruncStore : Op::Plain, pad, 1,
                        Np1 * Nf, 0, plain(S), 0, plain(Np1 * Nf), 1.0 / sc3));
     return 0;
   }));

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 #include "fft_kernels.h"
 #include "fft_chirpz.h"
@@ -19,15 +20,42 @@ enum Family {
   FAM_NLZ = 10                     // fused nonlinear z stage (fft_nlz.h): entry.n is the REAL length of a z row, tile = row PAIRS per workgroup
 };
 
+// What a kernel computes beyond the plain transform: what the caller asks for.
+enum class Op : unsigned {
+  Plain = 0,
+  // FAM_COL, one of (the values are ColFft's PAD parameter):
+  PadLoad = 1,      // inverse: the input has 2n/3 physical rows, the zero band is skipped (3/2-rule)
+  TruncStore = 2,   // forward: the output is truncated to 2n/3 rows (3/2-rule)
+  MaskLoad = 3,     // inverse: the dealias mask is applied on load (2/3-rule)
+  Band = 4,         // inverse: band-pruned 2/3-rule pass
+  // FAM_ROW / FAM_R2C / FAM_C2R, flags (Limited | ZChunk: the 3/2-rule pencils):
+  Limited = 8,      // column-limited (3/2-rule, pruned 2/3-rule)
+  ZChunk = 16,      // complex side split into z chunks (fused pencil pack / unpack)
+  TopFlag = ZChunk
+};
+constexpr Op operator|(Op a, Op b) { return (Op)((unsigned)a | (unsigned)b); }
+constexpr bool has(Op a, Op flag) { return ((unsigned)a & (unsigned)flag) != 0; }
+// Which implementation of that operation an entry is: what the launch rules of core.hip choose between.
+enum class Build : unsigned {
+  Default = 0,
+  NonTemporal,      // COL: non-temporal accesses (128-byte aligned rows only)
+  YTile,            // COL: y-pass build, 64-byte tiles (register_col_ytile)
+  Col3,             // COL: ColFft3 (fft_col3.h)
+  Col3NT,           // COL: ColFft3 with non-temporal accesses
+  Col3Thirds,       // COL: ColFft3S, one third of a tile's transform per workgroup
+  LdsMirrors,       // C2R: mirrored bins through LDS instead of a second load
+  Nlz3,             // NLZ: Nlz3Fft (fft_nlz.h)
+  Last = Nlz3
+};
+
 struct KernelEntry {
   int family;
   int n;            // transform length (R2C/C2R: the REAL length)
   int prec;         // 0 single, 1 double
   int inv;          // COL/ROW: 1 = inverse
-  int nt;           // COL: 1 = non-temporal variant (128-byte aligned rows only)
-  int nt_inplace;   // COL, nt = 1: also faster than the regular variant when the transform is in place
-  int pad;          // COL: 1 = zero-padded input (inverse), 2 = truncated output (forward); ROW / R2C / C2R: 3 = column-limited
-                    // (3/2-rule), 4 = complex side split into z chunks (fused pencil pack / unpack), 7 = both (3/2-rule pencils)
+  Op op;
+  Build build;
+  int nt_inplace;   // COL, non-temporal builds: also faster than the regular build when the transform is in place
   int tile;         // COLS (COL) or ROWS (others)
   int threads;
   int lds_bytes;
@@ -40,7 +68,7 @@ struct KernelEntry {
 };
 
 std::vector<KernelEntry>& kernel_registry();
-const KernelEntry* find_kernel(int family, int n, int prec, int inv, int nt = 0, int pad = 0);
+const KernelEntry* find_kernel(int family, int n, int prec, int inv, Op op = Op::Plain, Build build = Build::Default);
 // chirp-z kernel with the smallest convolution length M >= 2n-1 (nullptr: n too long)
 const KernelEntry* find_chirpz(int family, int n, int prec, int inv);
 
@@ -259,28 +287,33 @@ void tw_thunk(void* dst) {
   memcpy(dst, v.data(), v.size() * sizeof(cx<T>));
 }
 
+// (the ColFft3 kernels have a table of their own: tw_count, build_tw)
 template <class K, class P, class S, typename T, int WGS = 0>
-KernelEntry make_entry(int family, int n, int inv, int tile, const char* name) {
+KernelEntry make_entry(int family, int n, int inv, Op op, Build build, int tile, const char* name, bool nt_inplace = false,
+                       int tw_count = S::TW, void (*build_tw)(void*) = &tw_thunk<S, T>) {
   KernelEntry e;
   e.family = family;
   e.n = n;
   e.prec = sizeof(T) == 8 ? 1 : 0;
   e.inv = inv;
-  e.nt = 0;
-  e.nt_inplace = 0;
-  e.pad = 0;
+  e.op = op;
+  e.build = build;
+  e.nt_inplace = nt_inplace ? 1 : 0;
   e.tile = tile;
   e.threads = K::THREADS;
   e.lds_bytes = K::LDS_BYTES;
-  e.tw_count = S::TW;
-  e.grid_mult = 1;
-  e.build_tw = &tw_thunk<S, T>;
+  e.tw_count = tw_count;
+  e.grid_mult = build == Build::Col3Thirds ? 3 : 1;
+  e.build_tw = build_tw;
   e.launch = &launch_thunk<K, P, WGS>;
   if constexpr (WGS > 1) e.func = reinterpret_cast<const void*>(&mfft_kern_occ<K, P, WGS>);
   else e.func = reinterpret_cast<const void*>(&mfft_kern<K, P>);
   e.name = name;
   return e;
 }
+// a compile-time value as a function argument: the registration lambdas below take their template arguments this way
+template <auto V> inline constexpr std::integral_constant<decltype(V), V> tag{};
+template <class K> struct type_tag { using type = K; };
 
 // (the masked-load / pruned 2/3-rule variants of the plans capped in round 5 hold 10 - 40 registers more than the plain
 // kernels: under the same cap they would spill 100 - 170 bytes, so they keep the compiler's allocation)
@@ -306,43 +339,29 @@ void register_col(const char* name) {
   constexpr bool CT = col_twlds<S, T>() || col_narrow_f32<S, T>() || (sizeof(T) == 4 && S::N == 1536 && W == 3);
   constexpr bool CS = col_split<S, T>() || (W > 1 && (long long)S::N * C * (int)sizeof(cx<T>) * col_wgs_count(W) > 163840);
   constexpr int CV = col_narrow_f32<S, T>() ? 1 : col_vec<S, T>();
-  reg.push_back(make_entry<ColFft<S, T, C, false, CT, CS, CV>, ColParams<T>, S, T, W>(FAM_COL, S::N, 0, C, name));
-  reg.push_back(make_entry<ColFft<S, T, C, true, CT, CS, CV>, ColParams<T>, S, T, W>(FAM_COL, S::N, 1, C, name));
-  if constexpr (S::E % 3 == 0 && S::N >= 6) {   // 3/2-rule lengths: pad-on-load (inverse) / truncate-on-store (forward)
-    reg.push_back(make_entry<ColFft<S, T, C, true, CT, CS, CV, false, 1>, ColParams<T>, S, T, W>(FAM_COL, S::N, 1, C, name));
-    reg.back().pad = 1;
-    reg.push_back(make_entry<ColFft<S, T, C, false, CT, CS, CV, false, 2>, ColParams<T>, S, T, W>(FAM_COL, S::N, 0, C, name));
-    reg.back().pad = 2;
+  constexpr bool NIP = col_pair<S, T>() && S::N != 512;      // non-temporal in place too
+  auto add = [&](auto inv, auto op, auto nt, auto wgs) {
+    constexpr bool INV = decltype(inv)::value, NT = decltype(nt)::value;
+    constexpr Op OP = decltype(op)::value;
+    if constexpr (!NT || col_has_nt<S, T>())      // aligned-row (non-temporal) builds
+      reg.push_back(make_entry<ColFft<S, T, C, INV, CT, CS, CV, NT, (int)OP>, ColParams<T>, S, T, decltype(wgs)::value>(
+          FAM_COL, S::N, INV, OP, NT ? Build::NonTemporal : Build::Default, C, name, NT && NIP));
+  };
+  add(tag<false>, tag<Op::Plain>, tag<false>, tag<W>);
+  add(tag<true>, tag<Op::Plain>, tag<false>, tag<W>);
+  if constexpr (S::E % 3 == 0 && S::N >= 6) {   // 3/2-rule lengths
+    add(tag<true>, tag<Op::PadLoad>, tag<false>, tag<W>);
+    add(tag<false>, tag<Op::TruncStore>, tag<false>, tag<W>);
   }
-  // 2/3-rule: inverse transform with the dealias mask applied on load (pad = 5)
-  reg.push_back(make_entry<ColFft<S, T, C, true, CT, CS, CV, false, 3>, ColParams<T>, S, T, WM>(FAM_COL, S::N, 1, C, name));
-  reg.back().pad = 5;
-  if constexpr (col_has_nt<S, T>()) {
-    reg.push_back(make_entry<ColFft<S, T, C, true, CT, CS, CV, true, 3>, ColParams<T>, S, T, WM>(FAM_COL, S::N, 1, C, name));
-    reg.back().pad = 5;
-    reg.back().nt = 1;
-    reg.back().nt_inplace = (col_pair<S, T>() && S::N != 512) ? 1 : 0;
-  }
-  // pruned 2/3-rule passes (pad = 6)
-  reg.push_back(make_entry<ColFft<S, T, C, true, CT, CS, CV, false, 4>, ColParams<T>, S, T, WM>(FAM_COL, S::N, 1, C, name));
-  reg.back().pad = 6;
-  if constexpr (col_has_nt<S, T>()) {
-    reg.push_back(make_entry<ColFft<S, T, C, true, CT, CS, CV, true, 4>, ColParams<T>, S, T, WM>(FAM_COL, S::N, 1, C, name));
-    reg.back().pad = 6;
-    reg.back().nt = 1;
-    reg.back().nt_inplace = (col_pair<S, T>() && S::N != 512) ? 1 : 0;
-  }
-  if constexpr (col_has_nt<S, T>()) {     // aligned-row (non-temporal) variants
-    reg.push_back(make_entry<ColFft<S, T, C, false, CT, CS, CV, true>, ColParams<T>, S, T, W>(FAM_COL, S::N, 0, C, name));
-    reg.back().nt = 1;
-    reg.back().nt_inplace = (col_pair<S, T>() && S::N != 512) ? 1 : 0;
-    reg.push_back(make_entry<ColFft<S, T, C, true, CT, CS, CV, true>, ColParams<T>, S, T, W>(FAM_COL, S::N, 1, C, name));
-    reg.back().nt = 1;
-    reg.back().nt_inplace = (col_pair<S, T>() && S::N != 512) ? 1 : 0;
-  }
+  add(tag<true>, tag<Op::MaskLoad>, tag<false>, tag<WM>);     // 2/3-rule
+  add(tag<true>, tag<Op::MaskLoad>, tag<true>, tag<WM>);
+  add(tag<true>, tag<Op::Band>, tag<false>, tag<WM>);         // pruned 2/3-rule passes
+  add(tag<true>, tag<Op::Band>, tag<true>, tag<WM>);
+  add(tag<false>, tag<Op::Plain>, tag<true>, tag<W>);
+  add(tag<true>, tag<Op::Plain>, tag<true>, tag<W>);
 }
 
-// Round 5, y-pass builds (KernelEntry::nt == 2; core.hip launch_col takes them when the rows of a tile lie at most 64 KB
+// Round 5, y-pass builds (Build::YTile; core.hip select_col takes them when the rows of a tile lie at most 64 KB
 // apart): 64-byte tiles with LDS twiddles, two workgroups per CU by LDS alone (3 - 4 waves each, so the dispatcher's rule
 // leaves them 256 registers).  kbench3 tw64, double precision, y in place / x in place / x out of place, ms:
 //   1440  12.95 / 12.85 / 13.43 -> 9.62 / 14.49 / 14.39        1536  13.74 / 12.56 / 13.37 -> 11.55 / 14.41 / 14.04
@@ -361,50 +380,28 @@ void register_col_ytile(const char* name) {
   if constexpr (col_ytile<S, T>()) {
     auto& reg = kernel_registry();
     constexpr int C = 64 / (int)sizeof(cx<T>);
-    auto add = [&](KernelEntry e, int pad) {
-      e.nt = 2;
-      e.pad = pad;
-      reg.push_back(e);
+    auto add = [&](auto inv, auto op) {
+      constexpr bool INV = decltype(inv)::value;
+      constexpr Op OP = decltype(op)::value;
+      reg.push_back(make_entry<ColFft<S, T, C, INV, true, 1, 1, false, (int)OP>, ColParams<T>, S, T>(FAM_COL, S::N, INV, OP, Build::YTile, C, name));
     };
-    add(make_entry<ColFft<S, T, C, false, true, 1, 1>, ColParams<T>, S, T>(FAM_COL, S::N, 0, C, name), 0);
-    add(make_entry<ColFft<S, T, C, true, true, 1, 1>, ColParams<T>, S, T>(FAM_COL, S::N, 1, C, name), 0);
+    add(tag<false>, tag<Op::Plain>);
+    add(tag<true>, tag<Op::Plain>);
     if constexpr (S::E % 3 == 0) {
-      add(make_entry<ColFft<S, T, C, true, true, 1, 1, false, 1>, ColParams<T>, S, T>(FAM_COL, S::N, 1, C, name), 1);
-      add(make_entry<ColFft<S, T, C, false, true, 1, 1, false, 2>, ColParams<T>, S, T>(FAM_COL, S::N, 0, C, name), 2);
+      add(tag<true>, tag<Op::PadLoad>);
+      add(tag<false>, tag<Op::TruncStore>);
     }
-    add(make_entry<ColFft<S, T, C, true, true, 1, 1, false, 3>, ColParams<T>, S, T>(FAM_COL, S::N, 1, C, name), 5);
+    add(tag<true>, tag<Op::MaskLoad>);
   }
 }
 
-// ColFft3 (fft_col3.h): N = 3 L as three sub-transforms of the plan SL.  Registered under pad codes 16 (plain), 17 (pad
-// on load, inverse), 18 (truncate on store, forward): launch_col chooses between them and the ColFft kernels of the same
+// ColFft3 (fft_col3.h): N = 3 L as three sub-transforms of the plan SL.  Registered as Build::Col3 (plain, pad on load,
+// truncate on store) and Build::Col3NT (plain): select_col chooses between them and the ColFft kernels of the same
 // length (MFFT_COL3=0 / 1 force either in the same process).
 template <class SL, typename T>
 void tw3_thunk(void* dst) {
   auto v = build_col3_twiddles<SL, T>();
   memcpy(dst, v.data(), v.size() * sizeof(cx<T>));
-}
-template <class K, class SL, typename T, int WGS>
-KernelEntry make_entry3(int inv, int nt, int pad, int tile, const char* name) {
-  KernelEntry e;
-  e.family = FAM_COL;
-  e.n = 3 * SL::N;
-  e.prec = sizeof(T) == 8 ? 1 : 0;
-  e.inv = inv;
-  e.nt = nt;
-  e.nt_inplace = nt;                    // two workgroups per CU (or 1024 threads): non-temporal in place too
-  e.pad = pad;
-  e.tile = tile;
-  e.threads = K::THREADS;
-  e.lds_bytes = K::LDS_BYTES;
-  e.tw_count = K::TW;
-  e.grid_mult = 1;
-  e.build_tw = &tw3_thunk<SL, T>;
-  e.launch = &launch_thunk<K, ColParams<T>, WGS>;
-  if constexpr (WGS > 1) e.func = reinterpret_cast<const void*>(&mfft_kern_occ<K, ColParams<T>, WGS>);
-  else e.func = reinterpret_cast<const void*>(&mfft_kern<K, ColParams<T>>);
-  e.name = name;
-  return e;
 }
 template <class SL, typename T>
 void register_col3(const char* name) {
@@ -415,16 +412,21 @@ void register_col3(const char* name) {
   // whole-complex exchange while two workgroups of it (and their twiddles) fit the CU's 160 KB, else real / imaginary parts
   constexpr int SPL = ((long long)SL::N * C * (int)sizeof(cx<T>) + SL::TW * (int)sizeof(cx<T>) <= 81920) ? 0 : 1;
   constexpr int W = THR <= 512 ? 2 : 0;                           // register cap for two workgroups per CU
-  reg.push_back(make_entry3<ColFft3<SL, T, C, false, true, SPL, VEC, false, 0>, SL, T, W>(0, 0, 16, C, name));
-  reg.push_back(make_entry3<ColFft3<SL, T, C, true, true, SPL, VEC, false, 0>, SL, T, W>(1, 0, 16, C, name));
-  reg.push_back(make_entry3<ColFft3<SL, T, C, false, true, SPL, VEC, true, 0>, SL, T, W>(0, 1, 16, C, name));
-  reg.push_back(make_entry3<ColFft3<SL, T, C, true, true, SPL, VEC, true, 0>, SL, T, W>(1, 1, 16, C, name));
-  reg.push_back(make_entry3<ColFft3<SL, T, C, true, true, SPL, VEC, false, 1>, SL, T, W>(1, 0, 17, C, name));
-  reg.push_back(make_entry3<ColFft3<SL, T, C, false, true, SPL, VEC, false, 2>, SL, T, W>(0, 0, 18, C, name));
-  // pad code 33: the pad-on-load inverse with one third of a tile's transform per workgroup (ColFft3S), registers capped for
+  auto add = [&](auto kernel, auto wgs, int inv, Op op, Build build) {
+    using K = typename decltype(kernel)::type;
+    // two workgroups per CU (or 1024 threads): non-temporal in place too
+    reg.push_back(make_entry<K, ColParams<T>, SL, T, decltype(wgs)::value>(FAM_COL, 3 * SL::N, inv, op, build, C, name, build == Build::Col3NT,
+                                                                           K::TW, &tw3_thunk<SL, T>));
+  };
+  add(type_tag<ColFft3<SL, T, C, false, true, SPL, VEC, false, 0>>{}, tag<W>, 0, Op::Plain, Build::Col3);
+  add(type_tag<ColFft3<SL, T, C, true, true, SPL, VEC, false, 0>>{}, tag<W>, 1, Op::Plain, Build::Col3);
+  add(type_tag<ColFft3<SL, T, C, false, true, SPL, VEC, true, 0>>{}, tag<W>, 0, Op::Plain, Build::Col3NT);
+  add(type_tag<ColFft3<SL, T, C, true, true, SPL, VEC, true, 0>>{}, tag<W>, 1, Op::Plain, Build::Col3NT);
+  add(type_tag<ColFft3<SL, T, C, true, true, SPL, VEC, false, 1>>{}, tag<W>, 1, Op::PadLoad, Build::Col3);
+  add(type_tag<ColFft3<SL, T, C, false, true, SPL, VEC, false, 2>>{}, tag<W>, 0, Op::TruncStore, Build::Col3);
+  // the pad-on-load inverse with one third of a tile's transform per workgroup (ColFft3S), registers capped for
   // two workgroups per CU (1024 threads at L = 512: 64 VGPRs, what the length-L ColFft kernel runs with)
-  reg.push_back(make_entry3<ColFft3S<SL, T, C, true, true, SPL, VEC, false, 1>, SL, T, 2>(1, 0, 33, C, name));
-  reg.back().grid_mult = 3;
+  add(type_tag<ColFft3S<SL, T, C, true, true, SPL, VEC, false, 1>>{}, tag<2>, 1, Op::PadLoad, Build::Col3Thirds);
 }
 
 // Register cap of the contiguous-axis kernels: the 30-values-per-thread plans in double precision come out at 256 VGPRs plus
@@ -554,49 +556,49 @@ void register_rows(const char* name) {
   constexpr int WOC5 = row_occ_r5<S, T, 2>(c2r_threads<S, T>());       // plain c2r only
   constexpr bool SC = row_split<S, T, true>();
   constexpr bool RTC = row_twlds<S, T, true>();
-  reg.push_back(make_entry<RowFft<S, T, R, false, RT, false, SP>, RowParams<T>, S, T, WO5>(FAM_ROW, S::N, 0, R, name));
-  reg.push_back(make_entry<RowFft<S, T, R, true, RT, false, SP>, RowParams<T>, S, T, WO5>(FAM_ROW, S::N, 1, R, name));
-  reg.push_back(make_entry<R2CFft<S, T, RR, RT, false, false, SP, WPR>, RealParams<T>, S, T, WOR5>(FAM_R2C, 2 * S::N, 0, RR, name));
-  reg.push_back(make_entry<C2RFft<S, T, RC, RTC, false, false, SC, WPC>, RealParams<T>, S, T, (WOC5 ? WOC5 : WOC)>(FAM_C2R, 2 * S::N, 1, RC, name));
-  // pencil decompositions: the z-chunk pack / unpack fused into the stores / loads (pad = 4)
-  reg.push_back(make_entry<RowFft<S, T, R, false, RT, true, SP>, RowParams<T>, S, T, WO>(FAM_ROW, S::N, 0, R, name));
-  reg.back().pad = 4;
-  reg.push_back(make_entry<RowFft<S, T, R, true, RT, true, SP>, RowParams<T>, S, T, WO>(FAM_ROW, S::N, 1, R, name));
-  reg.back().pad = 4;
-  reg.push_back(make_entry<R2CFft<S, T, RR, RT, false, true, SP, WPR>, RealParams<T>, S, T, WOR>(FAM_R2C, 2 * S::N, 0, RR, name));
-  reg.back().pad = 4;
-  reg.push_back(make_entry<C2RFft<S, T, RC, RTC, false, true, SC, WPC>, RealParams<T>, S, T, WOV>(FAM_C2R, 2 * S::N, 1, RC, name));
-  reg.back().pad = 4;
-  if constexpr (S::N % 3 == 0 && S::N >= 6) {   // 3/2-rule lengths: column-limited real transforms (pad = 3)
-    reg.push_back(make_entry<R2CFft<S, T, RR, RT, true, false, SP, WPR>, RealParams<T>, S, T, WOR>(FAM_R2C, 2 * S::N, 0, RR, name));
-    reg.back().pad = 3;
-    // ... and with the kept columns split into the z chunks of the pencils' exchange (pad = 7): the 3/2-rule pencil
+  constexpr Op LZ = Op::Limited | Op::ZChunk;
+  auto row = [&](auto inv, auto op, auto wgs) {
+    constexpr bool INV = decltype(inv)::value;
+    constexpr Op OP = decltype(op)::value;
+    reg.push_back(make_entry<RowFft<S, T, R, INV, RT, has(OP, Op::ZChunk), SP>, RowParams<T>, S, T, decltype(wgs)::value>(
+        FAM_ROW, S::N, INV, OP, Build::Default, R, name));
+  };
+  auto r2c = [&](auto op, auto wgs) {
+    constexpr Op OP = decltype(op)::value;
+    reg.push_back(make_entry<R2CFft<S, T, RR, RT, has(OP, Op::Limited), has(OP, Op::ZChunk), SP, WPR>, RealParams<T>, S, T, decltype(wgs)::value>(
+        FAM_R2C, 2 * S::N, 0, OP, Build::Default, RR, name));
+  };
+  auto c2r = [&](auto op, auto mlds, auto wgs) {      // (the LDS-mirror builds are never wave-packed: c2r_mlds_candidate)
+    constexpr Op OP = decltype(op)::value;
+    constexpr bool MLDS = decltype(mlds)::value;
+    reg.push_back(make_entry<C2RFft<S, T, RC, RTC, has(OP, Op::Limited), has(OP, Op::ZChunk), SC, MLDS ? false : WPC, MLDS>, RealParams<T>, S, T,
+                             decltype(wgs)::value>(FAM_C2R, 2 * S::N, 1, OP, MLDS ? Build::LdsMirrors : Build::Default, RC, name));
+  };
+  row(tag<false>, tag<Op::Plain>, tag<WO5>);
+  row(tag<true>, tag<Op::Plain>, tag<WO5>);
+  r2c(tag<Op::Plain>, tag<WOR5>);
+  c2r(tag<Op::Plain>, tag<false>, tag<(WOC5 ? WOC5 : WOC)>);
+  // pencil decompositions: the z-chunk pack / unpack fused into the stores / loads
+  row(tag<false>, tag<Op::ZChunk>, tag<WO>);
+  row(tag<true>, tag<Op::ZChunk>, tag<WO>);
+  r2c(tag<Op::ZChunk>, tag<WOR>);
+  c2r(tag<Op::ZChunk>, tag<false>, tag<WOV>);
+  if constexpr (S::N % 3 == 0 && S::N >= 6) {   // 3/2-rule lengths: column-limited real transforms
+    r2c(tag<Op::Limited>, tag<WOR>);
+    // ... and with the kept columns split into the z chunks of the pencils' exchange: the 3/2-rule pencil
     // transforms write / read the exchange blocks themselves (pencil.py:511-632, 758-883 do it in the MPI datatypes)
-    reg.push_back(make_entry<R2CFft<S, T, RR, RT, true, true, SP, WPR>, RealParams<T>, S, T, WOR>(FAM_R2C, 2 * S::N, 0, RR, name));
-    reg.back().pad = 7;
-    reg.push_back(make_entry<C2RFft<S, T, RC, RTC, true, true, SC, WPC>, RealParams<T>, S, T, WOV>(FAM_C2R, 2 * S::N, 1, RC, name));
-    reg.back().pad = 7;
+    r2c(tag<LZ>, tag<WOR>);
+    c2r(tag<LZ>, tag<false>, tag<WOV>);
   }
-  if constexpr (S::N >= 4) {                    // column-limited c2r: 3/2-rule lengths and the pruned 2/3-rule (any length)
-    reg.push_back(make_entry<C2RFft<S, T, RC, RTC, true, false, SC, WPC>, RealParams<T>, S, T, WOV>(FAM_C2R, 2 * S::N, 1, RC, name));
-    reg.back().pad = 3;
-  }
+  if constexpr (S::N >= 4)                      // column-limited c2r: 3/2-rule lengths and the pruned 2/3-rule (any length)
+    c2r(tag<Op::Limited>, tag<false>, tag<WOV>);
   // Round 6: c2r kernels that no wave shuffle serves, with the mirrors through LDS instead of a second load (C2RFft MLDS;
-  // KernelEntry::nt = 1; core.hip launch_real takes them where they exist, MFFT_C2R_MLDS=0: never)
+  // Build::LdsMirrors; core.hip select_real takes them where they exist, MFFT_C2R_MLDS=0: never)
   if constexpr (c2r_mlds_candidate<S, T>()) {
-    reg.push_back(make_entry<C2RFft<S, T, RC, RTC, false, false, SC, false, true>, RealParams<T>, S, T, WOC>(FAM_C2R, 2 * S::N, 1, RC, name));
-    reg.back().nt = 1;
-    reg.push_back(make_entry<C2RFft<S, T, RC, RTC, false, true, SC, false, true>, RealParams<T>, S, T, WOV>(FAM_C2R, 2 * S::N, 1, RC, name));
-    reg.back().nt = 1;
-    reg.back().pad = 4;
-    reg.push_back(make_entry<C2RFft<S, T, RC, RTC, true, false, SC, false, true>, RealParams<T>, S, T, WOV>(FAM_C2R, 2 * S::N, 1, RC, name));
-    reg.back().nt = 1;
-    reg.back().pad = 3;
-    if constexpr (S::N % 3 == 0 && S::N >= 6) {
-      reg.push_back(make_entry<C2RFft<S, T, RC, RTC, true, true, SC, false, true>, RealParams<T>, S, T, WOV>(FAM_C2R, 2 * S::N, 1, RC, name));
-      reg.back().nt = 1;
-      reg.back().pad = 7;
-    }
+    c2r(tag<Op::Plain>, tag<true>, tag<WOC>);
+    c2r(tag<Op::ZChunk>, tag<true>, tag<WOV>);
+    c2r(tag<Op::Limited>, tag<true>, tag<WOV>);
+    if constexpr (S::N % 3 == 0 && S::N >= 6) c2r(tag<LZ>, tag<true>, tag<WOV>);
   }
 }
 
@@ -622,8 +624,8 @@ void register_col_z(const char* name) {
     constexpr int C = colz_cols<S, T>();
     constexpr bool CS = colz_split<S, T>();
     constexpr int CV = col_vec<S, T>();
-    reg.push_back(make_entry<ColFftZ<S, T, C, false, CS, CV>, ColParamsZ<T>, S, T>(FAM_COLZ, S::N, 0, C, name));
-    reg.push_back(make_entry<ColFftZ<S, T, C, true, CS, CV>, ColParamsZ<T>, S, T>(FAM_COLZ, S::N, 1, C, name));
+    reg.push_back(make_entry<ColFftZ<S, T, C, false, CS, CV>, ColParamsZ<T>, S, T>(FAM_COLZ, S::N, 0, Op::Plain, Build::Default, C, name));
+    reg.push_back(make_entry<ColFftZ<S, T, C, true, CS, CV>, ColParamsZ<T>, S, T>(FAM_COLZ, S::N, 1, Op::Plain, Build::Default, C, name));
   }
 }
 template <class S, typename T>
@@ -631,12 +633,12 @@ void register_rows_z(const char* name) {
   if constexpr (S::N >= 16) {
     auto& reg = kernel_registry();
     constexpr int R = row_rows_n<S, T, false>();     // the chirp-z kernels exchange whole complex values
-    reg.push_back(make_entry<RowFftZ<S, T, R, 0, false>, RowParamsZ<T>, S, T>(FAM_ROWZ, S::N, 0, R, name));
-    reg.push_back(make_entry<RowFftZ<S, T, R, 0, true>, RowParamsZ<T>, S, T>(FAM_ROWZ, S::N, 1, R, name));
-    reg.push_back(make_entry<RowFftZ<S, T, R, 1, false>, RealParamsZ<T>, S, T>(FAM_R2CZ, S::N, 0, R, name));
-    reg.push_back(make_entry<RowFftZ<S, T, R, 2, true>, RealParamsZ<T>, S, T>(FAM_C2RZ, S::N, 1, R, name));
-    reg.push_back(make_entry<RowFftZ<S, T, R, 3, false>, RealParamsZ<T>, S, T>(FAM_R2CZH, S::N, 0, R, name));
-    reg.push_back(make_entry<RowFftZ<S, T, R, 4, true>, RealParamsZ<T>, S, T>(FAM_C2RZH, S::N, 1, R, name));
+    reg.push_back(make_entry<RowFftZ<S, T, R, 0, false>, RowParamsZ<T>, S, T>(FAM_ROWZ, S::N, 0, Op::Plain, Build::Default, R, name));
+    reg.push_back(make_entry<RowFftZ<S, T, R, 0, true>, RowParamsZ<T>, S, T>(FAM_ROWZ, S::N, 1, Op::Plain, Build::Default, R, name));
+    reg.push_back(make_entry<RowFftZ<S, T, R, 1, false>, RealParamsZ<T>, S, T>(FAM_R2CZ, S::N, 0, Op::Plain, Build::Default, R, name));
+    reg.push_back(make_entry<RowFftZ<S, T, R, 2, true>, RealParamsZ<T>, S, T>(FAM_C2RZ, S::N, 1, Op::Plain, Build::Default, R, name));
+    reg.push_back(make_entry<RowFftZ<S, T, R, 3, false>, RealParamsZ<T>, S, T>(FAM_R2CZH, S::N, 0, Op::Plain, Build::Default, R, name));
+    reg.push_back(make_entry<RowFftZ<S, T, R, 4, true>, RealParamsZ<T>, S, T>(FAM_C2RZH, S::N, 1, Op::Plain, Build::Default, R, name));
   }
 }
 

@@ -31,17 +31,16 @@ void register_nlz(const char* name) {
   auto& reg = kernel_registry();
   constexpr int R = nlz_rows<S, T>();
   constexpr int W = MFFT_NLZ_OCC > 1 ? 16 + MFFT_NLZ_OCC : 0;        // waves per SIMD, said directly (registry.h mfft_kern_occ)
-  reg.push_back(make_entry<NlzFft<S, T, R, nlz_twlds<S, T>(), nlz_split<S, T>(), nlz_wave<S, T>()>, NlzParams<T>, S, T, W>(FAM_NLZ, S::N, 0, R, name));
+  reg.push_back(make_entry<NlzFft<S, T, R, nlz_twlds<S, T>(), nlz_split<S, T>(), nlz_wave<S, T>()>, NlzParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::Plain, Build::Default, R, name));
 }
 
-// ... and its pruned 3/2-rule flavour (Nlz3Fft: pad code 3, entry.n = M = 3 L): three thread groups of SL::TPT threads per row
+// ... and its pruned 3/2-rule flavour (Nlz3Fft: Build::Nlz3, entry.n = M = 3 L): three thread groups of SL::TPT threads per row
 template <class SL, typename T> constexpr int nlz3_rows() { return 256 / (3 * SL::TPT) > 0 ? 256 / (3 * SL::TPT) : 1; }
 template <class SL, typename T>
 void register_nlz3(const char* name) {
   auto& reg = kernel_registry();
   constexpr int R = nlz3_rows<SL, T>();
-  reg.push_back(make_entry<Nlz3Fft<SL, T, R, true>, NlzParams<T>, SL, T>(FAM_NLZ, 3 * SL::N, 0, R, name));
-  reg.back().pad = 3;
+  reg.push_back(make_entry<Nlz3Fft<SL, T, R, true>, NlzParams<T>, SL, T>(FAM_NLZ, 3 * SL::N, 0, Op::Plain, Build::Nlz3, R, name));
 }
 
 }  // namespace mfft
