@@ -207,7 +207,9 @@ MFFT_API int mfft_plan_set_dealias_mask(mfft_plan_t plan, const uint8_t* mask_ho
  * 1 = pruned passes and a smaller exchange, 2 = the same with every ky of THIS rank removed), "comm_cus" (CUs set aside
  * for the communication stream, 0 = no masks), "kz_slices", "row_batches" (pieces of the exchange pipeline), "zfuse"
  * (pencils: z-chunk pack fused into the z transform), "ranks", "plane_pad" (one-rank slab plans: elements added to the
- * plane pitch of the intermediate because the mesh's own plane pitch is one the strided x pass reads slowly).  Unknown keys are MFFT_ERR_INVALID. */
+ * plane pitch of the intermediate because the mesh's own plane pitch is one the strided x pass reads slowly),
+ * "split_last" (one-rank slab R2C plans: 1 = the plain transforms split real / complex at the spectrum end, MFFT_SPLIT_LAST;
+ * asked before the first transform, the key decides then whether the route's work buffer fits).  Unknown keys are MFFT_ERR_INVALID. */
 MFFT_API int mfft_plan_get_info(mfft_plan_t plan, const char* key, int64_t* value);
 
 /* per-stage timing with HIP events on the plan's own streams (bench roofline) */

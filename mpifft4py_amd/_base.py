@@ -326,7 +326,7 @@ class DistFFTBase(object):
 
     def plan_info(self, key):
         """What the plan decided (mfft_plan_get_info): "pruned_route", "comm_cus", "kz_slices", "row_batches", "zfuse",
-        "plane_pad", "complex_pitch", "complex_pitch_native", "nonlinear_fused_3_2" / "_none" / "_2_3", "nonlinear_bytes"."""
+        "plane_pad", "split_last", "complex_pitch", "complex_pitch_native", "nonlinear_fused_3_2" / "_none" / "_2_3", "nonlinear_bytes"."""
         v = ctypes.c_int64(0)
         _lib.call("mfft_plan_get_info", self._plan, key.encode(), ctypes.byref(v))
         return int(v.value)

@@ -35,7 +35,7 @@ std::vector<KernelEntry>& kernel_registry() {
 
 // The registry is complete once the static initialisers of the kernels_*.hip units have run; lookups go
 // through hash maps built on first use (a linear scan of ~2000 entries per launch costs ~0.3 us, visible at 32^3).
-constexpr int OP_BITS = 5, BUILD_BITS = 3, FAMILY_BITS = 6;
+constexpr int OP_BITS = 6, BUILD_BITS = 3, FAMILY_BITS = 6;
 static_assert(2 * (unsigned)Op::TopFlag <= (1u << OP_BITS) && (unsigned)Op::Band < (unsigned)Op::Limited, "Op does not fit its key field");
 static_assert((unsigned)Build::Last < (1u << BUILD_BITS), "Build does not fit its key field");
 static_assert((unsigned)FAM_NLZ < (1u << FAMILY_BITS), "Family does not fit its key field");
@@ -422,6 +422,26 @@ static int launch_real_t(const KernelEntry* e, const RealArgs& a, void* tw, void
   if constexpr (std::is_same<PT, RealParams<T>>::value) set_zsplit(P, a.zs);
   return launch_rows(e, P, a.nrows, e->tile, s);
 }
+// pair-row kernels (Op::PairRows): a workgroup holds tile / 2 of the (n0 / 2 + 1) * n1 pair slots (fft_kernels.h pair_row)
+template <typename T>
+static int launch_pair_t(const KernelEntry* e, const RealArgs& a, void* tw, void* rtw, hipStream_t s) {
+  RealPairParams<T> P;
+  P.in = a.in;
+  P.out = a.out;
+  P.tw = static_cast<const cx<T>*>(tw);
+  P.rtw = static_cast<const cx<T>*>(rtw);
+  P.in_stride = a.in_stride;
+  P.out_stride = a.out_stride;
+  P.nrows = (int64_t)(a.pair_n0 / 2 + 1) * a.pair_n1;
+  P.valid = a.n / 2 + 1;
+  P.scale = (T)a.scale;
+  set_zsplit(P, a.zs);
+  P.pn0 = a.pair_n0;
+  P.pn1 = a.pair_n1;
+  P.p_rplane = a.pair_rplane;
+  P.p_cplane = a.pair_cplane;
+  return launch_rows(e, P, P.nrows, e->tile / 2, s);
+}
 
 // c2r kernels with the mirrors through LDS (registry.h c2r_mlds_candidate: built where they were measured ahead): taken where
 // they exist; MFFT_C2R_MLDS=0: never
@@ -472,8 +492,22 @@ static int select_real(int fam, const RealArgs& a, const KernelEntry** out) {
   *out = e;
   return 0;
 }
+bool pair_rows_supported(int64_t n, int prec) {
+  return n >= 2 && n < 65536 && find_kernel(FAM_R2C, (int)n, prec, 0, Op::PairRows) && find_kernel(FAM_C2R, (int)n, prec, 1, Op::PairRows);
+}
 static int launch_real(int fam, const RealArgs& a, hipStream_t s) {
   const KernelEntry* e = nullptr;
+  if (a.pair_n0 > 0) {
+    e = find_kernel(fam, a.n, a.prec, fam == FAM_C2R ? 1 : 0, Op::PairRows);
+    const int64_t real_stride = fam == FAM_R2C ? a.in_stride : a.out_stride;
+    if (!e || a.zs.nchunk || a.valid > 0 || real_stride % 2 != 0 || a.pair_rplane % 2 != 0 ||
+        a.nrows != (int64_t)a.pair_n0 * a.pair_n1 || a.nrows >= (int64_t)1 << 31)
+      return set_error(MFFT_ERR_UNSUPPORTED, "no pair-row real kernel of length %d for this layout", a.n);
+    void *tw = nullptr, *rtw = nullptr;
+    MFFT_TRY(prepare_kernel(e, &tw));
+    MFFT_TRY(real_twiddles(a.n, a.prec, &rtw));
+    return by_prec(a.prec, [&](auto t) { return launch_pair_t<decltype(t)>(e, a, tw, rtw, s); });
+  }
   MFFT_TRY(select_real(fam, a, &e));
   if (!e) return big_real(fam == FAM_C2R, a, s);
   void *tw = nullptr, *rtw = nullptr, *chirp = nullptr, *bhat = nullptr;

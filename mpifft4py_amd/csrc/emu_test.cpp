@@ -747,6 +747,122 @@ static void test_real() {
 // ---------------------------------------------------------------------------
 // chirp-z (Bluestein) kernels: runtime length n on the compiled plan S of length M >= 2n-1
 // ---------------------------------------------------------------------------
+// Pair-row kernels (R2CFft / C2RFft PAIR): the z pass of the route that splits real / complex LAST.  Forward: the x and y
+// transforms of a real (n0, n1, N) field read as complex pairs go in, its half-spectrum must come out.  Inverse: an ARBITRARY
+// complex (n0, n1, N/2 + 1) array goes in (not the transform of a real field: the planes kz = 0 and N/2 are not Hermitian); the
+// inverse x and y transforms of what comes out, read as reals, must be numpy's irfftn of it (inverse c2c over x and y, then the
+// c2r that ignores the imaginary parts of bins 0 and N/2).  Rows and planes of both sides are pitched.
+template <class S, typename T, int ROWS, bool TWLDS>
+static void test_pair(int n0, int n1) {
+  const int M = S::N, N = 2 * M, Nf = M + 1;
+  std::mt19937_64 rng(11 + N + 7 * n0 + n1);
+  std::uniform_real_distribution<double> U(-1, 1);
+  const int wrow = M + 1, wplane = n1 * wrow + 3, crow = Nf + 2, cplane = n1 * crow + 5;      // complex elements
+  auto tw = build_pass_twiddles<S, T>();
+  auto rtw = build_real_twiddles<T>(N);
+  // the long-double transform of axis `ax` (0: x, 1: y) of an (n0, n1, len) array
+  auto xy = [&](std::vector<cx<long double>>& a, int len, int ax, int sign) {
+    const int n = ax == 0 ? n0 : n1;
+    for (int o = 0; o < (ax == 0 ? n1 : n0); ++o)
+      for (int k = 0; k < len; ++k) {
+        lvec v(n);
+        for (int i = 0; i < n; ++i) v[i] = a[((size_t)(ax == 0 ? i : o) * n1 + (ax == 0 ? o : i)) * len + k];
+        v = naive_dft(v, sign);
+        for (int i = 0; i < n; ++i) a[((size_t)(ax == 0 ? i : o) * n1 + (ax == 0 ? o : i)) * len + k] = v[i];
+      }
+  };
+  const int slots = (n0 / 2 + 1) * n1, grid = (slots + ROWS / 2 - 1) / (ROWS / 2);
+  char name[64];
+  {
+    std::vector<long double> u((size_t)n0 * n1 * N);
+    for (auto& z : u) z = U(rng);
+    std::vector<cx<long double>> w((size_t)n0 * n1 * M), ref((size_t)n0 * n1 * Nf);
+    for (size_t i = 0; i < w.size(); ++i) { w[i].x = u[2 * i]; w[i].y = u[2 * i + 1]; }
+    xy(w, M, 1, -1);
+    xy(w, M, 0, -1);
+    for (int r = 0; r < n0 * n1; ++r) {
+      lvec x(N);
+      for (int i = 0; i < N; ++i) { x[i].x = u[(size_t)r * N + i]; x[i].y = 0; }
+      lvec X = naive_dft(x, -1);
+      for (int k = 0; k < Nf; ++k) ref[(size_t)r * Nf + k] = X[k];
+    }
+    xy(ref, Nf, 1, -1);
+    xy(ref, Nf, 0, -1);
+    std::vector<cx<T>> W((size_t)n0 * wplane, mk<T>((T)9, (T)9)), fu((size_t)n0 * cplane, mk<T>((T)7, (T)7));
+    for (int x = 0; x < n0; ++x)
+      for (int y = 0; y < n1; ++y)
+        for (int k = 0; k < M; ++k) {
+          const cx<long double> z = w[((size_t)x * n1 + y) * M + k];
+          W[(size_t)x * wplane + (size_t)y * wrow + k] = mk<T>((T)z.x, (T)z.y);
+        }
+    typedef R2CFft<S, T, ROWS, TWLDS, false, false, false, false, true> K;
+    RealPairParams<T> P{{W.data(), fu.data(), tw.data(), rtw.data(), 2 * wrow, crow, slots, Nf, (T)1}};
+    P.pn0 = n0; P.pn1 = n1; P.p_rplane = 2 * wplane; P.p_cplane = cplane;
+    emu_launch(grid, K::THREADS, K::LDS_BYTES, [&](int b, int t, char* lds) { K::body(P, b, t, lds); });
+    long double num = 0, den = 0;
+    bool gaps = true;        // nothing outside the rows is written
+    for (size_t i = 0; i < fu.size(); ++i) {
+      const int x = (int)(i / cplane), rem = (int)(i % cplane), y = rem / crow, k = rem % crow;
+      if (y < n1 && k < Nf) {
+        const cx<long double> e = ref[((size_t)x * n1 + y) * Nf + k];
+        num += (fu[i].x - e.x) * (fu[i].x - e.x) + (fu[i].y - e.y) * (fu[i].y - e.y);
+        den += e.x * e.x + e.y * e.y;
+      } else if (fu[i].x != (T)7 || fu[i].y != (T)7) {
+        gaps = false;
+      }
+    }
+    snprintf(name, sizeof name, "r2c pair r%d %dx%d%s", ROWS, n0, n1, TWLDS ? " twlds" : "");
+    report(name, N, pname<T>(), gaps ? (double)sqrtl(num / den) : 1.0, tol_of<T>());
+  }
+  {
+    std::vector<cx<long double>> f((size_t)n0 * n1 * Nf);
+    for (auto& z : f) { z.x = U(rng); z.y = U(rng); }
+    std::vector<cx<T>> fu((size_t)n0 * cplane, mk<T>((T)7, (T)7)), W((size_t)n0 * wplane, mk<T>((T)9, (T)9));
+    for (int r = 0; r < n0 * n1; ++r)
+      for (int k = 0; k < Nf; ++k) {
+        const cx<T> z = mk<T>((T)f[(size_t)r * Nf + k].x, (T)f[(size_t)r * Nf + k].y);
+        fu[(size_t)(r / n1) * cplane + (size_t)(r % n1) * crow + k] = z;
+        f[(size_t)r * Nf + k].x = z.x;
+        f[(size_t)r * Nf + k].y = z.y;
+      }
+    // irfftn: inverse x and y, then c2r row by row
+    std::vector<cx<long double>> g = f;
+    xy(g, Nf, 0, +1);
+    xy(g, Nf, 1, +1);
+    std::vector<long double> ref((size_t)n0 * n1 * N);
+    for (int r = 0; r < n0 * n1; ++r) {
+      lvec X(N);
+      for (int k = 0; k < Nf; ++k) X[k] = g[(size_t)r * Nf + k];
+      X[0].y = 0;
+      X[M].y = 0;
+      for (int k = 1; k < M; ++k) { X[N - k].x = X[k].x; X[N - k].y = -X[k].y; }
+      lvec x = naive_dft(X, +1);
+      for (int i = 0; i < N; ++i) ref[(size_t)r * N + i] = x[i].x / ((long double)N * n0 * n1);
+    }
+    typedef C2RFft<S, T, ROWS, TWLDS, false, false, false, false, false, true> K;
+    RealPairParams<T> P{{fu.data(), W.data(), tw.data(), rtw.data(), crow, 2 * wrow, slots, Nf, (T)(1.0 / N)}};
+    P.pn0 = n0; P.pn1 = n1; P.p_rplane = 2 * wplane; P.p_cplane = cplane;
+    emu_launch(grid, K::THREADS, K::LDS_BYTES, [&](int b, int t, char* lds) { K::body(P, b, t, lds); });
+    bool gaps = true;
+    std::vector<cx<long double>> w((size_t)n0 * n1 * M);
+    for (size_t i = 0; i < W.size(); ++i) {
+      const int x = (int)(i / wplane), rem = (int)(i % wplane), y = rem / wrow, k = rem % wrow;
+      if (y < n1 && k < M) { w[((size_t)x * n1 + y) * M + k].x = W[i].x; w[((size_t)x * n1 + y) * M + k].y = W[i].y; }
+      else if (W[i].x != (T)9 || W[i].y != (T)9) gaps = false;
+    }
+    xy(w, M, 1, +1);
+    xy(w, M, 0, +1);
+    long double num = 0, den = 0;
+    for (size_t i = 0; i < w.size(); ++i) {
+      const long double a = w[i].x / ((long double)n0 * n1) - ref[2 * i], b = w[i].y / ((long double)n0 * n1) - ref[2 * i + 1];
+      num += a * a + b * b;
+      den += ref[2 * i] * ref[2 * i] + ref[2 * i + 1] * ref[2 * i + 1];
+    }
+    snprintf(name, sizeof name, "c2r pair r%d %dx%d%s", ROWS, n0, n1, TWLDS ? " twlds" : "");
+    report(name, N, pname<T>(), gaps ? (double)sqrtl(num / den) : 1.0, 4 * tol_of<T>());
+  }
+}
+
 template <class S, typename T, int COLS, bool INV, bool SPLIT, int VEC>
 static void test_col_z(int n) {
   typedef ColFftZ<S, T, COLS, INV, SPLIT, VEC> K;
@@ -1443,6 +1559,18 @@ int main() {
   MFFT_NLZ3PLANS(MFFT_NLZ3)
   test_nlz3_all<Spec<256, 8, 8, 4>>();
 #undef MFFT_NLZ3
+#endif
+#if EMU_HAS(1)
+  // pair-row kernels (with plan group B, where the shipped 512 / 1024 plans are; tests/test_cabi.py fixes the number of parts): even and odd meshes (self-paired planes and rows), a partial last workgroup, the shipped shapes
+  test_pair<Spec<32, 8, 4>, double, 4, true>(4, 6);
+  test_pair<Spec<32, 8, 4>, double, 4, true>(3, 5);
+  test_pair<Spec<32, 8, 4>, double, 4, false>(5, 4);
+  test_pair<Spec<32, 8, 4>, double, 2, true>(2, 2);
+  test_pair<Spec<32, 8, 4>, double, 64, true>(9, 15);
+  test_pair<Spec<32, 8, 4>, float, 8, true>(6, 3);
+  test_pair<Spec<128, 16, 8>, double, 32, true>(12, 20);
+  test_pair<Spec<512, 8, 8, 8>, double, 4, true>(3, 4);
+  test_pair<Spec<1024, 16, 8, 8>, double, 2, false>(2, 3);
 #endif
 #undef MFFT_PLAN
   printf("%s (%d failures)\n", g_fail ? "EMU TESTS FAILED" : "EMU TESTS PASSED", g_fail);

@@ -22,6 +22,7 @@
 // the __global__ wrappers in kernels.hip call, and (b) by g++ for the fibre-based
 // workgroup emulator (emu_test.cpp), where MFFT_BARRIER() yields to a scheduler.
 #pragma once
+#include <type_traits>
 #include "fft_core.h"
 
 #if defined(__HIPCC__)
@@ -223,6 +224,41 @@ struct RealParams {            // r2c: in = real rows, out = complex rows; c2r t
   ZSplit zs;                   // CHUNK kernels: the complex side is split into z chunks
   i64 row0;                    // first row of this launch inside the chunk blocks
 };
+// PAIR kernels: the rows are the (x, y) lines of a (pn0, pn1) mesh whose planes lie p_rplane reals (real side) and p_cplane
+// complex elements (complex side) apart, the strides of RealParams are the row pitches inside a plane, nrows counts row PAIRS
+// (a type of its own: the other kernels' arguments stay what they were)
+template <typename T>
+struct RealPairParams : RealParams<T> {
+  int pn0, pn1;
+  i64 p_rplane, p_cplane;
+};
+
+// PAIR kernels (R2CFft / C2RFft): the real side holds, row by row, the x and y transforms of the real field read as complex
+// pairs w[m] = u[2m] + i u[2m+1] -- a COMPLEX field, so the half-spectrum row (kx, ky) needs the mirrored bins of its
+// Hermitian partner row ((n0 - kx) % n0, (n1 - ky) % n1) where the plain kernels take their own.  Slot q lists the row
+// (kx, ky) = (q / n1, q % n1) of the planes kx <= n0 / 2 as side 0 and its partner as side 1.  In a plane that is its own
+// partner (kx = 0, 2 kx = n0) the rows ky > n1 / 2 have been listed as partners already: such a slot does nothing, and a row
+// that is its own partner is stored by side 0 alone.  Every row belongs to exactly one live (slot, side).
+struct PairRow {
+  i64 real_off, cplx_off;      // element offsets of the row on the two sides
+  bool live;                   // this (slot, side) stores a row
+};
+template <typename T>
+MFFT_D PairRow pair_row(const RealPairParams<T>& P, i64 q, int side, i64 real_pitch, i64 cplx_pitch) {
+  const bool inrange = q < P.nrows;
+  if (!inrange) q = P.nrows - 1;         // loads stay unconditional (see RowFft)
+  const unsigned n0 = (unsigned)P.pn0, n1 = (unsigned)P.pn1;
+  const unsigned kx = (unsigned)q / n1, ky = (unsigned)q - kx * n1;
+  const unsigned px = kx ? n0 - kx : 0u, py = ky ? n1 - ky : 0u;
+  bool live = inrange && !(px == kx && ky > py);
+  if (side && px == kx && py == ky) live = false;
+  const unsigned x = side ? px : kx, y = side ? py : ky;
+  PairRow r;
+  r.real_off = (i64)x * P.p_rplane + (i64)y * real_pitch;
+  r.cplx_off = (i64)x * P.p_cplane + (i64)y * cplx_pitch;
+  r.live = live;
+  return r;
+}
 
 // position -> padded LDS slot for row-major (lane-along-row) exchange buffers:
 // one pad element every PD positions breaks the stride-R0 bank aliasing of the
@@ -770,9 +806,14 @@ struct RowFft {
 // WP: the wave-packed thread layout described at C2RFft (threads per transform that do not divide a wave): the mirrored
 // value Z[M - pos] of the split post-pass comes through a wave shuffle instead of an LDS round trip with three more
 // barriers and E more live registers (the r2c stage of 720^3 / 900^3 took 1.8 x the c2r stage's time, round 3).
-template <class S, typename T, int ROWS, bool TWLDS, bool LIMIT = false, bool CHUNK = false, bool SPLIT = false, bool WP = false>
+// PAIR: the real side is a COMPLEX field (pair_row above): the mirrored value of the split post-pass is the partner row's, taken
+// from its exchange buffer (a workgroup holds ROWS / 2 row pairs, partners in neighbouring rows of it).
+template <class S, typename T, int ROWS, bool TWLDS, bool LIMIT = false, bool CHUNK = false, bool SPLIT = false, bool WP = false,
+          bool PAIR = false>
 struct R2CFft {
   typedef typename RowXch<SPLIT, T, PadSlot<S::R(0)>>::elem XE;
+  static_assert(!PAIR || (!LIMIT && !CHUNK && !SPLIT && !WP && ROWS % 2 == 0 && S::NP > 1), "pair rows: plain dense kernels, whole pairs");
+  typedef typename std::conditional<PAIR, RealPairParams<T>, RealParams<T>>::type Params;
   static constexpr int M = S::N;
   static constexpr int RPW = WP ? 64 / S::TPT : 1;
   static_assert(!WP || (S::TPT < 64 && 64 % S::TPT != 0 && ROWS % (64 / S::TPT) == 0), "wave-packed rows: whole waves of rows");
@@ -783,7 +824,7 @@ struct R2CFft {
   static constexpr int XCH_BYTES = (int)(PLEN * ROWS * sizeof(XE));
   static constexpr int LDS_BYTES = TW_BYTES + XCH_BYTES;
 
-  static MFFT_D void body(const RealParams<T>& P, int bid, int tid, char* lds) {
+  static MFFT_D void body(const Params& P, int bid, int tid, char* lds) {
     cx<T>* ltw = reinterpret_cast<cx<T>*>(lds);
     int rl, j, lane0 = 0;
     bool dup = false;
@@ -804,12 +845,14 @@ struct R2CFft {
     }
     XE* xch = reinterpret_cast<XE*>(lds + TW_BYTES) + rl * PLEN;
     const i64 row = (i64)bid * ROWS + rl;
-    const bool inrange = row < P.nrows;
-    const bool active = inrange && !dup;
+    PairRow pr{};
+    if constexpr (PAIR) pr = pair_row<T>(P, (i64)bid * (ROWS / 2) + (rl >> 1), rl & 1, P.in_stride, P.out_stride);
+    const bool inrange = PAIR ? true : row < P.nrows;
+    const bool active = PAIR ? pr.live : inrange && !dup;
     // a row of N reals read as N/2 complex (x[2n], x[2n+1])
     const cx<T>* ip =
-        reinterpret_cast<const cx<T>*>(static_cast<const T*>(P.in) + (inrange ? row : P.nrows - 1) * P.in_stride);
-    cx<T>* op = static_cast<cx<T>*>(P.out) + row * P.out_stride;
+        reinterpret_cast<const cx<T>*>(static_cast<const T*>(P.in) + (PAIR ? pr.real_off : (inrange ? row : P.nrows - 1) * P.in_stride));
+    cx<T>* op = static_cast<cx<T>*>(P.out) + (PAIR ? pr.cplx_off : row * P.out_stride);
 
     cx<T> v[S::E];
 #pragma unroll
@@ -847,7 +890,41 @@ struct R2CFft {
     };
     auto emit = [&](int pos, cx<T> zk, cx<T> zpartner) { emit_w(pos, zk, zpartner, P.rtw[pos]); };
     constexpr bool SHFL = WP || (S::TPT <= 64 && (64 % S::TPT) == 0);
-    if constexpr (SHFL) {
+    if constexpr (PAIR) {
+      // Z'[M-pos] of the partner row out of ITS exchange buffer: fu[k] = A + w_k B with A = (Z[k] + conj Z'[M-k]) / 2,
+      // B = -i (Z[k] - conj Z'[M-k]) / 2; bin M = A[0] - B[0].  A row that is its own partner reduces to the formula above.
+      const XE* pxch = reinterpret_cast<const XE*>(lds + TW_BYTES) + (rl ^ 1) * PLEN;
+      // the post-pass twiddles before the loop where the plan is small (see RTW_EARLY in the shuffle path below: loaded next to
+      // their use, every step waits for the previous step's store)
+      constexpr bool RTW_EARLY = S::E * (int)sizeof(cx<T>) <= 128;
+      cx<T> rt[RTW_EARLY ? S::E : 1];
+      if constexpr (RTW_EARLY) {
+#pragma unroll
+        for (int k = 0; k < S::E; ++k) rt[k] = P.rtw[j + k * S::TPT];
+      }
+      MFFT_BARRIER();
+#pragma unroll
+      for (int k = 0; k < S::E; ++k) xc.put(j + k * S::TPT, v[k]);
+      MFFT_BARRIER();
+      if (active) {
+#pragma unroll
+        for (int k = 0; k < S::E; ++k) {
+          const int pos = j + k * S::TPT;
+          const cx<T> zm = conj(pxch[padpos<PD>(pos == 0 ? 0 : M - pos)]);
+          const cx<T> e = scale(v[k] + zm, half);
+          const cx<T> o = mul_mi(scale(v[k] - zm, half));
+          if (pos == 0) {
+            put(0, scale(e + o, P.scale));
+            put(M, scale(e - o, P.scale));
+          } else {
+            cx<T> w;
+            if constexpr (RTW_EARLY) w = rt[k];
+            else w = P.rtw[pos];
+            put(pos, scale(e + w * o, P.scale));
+          }
+        }
+      }
+    } else if constexpr (SHFL) {
       // Z[M-pos] of (lane j, register k) is register E-1-k of lane TPT-j of the same row: one
       // wave shuffle instead of an LDS round trip and two barriers (lane 0: its own register E-k)
       const int src = WP ? lane0 + (j == 0 ? 0 : S::TPT - j) : (tid & 63) - j + ((S::TPT - j) & (S::TPT - 1));
@@ -933,10 +1010,16 @@ struct R2CFft {
 // wave-packed: 15, 24, 30, 48 ... threads), every bin is still read from memory ONCE and the mirrors come through the
 // exchange buffer, which is idle before the first pass -- instead of a second global load per bin (1.31 x the algorithmic
 // fetch at 1440^3, profiles/r05_ytile_builds.txt).
+// PAIR: the inverse of R2CFft's PAIR -- the real side receives the complex field whose inverse x and y transforms are the real
+// output read as complex pairs.  The mirrored bins are the partner row's (through the exchange buffers, MLDS-style: every bin
+// is read from memory once), and bins 0 and N/2 are first projected onto their Hermitian part, (X[0] + conj X'[0]) / 2: what
+// "imaginary parts ignored" of the plain kernel amounts to once the x and y transforms come AFTER this pass.
 template <class S, typename T, int ROWS, bool TWLDS, bool LIMIT = false, bool CHUNK = false, bool SPLIT = false, bool WP = false,
-          bool MLDS = false>
+          bool MLDS = false, bool PAIR = false>
 struct C2RFft {
   typedef typename RowXch<SPLIT, T, PadSlot<S::R(0)>>::elem XE;
+  static_assert(!PAIR || (!LIMIT && !CHUNK && !SPLIT && !WP && !MLDS && ROWS % 2 == 0 && S::NP > 1), "pair rows: plain dense kernels, whole pairs");
+  typedef typename std::conditional<PAIR, RealPairParams<T>, RealParams<T>>::type Params;
   static constexpr int M = S::N;
   static constexpr int RPW = WP ? 64 / S::TPT : 1;                      // rows per wave (wave-packed layout)
   static_assert(!WP || (S::TPT < 64 && 64 % S::TPT != 0 && ROWS % (64 / S::TPT) == 0), "wave-packed rows: whole waves of rows");
@@ -947,7 +1030,7 @@ struct C2RFft {
   static constexpr int XCH_BYTES = S::NP > 1 ? (int)(PLEN * ROWS * sizeof(XE)) : 0;
   static constexpr int LDS_BYTES = TW_BYTES + XCH_BYTES;
 
-  static MFFT_D void body(const RealParams<T>& P, int bid, int tid, char* lds) {
+  static MFFT_D void body(const Params& P, int bid, int tid, char* lds) {
     cx<T>* ltw = reinterpret_cast<cx<T>*>(lds);
     int rl, j, lane0 = 0;          // row of the workgroup, thread of the row, (WP) lane of the row's thread 0
     bool dup = false;              // (WP) a lane that duplicates a thread of the wave's last row
@@ -966,11 +1049,13 @@ struct C2RFft {
     }
     XE* xch = reinterpret_cast<XE*>(lds + TW_BYTES) + rl * PLEN;
     const i64 row = (i64)bid * ROWS + rl;
-    const bool inrange = row < P.nrows;
-    const bool active = inrange && !dup;
+    PairRow pr{};
+    if constexpr (PAIR) pr = pair_row<T>(P, (i64)bid * (ROWS / 2) + (rl >> 1), rl & 1, P.out_stride, P.in_stride);
+    const bool inrange = PAIR ? true : row < P.nrows;
+    const bool active = PAIR ? pr.live : inrange && !dup;
     // rows past the end re-read the last row (unconditional loads: see RowFft) and store nothing
-    const cx<T>* ip = static_cast<const cx<T>*>(P.in) + (inrange ? row : P.nrows - 1) * P.in_stride;
-    cx<T>* op = reinterpret_cast<cx<T>*>(static_cast<T*>(P.out) + row * P.out_stride);
+    const cx<T>* ip = static_cast<const cx<T>*>(P.in) + (PAIR ? pr.cplx_off : (inrange ? row : P.nrows - 1) * P.in_stride);
+    cx<T>* op = reinterpret_cast<cx<T>*>(static_cast<T*>(P.out) + (PAIR ? pr.real_off : row * P.out_stride));
 
     // bin `pos` of this row; CHUNK: out of its z chunk, a position the last chunk does not hold (dropped Nyquist
     // column) reads as zero -- the load itself stays unconditional (clamped offset + select), see RowFft
@@ -990,7 +1075,34 @@ struct C2RFft {
     // (twice the textbook value; the factor is folded into the normalisation)
     cx<T> v[S::E];
     constexpr bool SHFL = WP || (S::TPT <= 64 && (64 % S::TPT) == 0);
-    if constexpr (SHFL) {
+    if constexpr (PAIR) {
+      // every bin once into v (bin M beside it), all of them into the row's exchange buffer, the mirrors out of the partner's
+      static_assert(PD > 0, "slot padpos(M) exists only in padded rows: PLEN = M + M / PD + 1");
+#pragma unroll
+      for (int k = 0; k < S::E; ++k) v[k] = ip[j + k * S::TPT];
+      cx<T> xM = mk<T>((T)0, (T)0);
+      if (j == 0) xM = ip[M];
+      const XE* pxch = reinterpret_cast<const XE*>(lds + TW_BYTES) + (rl ^ 1) * PLEN;
+#pragma unroll
+      for (int k = 0; k < S::E; ++k) xch[padpos<PD>(j + k * S::TPT)] = v[k];
+      if (j == 0) xch[padpos<PD>(M)] = xM;
+      MFFT_BARRIER();
+      const T half = (T)0.5;
+#pragma unroll
+      for (int k = 0; k < S::E; ++k) {
+        const int pos = j + k * S::TPT;
+        cx<T> xk = v[k];
+        cx<T> xm = conj(pxch[padpos<PD>(M - pos)]);
+        if (pos == 0) {              // Hermitian parts of the k=0 and k=N/2 bins
+          xk = scale(xk + conj(pxch[padpos<PD>(0)]), half);
+          xm = scale(xM + xm, half);
+        }
+        const cx<T> e = xk + xm;
+        const cx<T> dd = xk - xm;
+        v[k] = swapri(e + mul_pi(dd * conj(P.rtw[pos])));
+      }
+      MFFT_BARRIER();                // the buffer goes back to the passes' exchanges
+    } else if constexpr (SHFL) {
       // Every bin is read from memory ONCE.  The mirrored partner X[M-pos] of (lane j, register k)
       // is register E-1-k of lane TPT-j of the same row (all inside one wave), fetched with a
       // wave shuffle; lane 0's partners are its own registers E-k and the extra bin X[M].
@@ -1059,6 +1171,7 @@ struct C2RFft {
       }
     } else if constexpr (MLDS && S::NP > 1) {
       // every bin once into v, position M (thread 0's partner of position 0) beside it; the mirrors through LDS
+      static_assert(PD > 0, "slot padpos(M) exists only in padded rows: PLEN = M + M / PD + 1");
 #pragma unroll
       for (int k = 0; k < S::E; ++k) {
         const int pos = j + k * S::TPT;

@@ -103,9 +103,14 @@ struct RealArgs {
   double scale = 1.0;
   int valid = 0;         // complex columns present in memory (0 = all n/2+1)
   ZSplitArgs zs;         // of the complex side
+  // pair-row kernels (Op::PairRows): the rows are the (x, y) lines of a (pair_n0, pair_n1) mesh, nrows = pair_n0 * pair_n1, the
+  // strides above are the row pitches inside a plane and the planes lie pair_rplane reals / pair_cplane complex elements apart
+  int pair_n0 = 0, pair_n1 = 0;      // 0: plain rows
+  int64_t pair_rplane = 0, pair_cplane = 0;
 };
 int launch_r2c(const RealArgs& a, hipStream_t s);
 int launch_c2r(const RealArgs& a, hipStream_t s);
+bool pair_rows_supported(int64_t n, int prec);     // both pair-row kernels of real length n exist
 
 // fused nonlinear z stage (fft_nlz.h): rows of half-spectra of two vector fields in, rows of the half-spectra of their
 // cross product out (may alias the inputs row for row)

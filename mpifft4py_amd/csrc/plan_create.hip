@@ -365,6 +365,7 @@ int mfft_plan_get_info(mfft_plan_t p, const char* key, int64_t* value) {
   else if (k == "nonlinear_fused_2_3") *value = p->nonlinear_fusable(MFFT_DEALIAS_2_3) ? 1 : 0;
   else if (k == "nonlinear_fused_3_2") *value = p->nonlinear_fusable(MFFT_DEALIAS_3_2) ? 1 : 0;
   else if (k == "nonlinear_bytes") *value = (int64_t)(p->nlx.bytes + p->nly.bytes + p->nlr.bytes + p->nlw[0].bytes + p->nlw[1].bytes);
+  else if (k == "split_last") *value = p->split_last_route() ? 1 : 0;   // the one-rank route that splits real / complex last (decides whether the work buffer fits, if no call has yet)
   else if (k == "plane_pad") *value = (p->P == 1 && p->d.decomp == MFFT_SLAB) ? p->p1_plane_pad() : 0;   // elements added to the intermediate's plane pitch
   else return set_error(MFFT_ERR_INVALID, "mfft_plan_get_info: unknown key '%s'", key);
   return 0;

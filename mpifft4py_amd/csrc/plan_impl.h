@@ -353,6 +353,14 @@ struct mfft_plan_s {
 
   // ---- slab (plan_slab.hip) ------------------------------------------------------
   bool fwd_out_of_place(size_t cbytes);
+  // one rank, real data: real / complex split at the SPECTRUM end of the transform (slab_forward_split_last)
+  int split_last = -1;          // MFFT_SPLIT_LAST, read when the plan is created: 0 never, 1 wherever the kernels exist, unset: by rule
+  int split_last_fit = -1;      // the work buffer fits: decided at the first call
+  int64_t split_last_pad() const { return plane_pad(N1 * (N2 / 2)); }
+  bool split_last_eligible() const;
+  bool split_last_route();
+  int slab_forward_split_last(const void* u, void* fu);
+  int slab_backward_split_last(const void* fu, void* u);
   int slab_forward(const void* u, void* fu);
   int slab_backward(const void* fu, void* u, bool masked);
   int slab_backward_pruned(const void* fu, void* u);

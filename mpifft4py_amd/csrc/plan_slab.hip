@@ -21,11 +21,74 @@ bool mfft_plan_s::fwd_out_of_place(size_t cbytes) {
 }
 
 // ===========================================================================
+// one rank, real data: real / complex split at the spectrum end
+// ===========================================================================
+// The regular route turns real rows into half-spectrum rows FIRST, so both strided passes run on rows of N2/2 + 1 bins:
+// 8208 bytes at 1024^3 in double precision, every 128-byte tile row across two lines, no non-temporal build.  Here the
+// real array is read as the complex field w[x, y, m] = u[x, y, 2m] + i u[x, y, 2m+1] (no copy), x and y are transformed as
+// c2c passes on rows of N2/2 complex values -- whole lines for N2 >= 16 -- between u and a work array W of (N0, N1, N2/2)
+// whose planes the plan may pad (split_last_pad), and the z pass does the real / complex split LAST: per row a length-N2/2
+// c2c and the split post-pass with the mirrored value taken from the Hermitian partner row (fft_kernels.h PAIR).  Only the
+// contiguous-axis kernels ever touch the caller's compact rows.  Same six launches, same bytes (2 * 6 R against 2 (R + 5 C)).
+// The inverse mirrors it: pair-merge z pass fu -> W, y in place on W, x out of place into u -- the pass that READS
+// power-of-two planes is the slow one (profiles/r02_power_of_two_stride.txt), so the padded W is what x reads.
+// Results differ from the regular route's in the last bits (another order of the same sums).
+bool mfft_plan_s::split_last_eligible() const {
+  if (d.decomp != MFFT_SLAB || P != 1 || !r2c || nat_pitch() || d.line2d || d.drop_nyquist || split_last == 0) return false;
+  if (N0 < 2 || N1 < 2 || N2 % 2 || !pair_rows_supported(N2, prec)) return false;
+  if (split_last > 0) return true;
+  // by rule: only where it was measured to pay (profiles/split_last_ab.txt), which is the 1024^3 mesh in double precision.  Other
+  // large meshes with z rows of 8 KiB and more probably gain as well (same kernels, same strides in y); nobody has measured them.
+  return prec == MFFT_DOUBLE && N0 == 1024 && N1 == 1024 && N2 == 1024;
+}
+bool mfft_plan_s::split_last_route() {
+  if (!split_last_eligible()) return false;
+  if (split_last_fit < 0) {      // the forward transform needs a work buffer now: as fwd_out_of_place decides
+    const size_t need = (size_t)(N0 * (N1 * (N2 / 2) + split_last_pad())) * es;
+    size_t fr = 0, tot = 0;
+    if (work[0].bytes >= need) split_last_fit = 1;
+    else if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); split_last_fit = 0; }
+    else split_last_fit = need <= fr / 4 ? 1 : 0;
+  }
+  return split_last_fit == 1;
+}
+int mfft_plan_s::slab_forward_split_last(const void* u, void* fu) {
+  const int64_t M = N2 / 2, pl = N1 * M + split_last_pad();
+  const double Wb = (double)(N0 * N1 * M) * es;
+  MFFT_TRY(ensure(work[0], (size_t)(N0 * pl) * es));
+  void* W = work[0].p;
+  // x first (out of place from u), y in place on W: the order the headline A/B was taken with (profiles/split_last_ab.txt
+  // section 1).  y first came out 0.1 - 0.25 ms ahead in two in-process rounds (section 2) but has no series of fresh
+  // processes against the parent behind it.
+  MFFT_TRY(stage("fwd_x", 2 * Wb, [&] { return col(u, W, N0, false, 1, N1 * M, 0, plain(N1 * M), 0, plain(pl)); }));
+  MFFT_TRY(stage("fwd_y", 2 * Wb, [&] { return col(W, W, N1, false, N0, M, pl, plain(M), pl, plain(M)); }));
+  return stage("fwd_z", Wb + (double)(N0 * N1 * Nf) * es, [&] {
+    RealArgs a = real_args(W, fu, N0 * N1, N2, N2, Nf, 1.0);
+    a.pair_n0 = (int)N0; a.pair_n1 = (int)N1; a.pair_rplane = 2 * pl; a.pair_cplane = N1 * Nf;
+    return mfft::launch_r2c(a, stream);
+  });
+}
+int mfft_plan_s::slab_backward_split_last(const void* fu, void* u) {
+  const int64_t M = N2 / 2, pl = N1 * M + split_last_pad();
+  const double Wb = (double)(N0 * N1 * M) * es;
+  MFFT_TRY(ensure(work[0], (size_t)(N0 * pl) * es));
+  void* W = work[0].p;
+  MFFT_TRY(stage("bwd_z", Wb + (double)(N0 * N1 * Nf) * es, [&] {
+    RealArgs a = real_args(fu, W, N0 * N1, N2, Nf, N2, 1.0 / (double)N2);
+    a.pair_n0 = (int)N0; a.pair_n1 = (int)N1; a.pair_rplane = 2 * pl; a.pair_cplane = N1 * Nf;
+    return mfft::launch_c2r(a, stream);
+  }));
+  MFFT_TRY(stage("bwd_y", 2 * Wb, [&] { return col(W, W, N1, true, N0, M, pl, plain(M), pl, plain(M)); }));
+  return stage("bwd_x", 2 * Wb, [&] { return col(W, u, N0, true, 1, N1 * M, 0, plain(pl), 0, plain(N1 * M)); });
+}
+
+// ===========================================================================
 // slab
 // ===========================================================================
 int mfft_plan_s::slab_forward(const void* u, void* fu) {
   const double Cb = (double)(N0 * Np1 * Nf) * es;            // local complex bytes
   const double Rb = (double)(Np0 * N1 * N2) * rs;            // local real-space bytes
+  if (P == 1 && split_last_route()) return slab_forward_split_last(u, fu);
   if (P == 1) {
     const int64_t Z = Zc();          // row pitch of the spectrum and of the intermediates: Nf, or the caller's pitch
     if (const int64_t xpad = p1_plane_pad()) {
@@ -136,6 +199,7 @@ int mfft_plan_s::slab_backward(const void* fu, void* u, bool masked) {
   const double Rb = (double)(Np0 * N1 * N2) * rs;
   const void* src = fu;
   MaskScope mask_scope{this};
+  if (!masked && P == 1 && split_last_route()) return slab_backward_split_last(fu, u);
   if (masked && band_ok && prune_enabled()) {
     MFFT_TRY(require_mask());
     return slab_backward_pruned(fu, u);

@@ -31,7 +31,9 @@ enum class Op : unsigned {
   // FAM_ROW / FAM_R2C / FAM_C2R, flags (Limited | ZChunk: the 3/2-rule pencils):
   Limited = 8,      // column-limited (3/2-rule, pruned 2/3-rule)
   ZChunk = 16,      // complex side split into z chunks (fused pencil pack / unpack)
-  TopFlag = ZChunk
+  // FAM_R2C / FAM_C2R, on its own:
+  PairRows = 32,    // the real side is the x and y transform of the real field read as complex pairs (fft_kernels.h PAIR)
+  TopFlag = PairRows
 };
 constexpr Op operator|(Op a, Op b) { return (Op)((unsigned)a | (unsigned)b); }
 constexpr bool has(Op a, Op flag) { return ((unsigned)a & (unsigned)flag) != 0; }
@@ -530,6 +532,17 @@ template <class S, typename T> constexpr bool c2r_mlds_candidate() {
   if (S::E == 20 && (S::N == 400 || S::N == 500 || S::N == 800 || S::N == 1000 || S::N == 2000)) return true;
   return false;
 }
+// Pair-row kernels (Op::PairRows; the one-rank slab route that splits real / complex at the spectrum end, plan_slab.hip): double
+// precision, real length 1024 -- where the route was measured -- and 2048, and real 64 / 256 so that tests and the emulator can
+// force the route on small meshes.  Whole-complex exchange buffers (the partner row's mirrors are read out of them), rows by
+// the same LDS budget as the plain kernels.
+template <class S, typename T> constexpr bool pair_rows_plan() {
+  return sizeof(T) == 8 && S::NP > 1 && (S::N == 32 || S::N == 128 || S::N == 512 || S::N == 1024);
+}
+template <class S, typename T> constexpr int pair_rows() {
+  constexpr int r = row_rows_n<S, T, false>();
+  return r < 2 ? 2 : r;
+}
 template <class S, typename T>
 void register_rows(const char* name) {
   auto& reg = kernel_registry();
@@ -594,6 +607,14 @@ void register_rows(const char* name) {
     c2r(tag<Op::Limited>, tag<false>, tag<WOV>);
   // Round 6: c2r kernels that no wave shuffle serves, with the mirrors through LDS instead of a second load (C2RFft MLDS;
   // Build::LdsMirrors; core.hip select_real takes them where they exist, MFFT_C2R_MLDS=0: never)
+  if constexpr (pair_rows_plan<S, T>()) {
+    constexpr int RP = pair_rows<S, T>();
+    constexpr bool TP = S::N <= 512;       // twiddles in LDS where the plain kernels of the plan keep them there
+    reg.push_back(make_entry<R2CFft<S, T, RP, TP, false, false, false, false, true>, RealPairParams<T>, S, T>(
+        FAM_R2C, 2 * S::N, 0, Op::PairRows, Build::Default, RP, name));
+    reg.push_back(make_entry<C2RFft<S, T, RP, TP, false, false, false, false, false, true>, RealPairParams<T>, S, T>(
+        FAM_C2R, 2 * S::N, 1, Op::PairRows, Build::Default, RP, name));
+  }
   if constexpr (c2r_mlds_candidate<S, T>()) {
     c2r(tag<Op::Plain>, tag<true>, tag<WOC>);
     c2r(tag<Op::ZChunk>, tag<true>, tag<WOV>);

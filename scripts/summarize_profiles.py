@@ -36,6 +36,9 @@ def short(name):
         for i, nm in enumerate(("limit", "chunk", "split")):
             if len(tail) > i and tail[i] == "true":
                 extra += " " + nm
+        pair_at = 4 if fam == "R2CFft" else 5                         # ..., WP, (MLDS), PAIR
+        if len(tail) > pair_at and tail[pair_at] == "true":
+            extra += " pair"
     elif fam == "RowFft":                                             # (INV), TWLDS, CHUNK, SPLIT
         for i, nm in ((1, "chunk"), (2, "split")):
             if len(tail) > i and tail[i] == "true":
