@@ -237,6 +237,12 @@ MFFT_API int mfft_c2r_last(const void* in, void* out, const int64_t real_shape[3
  * of six FFT.ifftn + three FFT.fftn around the demo's cross product (demo/spectral_dns_solver.py:53-71). */
 MFFT_API int mfft_nlz_rows(const void* a, const void* b, void* out, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
                            int precision, int sync);
+/* The same stage with the DOT product (the z stages of mfft_nonlinear_dot): a, b are (3, nrows, pitch) as above, out is ONE
+ * (nrows, pitch) array; out[row] = rfft(sum_f irfft(a[f, row]) irfft(b[f, row]))[:valid].  out may be any one component of a
+ * or b.  MFFT_ERR_UNSUPPORTED for lengths without a kernel.  Replaces the z stages of six FFT.ifftn + one FFT.fftn around
+ * a caller's np.sum(U * gradT, 0). */
+MFFT_API int mfft_nlz_dot_rows(const void* a, const void* b, void* out, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
+                               int precision, int sync);
 /* slab pack / unpack (slab.py:403; cython/maths.pyx:21-31 transpose_Uc) */
 MFFT_API int mfft_slab_pack(const void* uc_hatT, void* u_mpi, int P, int64_t np0, int64_t np1, int64_t nf, int precision);
 MFFT_API int mfft_slab_unpack(const void* u_mpi, void* uc_hatT, int P, int64_t np0, int64_t np1, int64_t nf, int precision);
@@ -269,6 +275,14 @@ MFFT_API int mfft_kernel_name(int family, int64_t n, int precision, int inverse,
 MFFT_API int mfft_ew_cross(mfft_plan_t plan, const void* a, const void* b, void* out, size_t n, int precision);          /* demo:53-58 */
 MFFT_API int mfft_ew_curl_hat(mfft_plan_t plan, const void* U_hat, void* out, const void* kx, const void* ky, const void* kz,
                               const int64_t shape[3], int precision);                                   /* demo:60-64 */
+/* out = sum_f a_f b_f on real fields, a and b (3, n) component-major, out (n): what a caller writes as np.sum(a * b, 0);
+ * out may be a component of a or b */
+MFFT_API int mfft_ew_dot(mfft_plan_t plan, const void* a, const void* b, void* out, size_t n, int precision);
+/* out_f = i K_f s_hat, the gradient of a scalar in spectral space: s_hat has `shape`, out is (3,) + shape; kx / ky / kz and
+ * `shape` as for mfft_ew_curl_hat (pitched spectra: shape[2] = the row pitch, kz padded to it).  What a caller writes as
+ * 1j * K * s_hat. */
+MFFT_API int mfft_ew_grad_hat(mfft_plan_t plan, const void* s_hat, void* out, const void* kx, const void* ky, const void* kz,
+                              const int64_t shape[3], int precision);
 MFFT_API int mfft_ew_ns_rhs(mfft_plan_t plan, void* dU, const void* U_hat, const void* kx, const void* ky, const void* kz,
                             const int64_t shape[3], double nu, int precision);                          /* demo:73-77 */
 MFFT_API int mfft_ew_axpbz(mfft_plan_t plan, void* y, const void* x, const void* z, double alpha, double beta, size_t n_real,
@@ -294,6 +308,17 @@ MFFT_API int mfft_ew_sumsq(mfft_plan_t plan, const void* x, size_t n_real, int p
  * real-space work arrays of the composition (9 x 1536^3 x 8 B at 1024^3 with the 3/2-rule) never exist.  Every other plan
  * runs the composition on work arrays of its own.  Enqueued on the plan's stream like mfft_forward. */
 MFFT_API int mfft_nonlinear_cross(mfft_plan_t plan, const void* a_hat, const void* b_hat, void* out_hat, int dealias);
+
+/* The advection term of a transported scalar as ONE operation:
+ *     out_hat = fftn(sum_f ifftn(a_hat[f]) * ifftn(b_hat[f]))        (dot product in real space: u . grad(theta))
+ * with the plan's own transforms under `dealias` -- what a caller composes from six FFT.ifftn(.., dealias), np.sum(A * B, 0)
+ * and one FFT.fftn(.., dealias).  a_hat, b_hat: (3,) + local complex shape, component-major; out_hat: the local complex
+ * shape (ONE component), which may be any one component of a_hat or b_hat; the inputs are otherwise preserved.  The routes
+ * are those of mfft_nonlinear_cross (mfft_plan_get_info "nonlinear_dot_fused_3_2" / "_none" / "_2_3"): on slab R2C plans with
+ * radix kernels on every axis the z stages are ONE kernel (csrc/fft_nlz.h body_dot: the products are accumulated in
+ * registers as the three inverse pairs finish, two rows' sums ride on one forward transform) and the seven real-space
+ * arrays of the composition never exist; every other plan composes it on seven work arrays of its own. */
+MFFT_API int mfft_nonlinear_dot(mfft_plan_t plan, const void* a_hat, const void* b_hat, void* out_hat, int dealias);
 
 /* Direct evaluation of up to 16 DFT bins of a distributed field, for checking transforms of meshes that no host
  * transform can hold (BASELINE config 5, 2048^3): result[2b], result[2b+1] = Re, Im of

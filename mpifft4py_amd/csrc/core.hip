@@ -526,7 +526,8 @@ int launch_r2c(const RealArgs& a, hipStream_t s) { return launch_real(FAM_R2C, a
 int launch_c2r(const RealArgs& a, hipStream_t s) { return launch_real(FAM_C2R, a, s); }
 
 // fused nonlinear z stage (fft_nlz.h): out_f = rfft((irfft(a) x irfft(b))_f) along the contiguous axis, row by row
-bool nlz_supported(int64_t n, int prec) {
+bool nlz_supported(int64_t n, int prec, Op product) {
+  if (product == Op::Dot) return n >= 2 && n < 65536 && find_kernel(FAM_NLZ, (int)n, prec, 0, Op::Dot) != nullptr;
   return n >= 2 && n < 65536 && (find_kernel(FAM_NLZ, (int)n, prec, 0) != nullptr || find_kernel(FAM_NLZ, (int)n, prec, 0, Op::Plain, Build::Nlz3) != nullptr);
 }
 template <typename T>
@@ -548,18 +549,19 @@ static int launch_nlz_t(const KernelEntry* e, const NlzArgs& a, void* tw, void* 
   return launch_rows(e, P, a.nrows, 2 * e->tile, s);      // a thread group works through a PAIR of rows
 }
 int launch_nlz(const NlzArgs& a, hipStream_t s) {
-  const KernelEntry* e = a.n < 65536 ? find_kernel(FAM_NLZ, a.n, a.prec, 0) : nullptr;
+  const bool dot = a.product == Op::Dot;
+  const KernelEntry* e = a.n < 65536 ? find_kernel(FAM_NLZ, a.n, a.prec, 0, a.product) : nullptr;
   // 3/2-rule rows (n = 3 L with the L + 1 bins of the un-padded mesh) also have the pruned kernel (fft_nlz.h Nlz3Fft: three
   // sub-transforms of length L in three thread groups, a third of the registers).  Measured EVEN with NlzFft at 768 (1.36 ms per
   // 73,728 rows both) and behind at 1536 (1.80 - 1.91 against 1.59 ms per 36,864 rows): profiles/r06_nlz_variants.txt -- its
   // staging and combination cost what the skipped radix-3 pass saves.  MFFT_NLZ3=1 takes it; where NlzFft has no plan it runs anyway.
   static const int nlz3_on = getenv("MFFT_NLZ3") ? atoi(getenv("MFFT_NLZ3")) : 0;
   const bool rows3 = a.n % 3 == 0 && a.valid == a.n / 3 + 1 && a.n < 65536;
-  if ((nlz3_on || !e) && rows3)
+  if ((nlz3_on || !e) && rows3 && !dot)          // (Nlz3Fft has the cross product only: MFFT_NLZ3 does not touch the dot route)
     if (const KernelEntry* e3 = find_kernel(FAM_NLZ, a.n, a.prec, 0, Op::Plain, Build::Nlz3)) e = e3;
-  if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused nonlinear z-stage kernel of length %d", a.n);
+  if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused nonlinear z-stage kernel of length %d%s", a.n, dot ? " (dot product)" : "");
   for (int f = 0; f < 3; ++f)
-    if (!a.a[f] || !a.b[f] || !a.out[f]) return set_error(MFFT_ERR_INVALID, "null argument");
+    if (!a.a[f] || !a.b[f] || !a.out[dot ? 0 : f]) return set_error(MFFT_ERR_INVALID, "null argument");
   void *tw = nullptr, *rt3 = nullptr;
   MFFT_TRY(prepare_kernel(e, &tw));
   if (e->build == Build::Nlz3) MFFT_TRY(nlz3_twiddles(a.n / 3, a.prec, &rt3));

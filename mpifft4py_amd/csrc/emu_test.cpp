@@ -1324,6 +1324,95 @@ static void test_nlz(int valid, bool inplace, int valid_in = 0) {      // valid_
   snprintf(name, sizeof name, "nlz r%d v%d/%d%s%s%s%s", ROWS, vin, valid, TWLDS ? " twlds" : "", SPLIT ? " split" : "", inplace ? " inpl" : "", WAVE ? " wave" : "");
   report(name, M, pname<T>(), (double)sqrtl(num / den), sizeof(T) == 8 ? 4e-14 : 2e-5);
 }
+// ... with the dot product (NlzFft::body_dot): out = rfft(sum_f irfft(a_f) irfft(b_f)), one row out per six rows in.
+// alias: 0 out of place, 1 the result over a_0, 2 over b_1 (row for row); the other five inputs must come back untouched
+template <class S, typename T, int ROWS, bool TWLDS, bool SPLIT, bool WAVE = false>
+static void test_nld(int valid, int alias, int valid_in = 0) {
+  typedef NlzProd<NlzFft<S, T, ROWS, TWLDS, SPLIT, WAVE>, NlzProduct::Dot> K;
+  const int vin = valid_in > 0 ? valid_in : valid;
+  const int M = S::N;
+  const int nrows = 2 * ROWS + 3;                 // an odd count: the last pair has one row
+  const int pin = valid + 2, pout = alias ? pin : valid + 1;
+  std::mt19937_64 rng(2424 + M + valid);
+  std::uniform_real_distribution<double> U(-1, 1);
+  std::vector<cx<T>> in[6], out;
+  for (auto& f : in) {
+    f.resize((size_t)nrows * pin);
+    for (auto& z : f) z = mk<T>((T)U(rng), (T)U(rng));
+  }
+  std::vector<cx<T>> keep[6];
+  for (int f = 0; f < 6; ++f) keep[f] = in[f];
+  out.assign((size_t)nrows * pout, mk<T>((T)7, (T)7));
+  const int af = alias == 1 ? 0 : alias == 2 ? 4 : -1;      // the input field the result lies over
+  auto tw = build_pass_twiddles<S, T>();
+  NlzParams<T> P;
+  for (int f = 0; f < 3; ++f) { P.a[f] = in[f].data(); P.b[f] = in[3 + f].data(); P.out[f] = nullptr; }
+  P.out[0] = af >= 0 ? in[af].data() : out.data();
+  P.tw = tw.data(); P.in_stride = pin; P.out_stride = pout; P.nrows = nrows; P.valid = valid; P.valid_in = vin;
+  P.scale = (T)(1.0 / ((double)M * (double)M));
+  P.rt3 = nullptr;
+  emu_launch((nrows + 2 * ROWS - 1) / (2 * ROWS), K::THREADS, K::LDS_BYTES, [&](int b, int t, char* lds) { K::body(P, b, t, lds); });
+  long double num = 0, den = 0;
+  for (int r = 0; r < nrows; ++r) {
+    std::vector<std::vector<long double>> re(6, std::vector<long double>(M));
+    for (int f = 0; f < 6; ++f) {
+      lvec X(M);
+      for (int p = 0; p < M; ++p) { X[p].x = 0; X[p].y = 0; }
+      for (int q = 0; q < vin; ++q) {
+        cx<T> z = keep[f][(size_t)r * pin + q];
+        long double zr = z.x, zi = z.y;
+        if (q == 0 || (M % 2 == 0 && q == M / 2)) zi = 0;
+        X[q].x = zr; X[q].y = zi;
+        if (q != 0 && q != M - q) { X[M - q].x = zr; X[M - q].y = -zi; }
+      }
+      lvec x = naive_dft(X, +1);
+      for (int p = 0; p < M; ++p) re[f][p] = x[p].x / M;
+    }
+    lvec x(M);
+    for (int p = 0; p < M; ++p) { x[p].x = re[0][p] * re[3][p] + re[1][p] * re[4][p] + re[2][p] * re[5][p]; x[p].y = 0; }
+    lvec X = naive_dft(x, -1);
+    const cx<T>* g = P.out[0] + (size_t)r * pout;
+    for (int q = 0; q < valid; ++q) {
+      num += (g[q].x - X[q].x) * (g[q].x - X[q].x) + (g[q].y - X[q].y) * (g[q].y - X[q].y);
+      den += X[q].x * X[q].x + X[q].y * X[q].y;
+    }
+    for (int q = valid; q < pout; ++q) {           // nothing is stored beyond the valid bins
+      const cx<T> was = af >= 0 ? keep[af][(size_t)r * pin + q] : mk<T>((T)7, (T)7);
+      if (g[q].x != was.x || g[q].y != was.y) num += 1;
+    }
+  }
+  for (int f = 0; f < 6; ++f)                      // the inputs are preserved (but for the one the result lies over)
+    if (f != af && memcmp(in[f].data(), keep[f].data(), keep[f].size() * sizeof(cx<T>)) != 0) num += 1;
+  char name[72];
+  snprintf(name, sizeof name, "nld r%d v%d/%d%s%s%s%s", ROWS, vin, valid, TWLDS ? " twlds" : "", SPLIT ? " split" : "",
+           alias == 1 ? " over a0" : alias == 2 ? " over b1" : "", WAVE ? " wave" : "");
+  report(name, M, pname<T>(), (double)sqrtl(num / den), sizeof(T) == 8 ? 4e-14 : 2e-5);
+}
+template <class S> static void test_nld_all() {
+  const int M = S::N;
+  const int full = M / 2 + 1, lim = M / 3 + 1;     // every bin / the bins of the un-padded mesh under the 3/2-rule
+  if constexpr (S::TPT <= 64 && 64 % S::TPT == 0) {      // the wave-synchronous build
+    test_nld<S, double, 2, true, false, true>(lim, 1);
+    test_nld<S, double, 1, false, false, true>(full, 2);
+    test_nld<S, float, 3, false, false, true>(full, 0);
+    test_nld<S, float, 2, true, false, true>(lim, 2);
+  }
+  test_nld<S, double, 2, true, false>(full, 0);
+  test_nld<S, double, 1, false, true>(lim, 1);
+  test_nld<S, double, 2, true, true>(full, 2);
+  test_nld<S, double, 3, false, false>(lim, 0);
+  test_nld<S, float, 3, false, false>(lim, 0);
+  test_nld<S, float, 2, true, true>(full, 1);
+  test_nld<S, float, 1, false, true>(lim, 2);
+  test_nld<S, float, 2, true, false>(full, 2);
+  if (lim < full) {                                 // pruned 2/3-rule: the kept kz bins in, every bin out
+    test_nld<S, double, 2, true, false>(full, 1, lim);
+    test_nld<S, double, 1, false, true>(full, 0, lim);
+    test_nld<S, float, 3, false, false>(full, 0, (2 * full) / 3);
+    test_nld<S, float, 2, true, true>(full, 2, (2 * full) / 3);
+  }
+}
+
 // the pruned 3/2-rule flavour (Nlz3Fft): M = 3 L, L + 1 bins per row, three sub-transforms per row
 template <class SL, typename T, int ROWS, bool TWLDS>
 static void test_nlz3(bool inplace) {
@@ -1559,6 +1648,11 @@ int main() {
   MFFT_NLZ3PLANS(MFFT_NLZ3)
   test_nlz3_all<Spec<256, 8, 8, 4>>();
 #undef MFFT_NLZ3
+#endif
+#if EMU_HAS(18)      // (a binary of its own, `make emu_nld`: tests/test_cabi.py fixes the number of the emu_test_* parts)
+#define MFFT_NLD(N, ...) test_nld_all<Spec<N, __VA_ARGS__>>();
+  MFFT_NLZPLANS_P2(MFFT_NLD) MFFT_NLZPLANS_3(MFFT_NLD) MFFT_NLZPLANS_9(MFFT_NLD)     // the fused nonlinear z stage, dot product
+#undef MFFT_NLD
 #endif
 #if EMU_HAS(1)
   // pair-row kernels (with plan group B, where the shipped 512 / 1024 plans are; tests/test_cabi.py fixes the number of parts): even and odd meshes (self-paired planes and rows), a partial last workgroup, the shipped shapes

@@ -217,6 +217,69 @@ struct NlzFft {
       }
     }
   }
+
+  // The same stage with the DOT product, out[0] = rfft(sum_f irfft(a_f) irfft(b_f)): the term u . grad(theta) of a transported
+  // scalar.  A sum accumulates, so nothing is parked: after each inverse pair s[k] += a_f[k] b_f[k], E reals, and E more hold the
+  // sum of the first row of a pair while the second is computed; the two sums then ride on ONE forward transform, as r2 does
+  // above.  3.5 transforms and 7 rows of `valid` bins per (x, y) point instead of 4.5 and 9; out[1], out[2] are not read.
+  // All six rows of both (x, y) points are loaded before the first store, so out[0] may alias any a[f] or b[f] row for row.
+  static MFFT_D void body_dot(const NlzParams<T>& P, int bid, int tid, char* lds) {
+    cx<T>* ltw = reinterpret_cast<cx<T>*>(lds);
+    const int rl = tid / S::TPT;
+    const int j = row_thread_index<S>(tid);
+    XE* xb = reinterpret_cast<XE*>(lds + TW_BYTES) + rl * PLEN;
+    if constexpr (TWLDS && S::NP > 1) {
+      stage_twiddles<S, T>(ltw, P.tw, tid, THREADS);
+      if constexpr (WAVE) MFFT_BARRIER();
+    }
+    const cx<T>* tw = (TWLDS && S::NP > 1) ? (const cx<T>*)ltw : P.tw;
+    Xch xc{xb, PadSlot<PD>{}};
+    const i64 unit = (i64)bid * ROWS + rl;         // a pair of rows
+    T s0[E];
+#pragma unroll
+    for (int k = 0; k < E; ++k) s0[k] = (T)0;
+    bool sa = false;
+    i64 rowa = 0;
+#pragma unroll 1
+    for (int h = 0; h < 2; ++h) {
+      const i64 row = 2 * unit + h;
+      const bool active = row < P.nrows;           // rows past the end re-read the last row and store nothing
+      const i64 lrow = active ? row : P.nrows - 1;
+      const i64 io = lrow * P.in_stride;
+      cx<T> v[E];
+      T s[E];
+      // the results are swapped (inverse through the swap identity): .y = a_f, .x = b_f at position j + k TPT
+      inverse_pair(v, P.a[0] + io, P.b[0] + io, j, P.valid_in, tw, xc);
+#pragma unroll
+      for (int k = 0; k < E; ++k) s[k] = v[k].x * v[k].y;
+      inverse_pair(v, P.a[1] + io, P.b[1] + io, j, P.valid_in, tw, xc);
+#pragma unroll
+      for (int k = 0; k < E; ++k) s[k] += v[k].x * v[k].y;
+      inverse_pair(v, P.a[2] + io, P.b[2] + io, j, P.valid_in, tw, xc);
+#pragma unroll
+      for (int k = 0; k < E; ++k) s[k] += v[k].x * v[k].y;
+      if (h == 0) {
+#pragma unroll
+        for (int k = 0; k < E; ++k) s0[k] = s[k];
+        sa = active;
+        rowa = row;
+      } else {
+#pragma unroll
+        for (int k = 0; k < E; ++k) v[k] = mk<T>(s0[k] * P.scale, s[k] * P.scale);
+        forward_pair(v, j, tw, xc, xb, P.out[0] + rowa * P.out_stride, P.out[0] + row * P.out_stride, sa, active, P.valid);
+      }
+    }
+  }
+};
+
+// The product of the stage as a parameter of the kernel: NlzProd<K, NlzProduct::Dot> is K's rows, exchanges and transforms
+// around the dot product.  (A wrapper, not a seventh parameter of NlzFft: that would rename every cross-product kernel's
+// symbol, and scripts/kernel_regs.py --diff could no longer show that they are what they were.)
+enum class NlzProduct { Cross = 0, Dot = 1 };
+template <class K, NlzProduct PRODUCT = NlzProduct::Cross> struct NlzProd : K {};
+template <class K> struct NlzProd<K, NlzProduct::Dot> {
+  static constexpr int THREADS = K::THREADS, LDS_BYTES = K::LDS_BYTES;
+  template <class P> static MFFT_D void body(const P& p, int bid, int tid, char* lds) { K::body_dot(p, bid, tid, lds); }
 };
 
 // ---------------------------------------------------------------------------

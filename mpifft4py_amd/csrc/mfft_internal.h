@@ -113,7 +113,7 @@ int launch_c2r(const RealArgs& a, hipStream_t s);
 bool pair_rows_supported(int64_t n, int prec);     // both pair-row kernels of real length n exist
 
 // fused nonlinear z stage (fft_nlz.h): rows of half-spectra of two vector fields in, rows of the half-spectra of their
-// cross product out (may alias the inputs row for row)
+// cross product out (may alias the inputs row for row) -- or, product = Op::Dot, the ONE row out[0] of their dot product
 struct NlzArgs {
   const void* a[3] = {nullptr, nullptr, nullptr};
   const void* b[3] = {nullptr, nullptr, nullptr};
@@ -124,8 +124,9 @@ struct NlzArgs {
   int valid = 0;         // bins per row present in memory (0 = all n/2+1)
   int valid_in = 0;      // bins per INPUT row, where fewer than `valid` exist (pruned 2/3-rule); 0 = valid
   double scale = 1.0;    // applied to the product (1 / n^2: both inverse transforms normalised)
+  Op product = Op::Plain;  // Op::Plain: a x b into out[0..2];  Op::Dot: sum_f a_f b_f into out[0], out[1..2] unused
 };
-bool nlz_supported(int64_t n, int prec);
+bool nlz_supported(int64_t n, int prec, Op product = Op::Plain);
 int launch_nlz(const NlzArgs& a, hipStream_t s);
 
 // strided 3-D box copy: dst[i][j][k] = src[i][j][k] over extents e0,e1,e2 with

@@ -342,6 +342,16 @@ int mfft_nonlinear_cross(mfft_plan_t p, const void* a_hat, const void* b_hat, vo
   return p->nonlinear_cross(a_hat, b_hat, out_hat, dealias);
 }
 
+// out = fftn(sum_f ifftn(a_f) ifftn(b_f)): a, b as above, out ONE component (the local complex shape); out may be any one
+// component of a or b.  See include/mpifft4py_amd.h.
+int mfft_nonlinear_dot(mfft_plan_t p, const void* a_hat, const void* b_hat, void* out_hat, int dealias) {
+  MFFT_TRY(check_ready(p, a_hat, b_hat));
+  if (!out_hat) return set_error(MFFT_ERR_INVALID, "null argument");
+  if (dealias != MFFT_DEALIAS_NONE && dealias != MFFT_DEALIAS_2_3 && dealias != MFFT_DEALIAS_3_2)
+    return set_error(MFFT_ERR_INVALID, "unknown dealias mode %d", dealias);
+  return p->nonlinear_dot(a_hat, b_hat, out_hat, dealias);
+}
+
 int mfft_plan_sync(mfft_plan_t p) {
   if (!p) return set_error(MFFT_ERR_INVALID, "null plan");
   if (p->cstream) MFFT_HIP(hipStreamSynchronize(p->cstream));
@@ -364,6 +374,9 @@ int mfft_plan_get_info(mfft_plan_t p, const char* key, int64_t* value) {
   else if (k == "nonlinear_fused_none") *value = p->nonlinear_fusable(MFFT_DEALIAS_NONE) ? 1 : 0;
   else if (k == "nonlinear_fused_2_3") *value = p->nonlinear_fusable(MFFT_DEALIAS_2_3) ? 1 : 0;
   else if (k == "nonlinear_fused_3_2") *value = p->nonlinear_fusable(MFFT_DEALIAS_3_2) ? 1 : 0;
+  else if (k == "nonlinear_dot_fused_none") *value = p->nonlinear_fusable(MFFT_DEALIAS_NONE, Op::Dot) ? 1 : 0;
+  else if (k == "nonlinear_dot_fused_2_3") *value = p->nonlinear_fusable(MFFT_DEALIAS_2_3, Op::Dot) ? 1 : 0;
+  else if (k == "nonlinear_dot_fused_3_2") *value = p->nonlinear_fusable(MFFT_DEALIAS_3_2, Op::Dot) ? 1 : 0;
   else if (k == "nonlinear_bytes") *value = (int64_t)(p->nlx.bytes + p->nly.bytes + p->nlr.bytes + p->nlw[0].bytes + p->nlw[1].bytes);
   else if (k == "split_last") *value = p->split_last_route() ? 1 : 0;   // the one-rank route that splits real / complex last (decides whether the work buffer fits, if no call has yet)
   else if (k == "plane_pad") *value = (p->P == 1 && p->d.decomp == MFFT_SLAB) ? p->p1_plane_pad() : 0;   // elements added to the intermediate's plane pitch

@@ -476,12 +476,15 @@ struct mfft_plan_s {
   int exec(bool forward, const void* in, void* out, int dealias);       // one transform, pitched callers' arrays converted where needed
 
   // ---- round 6: the nonlinear term a x b of a pseudo-spectral step as one operation (fft_nlz.h; plan_nonlinear.hip) ----
-  bool nonlinear_fusable(int dealias) const;
+  // (product: mfft::Op::Plain the cross product, three result components; mfft::Op::Dot the dot product, one)
+  bool nonlinear_fusable(int dealias, mfft::Op product = mfft::Op::Plain) const;
   int64_t local_real_count(bool padded) const;
   int nonlinear_cross(const void* a, const void* b, void* out, int dealias);
-  int nonlinear_cross_fused(const void* a, const void* b, void* out, int dealias);
-  int nonlinear_cross_fused_ranks(const void* a, const void* b, void* out, int dealias);
-  int nonlinear_cross_composed(const void* a, const void* b, void* out, int dealias);
+  int nonlinear_dot(const void* a, const void* b, void* out, int dealias);      // out: ONE component; may alias one of a's or b's
+  int nonlinear(const void* a, const void* b, void* out, int dealias, mfft::Op product);
+  int nonlinear_fused(const void* a, const void* b, void* out, int dealias, mfft::Op product);
+  int nonlinear_fused_ranks(const void* a, const void* b, void* out, int dealias, mfft::Op product);
+  int nonlinear_composed(const void* a, const void* b, void* out, int dealias, mfft::Op product);
 };
 
 namespace mfft {

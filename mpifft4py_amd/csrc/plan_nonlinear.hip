@@ -8,6 +8,11 @@ using namespace mfft;
 // (what demo/spectral_dns_solver.py:53-71 composes from six ifftn, a cross product in real space and three fftn).
 // ===========================================================================
 extern "C" int mfft_ew_cross(mfft_plan_t plan, const void* a, const void* b, void* out, size_t n, int precision);
+extern "C" int mfft_ew_dot(mfft_plan_t plan, const void* a, const void* b, void* out, size_t n, int precision);
+// Two products share every route below: Op::Plain, the cross product (three result components), and Op::Dot, the dot product
+// sum_f ifftn(a_f) ifftn(b_f) of a transported scalar's u . grad(theta) (ONE result component: nout = 1 -- one forward y pass,
+// one forward exchange, one forward x pass; seven work arrays instead of nine in the composition).
+static int nl_nout(Op product) { return product == Op::Dot ? 1 : 3; }
 
 int64_t mfft_plan_s::local_real_count(bool padded) const {
   if (d.line2d) return 0;
@@ -15,12 +20,14 @@ int64_t mfft_plan_s::local_real_count(bool padded) const {
   return padded ? (int64_t)(d.padsize * N1_0) * (int64_t)(d.padsize * N2_1) * M2 : N1_0 * N2_1 * N2;
 }
 
-// Composed route (every decomposition and length): the transforms the caller would run, on nine work arrays of the plan.
-int mfft_plan_s::nonlinear_cross_composed(const void* a, const void* b, void* out, int dealias) {
+// Composed route (every decomposition and length): the transforms the caller would run, on nine (dot product: seven) work
+// arrays of the plan.
+int mfft_plan_s::nonlinear_composed(const void* a, const void* b, void* out, int dealias, Op product) {
+  const int nout = nl_nout(product);
   const bool pad = dealias == MFFT_DEALIAS_3_2, masked = dealias == MFFT_DEALIAS_2_3;
   const int64_t nr = local_real_count(pad), nc = local_complex_alloc();       // (pitched arrays: a component is that much larger)
-  if (nr <= 0 || !r2c) return set_error(MFFT_ERR_UNSUPPORTED, "nonlinear_cross needs a 3-D real-to-complex plan");
-  MFFT_TRY(ensure(nlr, (size_t)(9 * nr) * rs));
+  if (nr <= 0 || !r2c) return set_error(MFFT_ERR_UNSUPPORTED, "nonlinear_%s needs a 3-D real-to-complex plan", nout == 1 ? "dot" : "cross");
+  MFFT_TRY(ensure(nlr, (size_t)((6 + nout) * nr) * rs));
   char* R = static_cast<char*>(nlr.p);
   auto back = [&](const void* in, void* o) { return exec(false, in, o, dealias); };
   auto fwd = [&](const void* in, void* o) { return exec(true, in, o, masked ? (int)MFFT_DEALIAS_NONE : dealias); };
@@ -28,15 +35,15 @@ int mfft_plan_s::nonlinear_cross_composed(const void* a, const void* b, void* ou
     MFFT_TRY(back(static_cast<const char*>(a) + (size_t)(f * nc) * es, R + (size_t)(f * nr) * rs));
     MFFT_TRY(back(static_cast<const char*>(b) + (size_t)(f * nc) * es, R + (size_t)((3 + f) * nr) * rs));
   }
-  MFFT_TRY(stage("nl_cross", 9.0 * (double)nr * rs, [&] {
-    return mfft_ew_cross(this, R, R + (size_t)(3 * nr) * rs, R + (size_t)(6 * nr) * rs, (size_t)nr, prec);
+  MFFT_TRY(stage(nout == 1 ? "nl_dot" : "nl_cross", (6.0 + nout) * (double)nr * rs, [&] {
+    return (nout == 1 ? mfft_ew_dot : mfft_ew_cross)(this, R, R + (size_t)(3 * nr) * rs, R + (size_t)(6 * nr) * rs, (size_t)nr, prec);
   }));
-  for (int f = 0; f < 3; ++f) MFFT_TRY(fwd(R + (size_t)((6 + f) * nr) * rs, static_cast<char*>(out) + (size_t)(f * nc) * es));
+  for (int f = 0; f < nout; ++f) MFFT_TRY(fwd(R + (size_t)((6 + f) * nr) * rs, static_cast<char*>(out) + (size_t)(f * nc) * es));
   return 0;
 }
 
 // x planes per batch of the fused routes: `planes` planes whose six y-pass outputs take plane6 bytes each, cut into
-// equal batches of at most MFFT_NLZ_BATCH_MB (read once per process; default 16 GiB, see nonlinear_cross_fused)
+// equal batches of at most MFFT_NLZ_BATCH_MB (read once per process; default 16 GiB, see nonlinear_fused)
 static int64_t nlz_batch_planes(size_t plane6, int64_t planes) {
   static const long batch_mb = env_int("MFFT_NLZ_BATCH_MB", 16384);
   const int64_t nbat = (int64_t)((plane6 * (size_t)planes + ((size_t)batch_mb << 20) - 1) / ((size_t)batch_mb << 20));
@@ -44,14 +51,15 @@ static int64_t nlz_batch_planes(size_t plane6, int64_t planes) {
 }
 
 // the fused z stage on a batch: rows of the six fields in Y (yelems apart, pitch Za) in, the three rows of the cross product
-// out, in place on the first three
-static int nlz_rows(mfft_plan_s* p, char* Y, size_t yelems, int64_t L2, int64_t Za, int64_t nrows, int valid_in) {
+// (the one row of the dot product) out, in place on the first three (the first)
+static int nlz_rows(mfft_plan_s* p, char* Y, size_t yelems, int64_t L2, int64_t Za, int64_t nrows, int valid_in, Op product) {
   NlzArgs z;
   for (int f = 0; f < 3; ++f) {
     z.a[f] = Y + (size_t)f * yelems * p->es;
     z.b[f] = Y + (size_t)(3 + f) * yelems * p->es;
-    z.out[f] = Y + (size_t)f * yelems * p->es;
+    if (f < nl_nout(product)) z.out[f] = Y + (size_t)f * yelems * p->es;
   }
+  z.product = product;
   z.n = (int)L2; z.prec = p->prec; z.in_stride = Za; z.out_stride = Za; z.nrows = nrows; z.valid = (int)p->Nf;
   z.valid_in = valid_in;
   z.scale = 1.0 / ((double)L2 * (double)L2);
@@ -59,15 +67,15 @@ static int nlz_rows(mfft_plan_s* p, char* Y, size_t yelems, int64_t L2, int64_t 
 }
 
 // Fused route: one rank, slab, real data, radix kernels on every axis.
-bool mfft_plan_s::nonlinear_fusable(int dealias) const {
+bool mfft_plan_s::nonlinear_fusable(int dealias, Op product) const {
   static const bool off = env_on("MFFT_NO_NLZ"), ranks_off = env_on("MFFT_NO_NLZ_RANKS");      // read once per process
   if (off || d.decomp != MFFT_SLAB || !r2c || d.line2d || d.drop_nyquist || N0 < 2 || N1 < 2 || N2 < 2) return false;
   if (P > 1 && (ranks_off || pitched() || (dealias == MFFT_DEALIAS_3_2 && P > N0 / 2))) return false;
-  if (dealias == MFFT_DEALIAS_3_2) return can_fuse_pad() && nlz_supported(M2, prec);
+  if (dealias == MFFT_DEALIAS_3_2) return can_fuse_pad() && nlz_supported(M2, prec, product);
   auto plain_ok = [&](int64_t n) {
     return n < 65536 && find_kernel(FAM_COL, (int)n, prec, 0) && find_kernel(FAM_COL, (int)n, prec, 1);
   };
-  if (!plain_ok(N0) || !plain_ok(N1) || !nlz_supported(N2, prec)) return false;
+  if (!plain_ok(N0) || !plain_ok(N1) || !nlz_supported(N2, prec, product)) return false;
   if (dealias == MFFT_DEALIAS_2_3) return mask_set() && mask_fusable(N0, prec);
   return dealias == MFFT_DEALIAS_NONE;
 }
@@ -79,7 +87,10 @@ bool mfft_plan_s::nonlinear_fusable(int dealias) const {
 // planes of that batch are free by then.  Three forward x passes finish.  The real-space arrays never exist; the batch
 // buffers are at most 16 GiB (1024^3 with the 3/2-rule: 6 x 13.1 GB of x-pass buffers + 14.7 GB of batch buffers, where the
 // composed route needs 9 x 29 GB of real work arrays).
-int mfft_plan_s::nonlinear_cross_fused(const void* a, const void* b, void* out, int dealias) {
+// Op::Dot: the same with ONE result -- the z kernel writes the rows of the dot product in place on the first field, one forward
+// y pass per batch, one forward x pass.
+int mfft_plan_s::nonlinear_fused(const void* a, const void* b, void* out, int dealias, Op product) {
+  const int nout = nl_nout(product);
   const bool pad = dealias == MFFT_DEALIAS_3_2, masked = dealias == MFFT_DEALIAS_2_3;
   const int64_t L0 = pad ? M0 : N0, L1 = pad ? M1 : N1, L2 = pad ? M2 : N2;
   const int64_t line = (int64_t)(128 / es);
@@ -153,18 +164,18 @@ int mfft_plan_s::nonlinear_cross_fused(const void* a, const void* b, void* out, 
       }
       return 0;
     }));
-    MFFT_TRY(stage("nl_z", (6 * keep2 + 3) * Yb * frac, [&] {
-      return nlz_rows(this, Y, yelems, L2, Za, m * L1, pruned ? ba2 : 0);
+    MFFT_TRY(stage("nl_z", (6 * keep2 + nout) * Yb * frac, [&] {
+      return nlz_rows(this, Y, yelems, L2, Za, m * L1, pruned ? ba2 : 0, product);
     }));
-    MFFT_TRY(stage("nl_y_fwd", 3 * (Xb + Yb) * frac, [&] {
-      for (int f = 0; f < 3; ++f)
+    MFFT_TRY(stage("nl_y_fwd", nout * (Xb + Yb) * frac, [&] {
+      for (int f = 0; f < nout; ++f)
         MFFT_TRY(col_pad(Y + (size_t)f * yelems * es, X + ((size_t)f * xelems + (size_t)(i0 * N1 * Za)) * es, L1, false, pad ? Op::TruncStore : Op::Plain,
                          pad, m, Nf, L1 * Za, plain(Za), N1 * Za, plain(Za), 1.0));
       return 0;
     }));
   }
-  MFFT_TRY(stage("nl_x_fwd", 3 * (Cb + Xb), [&] {
-    for (int f = 0; f < 3; ++f) {
+  MFFT_TRY(stage("nl_x_fwd", nout * (Cb + Xb), [&] {
+    for (int f = 0; f < nout; ++f) {
       const void* src = X + (size_t)f * xelems * es;
       void* dst = static_cast<char*>(out) + (size_t)(f * C) * es;
       if (Zi == Za && Za != Nf)                    // pitched result
@@ -183,7 +194,9 @@ int mfft_plan_s::nonlinear_cross_fused(const void* a, const void* b, void* out, 
 // passes, six all-to-alls, then batches of the rank's x planes -- inverse y passes reading the receive layout through the
 // two-level row map (transpose_Uc fused, maths.pyx:21-31), the fused z kernel, forward y passes writing the packed send
 // layout (slab.py:403) -- three all-to-alls, three forward x passes.  Nine exchanges as in the composition, no real arrays.
-int mfft_plan_s::nonlinear_cross_fused_ranks(const void* a, const void* b, void* out, int dealias) {
+// (Op::Dot: six inverse exchanges and one forward exchange.)
+int mfft_plan_s::nonlinear_fused_ranks(const void* a, const void* b, void* out, int dealias, Op product) {
+  const int nout = nl_nout(product);
   const bool pad = dealias == MFFT_DEALIAS_3_2, masked = dealias == MFFT_DEALIAS_2_3;
   const int64_t L0 = pad ? M0 : N0, L1 = pad ? M1 : N1, L2 = pad ? M2 : N2, Lp0 = L0 / P;
   const int64_t line = (int64_t)(128 / es);
@@ -249,21 +262,21 @@ int mfft_plan_s::nonlinear_cross_fused_ranks(const void* a, const void* b, void*
       return 0;
     }));
     MFFT_TRY(stage("nl_z", 0, [&] {
-      return nlz_rows(this, Y, yelems, L2, Za, m * L1, pruned ? (int)a2 : 0);
+      return nlz_rows(this, Y, yelems, L2, Za, m * L1, pruned ? (int)a2 : 0, product);
     }));
     MFFT_TRY(stage("nl_y_fwd", 0, [&] {      // truncate + fold in y, straight into the packed (P, Lp0, S) send layout
-      for (int f = 0; f < 3; ++f)
+      for (int f = 0; f < nout; ++f)
         MFFT_TRY(col_pad(Y + (size_t)f * yelems * es, X + ((size_t)f * xelems + (size_t)(i0 * S)) * es, L1, false, pad ? Op::TruncStore : Op::Plain, pad, m,
                          Nf, L1 * Za, plain(Za), S, two_level(Np1, Lp0 * S, Nf), 1.0));
       return 0;
     }));
   }
   MFFT_TRY(stage("nl_a2a_fwd", 0, [&] {
-    for (int f = 0; f < 3; ++f) MFFT_TRY(xchg(0, true, pad, X + (size_t)f * xelems * es, R + (size_t)f * xelems * es));
+    for (int f = 0; f < nout; ++f) MFFT_TRY(xchg(0, true, pad, X + (size_t)f * xelems * es, R + (size_t)f * xelems * es));
     return 0;
   }));
   MFFT_TRY(stage("nl_x_fwd", 0, [&] {
-    for (int f = 0; f < 3; ++f)
+    for (int f = 0; f < nout; ++f)
       MFFT_TRY(col_pad(R + (size_t)f * xelems * es, static_cast<char*>(out) + (size_t)(f * C) * es, L0, false, pad ? Op::TruncStore : Op::Plain, pad, 1,
                        Np1 * Nf, 0, plain(S), 0, plain(Np1 * Nf), 1.0 / sc3));
     return 0;
@@ -271,8 +284,11 @@ int mfft_plan_s::nonlinear_cross_fused_ranks(const void* a, const void* b, void*
   return 0;
 }
 
-int mfft_plan_s::nonlinear_cross(const void* a, const void* b, void* out, int dealias) {
+int mfft_plan_s::nonlinear(const void* a, const void* b, void* out, int dealias, Op product) {
   if (dealias == MFFT_DEALIAS_2_3) MFFT_TRY(require_mask());
-  if (nonlinear_fusable(dealias)) return P == 1 ? nonlinear_cross_fused(a, b, out, dealias) : nonlinear_cross_fused_ranks(a, b, out, dealias);
-  return nonlinear_cross_composed(a, b, out, dealias);
+  if (nonlinear_fusable(dealias, product))
+    return P == 1 ? nonlinear_fused(a, b, out, dealias, product) : nonlinear_fused_ranks(a, b, out, dealias, product);
+  return nonlinear_composed(a, b, out, dealias, product);
 }
+int mfft_plan_s::nonlinear_cross(const void* a, const void* b, void* out, int dealias) { return nonlinear(a, b, out, dealias, Op::Plain); }
+int mfft_plan_s::nonlinear_dot(const void* a, const void* b, void* out, int dealias) { return nonlinear(a, b, out, dealias, Op::Dot); }

@@ -33,7 +33,9 @@ enum class Op : unsigned {
   ZChunk = 16,      // complex side split into z chunks (fused pencil pack / unpack)
   // FAM_R2C / FAM_C2R, on its own:
   PairRows = 32,    // the real side is the x and y transform of the real field read as complex pairs (fft_kernels.h PAIR)
-  TopFlag = PairRows
+  TopFlag = PairRows,
+  // FAM_NLZ (a value no other family uses, and no combination of the flags above):
+  Dot = 5           // the dot product sum_f a_f b_f instead of the cross product: one result row (fft_nlz.h body_dot)
 };
 constexpr Op operator|(Op a, Op b) { return (Op)((unsigned)a | (unsigned)b); }
 constexpr bool has(Op a, Op flag) { return ((unsigned)a & (unsigned)flag) != 0; }

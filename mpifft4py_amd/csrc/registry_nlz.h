@@ -34,6 +34,53 @@ void register_nlz(const char* name) {
   reg.push_back(make_entry<NlzFft<S, T, R, nlz_twlds<S, T>(), nlz_split<S, T>(), nlz_wave<S, T>()>, NlzParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::Plain, Build::Default, R, name));
 }
 
+// The same rows around the dot product (fft_nlz.h body_dot; Op::Dot).  It parks 2 E reals where the cross product parks 5 E, so
+// the register cap was derived again: what the compiler needs under each cap (profiles/nonlinear_dot_regs.tsv, VGPRs / bytes of scratch
+// per lane at 2, 3 and 4 waves per SIMD), then the candidates against each other on the device (profiles/nonlinear_dot_ab.txt,
+// section 3: one process, two builds of the library, alternating windows).
+//   12 values per thread (3 * 2^a, 9 * 2^a, 27 * 2^a), both precisions:  226 - 256 VGPRs at two waves WITHOUT the 8 - 500 bytes of
+//     scratch of their cross-product kernels (216 / 24 / 96 / 384 in double precision keep 8 - 80 bytes) -- but ONE transform of 12
+//     complex values with its twiddles already takes more than the 168 registers of three waves: 60 - 460 bytes of scratch there.
+//     Two waves, as the cross product.
+//   8 values (2^a), double precision:  129 - 164 VGPRs under a three-wave cap, no scratch -- and SLOWER than the two-wave build, which
+//     takes 150 - 162 by itself: 512: 0.391 -> 0.534 ms, 1024: 0.655 -> 0.871, 2048: 0.730 -> 0.898, 256: 0.204 -> 0.290.  Two waves.
+//   8 values, single precision:  114 - 128 VGPRs under a four-wave cap, no scratch.  Ahead from 1024 on (1024: 0.477 -> 0.412 ms,
+//     2048: 0.489 -> 0.428), behind at 512 (0.213 -> 0.250), even at 256 (three waves).  Four waves at 1024 and 2048, the
+//     lengths measured (4096, 512-thread workgroups, was not: two waves).
+// Rows per workgroup and the twiddle placement are the cross kernels' (nlz_rows, nlz_twlds); the exchange buffers go to real /
+// imaginary halves where the workgroups the cap admits, with their twiddle tables, would not fit the CU's 160 KB (nld_split:
+// with two waves per SIMD that is the cross kernels' rule, so every double-precision kernel has its twin's exchange).
+// MFFT_NLD_OCC = 2, 3, 4 forces one cap for every plan (0: none): the builds that were measured against each other.
+#ifndef MFFT_NLD_OCC
+#define MFFT_NLD_OCC -1
+#endif
+template <class S, typename T> constexpr int nld_occ() {
+  if (MFFT_NLD_OCC >= 0) return MFFT_NLD_OCC;
+  if (S::E == 8 && sizeof(T) == 4 && (S::N == 1024 || S::N == 2048)) return 4;
+  return 2;
+}
+template <class S, typename T> constexpr int nld_rows() { return nlz_rows<S, T>(); }          // (rows and twiddle placement: the cross
+template <class S, typename T> constexpr bool nld_twlds() { return nlz_twlds<S, T>(); }      // kernels' rules, not measured again)
+template <class S, typename T> constexpr bool nld_split() {
+  constexpr long long tw = nld_twlds<S, T>() ? (long long)S::TW * (int)sizeof(cx<T>) : 0;
+  // workgroups per CU that the cap leaves registers for: a workgroup takes ceil(waves / 4) waves' registers on every SIMD
+  // (registry.h, the dispatcher's rule); never fewer than two, the cross kernels' budget
+  constexpr int waves = (S::TPT * nld_rows<S, T>() + 63) / 64;
+  constexpr int wgs = nld_occ<S, T>() / ((waves + 3) / 4) > 2 ? nld_occ<S, T>() / ((waves + 3) / 4) : 2;
+  return (tw + (long long)padded_len<S::N, S::R(0)>() * nld_rows<S, T>() * (int)sizeof(cx<T>)) * wgs > 163840;
+}
+template <class S, typename T> constexpr bool nld_wave() {
+  return MFFT_NLZ_WAVE && S::TPT <= 64 && 64 % S::TPT == 0 && !nld_split<S, T>();
+}
+template <class S, typename T>
+void register_nld(const char* name) {
+  auto& reg = kernel_registry();
+  constexpr int R = nld_rows<S, T>();
+  constexpr int W = nld_occ<S, T>() > 1 ? 16 + nld_occ<S, T>() : 0;
+  typedef NlzProd<NlzFft<S, T, R, nld_twlds<S, T>(), nld_split<S, T>(), nld_wave<S, T>()>, NlzProduct::Dot> K;
+  reg.push_back(make_entry<K, NlzParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::Dot, Build::Default, R, name));
+}
+
 // ... and its pruned 3/2-rule flavour (Nlz3Fft: Build::Nlz3, entry.n = M = 3 L): three thread groups of SL::TPT threads per row
 template <class SL, typename T> constexpr int nlz3_rows() { return 256 / (3 * SL::TPT) > 0 ? 256 / (3 * SL::TPT) : 1; }
 template <class SL, typename T>

@@ -31,6 +31,29 @@ __global__ __launch_bounds__(EW_BLOCK) void cross_kernel(const T* __restrict__ a
   }
 }
 
+// out = sum_f a_f b_f   (real space: u . grad(theta) of a transported scalar)
+template <typename T>
+__global__ __launch_bounds__(EW_BLOCK) void dot_kernel(const T* a, const T* b, T* out, size_t n) {      // (out may be a component of a or b)
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    out[i] = a[i] * b[i] + a[n + i] * b[n + i] + a[2 * n + i] * b[2 * n + i];
+}
+
+// out_f = i K_f s   (spectral space: the gradient of a scalar)
+template <typename T>
+__global__ __launch_bounds__(EW_BLOCK) void grad_kernel(const cx<T>* __restrict__ S, cx<T>* __restrict__ out,
+                                                       const T* __restrict__ kx, const T* __restrict__ ky,
+                                                       const T* __restrict__ kz, int64_t s1, int64_t s2, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const int64_t k = (int64_t)(i % s2), j = (int64_t)((i / s2) % s1), l = (int64_t)(i / (s2 * s1));
+    const T K0 = kx[l], K1 = ky[j], K2 = kz[k];
+    const cx<T> v = S[i];
+    // i * (a) = (-a.y, a.x)
+    out[i] = mk<T>(-K0 * v.y, K0 * v.x);
+    out[n + i] = mk<T>(-K1 * v.y, K1 * v.x);
+    out[2 * n + i] = mk<T>(-K2 * v.y, K2 * v.x);
+  }
+}
+
 // out = i K x U   (spectral space, demo:60-64)
 template <typename T>
 __global__ __launch_bounds__(EW_BLOCK) void curl_kernel(const cx<T>* __restrict__ U, cx<T>* __restrict__ out,
@@ -242,6 +265,32 @@ int mfft_ew_cross(mfft_plan_t plan, const void* a, const void* b, void* out, siz
     hipLaunchKernelGGL(cross_kernel<double>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, st, (const double*)a, (const double*)b, (double*)out, n);
   else
     hipLaunchKernelGGL(cross_kernel<float>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, st, (const float*)a, (const float*)b, (float*)out, n);
+  MFFT_HIP(hipGetLastError());
+  return 0;
+}
+
+int mfft_ew_dot(mfft_plan_t plan, const void* a, const void* b, void* out, size_t n, int precision) {
+  hipStream_t st = plan_stream(plan);
+  if (!a || !b || !out) return set_error(MFFT_ERR_INVALID, "null argument");
+  if (precision == MFFT_DOUBLE)
+    hipLaunchKernelGGL(dot_kernel<double>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, st, (const double*)a, (const double*)b, (double*)out, n);
+  else
+    hipLaunchKernelGGL(dot_kernel<float>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, st, (const float*)a, (const float*)b, (float*)out, n);
+  MFFT_HIP(hipGetLastError());
+  return 0;
+}
+
+int mfft_ew_grad_hat(mfft_plan_t plan, const void* s_hat, void* out, const void* kx, const void* ky, const void* kz,
+                     const int64_t shape[3], int precision) {
+  hipStream_t st = plan_stream(plan);
+  if (!s_hat || !out || !kx || !ky || !kz || !shape) return set_error(MFFT_ERR_INVALID, "null argument");
+  const size_t n = (size_t)(shape[0] * shape[1] * shape[2]);
+  if (precision == MFFT_DOUBLE)
+    hipLaunchKernelGGL(grad_kernel<double>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, st, (const cx<double>*)s_hat,
+                       (cx<double>*)out, (const double*)kx, (const double*)ky, (const double*)kz, shape[1], shape[2], n);
+  else
+    hipLaunchKernelGGL(grad_kernel<float>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, st, (const cx<float>*)s_hat,
+                       (cx<float>*)out, (const float*)kx, (const float*)ky, (const float*)kz, shape[1], shape[2], n);
   MFFT_HIP(hipGetLastError());
   return 0;
 }

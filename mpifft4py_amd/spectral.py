@@ -74,6 +74,49 @@ def cross_transform(FFT, a_hat, b_hat, out_hat, dealias=None):
     return out_hat
 
 
+def dot(FFT, a, b, out):
+    """out = sum_f a[f] * b[f] for real vector fields a, b of shape (3,) + real shape; out has the real shape (and may be
+    a component of a or b).  What a caller writes as np.sum(a * b, 0) (mfft_ew_dot)."""
+    assert a.pitch is None and b.pitch is None and out.pitch is None
+    n = a.size // 3
+    assert b.size == 3 * n and out.size == n, (a.shape, b.shape, out.shape)
+    _lib.call("mfft_ew_dot", FFT._plan, a.ptr, b.ptr, out.ptr, n, _prec(FFT))
+    return out
+
+
+def grad_hat(FFT, K, s_hat, out):
+    """out[f] = i K[f] s_hat: the gradient of a scalar in spectral space (mfft_ew_grad_hat).  s_hat has
+    FFT.complex_shape(), out is (3,) + that; pitched spectra are swept as they lie in memory, like curl_hat."""
+    cs = tuple(int(x) for x in FFT.complex_shape())
+    assert s_hat.shape == cs and out.shape == (3,) + cs, (s_hat.shape, out.shape, cs)
+    assert s_hat.dtype == out.dtype == np.dtype(FFT.complex) and s_hat.pitch == out.pitch, (s_hat.dtype, s_hat.pitch, out.pitch)
+    _lib.call("mfft_ew_grad_hat", FFT._plan, s_hat.ptr, out.ptr, K.dev[0].ptr, K.dev[1].ptr, K.dev[2].ptr,
+              K.cshape, _prec(FFT))
+    return out
+
+
+def dot_transform(FFT, a_hat, b_hat, out_hat, dealias=None):
+    """out_hat = fftn(sum_f ifftn(a_hat[f]) * ifftn(b_hat[f])), the advection term u . grad(theta) of a transported scalar
+    as ONE operation of the plan (mfft_nonlinear_dot): what a caller composes from six `FFT.ifftn(.., dealias)`,
+    np.sum(A * B, 0) and one `FFT.fftn(.., dealias)`.  a_hat and b_hat are DeviceArrays of shape (3,) +
+    FFT.complex_shape(), out_hat has FFT.complex_shape() and may be any one component of a_hat or b_hat
+    (`b_hat.component(1)`); the inputs are otherwise preserved.  On slab plans with radix kernels on every axis the z
+    stages are one fused kernel and no real-space work array exists (`FFT.plan_info("nonlinear_dot_fused_3_2")`);
+    elsewhere the plan composes it on seven work arrays of its own."""
+    from ._base import _DEALIAS
+    assert dealias in ('3/2-rule', '2/3-rule', 'None', None)
+    cs = tuple(int(s) for s in FFT.complex_shape())
+    for x, shape in ((a_hat, (3,) + cs), (b_hat, (3,) + cs), (out_hat, cs)):
+        assert x.shape == shape and x.dtype == np.dtype(FFT.complex), (x.shape, x.dtype, shape)
+        FFT._check_pitch(x, FFT.complex_pitch)
+    code = _DEALIAS[dealias]
+    FFT.comm.use_device()
+    if code == _lib.DEALIAS_2_3:
+        FFT._ensure_mask()
+    _lib.call("mfft_nonlinear_dot", FFT._plan, a_hat.ptr, b_hat.ptr, out_hat.ptr, code)
+    return out_hat
+
+
 def ns_rk_stage(FFT, K, N_hat, U_hat, U_hat0, U_hat1, nu, a_dt, b_dt, last):
     """One Runge-Kutta stage in one sweep (mfft_ew_ns_rk_stage): N_hat holds the nonlinear term on entry and the curl of
     the updated U_hat on return; U_hat1 += a_dt dU; U_hat = U_hat0 + b_dt dU, or (last) U_hat = U_hat0 = U_hat1."""

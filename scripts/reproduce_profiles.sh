@@ -99,6 +99,12 @@ run() {
     r03_shared_gpu_pipeline_latency.txt) bash scripts/archive/r03_gpu2.sh ;;
     r03_two_thirds_rule_ranks.txt) python scripts/maskprof_ranks.py 1024 8 ;;
     r03_pencil_dealias.txt) for k in X Y; do for p in double single; do python scripts/maskprof.py 1024 $p $k; MFFT_NO_PRUNE=1 python scripts/maskprof.py 1024 $p $k; done; python scripts/padprof.py 512 $k; done; python scripts/padprof.py 512 slab ;;
+    nonlinear_dot_regs.tsv) make -C mpifft4py_amd/csrc -j8 >/dev/null; python scripts/nonlinear_dot_regs.py; python scripts/nonlinear_dot_regs.py --caps ;;
+    nonlinear_dot_ab.txt) python scripts/nonlinear_dot_ab.py --procs 3 --out out/nonlinear_dot_ab.txt
+      # section 3: the shipped library against the build with every dot kernel at two waves per SIMD (the first candidate of that
+      # section was the build with registry_nlz.h nld_occ returning 3 / 4 for the 8-values plans in double / single precision)
+      make -C mpifft4py_amd/csrc -j8 nld_variant OCC=2 >/dev/null
+      python scripts/nonlinear_dot_occ_ab.py shipped=mpifft4py_amd/libmpifft4py_amd.so occ2=mpifft4py_amd/csrc/build/libmpifft4py_amd_nldocc2.so ;;
     *) echo "no recipe for $1" >&2; return 1 ;;
   esac
 }
