@@ -14,6 +14,7 @@ this example prints; the plan stages of `--stages` (nl_*) are the advection term
     python examples/passive_scalar_device.py --N 32               # Taylor-Green velocity, ten steps
     python examples/passive_scalar_device.py --N 256 --stages     # ms per step by plan stage
     python examples/passive_scalar_device.py --N 256 --composed   # the caller-side composition instead
+    python examples/passive_scalar_device.py --N 64 --spectrum    # the variance spectrum of the real field theta after the last step
 """
 import argparse
 import os
@@ -141,6 +142,7 @@ def main():
     ap.add_argument("--precision", default="double")
     ap.add_argument("--composed", action="store_true", help="six ifftn + dot + one fftn issued here instead of the plan operation")
     ap.add_argument("--stages", action="store_true", help="print ms per step by plan stage (HIP events)")
+    ap.add_argument("--spectrum", action="store_true", help="print the variance spectrum of theta after the last step (shells of integer |k|, binned on the device)")
     args = ap.parse_args()
     dealias = None if args.dealias == "None" else args.dealias
     # RK4 is explicit: kappa |k|^2 dt and |u| |k| dt must stay inside its stability region (|u| <= 1 for Taylor-Green)
@@ -161,6 +163,29 @@ def main():
         print("  %-10s %8.3f ms per step  (%d launches)" % (name, ms, calls))
     a, b = th0.get(), th.get()
     print("mean of theta: %.15e -> %.15e" % (a[0, 0, 0].real, b[0, 0, 0].real))
+    if args.spectrum:
+        # E[s] = sum over shell s of |theta_hat|^2 / (2 N^6): its sum is half the mean square of theta, taken here from the
+        # real field by the streaming reduction the library had before (spectral.sumsq).  It is the spectrum of the REAL
+        # field: the random theta has Nyquist modes, on which i k theta_hat is not the spectrum of a real field (and the
+        # planes kz = 0, N/2 of the stepped half spectrum are not kept conjugate-symmetric); the complex-to-real transform
+        # drops that part, so the stepped array itself sums to a little more than the field holds.
+        Kw = spectral.Wavenumbers(FFT)
+        stepped = spectral.energy_spectrum(FFT, Kw, th).sum()
+        theta = DeviceArray.empty(tuple(FFT.real_shape()), FFT.float)
+        FFT.ifftn(th, theta)
+        k = FFT.comm.allreduce(spectral.sumsq(FFT, theta)) / float(args.N) ** 3 / 2
+        th_real = FFT.empty_complex()                    # the stepped state th stays as it is
+        FFT.fftn(theta, th_real)
+        E = spectral.energy_spectrum(FFT, Kw, th_real)
+        print("variance spectrum of the REAL field theta = ifftn(theta_hat) after the last step, shells of integer |k| (sum %.15e, "
+              "half the mean square %.15e).  The stepped array theta_hat itself sums to %.15e: the excess is its part in the "
+              "Nyquist planes that is the spectrum of no real field, which the complex-to-real transform drops:" % (E.sum(), k, stepped))
+        for s_, e in enumerate(E):
+            if e > 0:
+                print("  %4d  %.6e" % (s_, e))
+        if args.precision == "double":
+            assert abs(E.sum() - k) <= 1e-12 * k, (E.sum(), k)
+            print("sum of the spectrum equals half the mean square to 1e-12")
 
 
 if __name__ == "__main__":

@@ -6,6 +6,7 @@ reference's demo/spectral_dns_solver.py (k = 0.124953117517 at 32^3, 10 steps).
 
     python examples/spectral_dns_device.py --M 5            # the reference demo's case
     python examples/spectral_dns_device.py --M 8 --steps 5  # 256^3, prints ms per RK4 step
+    python examples/spectral_dns_device.py --M 6 --spectrum # the energy spectrum E(k) after the last step
 """
 import argparse
 import os
@@ -28,11 +29,13 @@ def _zero(a):
 
 
 def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double", nu=0.000625, dt=0.01, steps=10,
-          report=None, fused=True, timing=False, complex_pitch="default", edge=None):
+          report=None, fused=True, timing=False, complex_pitch="default", edge=None, spectrum=False):
     """fused=True (round 6): the nonlinear term is ONE plan operation (spectral.cross_transform: no real-space work
     arrays, the z stages one kernel) and a Runge-Kutta stage's projection, viscous term, both updates and the next
     curl are ONE sweep (spectral.ns_rk_stage).  fused=False: the composition of rounds 3 - 5 (nine transforms, cross,
-    curl, rhs and axpbz kernels per stage), kept for A/B timing and as the parity partner of the fused path."""
+    curl, rhs and axpbz kernels per stage), kept for A/B timing and as the parity partner of the fused path.
+    spectrum=True: report["spectrum"] is the energy spectrum E(k) of the final state, binned on the device
+    (spectral.energy_spectrum; the sum over the ranks), whose sum is the k returned."""
     if complex_pitch == "default":       # the fused loop on ONE rank keeps its spectra pitched (rows a whole number of cache lines
         # apart: every pass runs on them); several ranks and the composition of rounds 3 - 5 keep compact rows
         complex_pitch = "auto" if (fused and comm.Get_size() == 1) else None
@@ -91,6 +94,10 @@ def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double
             report["work_bytes"] = FFT.plan_info("nonlinear_bytes") + FFT.workspace_bytes()
             if timing:
                 report["stages"] = {k: (v[0] / steps, v[1] // steps) for k, v in FFT.stage_times().items()}
+        if spectrum:
+            E = spectral.energy_spectrum(FFT, K, U_hat)         # (collective: every rank calls it)
+            if report is not None:
+                report["spectrum"] = E
         for i in range(3):
             FFT.ifftn(U_hat.component(i), U.component(i))
         return FFT.comm.reduce(spectral.sumsq(FFT, U) / float(N[0]) / float(N[1]) / float(N[2]) / 2)
@@ -129,6 +136,10 @@ def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double
         spectral.axpbz(FFT, U_hat, U_hat1, U_hat1, 1.0, 0.0)
     FFT.sync()
     wall = time.perf_counter() - t0
+    if spectrum:
+        E = spectral.energy_spectrum(FFT, K, U_hat)
+        if report is not None:
+            report["spectrum"] = E
     for i in range(3):
         FFT.ifftn(U_hat.component(i), U.component(i))
     k = FFT.comm.reduce(spectral.sumsq(FFT, U) / float(N[0]) / float(N[1]) / float(N[2]) / 2)
@@ -151,6 +162,7 @@ def main():
     ap.add_argument("--precision", default="double")
     ap.add_argument("--composed", action="store_true", help="the nine-transform composition of rounds 3 - 5 instead of the fused operations")
     ap.add_argument("--stages", action="store_true", help="print the per-stage HIP-event times")
+    ap.add_argument("--spectrum", action="store_true", help="print the energy spectrum E(k) of the final state (shells of integer |k|, binned on the device)")
     ap.add_argument("--compact", action="store_true", help="compact spectra (rows of Nf bins) instead of the fused loop's default, rows a whole number of cache lines apart")
     args = ap.parse_args()
     dealias = None if args.dealias == "None" else args.dealias
@@ -160,11 +172,11 @@ def main():
         ks = LocalGroup(args.ranks).run(lambda c: solve(c, args.M, dealias, steps=args.steps, precision=args.precision,
                                                         report=rep if c.Get_rank() == 0 else None, fused=not args.composed,
                                                         timing=args.stages, complex_pitch=None if args.compact else "default",
-                                                        edge=args.N or None))
+                                                        edge=args.N or None, spectrum=args.spectrum))
     else:
         ks = [solve(SelfComm(), args.M, dealias, steps=args.steps, precision=args.precision, report=rep,
                     fused=not args.composed, timing=args.stages, complex_pitch=None if args.compact else "default",
-                    edge=args.N or None)]
+                    edge=args.N or None, spectrum=args.spectrum)]
     print("N = %d^3, %d RK4 steps, %.3f ms per step (%s, device-resident; plan work buffers %.2f GB)"
           % (args.N or 2 ** args.M, args.steps, rep.get("ms_per_step", float("nan")),
              "composed: 36 transforms + element-wise kernels" if args.composed else
@@ -173,6 +185,15 @@ def main():
     for name, (ms, calls) in sorted(rep.get("stages", {}).items()):
         print("  %-10s %8.3f ms per step  (%d launches)" % (name, ms, calls))
     print("k =", repr(ks[0]))
+    if args.spectrum:
+        E = rep["spectrum"]
+        print("E(k), shells of integer |k| (sum %.15e):" % E.sum())
+        for s_, e in enumerate(E):
+            if e > 0:
+                print("  %4d  %.6e" % (s_, e))
+        if args.precision == "double":
+            assert abs(E.sum() - ks[0]) <= 1e-12 * ks[0], (E.sum(), ks[0])
+            print("sum of E(k) equals k to 1e-12")
     if args.M == 5 and not args.N and args.steps == 10 and args.precision == "double":
         assert round(ks[0] - 0.124953117517, 7) == 0
         print("matches the reference demo's known answer 0.124953117517")

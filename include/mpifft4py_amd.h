@@ -330,6 +330,28 @@ MFFT_API int mfft_ew_dft_bins(mfft_plan_t plan, const void* u, int is_complex, c
                               const int64_t n[3], int inverse, int nbins, const int64_t* bins_host, int precision,
                               double* result_host);
 
+/* Shell-binned sums of device-resident spectra: the energy, transfer, enstrophy / dissipation and variance spectra of a
+ * run whose fields no host copy can hold.  Over the local spectral block, for fields a, b of ncomp (1 or 3) components,
+ * component-major and shape[0] * shape[1] * shape[2] elements apart (b may be a: it is then read once),
+ *   result[s] = sum over the modes k with shell(k) = s of  h(k) w(k) sum_c Re(conj(a_c[k]) b_c[k]),   0 <= s < nshell.
+ * shell(k) is the integer nearest to |k| of the INTEGER wave numbers ikx[x], iky[y], ikz[z], decided in integer
+ * arithmetic: 0 for m = kx^2 + ky^2 + kz^2 = 0, else the s >= 1 with (2s-1)^2 <= 4m < (2s+1)^2.  h = hz[z]: the Hermitian
+ * weight of a real transform's half axis (1 for kz = 0 and the Nyquist mode of an even axis, 2 otherwise; 1 everywhere on
+ * complex plans); elements with hz = 0 (between the rows of a pitched spectrum: shape[2] is the row length as it lies in
+ * memory and the four z vectors have that length) are skipped, whatever they hold.  w = 1 for k2 == 0 (kx, ky, kz may
+ * then be null), else kx^2 + ky^2 + kz^2 of the scaled wave numbers (the vectors of mfft_ew_curl_hat), squared in double.
+ * Products and sums are in double whatever `precision`.  result_host receives THIS RANK's nshell partial sums (the caller
+ * adds the ranks'); the call synchronises the plan's stream.  One streaming sweep with a per-workgroup histogram in LDS
+ * (csrc/shells.hip); the workgroups' histograms live in a buffer of the plan and are summed in fixed order.  Every lane
+ * loads 16 bytes; in single precision that needs a and b 16-byte aligned and, for ncomp = 3, an even number of elements
+ * per component -- otherwise the call is as correct and loads 8 bytes per lane.
+ * MFFT_ERR_INVALID: null arguments (the plan included), ncomp not 1 or 3, nshell < 1, or a mode of the block in a shell
+ * >= nshell (found on the device, nothing is written out of range); MFFT_ERR_UNSUPPORTED: nshell * 8 bytes > 64 KiB. */
+MFFT_API int mfft_ew_shell_sums(mfft_plan_t plan, const void* a, const void* b, int ncomp, const int32_t* ikx,
+                                const int32_t* iky, const int32_t* ikz, const uint8_t* hz, const void* kx, const void* ky,
+                                const void* kz, int k2, const int64_t shape[3], int nshell, int precision,
+                                double* result_host);
+
 /* ---- HIP-event timers on the default stream (bench.py) ------------------ */
 typedef struct mfft_timer_s* mfft_timer_t;
 MFFT_API int mfft_timer_create(mfft_timer_t* t);

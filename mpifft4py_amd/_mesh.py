@@ -126,3 +126,38 @@ class Block(object):
             cond = np.abs(g) < kmax
             keep = cond if keep is None else keep & cond
         return np.ascontiguousarray(np.broadcast_to(keep, self.spectral_shape())).astype(np.uint8)
+
+    # ---- shell spectra (spectral.shell_sums) --------------------------------------------------------------------------
+    @staticmethod
+    def shell_of(m):
+        """Shell of the modes with integer |k|^2 = m (array or scalar): the integer nearest to |k|, decided in integer
+        arithmetic -- 0 for m = 0, else the s >= 1 with (2s-1)^2 <= 4m < (2s+1)^2.  A float square root only proposes
+        s; the integer comparisons decide, so a mode on a shell boundary lands where the device kernel puts it."""
+        m = np.asarray(m, dtype=np.int64)
+        s = np.floor(np.sqrt(m.astype(np.float64)) + 0.5).astype(np.int64)
+        s = np.maximum(s, 1)
+        for _ in range(2):                                   # the proposal is off by one at the most
+            s = s - (((2 * s - 1) ** 2 > 4 * m) & (s > 1))   # (no lower test at s = 0: m = 0 is set below)
+            s = s + ((2 * s + 1) ** 2 <= 4 * m)
+        assert np.all(((2 * s - 1) ** 2 <= 4 * m) | (m == 0)) and np.all(4 * m < (2 * s + 1) ** 2)
+        return np.where(m == 0, 0, s)
+
+    def shell_count(self):
+        """Number of shells of the GLOBAL mesh, the corner modes included: shell(sum_i (N_i // 2)^2) + 1."""
+        return int(self.shell_of(sum((n // 2) ** 2 for n in self.N))) + 1
+
+    def shell_index_vectors(self):
+        """Per axis the integer wave numbers of the block's spectral window as int32 (`mode_vectors`)."""
+        return [np.ascontiguousarray(k, dtype=np.int32) for k in self.mode_vectors()]
+
+    def hermitian_weights(self):
+        """uint8 weights along the last axis of the block's spectral window: on the half axis of a real transform 1
+        for k = 0 and for the Nyquist mode of an even axis, 2 for the modes whose conjugate partners are not stored;
+        all 1 without a half axis."""
+        a = self.nd - 1
+        assert self.half_axis in (None, a), "the half axis is the contiguous one"
+        k = self.mode_vectors()[a]
+        if self.half_axis is None:
+            return np.ones(len(k), dtype=np.uint8)
+        n = self.N[a]
+        return np.where((k == 0) | ((n % 2 == 0) & (k == n // 2)), 1, 2).astype(np.uint8)

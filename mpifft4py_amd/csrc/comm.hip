@@ -392,9 +392,10 @@ struct LocalComm : mfft_comm_s {
   int allreduce_host(double* vals, int count, int op) override {
     sh->posts[rank].host_ptr = vals;
     MFFT_LOCAL_WAIT();
-    std::vector<double> acc(vals, vals + count);
-    for (int r = 0; r < size; ++r) {
-      if (r == rank) continue;
+    // in rank order on every rank, as in IpcComm: a sum of three or more ranks is then the same bits everywhere
+    const double* first = static_cast<const double*>(sh->posts[0].host_ptr);
+    std::vector<double> acc(first, first + count);
+    for (int r = 1; r < size; ++r) {
       const double* o = static_cast<const double*>(sh->posts[r].host_ptr);
       for (int i = 0; i < count; ++i) acc[i] = op == 1 ? (o[i] > acc[i] ? o[i] : acc[i]) : acc[i] + o[i];
     }

@@ -111,9 +111,10 @@ struct mfft_plan_s {
   // graphs are P == 1 only, so it never dropped them and still does not) and nlw (several ranks: the six x-pass outputs /
   // exchange buffers of the nonlinear route).  Plain device memory: nlx (fused nonlinear route: the six spectra after their
   // inverse x pass, (L0, N1, Za) each), nly (a batch of their x planes after the inverse y pass, (mb, L1, Za) each), nlr
-  // (composed route: nine real-space work arrays), pcomp (compact copy for the plans that do not run on pitched rows natively).
+  // (composed route: nine real-space work arrays), pcomp (compact copy for the plans that do not run on pitched rows natively),
+  // shl (mfft_ew_shell_sums: the workgroups' histograms and the result; no captured sequence holds it).
   Buf work[3] = {{true, true}, {true, true}, {true, true}}, work3{true, false}, nlw[2] = {{true, true}, {true, true}};
-  Buf nlx{false, true}, nly{false, true}, nlr{false, true}, pcomp{false, true};
+  Buf nlx{false, true}, nly{false, true}, nlr{false, true}, pcomp{false, true}, shl{false, false};
   uint8_t* mask = nullptr;
   size_t mask_count = 0;
   bool timing = false;

@@ -12,7 +12,8 @@ from .device import DeviceArray
 
 
 class Wavenumbers(object):
-    """Scaled local wavenumbers (2*pi/L * k) of an FFT object's complex layout."""
+    """Scaled local wavenumbers (2*pi/L * k) of an FFT object's complex layout; for the shell spectra (`shell_sums`) of
+    3-D plans also the integer ones (`idev`, int32), the Hermitian weights along z (`hdev`, uint8) and `nshell`."""
 
     def __init__(self, FFT):
         K = FFT.get_local_wavenumbermesh(scaled=True)
@@ -26,6 +27,17 @@ class Wavenumbers(object):
             vecs[2] = np.concatenate([vecs[2], np.zeros(pitch - len(vecs[2]), dtype=vecs[2].dtype)])
         self.dev = [DeviceArray.from_numpy(v) for v in vecs]
         self.cshape = (ctypes.c_int64 * 3)(self.shape[0], self.shape[1], len(vecs[2]))
+        self.idev = self.hdev = self.nshell = None
+        mesh = getattr(FFT, "_mesh", None)
+        if mesh is not None and mesh.nd == 3:
+            ivecs, h = mesh.shell_index_vectors(), mesh.hermitian_weights()
+            assert tuple(len(v) for v in ivecs) == self.shape and len(h) == self.shape[2]
+            pad = len(vecs[2]) - self.shape[2]                 # pitched spectra: weight 0 between the rows = skipped
+            ivecs[2] = np.concatenate([ivecs[2], np.zeros(pad, dtype=np.int32)])
+            h = np.concatenate([h, np.zeros(pad, dtype=np.uint8)])
+            self.idev = [DeviceArray.from_numpy(v) for v in ivecs]
+            self.hdev = DeviceArray.from_numpy(h)
+            self.nshell = mesh.shell_count()
 
 
 def _prec(FFT):
@@ -160,3 +172,43 @@ def dft_bins(FFT, u, bins, start, is_input=True, inverse=False):
                   1 if inverse else 0, len(chunk), chunk.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _prec(FFT), res)
         out[i:i + len(chunk)] = np.array(res[:]).view(np.complex128)
     return out
+
+
+def shell_sums(FFT, K, a_hat, b_hat=None, k2=False, reduce=True):
+    """Shell-binned sums of spectra on the device (mfft_ew_shell_sums):
+        S[s] = sum over the modes k with shell(k) = s of  h(k) w(k) sum_c Re(conj(a_hat_c[k]) b_hat_c[k])
+    shell(k) the integer nearest to |k| of the integer wave numbers (`_mesh.Block.shell_of`), h the Hermitian weight of
+    the half axis (so the sum runs over the FULL spectrum of a real field), w = |K|^2 of the scaled wave numbers with
+    k2, else 1.  a_hat, b_hat (default a_hat, read once): DeviceArrays of FFT.complex_shape() or (3,) + that.  Returns
+    a float64 vector of K.nshell entries -- the corner modes included, so its sum is the Parseval sum --, added over
+    FFT.comm with `reduce`.  Products and sums in double whatever the precision; synchronises the plan's stream."""
+    if getattr(getattr(FFT, "_mesh", None), "nd", 0) != 3 or K is None or K.idev is None:
+        raise NotImplementedError("shell spectra need a 3-D plan (slab or pencil), not %s" % type(FFT).__name__)
+    if b_hat is None:
+        b_hat = a_hat
+    cs = tuple(int(x) for x in FFT.complex_shape())
+    assert a_hat.shape in (cs, (3,) + cs), (a_hat.shape, cs)
+    for x in (a_hat, b_hat):
+        assert x.shape == a_hat.shape and x.dtype == np.dtype(FFT.complex), (x.shape, x.dtype, a_hat.shape)
+        FFT._check_pitch(x, FFT.complex_pitch)
+    FFT.comm.use_device()
+    out = np.zeros(K.nshell, dtype=np.float64)
+    _lib.call("mfft_ew_shell_sums", FFT._plan, a_hat.ptr, b_hat.ptr, 3 if len(a_hat.shape) == 4 else 1,
+              K.idev[0].ptr, K.idev[1].ptr, K.idev[2].ptr, K.hdev.ptr, K.dev[0].ptr, K.dev[1].ptr, K.dev[2].ptr,
+              1 if k2 else 0, K.cshape, K.nshell, _prec(FFT), out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    return FFT.comm.allreduce(out) if reduce else out
+
+
+def _points(FFT):
+    return float(FFT.N[0]) * float(FFT.N[1]) * float(FFT.N[2])
+
+
+def energy_spectrum(FFT, K, U_hat):
+    """E[s] = shell_sums(U_hat, U_hat) / (2 (N0 N1 N2)^2): the forward transform is unnormalised (numpy's convention), so
+    E.sum() is the mean kinetic energy sum(U * U) / (2 N0 N1 N2) the examples print (half the variance for a scalar)."""
+    return shell_sums(FFT, K, U_hat) / (2.0 * _points(FFT) ** 2)
+
+
+def transfer_spectrum(FFT, K, U_hat, N_hat):
+    """T[s] = shell_sums(U_hat, N_hat) / (N0 N1 N2)^2 = Re <U_hat*, N_hat> per shell."""
+    return shell_sums(FFT, K, U_hat, N_hat) / _points(FFT) ** 2

@@ -105,6 +105,11 @@ run() {
       # section was the build with registry_nlz.h nld_occ returning 3 / 4 for the 8-values plans in double / single precision)
       make -C mpifft4py_amd/csrc -j8 nld_variant OCC=2 >/dev/null
       python scripts/nonlinear_dot_occ_ab.py shipped=mpifft4py_amd/libmpifft4py_amd.so occ2=mpifft4py_amd/csrc/build/libmpifft4py_amd_nldocc2.so ;;
+    shell_spectrum_ab.txt) python scripts/shell_spectrum_ab.py --procs 3 --out out/shell_spectrum_ab.txt
+      # its last section: the kernels' trace statistics, and in a run of their own the LDS counters
+      rocprofv3 --kernel-trace --stats --output-format csv -d out/shell_trace -- python scripts/shell_spectrum_ab.py --worker --cases 512:double,1024:double,1024:single
+      rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d out/shell_pmc -- python scripts/shell_spectrum_ab.py --worker --cases 512:double
+      python scripts/shell_spectrum_ab.py --out out/shell_spectrum_ab.txt --append-profiles out/shell_trace out/shell_pmc ;;
     *) echo "no recipe for $1" >&2; return 1 ;;
   esac
 }
