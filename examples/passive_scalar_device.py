@@ -45,11 +45,16 @@ def _to_device(FFT, x, components=None):
 
 
 def solve(comm, N, U_hat, theta0_hat, kappa, dt, steps, dealias, fused=True, precision="double", complex_pitch=None,
-          report=None, timing=False, FFT=None):
+          report=None, timing=False, FFT=None, cfl=None, dt_max=None):
     """Advance theta_hat by `steps` RK4 steps and return it (a DeviceArray of FFT.complex_shape()).  U_hat: (3,) + the local
     complex shape, theta0_hat: the local complex shape (numpy arrays or DeviceArrays; neither is modified).
     fused=True: the advection term is spectral.dot_transform.  fused=False: the composition a caller would write -- six
-    FFT.ifftn, spectral.dot on the real fields, one FFT.fftn -- kept for A/B timing and as the parity partner."""
+    FFT.ifftn, spectral.dot on the real fields, one FFT.fftn -- kept for A/B timing and as the parity partner.
+    cfl=C (fused only): the first Runge-Kutta stage of a step runs dot_transform with absmax=True and the step's
+    dt = min(dt_max, C / sum_f max|u_f| N_f / L_f) is fetched right after it (one synchronisation of the plan's stream per
+    step); `dt` is then not used.  report["dt"] lists the steps' dt; rank 0 prints them."""
+    if cfl is not None and not fused:
+        raise ValueError("cfl needs the plan operation: the composition has no statistics call")
     if FFT is None:
         FFT = make_plan(comm, N, precision, complex_pitch)
     K = spectral.Wavenumbers(FFT)
@@ -65,7 +70,7 @@ def solve(comm, N, U_hat, theta0_hat, kappa, dt, steps, dealias, fused=True, pre
     a = [1. / 6., 1. / 3., 1. / 3., 1. / 6.]
     b = [0.5, 0.5, 1.]
 
-    def rhs():
+    def rhs(stats=False):
         """adv <- d theta / dt of the current th"""
         spectral.grad_hat(FFT, K, th, G)
         # laplace(theta) is the divergence of the gradient the stage holds anyway: -|K|^2 theta = sum_f (i K_f)(i K_f theta),
@@ -77,7 +82,7 @@ def solve(comm, N, U_hat, theta0_hat, kappa, dt, steps, dealias, fused=True, pre
             else:
                 spectral.axpbz(FFT, lap, lap, W.component(f), 1.0, 1.0)
         if fused:
-            spectral.dot_transform(FFT, U, G, adv, dealias)
+            spectral.dot_transform(FFT, U, G, adv, dealias, absmax=stats)
         else:
             for f in range(3):
                 FFT.ifftn(U.component(f), Ur.component(f), dealias)
@@ -92,11 +97,20 @@ def solve(comm, N, U_hat, theta0_hat, kappa, dt, steps, dealias, fused=True, pre
         FFT.enable_timing(True)
         FFT.reset_timing()
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for step_ in range(steps):
         spectral.axpbz(FFT, th0, th, th, 1.0, 0.0)
         spectral.axpbz(FFT, th1, th, th, 1.0, 0.0)
         for rk in range(4):
-            rhs()
+            rhs(stats=(cfl is not None and rk == 0))
+            if cfl is not None and rk == 0:        # max |u_f| (and max |d theta / dx_f|) of the step's first stage: one synchronisation
+                am = spectral.nonlinear_absmax(FFT)
+                dt = spectral.advective_dt(FFT, am[0], cfl)
+                if dt_max is not None:
+                    dt = min(dt, dt_max)
+                if report is not None:
+                    report.setdefault("dt", []).append(dt)
+                if comm.Get_rank() == 0:
+                    print("step %d: dt = %.15e  max|grad theta| = %.6e" % (step_, dt, float(am[1].max())))
             if rk < 3:
                 spectral.axpbz(FFT, th, th0, adv, 1.0, b[rk] * dt)
             spectral.axpbz(FFT, th1, th1, adv, 1.0, a[rk] * dt)
@@ -143,6 +157,9 @@ def main():
     ap.add_argument("--composed", action="store_true", help="six ifftn + dot + one fftn issued here instead of the plan operation")
     ap.add_argument("--stages", action="store_true", help="print ms per step by plan stage (HIP events)")
     ap.add_argument("--spectrum", action="store_true", help="print the variance spectrum of theta after the last step (shells of integer |k|, binned on the device)")
+    ap.add_argument("--cfl", type=float, default=None, help="advective time step dt = CFL / sum_f max|u_f| N_f / L_f from the fused advection "
+                    "term's real-space maxima (one stream synchronisation per step) instead of --dt; prints dt per step")
+    ap.add_argument("--dt-max", type=float, default=None, help="with --cfl: dt = min(DT_MAX, advective dt)")
     args = ap.parse_args()
     dealias = None if args.dealias == "None" else args.dealias
     # RK4 is explicit: kappa |k|^2 dt and |u| |k| dt must stay inside its stability region (|u| <= 1 for Taylor-Green)
@@ -153,7 +170,7 @@ def main():
     U, th0 = taylor_green_hat(FFT), random_scalar_hat(FFT)
     rep = {}
     th = solve(comm, args.N, U, th0, args.kappa, dt, args.steps, dealias, fused=not args.composed, precision=args.precision,
-               report=rep, timing=args.stages, FFT=FFT)
+               report=rep, timing=args.stages, FFT=FFT, cfl=args.cfl, dt_max=args.dt_max)
     print("N = %d^3, %d RK4 steps of dt = %.3g, %.3f ms per step (%s; plan work buffers %.2f GB)"
           % (args.N, args.steps, dt, rep["ms_per_step"],
              "composed here: 28 transforms + element-wise kernels" if args.composed else

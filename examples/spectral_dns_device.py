@@ -29,18 +29,24 @@ def _zero(a):
 
 
 def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double", nu=0.000625, dt=0.01, steps=10,
-          report=None, fused=True, timing=False, complex_pitch="default", edge=None, spectrum=False):
+          report=None, fused=True, timing=False, complex_pitch="default", edge=None, spectrum=False, cfl=None, dt_max=None):
     """fused=True (round 6): the nonlinear term is ONE plan operation (spectral.cross_transform: no real-space work
     arrays, the z stages one kernel) and a Runge-Kutta stage's projection, viscous term, both updates and the next
     curl are ONE sweep (spectral.ns_rk_stage).  fused=False: the composition of rounds 3 - 5 (nine transforms, cross,
     curl, rhs and axpbz kernels per stage), kept for A/B timing and as the parity partner of the fused path.
     spectrum=True: report["spectrum"] is the energy spectrum E(k) of the final state, binned on the device
-    (spectral.energy_spectrum; the sum over the ranks), whose sum is the k returned."""
+    (spectral.energy_spectrum; the sum over the ranks), whose sum is the k returned.
+    cfl=C (fused loop): an advective time step.  The first Runge-Kutta stage of a step runs with absmax=True, so the
+    fused z kernel also leaves max |u_f| and max |omega_f| on the device; dt = min(dt_max, C / sum_f max|u_f| N_f / L_f)
+    is fetched right after it -- ONE synchronisation of the plan's stream per step -- and the step's four stages use
+    it.  report["dt"] lists the steps' dt, report["wmax"] their max |omega|; rank 0 prints both."""
     if complex_pitch == "default":       # the fused loop on ONE rank keeps its spectra pitched (rows a whole number of cache lines
         # apart: every pass runs on them); several ranks and the composition of rounds 3 - 5 keep compact rows
         complex_pitch = "auto" if (fused and comm.Get_size() == 1) else None
     N = np.array([edge or 2 ** M] * 3, dtype=int)        # edge: a mesh that is not a power of two (576, 1152 ...)
     L = np.array([2 * np.pi] * 3, dtype=float)
+    if cfl is not None and not fused:
+        raise ValueError("cfl needs the fused loop: the composition has no statistics call")
     if decomposition == 'slab':
         FFT = Slab_R2C(N, L, comm, precision, complex_pitch=complex_pitch)
     else:
@@ -81,9 +87,19 @@ def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double
         if timing:
             FFT.reset_timing()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for step_ in range(steps):
             for rk in range(4):
-                spectral.cross_transform(FFT, U_hat, dU, dU, dealias)          # dU = fftn(U x curl U)
+                spectral.cross_transform(FFT, U_hat, dU, dU, dealias, absmax=(cfl is not None and rk == 0))      # dU = fftn(U x curl U)
+                if cfl is not None and rk == 0:      # max |u_f|, max |omega_f| of the state the step starts from (one stream synchronisation)
+                    am = spectral.nonlinear_absmax(FFT)
+                    dt = spectral.advective_dt(FFT, am[0], cfl)
+                    if dt_max is not None:
+                        dt = min(dt, dt_max)
+                    if report is not None:
+                        report.setdefault("dt", []).append(dt)
+                        report.setdefault("wmax", []).append(float(am[1].max()))
+                    if comm.Get_rank() == 0:
+                        print("step %d: dt = %.15e  max|omega| = %.6e" % (step_, dt, float(am[1].max())))
                 spectral.ns_rk_stage(FFT, K, dU, U_hat, U_hat0, U_hat1, nu, a[rk] * dt, b[rk] * dt if rk < 3 else 0.0, rk == 3)
         FFT.sync()
         wall = time.perf_counter() - t0
@@ -164,6 +180,9 @@ def main():
     ap.add_argument("--stages", action="store_true", help="print the per-stage HIP-event times")
     ap.add_argument("--spectrum", action="store_true", help="print the energy spectrum E(k) of the final state (shells of integer |k|, binned on the device)")
     ap.add_argument("--compact", action="store_true", help="compact spectra (rows of Nf bins) instead of the fused loop's default, rows a whole number of cache lines apart")
+    ap.add_argument("--cfl", type=float, default=None, help="advective time step dt = CFL / sum_f max|u_f| N_f / L_f from the fused nonlinear term's "
+                    "real-space maxima (one stream synchronisation per step) instead of the fixed dt = 0.01; prints dt and max|omega| per step")
+    ap.add_argument("--dt-max", type=float, default=None, help="with --cfl: dt = min(DT_MAX, advective dt)")
     args = ap.parse_args()
     dealias = None if args.dealias == "None" else args.dealias
     from mpifft4py_amd import LocalGroup, SelfComm
@@ -172,11 +191,11 @@ def main():
         ks = LocalGroup(args.ranks).run(lambda c: solve(c, args.M, dealias, steps=args.steps, precision=args.precision,
                                                         report=rep if c.Get_rank() == 0 else None, fused=not args.composed,
                                                         timing=args.stages, complex_pitch=None if args.compact else "default",
-                                                        edge=args.N or None, spectrum=args.spectrum))
+                                                        edge=args.N or None, spectrum=args.spectrum, cfl=args.cfl, dt_max=args.dt_max))
     else:
         ks = [solve(SelfComm(), args.M, dealias, steps=args.steps, precision=args.precision, report=rep,
                     fused=not args.composed, timing=args.stages, complex_pitch=None if args.compact else "default",
-                    edge=args.N or None, spectrum=args.spectrum)]
+                    edge=args.N or None, spectrum=args.spectrum, cfl=args.cfl, dt_max=args.dt_max)]
     print("N = %d^3, %d RK4 steps, %.3f ms per step (%s, device-resident; plan work buffers %.2f GB)"
           % (args.N or 2 ** args.M, args.steps, rep.get("ms_per_step", float("nan")),
              "composed: 36 transforms + element-wise kernels" if args.composed else
@@ -194,7 +213,7 @@ def main():
         if args.precision == "double":
             assert abs(E.sum() - ks[0]) <= 1e-12 * ks[0], (E.sum(), ks[0])
             print("sum of E(k) equals k to 1e-12")
-    if args.M == 5 and not args.N and args.steps == 10 and args.precision == "double":
+    if args.M == 5 and not args.N and args.steps == 10 and args.precision == "double" and args.cfl is None:
         assert round(ks[0] - 0.124953117517, 7) == 0
         print("matches the reference demo's known answer 0.124953117517")
 

@@ -243,6 +243,12 @@ MFFT_API int mfft_nlz_rows(const void* a, const void* b, void* out, int64_t nrow
  * a caller's np.sum(U * gradT, 0). */
 MFFT_API int mfft_nlz_dot_rows(const void* a, const void* b, void* out, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
                                int precision, int sync);
+/* Either stage with the maxima of its six real rows, synchronous: `out` as mfft_nlz_rows (dot = 0) or mfft_nlz_dot_rows
+ * (dot = 1) leave it, and out6 = [max |irfft(a[f])|, f = 0..2, then max |irfft(b[f])|, f = 0..2] over all rows and all n
+ * points (numpy's normalisation).  A NaN in a field gives NaN for that field.  The z stage of mfft_nonlinear_cross_absmax /
+ * mfft_nonlinear_dot_absmax on its own, for tests. */
+MFFT_API int mfft_nlz_rows_absmax(const void* a, const void* b, void* out, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
+                                  int precision, int dot, double out6[6]);
 /* slab pack / unpack (slab.py:403; cython/maths.pyx:21-31 transpose_Uc) */
 MFFT_API int mfft_slab_pack(const void* uc_hatT, void* u_mpi, int P, int64_t np0, int64_t np1, int64_t nf, int precision);
 MFFT_API int mfft_slab_unpack(const void* u_mpi, void* uc_hatT, int P, int64_t np0, int64_t np1, int64_t nf, int precision);
@@ -297,6 +303,10 @@ MFFT_API int mfft_ew_ns_rk_stage(mfft_plan_t plan, void* N_hat, void* U_hat, voi
                                  const void* ky, const void* kz, const int64_t shape[3], double nu, double a_dt, double b_dt,
                                  int last, int precision);
 MFFT_API int mfft_ew_sumsq(mfft_plan_t plan, const void* x, size_t n_real, int precision, double* result_host);           /* demo:103 */
+/* out_host[c] = max |x[c, :]| of a real device array (ncomp, n), ncomp = 1, 2, 3 or 6, in the plan's precision: np.abs(x).max(1).
+ * One sweep, 16 bytes per lane, no atomics; a NaN in a component gives NaN for it; bitwise reproducible.  The plan must not be
+ * null (partial maxima live in a buffer of the plan); synchronises the plan's stream. */
+MFFT_API int mfft_ew_absmax(mfft_plan_t plan, const void* x, int ncomp, size_t n, int precision, double* out_host);
 
 /* The nonlinear term of a pseudo-spectral step as ONE operation:
  *     out_hat = fftn(ifftn(a_hat) x ifftn(b_hat))        (cross product in real space, component by component)
@@ -319,6 +329,21 @@ MFFT_API int mfft_nonlinear_cross(mfft_plan_t plan, const void* a_hat, const voi
  * registers as the three inverse pairs finish, two rows' sums ride on one forward transform) and the seven real-space
  * arrays of the composition never exist; every other plan composes it on seven work arrays of its own. */
 MFFT_API int mfft_nonlinear_dot(mfft_plan_t plan, const void* a_hat, const void* b_hat, void* out_hat, int dealias);
+
+/* The two operations above WITH STATISTICS: the call also records, on the device,
+ *     absmax[0][f] = max |ifftn(a_hat[f], dealias)|,   absmax[1][f] = max |ifftn(b_hat[f], dealias)|,   f = 0..2
+ * over this rank's part of the real-space grid on which the product is formed (the padded grid with the reference's pad scale
+ * under the 3/2-rule, the masked field under the 2/3-rule) -- what FFT.ifftn(a_hat[f], u, dealias); np.abs(u).max() gives.  It
+ * is the number an advective time step needs (velocity and vorticity for the cross product, velocity and grad(theta) for the
+ * dot product), taken where the real values sit in registers anyway (mfft_plan_get_info "nonlinear_absmax_fused_*" /
+ * "nonlinear_dot_absmax_fused_*"); plans on the composed route sweep their six real work arrays instead.  Both calls enqueue
+ * and return like the plain ones and compute the same out_hat.  mfft_plan_nonlinear_absmax synchronises the plan's stream and
+ * returns THIS RANK's six values of the LAST statistics call, out6 = [a0, a1, a2, b0, b1, b2] (MFFT_ERR_INVALID if none has run;
+ * a call without statistics leaves them alone).  A NaN anywhere in a field gives NaN, Inf gives Inf; the values are bitwise
+ * reproducible run to run.  Over several ranks reduce with a maximum that keeps NaNs (spectral.nonlinear_absmax does). */
+MFFT_API int mfft_nonlinear_cross_absmax(mfft_plan_t plan, const void* a_hat, const void* b_hat, void* out_hat, int dealias);
+MFFT_API int mfft_nonlinear_dot_absmax(mfft_plan_t plan, const void* a_hat, const void* b_hat, void* out_hat, int dealias);
+MFFT_API int mfft_plan_nonlinear_absmax(mfft_plan_t plan, double out6[6]);
 
 /* Direct evaluation of up to 16 DFT bins of a distributed field, for checking transforms of meshes that no host
  * transform can hold (BASELINE config 5, 2048^3): result[2b], result[2b+1] = Re, Im of

@@ -4,6 +4,7 @@
 #include <cstring>
 #include "comm.h"
 #include "mfft_internal.h"
+#include "fft_nlz.h"
 
 using namespace mfft;
 
@@ -286,6 +287,39 @@ int mfft_nlz_dot_rows(const void* a, const void* b, void* out, int64_t nrows, in
   MFFT_TRY(launch_nlz(z, nullptr));
   if (sync) MFFT_HIP(hipStreamSynchronize(nullptr));
   return 0;
+}
+
+// The stage with the maxima of its six real rows (fft_nlz.h NlzAbsMax), synchronous: out as mfft_nlz_rows (dot = 0) or
+// mfft_nlz_dot_rows (dot = 1) leave it, out6 = [max |irfft(a_f)|, f = 0..2, max |irfft(b_f)|, f = 0..2] over all rows.
+int mfft_nlz_rows_absmax(const void* a, const void* b, void* out, int64_t nrows, int64_t n, int64_t pitch, int64_t valid, int precision,
+                         int dot, double out6[6]) {
+  if (!a || !b || !out || !out6 || nrows < 1 || n < 2 || pitch < valid || valid < 1) return set_error(MFFT_ERR_INVALID, "bad argument");
+  if (precision != MFFT_DOUBLE && precision != MFFT_SINGLE) return set_error(MFFT_ERR_INVALID, "unknown precision %d", precision);
+  const size_t es = elem_bytes(precision, true);
+  NlzArgs z;
+  for (int f = 0; f < 3; ++f) {
+    z.a[f] = static_cast<const char*>(a) + (size_t)(f * nrows * pitch) * es;
+    z.b[f] = static_cast<const char*>(b) + (size_t)(f * nrows * pitch) * es;
+    if (!dot) z.out[f] = static_cast<char*>(out) + (size_t)(f * nrows * pitch) * es;
+  }
+  if (dot) z.out[0] = out;
+  z.product = dot ? Op::Dot : Op::Plain;
+  z.n = (int)n; z.prec = precision; z.in_stride = pitch; z.out_stride = pitch; z.nrows = nrows; z.valid = (int)valid;
+  z.scale = 1.0 / ((double)n * (double)n);
+  const int64_t waves = nlz_absmax_waves(n, precision, z.product, nrows);
+  if (waves < 1) return set_error(MFFT_ERR_UNSUPPORTED, "no fused nonlinear z-stage kernel of length %lld with maxima", (long long)n);
+  const size_t head = absmax_fold_scratch_bytes() + 6 * sizeof(double);
+  char* buf = nullptr;
+  MFFT_HIP(hipMalloc(reinterpret_cast<void**>(&buf), head + (size_t)waves * NLM_SLOTS * (es / 2)));
+  double* acc = reinterpret_cast<double*>(buf + absmax_fold_scratch_bytes());
+  z.part = buf + head;
+  int rc = hipMemsetAsync(acc, 0, 6 * sizeof(double), nullptr) == hipSuccess ? 0 : set_error(MFFT_ERR_HIP, "hipMemsetAsync failed");
+  if (!rc) rc = launch_nlz(z, nullptr);
+  if (!rc) rc = absmax_fold(z.part, (size_t)(2 * waves), 6, precision, 1.0 / (double)n, reinterpret_cast<double*>(buf), acc, nullptr);
+  if (!rc && hipMemcpy(out6, acc, 6 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemcpy failed");
+  if (hipStreamSynchronize(nullptr) != hipSuccess && !rc) rc = set_error(MFFT_ERR_HIP, "hipStreamSynchronize failed");
+  (void)hipFree(buf);
+  return rc;
 }
 
 // U_mpi[p, i, j, k] = Uc_hatT[i, p*Np1 + j, k]   (slab.py:403)

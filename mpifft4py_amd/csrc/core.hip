@@ -35,7 +35,7 @@ std::vector<KernelEntry>& kernel_registry() {
 
 // The registry is complete once the static initialisers of the kernels_*.hip units have run; lookups go
 // through hash maps built on first use (a linear scan of ~2000 entries per launch costs ~0.3 us, visible at 32^3).
-constexpr int OP_BITS = 6, BUILD_BITS = 3, FAMILY_BITS = 6;
+constexpr int OP_BITS = 6, BUILD_BITS = 4, FAMILY_BITS = 6;
 static_assert(2 * (unsigned)Op::TopFlag <= (1u << OP_BITS) && (unsigned)Op::Band < (unsigned)Op::Limited, "Op does not fit its key field");
 static_assert((unsigned)Build::Last < (1u << BUILD_BITS), "Build does not fit its key field");
 static_assert((unsigned)FAM_NLZ < (1u << FAMILY_BITS), "Family does not fit its key field");
@@ -526,13 +526,21 @@ int launch_r2c(const RealArgs& a, hipStream_t s) { return launch_real(FAM_R2C, a
 int launch_c2r(const RealArgs& a, hipStream_t s) { return launch_real(FAM_C2R, a, s); }
 
 // fused nonlinear z stage (fft_nlz.h): out_f = rfft((irfft(a) x irfft(b))_f) along the contiguous axis, row by row
-bool nlz_supported(int64_t n, int prec, Op product) {
+bool nlz_supported(int64_t n, int prec, Op product, bool absmax) {
+  if (absmax) return n >= 2 && n < 65536 && find_kernel(FAM_NLZ, (int)n, prec, 0, product, Build::AbsMax) != nullptr;
   if (product == Op::Dot) return n >= 2 && n < 65536 && find_kernel(FAM_NLZ, (int)n, prec, 0, Op::Dot) != nullptr;
   return n >= 2 && n < 65536 && (find_kernel(FAM_NLZ, (int)n, prec, 0) != nullptr || find_kernel(FAM_NLZ, (int)n, prec, 0, Op::Plain, Build::Nlz3) != nullptr);
 }
-template <typename T>
+// waves of the Build::AbsMax launch over nrows rows = groups of NLM_SLOTS values it writes to NlzArgs::part (0: no such kernel)
+int64_t nlz_absmax_waves(int64_t n, int prec, Op product, int64_t nrows) {
+  const KernelEntry* e = n >= 2 && n < 65536 ? find_kernel(FAM_NLZ, (int)n, prec, 0, product, Build::AbsMax) : nullptr;
+  if (!e || nrows < 1) return 0;
+  return (nrows + 2 * e->tile - 1) / (2 * e->tile) * ((e->threads + 63) / 64);
+}
+template <typename T, class PT = NlzParams<T>>
 static int launch_nlz_t(const KernelEntry* e, const NlzArgs& a, void* tw, void* rt3, hipStream_t s) {
-  NlzParams<T> P;
+  PT P;
+  if constexpr (std::is_same<PT, NlmParams<T>>::value) P.part = static_cast<T*>(a.part);
   P.rt3 = static_cast<const cx<T>*>(rt3);
   for (int f = 0; f < 3; ++f) {
     P.a[f] = static_cast<const cx<T>*>(a.a[f]);
@@ -550,6 +558,15 @@ static int launch_nlz_t(const KernelEntry* e, const NlzArgs& a, void* tw, void* 
 }
 int launch_nlz(const NlzArgs& a, hipStream_t s) {
   const bool dot = a.product == Op::Dot;
+  if (a.part) {                                  // Build::AbsMax: the same rows, and the partial maxima of the six real fields
+    const KernelEntry* em = a.n < 65536 ? find_kernel(FAM_NLZ, a.n, a.prec, 0, a.product, Build::AbsMax) : nullptr;
+    if (!em) return set_error(MFFT_ERR_UNSUPPORTED, "no fused nonlinear z-stage kernel of length %d with maxima%s", a.n, dot ? " (dot product)" : "");
+    for (int f = 0; f < 3; ++f)
+      if (!a.a[f] || !a.b[f] || !a.out[dot ? 0 : f]) return set_error(MFFT_ERR_INVALID, "null argument");
+    void* twm = nullptr;
+    MFFT_TRY(prepare_kernel(em, &twm));
+    return by_prec(a.prec, [&](auto t) { return launch_nlz_t<decltype(t), NlmParams<decltype(t)>>(em, a, twm, nullptr, s); });
+  }
   const KernelEntry* e = a.n < 65536 ? find_kernel(FAM_NLZ, a.n, a.prec, 0, a.product) : nullptr;
   // 3/2-rule rows (n = 3 L with the L + 1 bins of the un-padded mesh) also have the pruned kernel (fft_nlz.h Nlz3Fft: three
   // sub-transforms of length L in three thread groups, a third of the registers).  Measured EVEN with NlzFft at 768 (1.36 ms per

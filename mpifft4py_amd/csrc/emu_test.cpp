@@ -1413,6 +1413,163 @@ template <class S> static void test_nld_all() {
   }
 }
 
+// ... with the real-space maxima (fft_nlz.h NlzAbsMax, Build::AbsMax): the same rows, bit for bit, as the plain body in this
+// emulator, and max |irfft(a_f)|, max |irfft(b_f)| over all rows against long-double transforms of the six rows.  A spike can
+// be planted at one z position of one row of one field (over small noise), a NaN in one input bin of one field.
+struct NlmCase {
+  int valid = 0, valid_in = 0, nrows = 0;
+  int spike_field = -1, spike_row = 0, spike_pos = 0;
+  int nan_field = -1;
+};
+template <typename T> static T emu_nan_max(T m, T x) { return (x > m || x != x) ? x : m; }
+template <class S, typename T, int ROWS, bool TWLDS, bool SPLIT, bool WAVE, bool DOT>
+static double run_nlm(const NlmCase& c) {          // the worst relative error of the six maxima; 1e30 for a broken contract
+  typedef NlzFft<S, T, ROWS, TWLDS, SPLIT, WAVE> K0;
+  typedef NlzProd<K0, DOT ? NlzProduct::Dot : NlzProduct::Cross> KP;
+  typedef NlzAbsMax<K0, DOT ? NlzProduct::Dot : NlzProduct::Cross> KM;
+  const int M = S::N, valid = c.valid, vin = c.valid_in > 0 ? c.valid_in : c.valid, nrows = c.nrows;
+  const int pin = valid + 2, pout = valid + 1, nout = DOT ? 1 : 3;
+  std::mt19937_64 rng(777 + M + valid + 31 * c.spike_pos + 7 * c.spike_field);
+  const double amp = c.spike_field >= 0 ? 1e-3 : 1.0;
+  std::uniform_real_distribution<double> U(-amp, amp);
+  std::vector<cx<T>> in[6], out0[3], out1[3];
+  for (auto& f : in) {
+    f.resize((size_t)nrows * pin);
+    for (auto& z : f) z = mk<T>((T)U(rng), (T)U(rng));
+  }
+  if (c.spike_field >= 0) {
+    const long double two_pi = 6.283185307179586476925286766559L;
+    for (int q = 0; q < vin; ++q) {
+      const long double a = -two_pi * (long double)(((long long)q * c.spike_pos) % M) / M;
+      cx<T>& z = in[c.spike_field][(size_t)c.spike_row * pin + q];
+      z = mk<T>(z.x + (T)cosl(a), z.y + (T)sinl(a));
+    }
+  }
+  if (c.nan_field >= 0) in[c.nan_field][(size_t)(nrows / 2) * pin + 1].x = (T)NAN;
+  for (int f = 0; f < 3; ++f) { out0[f].assign((size_t)nrows * pout, mk<T>((T)7, (T)7)); out1[f] = out0[f]; }
+  auto tw = build_pass_twiddles<S, T>();
+  const int grid = (nrows + 2 * ROWS - 1) / (2 * ROWS);
+  NlmParams<T> P;
+  for (int f = 0; f < 3; ++f) { P.a[f] = in[f].data(); P.b[f] = in[3 + f].data(); P.out[f] = f < nout ? out0[f].data() : nullptr; }
+  P.tw = tw.data(); P.in_stride = pin; P.out_stride = pout; P.nrows = nrows; P.valid = valid; P.valid_in = vin;
+  P.scale = (T)(1.0 / ((double)M * (double)M));
+  P.rt3 = nullptr; P.part = nullptr;
+  const NlzParams<T>& P0 = P;
+  emu_launch(grid, KP::THREADS, KP::LDS_BYTES, [&](int b, int t, char* lds) { KP::body(P0, b, t, lds); });
+  std::vector<T> part((size_t)grid * KM::WAVES * NLM_SLOTS, (T)-1);
+  for (int f = 0; f < nout; ++f) P.out[f] = out1[f].data();
+  P.part = part.data();
+  emu_launch(grid, KM::THREADS, KM::LDS_BYTES, [&](int b, int t, char* lds) { KM::body(P, b, t, lds); });
+  double bad = 0;
+  for (int f = 0; f < nout; ++f) {                   // the statistic does not disturb the product: the same bits, NaNs where the plain body has NaNs
+    if (c.nan_field < 0 && memcmp(out0[f].data(), out1[f].data(), out0[f].size() * sizeof(cx<T>)) != 0) bad = 1e30;
+    for (size_t i = 0; i < out0[f].size(); ++i) {
+      const T p[2] = {out0[f][i].x, out0[f][i].y}, q[2] = {out1[f][i].x, out1[f][i].y};
+      for (int k = 0; k < 2; ++k)
+        if ((p[k] != p[k]) != (q[k] != q[k]) || (p[k] == p[k] && memcmp(&p[k], &q[k], sizeof(T)) != 0)) bad = 1e30;
+    }
+  }
+  T got[6] = {0, 0, 0, 0, 0, 0};
+  for (size_t g = 0; g < part.size() / 6; ++g)
+    for (int i = 0; i < 6; ++i) {
+      if (part[g * 6 + i] < (T)0) bad = 1e30;        // a slot nobody wrote (or a negative "maximum")
+      got[i] = emu_nan_max(got[i], part[g * 6 + i]);
+    }
+  long double want[6];
+  for (int f = 0; f < 6; ++f) {
+    want[f] = 0;
+    for (int r = 0; r < nrows; ++r) {
+      lvec X(M);
+      for (int p = 0; p < M; ++p) { X[p].x = 0; X[p].y = 0; }
+      for (int q = 0; q < vin; ++q) {
+        cx<T> z = in[f][(size_t)r * pin + q];
+        long double zr = z.x, zi = z.y;
+        if (zr != zr) zr = 0;                        // (the NaN field's expectation is NaN: no reference needed)
+        if (q == 0 || (M % 2 == 0 && q == M / 2)) zi = 0;
+        X[q].x = zr; X[q].y = zi;
+        if (q != 0 && q != M - q) { X[M - q].x = zr; X[M - q].y = -zi; }
+      }
+      lvec x = naive_dft(X, +1);
+      for (int p = 0; p < M; ++p) want[f] = std::max(want[f], fabsl(x[p].x / M));
+    }
+  }
+  for (int f = 0; f < 6; ++f) {
+    const double g = (double)got[f] / M;             // the kernel's inverse transforms are un-normalised
+    // NaN: for the field that holds it ONLY.  a_f and b_f are the two halves of ONE complex transform, which is why the STATS
+    // bodies take non-finite inputs out of it (fft_nlz.h take_out_nonfinite): the partner's maximum is finite and right.
+    if (f == c.nan_field) { if (g == g) bad = 1e30; continue; }
+    if (g != g) { bad = 1e30; continue; }
+    if (c.spike_field == f && !(want[f] > 0.3L)) bad = 1e30;      // the planted extreme is the maximum of its field
+    // relative to the field's OWN maximum.  One exception, the planted-extreme cases: there one field of a pair is a spike near 1
+    // over noise of 1e-3, and the two share one complex transform, whose rounding errors scale with the larger of its two fields
+    // (the plain kernel's rows are no better) -- the spiked field's partner, and only it, is taken relative to the pair's maximum.
+    const bool partner = c.spike_field >= 0 && f != c.spike_field && f % 3 == c.spike_field % 3;
+    const long double ref = partner ? std::max(want[f % 3], want[3 + f % 3]) : want[f];
+    bad = std::max(bad, (double)(fabsl((long double)g - want[f]) / ref));
+  }
+  return bad;
+}
+template <class S, typename T, int ROWS, bool TWLDS, bool SPLIT, bool WAVE, bool DOT>
+static void test_nlm(int valid, int valid_in, int nrows, bool with_nan) {
+  NlmCase c;
+  c.valid = valid; c.valid_in = valid_in; c.nrows = nrows;
+  const double tol = sizeof(T) == 8 ? 4e-14 : 2e-5;
+  char name[96];
+  const int vin = valid_in > 0 ? valid_in : valid;
+  snprintf(name, sizeof name, "nlm %s r%d n%d v%d/%d%s%s%s", DOT ? "dot" : "cross", ROWS, nrows, vin, valid, TWLDS ? " twlds" : "",
+           SPLIT ? " split" : "", WAVE ? " wave" : "");
+  report(name, S::N, pname<T>(), run_nlm<S, T, ROWS, TWLDS, SPLIT, WAVE, DOT>(c), tol);
+  if (!with_nan) return;
+  // a NaN in one input bin: NaN for that field, the other five as before
+  c.nan_field = (S::N + ROWS + (DOT ? 1 : 0)) % 6;
+  snprintf(name, sizeof name, "nlm %s r%d nan in field %d%s%s", DOT ? "dot" : "cross", ROWS, c.nan_field, SPLIT ? " split" : "", WAVE ? " wave" : "");
+  report(name, S::N, pname<T>(), run_nlm<S, T, ROWS, TWLDS, SPLIT, WAVE, DOT>(c), tol);
+}
+// planted extremes: every z position for rows up to 64 points, else the positions where a lane, a register or a row would
+// be left out (0, 1, TPT - 1, TPT, M/2, M - 1), in the first row and in the last row of an odd count; fields in turn
+template <class S, typename T, int ROWS, bool TWLDS, bool SPLIT, bool WAVE, bool DOT>
+static void test_nlm_spikes() {
+  const int M = S::N;
+  std::vector<int> pos;
+  if (M <= 64) for (int p = 0; p < M; ++p) pos.push_back(p);
+  else pos = {0, 1, S::TPT - 1, S::TPT, M / 2, M - 1};
+  double worst = 0;
+  int n = 0;
+  for (size_t i = 0; i < pos.size(); ++i)
+    for (int last = 0; last < 2; ++last) {
+      if (M > 64 && last != (int)(i % 2) && pos[i] != M - 1) continue;      // long rows: alternate, and both for the last position
+      NlmCase c;
+      c.valid = i % 3 == 1 ? M / 3 + 1 : M / 2 + 1;
+      c.nrows = 2 * ROWS + 1;                        // odd: the last row's partner is inactive and re-reads it
+      c.spike_field = (int)((i + 3 * last) % 6); c.spike_row = last ? c.nrows - 1 : 0; c.spike_pos = pos[i];
+      worst = std::max(worst, run_nlm<S, T, ROWS, TWLDS, SPLIT, WAVE, DOT>(c));
+      ++n;
+    }
+  char name[96];
+  snprintf(name, sizeof name, "nlm %s r%d %d spikes%s%s%s", DOT ? "dot" : "cross", ROWS, n, TWLDS ? " twlds" : "", SPLIT ? " split" : "", WAVE ? " wave" : "");
+  report(name, M, pname<T>(), worst, sizeof(T) == 8 ? 4e-14 : 2e-5);
+}
+template <class S> static void test_nlm_all() {
+  const int M = S::N;
+  const int full = M / 2 + 1, lim = M / 3 + 1;
+  if constexpr (S::TPT <= 64 && 64 % S::TPT == 0) {      // the wave-synchronous build
+    test_nlm<S, double, 2, true, false, true, false>(lim, 0, 7, true);
+    test_nlm<S, float, 3, false, false, true, true>(full, 0, 1, true);
+    test_nlm_spikes<S, double, 2, true, false, true, true>();
+    test_nlm_spikes<S, float, 3, false, false, true, false>();
+  }
+  test_nlm<S, double, 2, true, false, false, false>(full, 0, 7, false);
+  test_nlm<S, double, 1, false, true, false, true>(lim, 0, 1, true);
+  test_nlm<S, float, 2, true, true, false, false>(full, 0, 5, true);
+  test_nlm<S, float, 3, false, false, false, true>(lim, 0, 1, false);
+  test_nlm_spikes<S, double, 1, false, true, false, false>();
+  test_nlm_spikes<S, float, 1, true, false, false, true>();
+  if (lim < full) {                                 // pruned 2/3-rule: the kept kz bins in, every bin out
+    test_nlm<S, double, 2, true, false, false, true>(full, lim, 7, false);
+    test_nlm<S, float, 1, false, true, false, false>(full, (2 * full) / 3, 3, false);
+  }
+}
+
 // the pruned 3/2-rule flavour (Nlz3Fft): M = 3 L, L + 1 bins per row, three sub-transforms per row
 template <class SL, typename T, int ROWS, bool TWLDS>
 static void test_nlz3(bool inplace) {
@@ -1653,6 +1810,11 @@ int main() {
 #define MFFT_NLD(N, ...) test_nld_all<Spec<N, __VA_ARGS__>>();
   MFFT_NLZPLANS_P2(MFFT_NLD) MFFT_NLZPLANS_3(MFFT_NLD) MFFT_NLZPLANS_9(MFFT_NLD)     // the fused nonlinear z stage, dot product
 #undef MFFT_NLD
+#endif
+#if EMU_HAS(19)      // (`make emu_nlm`, a binary of its own as well)
+#define MFFT_NLM(N, ...) test_nlm_all<Spec<N, __VA_ARGS__>>();
+  MFFT_NLZPLANS_P2(MFFT_NLM) MFFT_NLZPLANS_3(MFFT_NLM) MFFT_NLZPLANS_9(MFFT_NLM)     // the fused nonlinear z stage with the real-space maxima
+#undef MFFT_NLM
 #endif
 #if EMU_HAS(1)
   // pair-row kernels (with plan group B, where the shipped 512 / 1024 plans are; tests/test_cabi.py fixes the number of parts): even and odd meshes (self-paired planes and rows), a partial last workgroup, the shipped shapes

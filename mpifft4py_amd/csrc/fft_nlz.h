@@ -43,6 +43,46 @@ struct NlzParams {
   T scale;                     // applied to a x b (both inverse transforms are un-normalised: 1 / M^2 gives numpy's irfft)
   const cx<T>* rt3;            // Nlz3Fft: exp(+2 pi i k / M), k = 0..L, then exp(+2 pi i 2k / M), k = 0..L   (M = 3 L)
 };
+// ... of the kernels that also emit max |a_f|, max |b_f| of the real rows (NlzAbsMax below).  A derived struct: a new field of
+// NlzParams would be an argument of every existing kernel.
+template <typename T>
+struct NlmParams : NlzParams<T> {
+  T* part;                     // (waves of the launch, 2 rows of a pair, [a, b], 3 fields) un-normalised maxima, every slot written
+};
+constexpr int NLM_SLOTS = 12;  // values per wave in NlmParams::part
+
+// Maximum that KEEPS a NaN (fmax drops it): a blown-up field must not report a finite maximum.  m is sticky once NaN.
+template <typename T> MFFT_D T nan_max(T m, T x) { return (x > m || x != x) ? x : m; }
+template <typename T> MFFT_D T abs_of(T x) { return x < (T)0 ? -x : x; }
+// STATS kernels: a value that is not finite (x - x is 0 only for finite x) leaves the transform -- it reads as 0 -- and is kept in
+// `bad` (the larger of the |x| met, NaN above Inf).  The two real fields of a pair share ONE complex transform, so left in
+// it would turn the partner field's values into NaNs as well; its own field gets it back after the transform (NlzFft::stats).
+template <typename T> MFFT_D void take_out_nonfinite(cx<T>& z, T& bad) {      // (the whole bin: its field is marked, whatever the other part was)
+  const T s = abs_of(z.x) + abs_of(z.y);
+  if ((s - s) != (T)0) {
+    bad = nan_max(bad, s);
+    z = mk<T>((T)0, (T)0);
+  }
+}
+// max over the WHOLE wave of two values (>= 0 or NaN), lane 0 stores them.  Lanes past the workgroup's last thread (a
+// workgroup need not be whole waves: 12 threads per row x 21 rows) are left out; lane 0 still ends with the maximum of
+// the lanes that exist, because a lane l < o whose partner l + o is missing has no one behind that partner either.
+template <typename T, int THREADS>
+MFFT_D void wave_absmax_store(T ma, T mb, int tid, T* slot) {
+  const int lane = tid & 63;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const T oa = wave_shfl(ma, lane ^ o), ob = wave_shfl(mb, lane ^ o);
+    if (THREADS % 64 == 0 || (tid ^ o) < THREADS) {
+      ma = nan_max(ma, oa);
+      mb = nan_max(mb, ob);
+    }
+  }
+  if (lane == 0) {
+    slot[0] = ma;
+    slot[3] = mb;
+  }
+}
 
 // WAVE: a row's threads sit inside ONE wave (TPT divides 64), so the exchanges of its transforms need no workgroup barrier at
 // all: LDS operations of a wave execute in issue order, what a lane wrote is there for every lane's later read, and the only
@@ -86,7 +126,10 @@ struct NlzFft {
   typedef typename std::conditional<WAVE, XchFullW<T, PadSlot<PD>, true>, typename RowXch<SPLIT, T, PadSlot<PD>>::type>::type Xch;
 
   // Z = A + iB at the positions of thread j, ready for the inverse passes (swap identity)
-  static MFFT_D void load_pair(cx<T> (&v)[E], const cx<T>* ra, const cx<T>* rb, int j, int valid) {
+  // (STATS: non-finite input values are taken out, bad[0] of field a, bad[1] of field b: take_out_nonfinite)
+  template <bool STATS = false>
+  static MFFT_D void load_pair(cx<T> (&v)[E], const cx<T>* ra, const cx<T>* rb, int j, int valid, T* bad = nullptr) {
+    if constexpr (STATS) bad[0] = bad[1] = (T)0;
 #pragma unroll
     for (int k = 0; k < E; ++k) {
       const int p = j + k * S::TPT;
@@ -99,17 +142,21 @@ struct NlzFft {
         xa.y = (T)0;
         xb.y = (T)0;
       }
+      if constexpr (STATS) {
+        take_out_nonfinite(xa, bad[0]);
+        take_out_nonfinite(xb, bad[1]);
+      }
       if (mir) { xa.y = -xa.y; xb.y = -xb.y; }
       v[k] = mk<T>(xa.y + xb.x, xa.x - xb.y);      // swapri(A + iB)
     }
   }
 
-  template <class TwPtr>
-  static MFFT_D void inverse_pair(cx<T> (&v)[E], const cx<T>* ra, const cx<T>* rb, int j, int valid, TwPtr tw, Xch& xc) {
+  template <bool STATS = false, class TwPtr>
+  static MFFT_D void inverse_pair(cx<T> (&v)[E], const cx<T>* ra, const cx<T>* rb, int j, int valid, TwPtr tw, Xch& xc, T* bad = nullptr) {
     // (Hiding j here and in forward_pair, as Nlz3Fft does, makes the address arithmetic local to each of the five transforms:
     // 216 -> 160 VGPRs for the 8-values plans -- and 5 % SLOWER, 512: 0.555 -> 0.583 ms, 1024: 0.879 -> 0.923; the 12-values plans
     // spill more, not less, 768: 1.36 -> 1.66 ms: profiles/r06_nlz_variants.txt.  Not done.)
-    load_pair(v, ra, rb, j, valid);
+    load_pair<STATS>(v, ra, rb, j, valid, bad);
     nlz_sync<WAVE>();
     run_passes<S, 0, T>(v, j, tw, xc);
   }
@@ -162,7 +209,37 @@ struct NlzFft {
     }
   }
 
-  static MFFT_D void body(const NlzParams<T>& P, int bid, int tid, char* lds) {
+  // STATS (NlzAbsMax): max |a_f|, max |b_f| over this thread's E positions of the pair just transformed (.y = a_f, .x = b_f),
+  // reduced over the wave and stored at once: the maxima themselves are not carried across the next transform.  What IS live
+  // across the transform before is bad[2] (two T: four VGPRs in double), from load_pair to here -- the variant is not
+  // register-neutral (profiles/nonlinear_absmax_regs.tsv).  A wave may hold several rows or a part of one: the slot is the
+  // launch's wave, the fold kernel does not care which rows went into it.
+  // bad[0], bad[1]: what load_pair took out of the spectra of a_f, b_f at this thread's bins (0: nothing).  It goes into that
+  // field's maximum -- a NaN bin makes the whole real row NaN, an Inf bin Inf or NaN -- and, as NaNs, into this thread's values
+  // of that field, so that the product rows come out NaN as the plain kernel's do (the forward transform spreads them over the
+  // row); the partner field stays what it is.
+  template <bool STATS, class PP>
+  static MFFT_D void stats(cx<T> (&v)[E], const PP& P, int bid, int tid, int h, int f, const T* bad) {
+    if constexpr (STATS) {
+      T ma = bad[0], mb = bad[1];
+#pragma unroll
+      for (int k = 0; k < E; ++k) {
+        ma = nan_max(ma, abs_of(v[k].y));
+        mb = nan_max(mb, abs_of(v[k].x));
+      }
+      const bool ba = bad[0] != (T)0, bb = bad[1] != (T)0;
+      const T pa = bad[0] * (T)0, pb = bad[1] * (T)0;        // NaN where something was taken out
+#pragma unroll
+      for (int k = 0; k < E; ++k) v[k] = mk<T>(bb ? pb : v[k].x, ba ? pa : v[k].y);
+      constexpr int NW = (THREADS + 63) / 64;
+      const i64 wave = (i64)bid * NW + tid / 64;
+      wave_absmax_store<T, THREADS>(ma, mb, tid, P.part + (wave * 2 + h) * 6 + f);
+    }
+  }
+
+  static MFFT_D void body(const NlzParams<T>& P, int bid, int tid, char* lds) { body_t<false>(P, bid, tid, lds); }
+  template <bool STATS, class PP>
+  static MFFT_D void body_t(const PP& P, int bid, int tid, char* lds) {
     cx<T>* ltw = reinterpret_cast<cx<T>*>(lds);
     const int rl = tid / S::TPT;
     const int j = row_thread_index<S>(tid);
@@ -187,13 +264,17 @@ struct NlzFft {
       const i64 io = lrow * P.in_stride;
       cx<T> pk[2][E];
       cx<T> v[E];
-      inverse_pair(v, P.a[0] + io, P.b[0] + io, j, P.valid_in, tw, xc);
+      T bad[2];
+      inverse_pair<STATS>(v, P.a[0] + io, P.b[0] + io, j, P.valid_in, tw, xc, bad);
+      stats<STATS>(v, P, bid, tid, h, 0, bad);
 #pragma unroll
       for (int k = 0; k < E; ++k) pk[0][k] = v[k];
-      inverse_pair(v, P.a[1] + io, P.b[1] + io, j, P.valid_in, tw, xc);
+      inverse_pair<STATS>(v, P.a[1] + io, P.b[1] + io, j, P.valid_in, tw, xc, bad);
+      stats<STATS>(v, P, bid, tid, h, 1, bad);
 #pragma unroll
       for (int k = 0; k < E; ++k) pk[1][k] = v[k];
-      inverse_pair(v, P.a[2] + io, P.b[2] + io, j, P.valid_in, tw, xc);
+      inverse_pair<STATS>(v, P.a[2] + io, P.b[2] + io, j, P.valid_in, tw, xc, bad);
+      stats<STATS>(v, P, bid, tid, h, 2, bad);
       // the results are swapped (inverse through the swap identity): .y = a_f, .x = b_f at position j + k TPT
       T r2[E];
 #pragma unroll
@@ -223,7 +304,9 @@ struct NlzFft {
   // sum of the first row of a pair while the second is computed; the two sums then ride on ONE forward transform, as r2 does
   // above.  3.5 transforms and 7 rows of `valid` bins per (x, y) point instead of 4.5 and 9; out[1], out[2] are not read.
   // All six rows of both (x, y) points are loaded before the first store, so out[0] may alias any a[f] or b[f] row for row.
-  static MFFT_D void body_dot(const NlzParams<T>& P, int bid, int tid, char* lds) {
+  static MFFT_D void body_dot(const NlzParams<T>& P, int bid, int tid, char* lds) { body_dot_t<false>(P, bid, tid, lds); }
+  template <bool STATS, class PP>
+  static MFFT_D void body_dot_t(const PP& P, int bid, int tid, char* lds) {
     cx<T>* ltw = reinterpret_cast<cx<T>*>(lds);
     const int rl = tid / S::TPT;
     const int j = row_thread_index<S>(tid);
@@ -248,14 +331,18 @@ struct NlzFft {
       const i64 io = lrow * P.in_stride;
       cx<T> v[E];
       T s[E];
+      T bad[2];
       // the results are swapped (inverse through the swap identity): .y = a_f, .x = b_f at position j + k TPT
-      inverse_pair(v, P.a[0] + io, P.b[0] + io, j, P.valid_in, tw, xc);
+      inverse_pair<STATS>(v, P.a[0] + io, P.b[0] + io, j, P.valid_in, tw, xc, bad);
+      stats<STATS>(v, P, bid, tid, h, 0, bad);
 #pragma unroll
       for (int k = 0; k < E; ++k) s[k] = v[k].x * v[k].y;
-      inverse_pair(v, P.a[1] + io, P.b[1] + io, j, P.valid_in, tw, xc);
+      inverse_pair<STATS>(v, P.a[1] + io, P.b[1] + io, j, P.valid_in, tw, xc, bad);
+      stats<STATS>(v, P, bid, tid, h, 1, bad);
 #pragma unroll
       for (int k = 0; k < E; ++k) s[k] += v[k].x * v[k].y;
-      inverse_pair(v, P.a[2] + io, P.b[2] + io, j, P.valid_in, tw, xc);
+      inverse_pair<STATS>(v, P.a[2] + io, P.b[2] + io, j, P.valid_in, tw, xc, bad);
+      stats<STATS>(v, P, bid, tid, h, 2, bad);
 #pragma unroll
       for (int k = 0; k < E; ++k) s[k] += v[k].x * v[k].y;
       if (h == 0) {
@@ -280,6 +367,17 @@ template <class K, NlzProduct PRODUCT = NlzProduct::Cross> struct NlzProd : K {}
 template <class K> struct NlzProd<K, NlzProduct::Dot> {
   static constexpr int THREADS = K::THREADS, LDS_BYTES = K::LDS_BYTES;
   template <class P> static MFFT_D void body(const P& p, int bid, int tid, char* lds) { K::body_dot(p, bid, tid, lds); }
+};
+
+// The stage that also emits the six maxima (Build::AbsMax): K's body with STATS on and NlmParams.  A wrapper again, for the
+// same reason -- and the plain bodies above forward to the same templates with STATS off, which compiles to what they were.
+template <class K, NlzProduct PRODUCT = NlzProduct::Cross> struct NlzAbsMax {
+  static constexpr int THREADS = K::THREADS, LDS_BYTES = K::LDS_BYTES;
+  static constexpr int WAVES = (K::THREADS + 63) / 64;       // slots of NlmParams::part per workgroup
+  template <class P> static MFFT_D void body(const P& p, int bid, int tid, char* lds) {
+    if constexpr (PRODUCT == NlzProduct::Dot) K::template body_dot_t<true>(p, bid, tid, lds);
+    else K::template body_t<true>(p, bid, tid, lds);
+  }
 };
 
 // ---------------------------------------------------------------------------

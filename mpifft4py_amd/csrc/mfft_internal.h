@@ -125,9 +125,16 @@ struct NlzArgs {
   int valid_in = 0;      // bins per INPUT row, where fewer than `valid` exist (pruned 2/3-rule); 0 = valid
   double scale = 1.0;    // applied to the product (1 / n^2: both inverse transforms normalised)
   Op product = Op::Plain;  // Op::Plain: a x b into out[0..2];  Op::Dot: sum_f a_f b_f into out[0], out[1..2] unused
+  void* part = nullptr;    // not null: the Build::AbsMax kernel runs and writes nlz_absmax_waves() groups of 12 un-normalised
+                           // partial maxima here, in the rows' precision: [wave][row of the pair][a, b][field] (fft_nlz.h NlmParams)
 };
-bool nlz_supported(int64_t n, int prec, Op product = Op::Plain);
+bool nlz_supported(int64_t n, int prec, Op product = Op::Plain, bool absmax = false);
+int64_t nlz_absmax_waves(int64_t n, int prec, Op product, int64_t nrows);
 int launch_nlz(const NlzArgs& a, hipStream_t s);
+// max |x| reductions (absmax.hip): acc[s] = max(acc[s], scale * max_g part[g * period + s]), NaNs kept; `scratch` holds
+// absmax_fold_scratch_bytes(), `part` is in precision `prec`, acc in double
+size_t absmax_fold_scratch_bytes();
+int absmax_fold(const void* part, size_t groups, int period, int prec, double scale, double* scratch, double* acc, hipStream_t s);
 
 // strided 3-D box copy: dst[i][j][k] = src[i][j][k] over extents e0,e1,e2 with
 // element strides (k contiguous); elem = bytes per element (8 or 16)

@@ -9,7 +9,7 @@ using namespace mfft;
 #endif
 
 mfft_plan_s::~mfft_plan_s() {
-  for (Buf* b : {&work[0], &work[1], &work[2], &work3, &nlw[0], &nlw[1], &nlx, &nly, &nlr, &pcomp, &shl})
+  for (Buf* b : {&work[0], &work[1], &work[2], &work3, &nlw[0], &nlw[1], &nlx, &nly, &nlr, &pcomp, &shl, &nlm, &nlmacc})
     if (b->p) (void)(b->arena ? wfree(b->p) : dev_free(b->p));
   if (mask) (void)hipFree(mask);
   if (band_tiles) (void)hipFree(band_tiles);
@@ -352,6 +352,25 @@ int mfft_nonlinear_dot(mfft_plan_t p, const void* a_hat, const void* b_hat, void
   return p->nonlinear_dot(a_hat, b_hat, out_hat, dealias);
 }
 
+// ... and the same two with statistics: the call also leaves the six real-space maxima in the plan (mfft_plan_nonlinear_absmax)
+static int nonlinear_stats(mfft_plan_t p, const void* a_hat, const void* b_hat, void* out_hat, int dealias, Op product) {
+  MFFT_TRY(check_ready(p, a_hat, b_hat));
+  if (!out_hat) return set_error(MFFT_ERR_INVALID, "null argument");
+  if (dealias != MFFT_DEALIAS_NONE && dealias != MFFT_DEALIAS_2_3 && dealias != MFFT_DEALIAS_3_2)
+    return set_error(MFFT_ERR_INVALID, "unknown dealias mode %d", dealias);
+  return p->nonlinear(a_hat, b_hat, out_hat, dealias, product, true);
+}
+int mfft_nonlinear_cross_absmax(mfft_plan_t p, const void* a_hat, const void* b_hat, void* out_hat, int dealias) {
+  return nonlinear_stats(p, a_hat, b_hat, out_hat, dealias, Op::Plain);
+}
+int mfft_nonlinear_dot_absmax(mfft_plan_t p, const void* a_hat, const void* b_hat, void* out_hat, int dealias) {
+  return nonlinear_stats(p, a_hat, b_hat, out_hat, dealias, Op::Dot);
+}
+int mfft_plan_nonlinear_absmax(mfft_plan_t p, double out6[6]) {
+  if (!p || !out6) return set_error(MFFT_ERR_INVALID, "null argument");
+  return p->nonlinear_absmax(out6);
+}
+
 int mfft_plan_sync(mfft_plan_t p) {
   if (!p) return set_error(MFFT_ERR_INVALID, "null plan");
   if (p->cstream) MFFT_HIP(hipStreamSynchronize(p->cstream));
@@ -377,6 +396,12 @@ int mfft_plan_get_info(mfft_plan_t p, const char* key, int64_t* value) {
   else if (k == "nonlinear_dot_fused_none") *value = p->nonlinear_fusable(MFFT_DEALIAS_NONE, Op::Dot) ? 1 : 0;
   else if (k == "nonlinear_dot_fused_2_3") *value = p->nonlinear_fusable(MFFT_DEALIAS_2_3, Op::Dot) ? 1 : 0;
   else if (k == "nonlinear_dot_fused_3_2") *value = p->nonlinear_fusable(MFFT_DEALIAS_3_2, Op::Dot) ? 1 : 0;
+  else if (k == "nonlinear_absmax_fused_none") *value = p->nonlinear_fusable(MFFT_DEALIAS_NONE, Op::Plain, true) ? 1 : 0;
+  else if (k == "nonlinear_absmax_fused_2_3") *value = p->nonlinear_fusable(MFFT_DEALIAS_2_3, Op::Plain, true) ? 1 : 0;
+  else if (k == "nonlinear_absmax_fused_3_2") *value = p->nonlinear_fusable(MFFT_DEALIAS_3_2, Op::Plain, true) ? 1 : 0;
+  else if (k == "nonlinear_dot_absmax_fused_none") *value = p->nonlinear_fusable(MFFT_DEALIAS_NONE, Op::Dot, true) ? 1 : 0;
+  else if (k == "nonlinear_dot_absmax_fused_2_3") *value = p->nonlinear_fusable(MFFT_DEALIAS_2_3, Op::Dot, true) ? 1 : 0;
+  else if (k == "nonlinear_dot_absmax_fused_3_2") *value = p->nonlinear_fusable(MFFT_DEALIAS_3_2, Op::Dot, true) ? 1 : 0;
   else if (k == "nonlinear_bytes") *value = (int64_t)(p->nlx.bytes + p->nly.bytes + p->nlr.bytes + p->nlw[0].bytes + p->nlw[1].bytes);
   else if (k == "split_last") *value = p->split_last_route() ? 1 : 0;   // the one-rank route that splits real / complex last (decides whether the work buffer fits, if no call has yet)
   else if (k == "plane_pad") *value = (p->P == 1 && p->d.decomp == MFFT_SLAB) ? p->p1_plane_pad() : 0;   // elements added to the intermediate's plane pitch

@@ -112,9 +112,12 @@ struct mfft_plan_s {
   // exchange buffers of the nonlinear route).  Plain device memory: nlx (fused nonlinear route: the six spectra after their
   // inverse x pass, (L0, N1, Za) each), nly (a batch of their x planes after the inverse y pass, (mb, L1, Za) each), nlr
   // (composed route: nine real-space work arrays), pcomp (compact copy for the plans that do not run on pitched rows natively),
-  // shl (mfft_ew_shell_sums: the workgroups' histograms and the result; no captured sequence holds it).
+  // shl (mfft_ew_shell_sums: the workgroups' histograms and the result; no captured sequence holds it), nlm (the partial maxima
+  // of a statistics call, absmax.hip: fold scratch, then the waves' slots) and nlmacc (twelve doubles that never move: the six
+  // maxima of the last statistics call, the result of mfft_ew_absmax); no captured sequence holds them either.
   Buf work[3] = {{true, true}, {true, true}, {true, true}}, work3{true, false}, nlw[2] = {{true, true}, {true, true}};
-  Buf nlx{false, true}, nly{false, true}, nlr{false, true}, pcomp{false, true}, shl{false, false};
+  Buf nlx{false, true}, nly{false, true}, nlr{false, true}, pcomp{false, true}, shl{false, false}, nlm{false, false}, nlmacc{false, false};
+  bool nlm_valid = false;       // a statistics call has run: nlmacc[0..5] hold max |ifftn(a_f)|, max |ifftn(b_f)| of this rank
   uint8_t* mask = nullptr;
   size_t mask_count = 0;
   bool timing = false;
@@ -478,14 +481,18 @@ struct mfft_plan_s {
 
   // ---- round 6: the nonlinear term a x b of a pseudo-spectral step as one operation (fft_nlz.h; plan_nonlinear.hip) ----
   // (product: mfft::Op::Plain the cross product, three result components; mfft::Op::Dot the dot product, one)
-  bool nonlinear_fusable(int dealias, mfft::Op product = mfft::Op::Plain) const;
+  // (stats: also the six real-space maxima, into nlmacc -- the Build::AbsMax z kernel on the fused routes, a sweep over the
+  // real work arrays on the composed one)
+  bool nonlinear_fusable(int dealias, mfft::Op product = mfft::Op::Plain, bool stats = false) const;
   int64_t local_real_count(bool padded) const;
   int nonlinear_cross(const void* a, const void* b, void* out, int dealias);
   int nonlinear_dot(const void* a, const void* b, void* out, int dealias);      // out: ONE component; may alias one of a's or b's
-  int nonlinear(const void* a, const void* b, void* out, int dealias, mfft::Op product);
-  int nonlinear_fused(const void* a, const void* b, void* out, int dealias, mfft::Op product);
-  int nonlinear_fused_ranks(const void* a, const void* b, void* out, int dealias, mfft::Op product);
-  int nonlinear_composed(const void* a, const void* b, void* out, int dealias, mfft::Op product);
+  int nonlinear(const void* a, const void* b, void* out, int dealias, mfft::Op product, bool stats = false);
+  int nonlinear_fused(const void* a, const void* b, void* out, int dealias, mfft::Op product, bool stats);
+  int nonlinear_fused_ranks(const void* a, const void* b, void* out, int dealias, mfft::Op product, bool stats);
+  int nonlinear_composed(const void* a, const void* b, void* out, int dealias, mfft::Op product, bool stats);
+  int nonlinear_absmax(double out6[6]);                                   // this rank's maxima of the last statistics call
+  int absmax_sweep(const void* x, int ncomp, size_t n, double* acc);      // absmax.hip
 };
 
 namespace mfft {

@@ -1,5 +1,6 @@
 // plan_nonlinear.hip -- the nonlinear term of a pseudo-spectral step as one plan-level operation.
 #include "plan_impl.h"
+#include "fft_nlz.h"
 
 using namespace mfft;
 
@@ -22,7 +23,7 @@ int64_t mfft_plan_s::local_real_count(bool padded) const {
 
 // Composed route (every decomposition and length): the transforms the caller would run, on nine (dot product: seven) work
 // arrays of the plan.
-int mfft_plan_s::nonlinear_composed(const void* a, const void* b, void* out, int dealias, Op product) {
+int mfft_plan_s::nonlinear_composed(const void* a, const void* b, void* out, int dealias, Op product, bool stats) {
   const int nout = nl_nout(product);
   const bool pad = dealias == MFFT_DEALIAS_3_2, masked = dealias == MFFT_DEALIAS_2_3;
   const int64_t nr = local_real_count(pad), nc = local_complex_alloc();       // (pitched arrays: a component is that much larger)
@@ -35,6 +36,8 @@ int mfft_plan_s::nonlinear_composed(const void* a, const void* b, void* out, int
     MFFT_TRY(back(static_cast<const char*>(a) + (size_t)(f * nc) * es, R + (size_t)(f * nr) * rs));
     MFFT_TRY(back(static_cast<const char*>(b) + (size_t)(f * nc) * es, R + (size_t)((3 + f) * nr) * rs));
   }
+  // statistics: the six real arrays exist here, one streaming sweep over them (absmax.hip) into the same accumulator
+  if (stats) MFFT_TRY(stage("nl_absmax", 6.0 * (double)nr * rs, [&] { return absmax_sweep(R, 6, (size_t)nr, static_cast<double*>(nlmacc.p)); }));
   MFFT_TRY(stage(nout == 1 ? "nl_dot" : "nl_cross", (6.0 + nout) * (double)nr * rs, [&] {
     return (nout == 1 ? mfft_ew_dot : mfft_ew_cross)(this, R, R + (size_t)(3 * nr) * rs, R + (size_t)(6 * nr) * rs, (size_t)nr, prec);
   }));
@@ -52,8 +55,17 @@ static int64_t nlz_batch_planes(size_t plane6, int64_t planes) {
 
 // the fused z stage on a batch: rows of the six fields in Y (yelems apart, pitch Za) in, the three rows of the cross product
 // (the one row of the dot product) out, in place on the first three (the first)
-static int nlz_rows(mfft_plan_s* p, char* Y, size_t yelems, int64_t L2, int64_t Za, int64_t nrows, int valid_in, Op product) {
+// (stats: the Build::AbsMax kernel, its partial maxima into nlm, folded into the plan's accumulator with 1 / L2 -- the kernel's
+// inverse transforms are un-normalised -- after the launch: the maxima accumulate over the batches)
+static int nlz_rows(mfft_plan_s* p, char* Y, size_t yelems, int64_t L2, int64_t Za, int64_t nrows, int valid_in, Op product, bool stats) {
   NlzArgs z;
+  int64_t waves = 0;
+  if (stats) {
+    waves = nlz_absmax_waves(L2, p->prec, product, nrows);
+    if (waves < 1) return set_error(MFFT_ERR_INTERNAL, "no fused z kernel with maxima of length %lld", (long long)L2);
+    MFFT_TRY(p->ensure(p->nlm, absmax_fold_scratch_bytes() + (size_t)waves * NLM_SLOTS * p->rs));
+    z.part = static_cast<char*>(p->nlm.p) + absmax_fold_scratch_bytes();
+  }
   for (int f = 0; f < 3; ++f) {
     z.a[f] = Y + (size_t)f * yelems * p->es;
     z.b[f] = Y + (size_t)(3 + f) * yelems * p->es;
@@ -63,14 +75,19 @@ static int nlz_rows(mfft_plan_s* p, char* Y, size_t yelems, int64_t L2, int64_t 
   z.n = (int)L2; z.prec = p->prec; z.in_stride = Za; z.out_stride = Za; z.nrows = nrows; z.valid = (int)p->Nf;
   z.valid_in = valid_in;
   z.scale = 1.0 / ((double)L2 * (double)L2);
-  return launch_nlz(z, p->stream);
+  MFFT_TRY(launch_nlz(z, p->stream));
+  if (stats)      // 2 * waves groups of [a, b][field]: period 6, the accumulator's order
+    MFFT_TRY(absmax_fold(z.part, (size_t)(2 * waves), 6, p->prec, 1.0 / (double)L2, static_cast<double*>(p->nlm.p),
+                         static_cast<double*>(p->nlmacc.p), p->stream));
+  return 0;
 }
 
 // Fused route: one rank, slab, real data, radix kernels on every axis.
-bool mfft_plan_s::nonlinear_fusable(int dealias, Op product) const {
+bool mfft_plan_s::nonlinear_fusable(int dealias, Op product, bool stats) const {
   static const bool off = env_on("MFFT_NO_NLZ"), ranks_off = env_on("MFFT_NO_NLZ_RANKS");      // read once per process
   if (off || d.decomp != MFFT_SLAB || !r2c || d.line2d || d.drop_nyquist || N0 < 2 || N1 < 2 || N2 < 2) return false;
   if (P > 1 && (ranks_off || pitched() || (dealias == MFFT_DEALIAS_3_2 && P > N0 / 2))) return false;
+  if (stats && !nlz_supported(dealias == MFFT_DEALIAS_3_2 ? M2 : N2, prec, product, true)) return false;
   if (dealias == MFFT_DEALIAS_3_2) return can_fuse_pad() && nlz_supported(M2, prec, product);
   auto plain_ok = [&](int64_t n) {
     return n < 65536 && find_kernel(FAM_COL, (int)n, prec, 0) && find_kernel(FAM_COL, (int)n, prec, 1);
@@ -89,7 +106,7 @@ bool mfft_plan_s::nonlinear_fusable(int dealias, Op product) const {
 // composed route needs 9 x 29 GB of real work arrays).
 // Op::Dot: the same with ONE result -- the z kernel writes the rows of the dot product in place on the first field, one forward
 // y pass per batch, one forward x pass.
-int mfft_plan_s::nonlinear_fused(const void* a, const void* b, void* out, int dealias, Op product) {
+int mfft_plan_s::nonlinear_fused(const void* a, const void* b, void* out, int dealias, Op product, bool stats) {
   const int nout = nl_nout(product);
   const bool pad = dealias == MFFT_DEALIAS_3_2, masked = dealias == MFFT_DEALIAS_2_3;
   const int64_t L0 = pad ? M0 : N0, L1 = pad ? M1 : N1, L2 = pad ? M2 : N2;
@@ -165,7 +182,7 @@ int mfft_plan_s::nonlinear_fused(const void* a, const void* b, void* out, int de
       return 0;
     }));
     MFFT_TRY(stage("nl_z", (6 * keep2 + nout) * Yb * frac, [&] {
-      return nlz_rows(this, Y, yelems, L2, Za, m * L1, pruned ? ba2 : 0, product);
+      return nlz_rows(this, Y, yelems, L2, Za, m * L1, pruned ? ba2 : 0, product, stats);
     }));
     MFFT_TRY(stage("nl_y_fwd", nout * (Xb + Yb) * frac, [&] {
       for (int f = 0; f < nout; ++f)
@@ -195,7 +212,7 @@ int mfft_plan_s::nonlinear_fused(const void* a, const void* b, void* out, int de
 // two-level row map (transpose_Uc fused, maths.pyx:21-31), the fused z kernel, forward y passes writing the packed send
 // layout (slab.py:403) -- three all-to-alls, three forward x passes.  Nine exchanges as in the composition, no real arrays.
 // (Op::Dot: six inverse exchanges and one forward exchange.)
-int mfft_plan_s::nonlinear_fused_ranks(const void* a, const void* b, void* out, int dealias, Op product) {
+int mfft_plan_s::nonlinear_fused_ranks(const void* a, const void* b, void* out, int dealias, Op product, bool stats) {
   const int nout = nl_nout(product);
   const bool pad = dealias == MFFT_DEALIAS_3_2, masked = dealias == MFFT_DEALIAS_2_3;
   const int64_t L0 = pad ? M0 : N0, L1 = pad ? M1 : N1, L2 = pad ? M2 : N2, Lp0 = L0 / P;
@@ -262,7 +279,7 @@ int mfft_plan_s::nonlinear_fused_ranks(const void* a, const void* b, void* out, 
       return 0;
     }));
     MFFT_TRY(stage("nl_z", 0, [&] {
-      return nlz_rows(this, Y, yelems, L2, Za, m * L1, pruned ? (int)a2 : 0, product);
+      return nlz_rows(this, Y, yelems, L2, Za, m * L1, pruned ? (int)a2 : 0, product, stats);
     }));
     MFFT_TRY(stage("nl_y_fwd", 0, [&] {      // truncate + fold in y, straight into the packed (P, Lp0, S) send layout
       for (int f = 0; f < nout; ++f)
@@ -284,11 +301,28 @@ int mfft_plan_s::nonlinear_fused_ranks(const void* a, const void* b, void* out, 
   return 0;
 }
 
-int mfft_plan_s::nonlinear(const void* a, const void* b, void* out, int dealias, Op product) {
+// stats: the call also leaves max |ifftn(a_f, dealias)|, max |ifftn(b_f, dealias)| over this rank's part of the real-space grid
+// the product is formed on (the padded one under the 3/2-rule) in the plan's accumulator, nlmacc[0..5] = [a, b][f]: cleared on
+// the stream here, raised by every batch's fold (or the composed route's sweep), read by nonlinear_absmax.  A call without
+// stats does not touch it.
+int mfft_plan_s::nonlinear(const void* a, const void* b, void* out, int dealias, Op product, bool stats) {
   if (dealias == MFFT_DEALIAS_2_3) MFFT_TRY(require_mask());
-  if (nonlinear_fusable(dealias, product))
-    return P == 1 ? nonlinear_fused(a, b, out, dealias, product) : nonlinear_fused_ranks(a, b, out, dealias, product);
-  return nonlinear_composed(a, b, out, dealias, product);
+  if (stats) {
+    MFFT_TRY(ensure(nlmacc, 12 * sizeof(double)));
+    MFFT_HIP(hipMemsetAsync(nlmacc.p, 0, 6 * sizeof(double), stream));
+    nlm_valid = false;          // cleared, and partial until every batch has folded: valid only once the route has enqueued it all
+  }
+  const int rc = nonlinear_fusable(dealias, product, stats)
+                     ? (P == 1 ? nonlinear_fused(a, b, out, dealias, product, stats) : nonlinear_fused_ranks(a, b, out, dealias, product, stats))
+                     : nonlinear_composed(a, b, out, dealias, product, stats);
+  if (stats && rc == 0) nlm_valid = true;
+  return rc;
+}
+int mfft_plan_s::nonlinear_absmax(double out6[6]) {
+  if (!nlm_valid) return set_error(MFFT_ERR_INVALID, "no nonlinear operation with statistics has run on this plan");
+  MFFT_HIP(hipMemcpyAsync(out6, nlmacc.p, 6 * sizeof(double), hipMemcpyDeviceToHost, stream));
+  MFFT_HIP(hipStreamSynchronize(stream));
+  return 0;
 }
 int mfft_plan_s::nonlinear_cross(const void* a, const void* b, void* out, int dealias) { return nonlinear(a, b, out, dealias, Op::Plain); }
 int mfft_plan_s::nonlinear_dot(const void* a, const void* b, void* out, int dealias) { return nonlinear(a, b, out, dealias, Op::Dot); }

@@ -49,7 +49,8 @@ enum class Build : unsigned {
   Col3Thirds,       // COL: ColFft3S, one third of a tile's transform per workgroup
   LdsMirrors,       // C2R: mirrored bins through LDS instead of a second load
   Nlz3,             // NLZ: Nlz3Fft (fft_nlz.h)
-  Last = Nlz3
+  AbsMax,           // NLZ: NlzFft that also emits max |ifft(a_f)|, max |ifft(b_f)| (fft_nlz.h NlzAbsMax; Op::Plain and Op::Dot)
+  Last = AbsMax
 };
 
 struct KernelEntry {

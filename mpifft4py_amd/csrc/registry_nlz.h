@@ -81,6 +81,31 @@ void register_nld(const char* name) {
   reg.push_back(make_entry<K, NlzParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::Dot, Build::Default, R, name));
 }
 
+// Build::AbsMax: both products once more, with the six real-space maxima emitted (fft_nlz.h NlzAbsMax; kernels_nlm*.hip).  Rows,
+// twiddle placement, exchange and register cap are those of the kernel it shadows (register_nlz / register_nld): the statistic
+// adds two live values per thread for the length of one wave reduction, and two more (`bad`: the non-finite input met on load)
+// that live across every inverse transform, plus two selects per value to put the NaNs back -- the double-precision 12-values
+// plans from 192 upward hold 24 - 128 bytes more scratch than the kernel they shadow (profiles/nonlinear_absmax_regs.tsv).  One exception: the
+// single-precision dot kernels of 1024 and 2048 run under a four-wave cap (nld_occ) that the plain kernel fills to the last of
+// its 128 registers; with the reduction it spills 130 bytes and more per lane there, so the variant takes three waves (168: 24 bytes).
+template <class S, typename T>
+void register_nlm(const char* name) {
+  auto& reg = kernel_registry();
+  {
+    constexpr int R = nlz_rows<S, T>();
+    constexpr int W = MFFT_NLZ_OCC > 1 ? 16 + MFFT_NLZ_OCC : 0;
+    typedef NlzAbsMax<NlzFft<S, T, R, nlz_twlds<S, T>(), nlz_split<S, T>(), nlz_wave<S, T>()>, NlzProduct::Cross> K;
+    reg.push_back(make_entry<K, NlmParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::Plain, Build::AbsMax, R, name));
+  }
+  {
+    constexpr int R = nld_rows<S, T>();
+    constexpr int O = nld_occ<S, T>() == 4 ? 3 : nld_occ<S, T>();
+    constexpr int W = O > 1 ? 16 + O : 0;
+    typedef NlzAbsMax<NlzFft<S, T, R, nld_twlds<S, T>(), nld_split<S, T>(), nld_wave<S, T>()>, NlzProduct::Dot> K;
+    reg.push_back(make_entry<K, NlmParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::Dot, Build::AbsMax, R, name));
+  }
+}
+
 // ... and its pruned 3/2-rule flavour (Nlz3Fft: Build::Nlz3, entry.n = M = 3 L): three thread groups of SL::TPT threads per row
 template <class SL, typename T> constexpr int nlz3_rows() { return 256 / (3 * SL::TPT) > 0 ? 256 / (3 * SL::TPT) : 1; }
 template <class SL, typename T>

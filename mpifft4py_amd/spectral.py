@@ -66,12 +66,14 @@ def ns_rhs(FFT, K, dU, U_hat, nu):
     return dU
 
 
-def cross_transform(FFT, a_hat, b_hat, out_hat, dealias=None):
+def cross_transform(FFT, a_hat, b_hat, out_hat, dealias=None, absmax=False):
     """out_hat = fftn(ifftn(a_hat) x ifftn(b_hat)), the nonlinear term of a pseudo-spectral step as ONE operation of the
     plan (mfft_nonlinear_cross): what the reference demo composes from six `FFT.ifftn(.., dealias)`, a cross product of
     numpy arrays and three `FFT.fftn(.., dealias)` (demo/spectral_dns_solver.py:53-71).  All three are DeviceArrays of
     shape (3,) + FFT.complex_shape(); out_hat may be a_hat or b_hat.  On one rank (slab) the z stages are one fused kernel
-    and no real-space work array exists (`FFT.plan_info("nonlinear_fused_3_2")`); elsewhere the plan composes it."""
+    and no real-space work array exists (`FFT.plan_info("nonlinear_fused_3_2")`); elsewhere the plan composes it.
+    With `absmax` the call also records max |ifftn(a_hat[f])| and max |ifftn(b_hat[f])| -- velocity and vorticity -- on the
+    device (mfft_nonlinear_cross_absmax); `nonlinear_absmax(FFT)` fetches them."""
     from ._base import _DEALIAS
     assert dealias in ('3/2-rule', '2/3-rule', 'None', None)
     shape = (3,) + tuple(int(s) for s in FFT.complex_shape())
@@ -82,7 +84,7 @@ def cross_transform(FFT, a_hat, b_hat, out_hat, dealias=None):
     FFT.comm.use_device()
     if code == _lib.DEALIAS_2_3:
         FFT._ensure_mask()
-    _lib.call("mfft_nonlinear_cross", FFT._plan, a_hat.ptr, b_hat.ptr, out_hat.ptr, code)
+    _lib.call("mfft_nonlinear_cross_absmax" if absmax else "mfft_nonlinear_cross", FFT._plan, a_hat.ptr, b_hat.ptr, out_hat.ptr, code)
     return out_hat
 
 
@@ -107,14 +109,15 @@ def grad_hat(FFT, K, s_hat, out):
     return out
 
 
-def dot_transform(FFT, a_hat, b_hat, out_hat, dealias=None):
+def dot_transform(FFT, a_hat, b_hat, out_hat, dealias=None, absmax=False):
     """out_hat = fftn(sum_f ifftn(a_hat[f]) * ifftn(b_hat[f])), the advection term u . grad(theta) of a transported scalar
     as ONE operation of the plan (mfft_nonlinear_dot): what a caller composes from six `FFT.ifftn(.., dealias)`,
     np.sum(A * B, 0) and one `FFT.fftn(.., dealias)`.  a_hat and b_hat are DeviceArrays of shape (3,) +
     FFT.complex_shape(), out_hat has FFT.complex_shape() and may be any one component of a_hat or b_hat
     (`b_hat.component(1)`); the inputs are otherwise preserved.  On slab plans with radix kernels on every axis the z
     stages are one fused kernel and no real-space work array exists (`FFT.plan_info("nonlinear_dot_fused_3_2")`);
-    elsewhere the plan composes it on seven work arrays of its own."""
+    elsewhere the plan composes it on seven work arrays of its own.  With `absmax` the call also records
+    max |ifftn(a_hat[f])| and max |ifftn(b_hat[f])| (mfft_nonlinear_dot_absmax; see `nonlinear_absmax`)."""
     from ._base import _DEALIAS
     assert dealias in ('3/2-rule', '2/3-rule', 'None', None)
     cs = tuple(int(s) for s in FFT.complex_shape())
@@ -125,8 +128,61 @@ def dot_transform(FFT, a_hat, b_hat, out_hat, dealias=None):
     FFT.comm.use_device()
     if code == _lib.DEALIAS_2_3:
         FFT._ensure_mask()
-    _lib.call("mfft_nonlinear_dot", FFT._plan, a_hat.ptr, b_hat.ptr, out_hat.ptr, code)
+    _lib.call("mfft_nonlinear_dot_absmax" if absmax else "mfft_nonlinear_dot", FFT._plan, a_hat.ptr, b_hat.ptr, out_hat.ptr, code)
     return out_hat
+
+
+def _max_over_ranks(FFT, v):
+    """Maximum over FFT.comm that keeps NaNs: the NaN flags are reduced beside the values and the NaNs put back."""
+    from .comm import MAX
+    v = np.asarray(v, dtype=np.float64)
+    nan = np.isnan(v)
+    both = np.concatenate([np.where(nan, 0.0, v).ravel(), nan.astype(np.float64).ravel()])
+    both = np.asarray(FFT.comm.allreduce(both, op=MAX)).reshape(2, -1)
+    return np.where(both[1] > 0.0, np.nan, both[0]).reshape(v.shape)
+
+
+def nonlinear_absmax(FFT, reduce=True):
+    """The six real-space maxima of the LAST `cross_transform` / `dot_transform` with `absmax=True`, a (2, 3) float64
+    array: [0][f] = max |ifftn(a_hat[f], dealias)|, [1][f] = max |ifftn(b_hat[f], dealias)| over the grid the product
+    was formed on (the padded grid under the 3/2-rule, the masked field under the 2/3-rule).  One synchronisation of the
+    plan's stream; with `reduce` the maximum over FFT.comm (every rank calls it), else this rank's x planes only.  A NaN
+    anywhere in a field gives NaN; the values are bitwise reproducible.  Raises if no such call has run on the plan."""
+    FFT.comm.use_device()
+    out = np.zeros(6, dtype=np.float64)
+    _lib.call("mfft_plan_nonlinear_absmax", FFT._plan, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    out = out.reshape(2, 3)
+    return _max_over_ranks(FFT, out) if reduce else out
+
+
+def absmax(FFT, x, reduce=False):
+    """max |x| of a real DeviceArray (mfft_ew_absmax, the companion of `sumsq`): a float for an array of the real shape,
+    a float64 vector of three for (3,) + the real shape (any leading extent of 1, 2, 3 or 6 is taken as components).
+    NaNs are kept.  With `reduce` the maximum over FFT.comm."""
+    if x.pitch is not None:
+        raise ValueError("absmax of a pitched array would look at the elements between its rows")
+    assert x.dtype == np.dtype(FFT.float), (x.dtype, FFT.float)
+    ncomp = int(x.shape[0]) if len(x.shape) == 4 else 1
+    FFT.comm.use_device()
+    out = np.zeros(6, dtype=np.float64)
+    _lib.call("mfft_ew_absmax", FFT._plan, x.ptr, ncomp, x.size // ncomp, _prec(FFT), out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    out = out[:ncomp]
+    if reduce:
+        out = _max_over_ranks(FFT, out)
+    return float(out[0]) if len(x.shape) != 4 else out
+
+
+def advective_dt(FFT, umax, cfl):
+    """cfl / sum_f umax[f] N[f] / L[f]: the advective (CFL) time step of a velocity whose components reach umax[f], on
+    the mesh FFT.N of the box FFT.L -- the mesh of the run, not the padded one of a 3/2-rule product.  Pure host
+    arithmetic; inf for a field at rest, nan if a maximum is."""
+    umax = np.asarray(umax, dtype=np.float64).reshape(-1)
+    N, L = np.asarray(FFT.N, dtype=np.float64), np.asarray(FFT.L, dtype=np.float64)
+    assert umax.size == N.size == L.size, (umax.size, N.size, L.size)
+    rate = float(np.sum(umax * N / L))
+    if rate != rate:
+        return float("nan")
+    return float("inf") if rate == 0.0 else float(cfl) / rate
 
 
 def ns_rk_stage(FFT, K, N_hat, U_hat, U_hat0, U_hat1, nu, a_dt, b_dt, last):

@@ -100,6 +100,8 @@ run() {
     r03_two_thirds_rule_ranks.txt) python scripts/maskprof_ranks.py 1024 8 ;;
     r03_pencil_dealias.txt) for k in X Y; do for p in double single; do python scripts/maskprof.py 1024 $p $k; MFFT_NO_PRUNE=1 python scripts/maskprof.py 1024 $p $k; done; python scripts/padprof.py 512 $k; done; python scripts/padprof.py 512 slab ;;
     nonlinear_dot_regs.tsv) make -C mpifft4py_amd/csrc -j8 >/dev/null; python scripts/nonlinear_dot_regs.py; python scripts/nonlinear_dot_regs.py --caps ;;
+    nonlinear_absmax_regs.tsv) make -C mpifft4py_amd/csrc -j8 >/dev/null; python scripts/nonlinear_absmax_regs.py ;;
+    nonlinear_absmax_ab.txt) python scripts/nonlinear_absmax_ab.py --procs 3 --out out/nonlinear_absmax_ab.txt ;;
     nonlinear_dot_ab.txt) python scripts/nonlinear_dot_ab.py --procs 3 --out out/nonlinear_dot_ab.txt
       # section 3: the shipped library against the build with every dot kernel at two waves per SIMD (the first candidate of that
       # section was the build with registry_nlz.h nld_occ returning 3 / 4 for the 8-values plans in double / single precision)
