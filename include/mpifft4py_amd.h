@@ -243,6 +243,13 @@ MFFT_API int mfft_nlz_rows(const void* a, const void* b, void* out, int64_t nrow
  * a caller's np.sum(U * gradT, 0). */
 MFFT_API int mfft_nlz_dot_rows(const void* a, const void* b, void* out, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
                                int precision, int sync);
+/* The same stage with BOTH products (the z stages of mfft_nonlinear_cross_dot): a, b, c, out are (3, nrows, pitch) as above, s
+ * is ONE (nrows, pitch) array; out_f[row] = rfft((irfft(a[:, row]) x irfft(b[:, row]))_f)[:valid] and s[row] =
+ * rfft(sum_f irfft(a[f, row]) irfft(c[f, row]))[:valid], with irfft(a) computed once.  out may be a or b, s any one component
+ * of a, b or c that out does not take.  MFFT_ERR_UNSUPPORTED for lengths without a kernel.  Replaces the z stages of nine
+ * FFT.ifftn + four FFT.fftn around a caller's np.cross(U, W) and np.sum(U * gradT, 0). */
+MFFT_API int mfft_nlz_cross_dot_rows(const void* a, const void* b, const void* c, void* out, void* s, int64_t nrows, int64_t n,
+                                     int64_t pitch, int64_t valid, int precision, int sync);
 /* Either stage with the maxima of its six real rows, synchronous: `out` as mfft_nlz_rows (dot = 0) or mfft_nlz_dot_rows
  * (dot = 1) leave it, and out6 = [max |irfft(a[f])|, f = 0..2, then max |irfft(b[f])|, f = 0..2] over all rows and all n
  * points (numpy's normalisation).  A NaN in a field gives NaN for that field.  The z stage of mfft_nonlinear_cross_absmax /
@@ -329,6 +336,19 @@ MFFT_API int mfft_nonlinear_cross(mfft_plan_t plan, const void* a_hat, const voi
  * registers as the three inverse pairs finish, two rows' sums ride on one forward transform) and the seven real-space
  * arrays of the composition never exist; every other plan composes it on seven work arrays of its own. */
 MFFT_API int mfft_nonlinear_dot(mfft_plan_t plan, const void* a_hat, const void* b_hat, void* out_hat, int dealias);
+
+/* Both terms of a velocity that carries a scalar (Boussinesq, a tracer in a DNS) as ONE operation:
+ *     out_hat = fftn(ifftn(a_hat) x ifftn(b_hat))                       (u x omega)
+ *     s_hat   = fftn(sum_f ifftn(a_hat[f]) * ifftn(c_hat[f]))           (u . grad(theta))
+ * = mfft_nonlinear_cross(a, b, out) and mfft_nonlinear_dot(a, c, s) with ifftn(a_hat) computed ONCE: nine inverse and four
+ * forward transforms instead of twelve and four.  a_hat, b_hat, c_hat, out_hat: (3,) + local complex shape; s_hat: the local
+ * complex shape (ONE component).  out_hat may be a_hat or b_hat, s_hat any one component of c_hat; the inputs are otherwise
+ * preserved.  Dealias conventions and routes are those of the two calls (mfft_plan_get_info "nonlinear_cross_dot_fused_3_2" /
+ * "_none" / "_2_3"): on slab R2C plans with radix kernels on every axis the z stages are ONE kernel (csrc/fft_nlz.h
+ * body_cross_dot: 6.5 complex transforms per (x, y) row instead of 8) and no real-space array exists; every other plan
+ * composes it on twelve work arrays of its own.  No statistics variant: take the maxima from mfft_nonlinear_cross_absmax. */
+MFFT_API int mfft_nonlinear_cross_dot(mfft_plan_t plan, const void* a_hat, const void* b_hat, const void* c_hat, void* out_hat,
+                                      void* s_hat, int dealias);
 
 /* The two operations above WITH STATISTICS: the call also records, on the device,
  *     absmax[0][f] = max |ifftn(a_hat[f], dealias)|,   absmax[1][f] = max |ifftn(b_hat[f], dealias)|,   f = 0..2

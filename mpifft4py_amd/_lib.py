@@ -91,6 +91,7 @@ _SIGNATURES = {
     "mfft_c2r_last": ([c_void_p, c_void_p, POINTER(c_int64), c_int], c_int),
     "mfft_nlz_rows": ([c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int], c_int),
     "mfft_nlz_dot_rows": ([c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int], c_int),
+    "mfft_nlz_cross_dot_rows": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int], c_int),
     "mfft_nlz_rows_absmax": ([c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, POINTER(c_double)], c_int),
     "mfft_slab_pack": ([c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int], c_int),
     "mfft_slab_unpack": ([c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int], c_int),
@@ -101,6 +102,7 @@ _SIGNATURES = {
     "mfft_kernel_name": ([c_int, c_int64, c_int, c_int, c_int, c_void_p, c_size_t], c_int),
     "mfft_nonlinear_cross": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int], c_int),
     "mfft_nonlinear_dot": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int], c_int),
+    "mfft_nonlinear_cross_dot": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int], c_int),
     "mfft_nonlinear_cross_absmax": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int], c_int),
     "mfft_nonlinear_dot_absmax": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int], c_int),
     "mfft_plan_nonlinear_absmax": ([c_void_p, POINTER(c_double)], c_int),

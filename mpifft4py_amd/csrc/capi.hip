@@ -289,6 +289,28 @@ int mfft_nlz_dot_rows(const void* a, const void* b, void* out, int64_t nrows, in
   return 0;
 }
 
+// ... and with both products (fft_nlz.h body_cross_dot): a, b, c, out (3, nrows, pitch), s (nrows, pitch); out may be a or b, s any
+// one component they leave alone
+int mfft_nlz_cross_dot_rows(const void* a, const void* b, const void* c, void* out, void* s, int64_t nrows, int64_t n, int64_t pitch,
+                            int64_t valid, int precision, int sync) {
+  if (!a || !b || !c || !out || !s || nrows < 1 || n < 2 || pitch < valid || valid < 1) return set_error(MFFT_ERR_INVALID, "bad argument");
+  const size_t es = elem_bytes(precision, true);
+  NlzArgs z;
+  for (int f = 0; f < 3; ++f) {
+    z.a[f] = static_cast<const char*>(a) + (size_t)(f * nrows * pitch) * es;
+    z.b[f] = static_cast<const char*>(b) + (size_t)(f * nrows * pitch) * es;
+    z.c[f] = static_cast<const char*>(c) + (size_t)(f * nrows * pitch) * es;
+    z.out[f] = static_cast<char*>(out) + (size_t)(f * nrows * pitch) * es;
+  }
+  z.out[3] = s;
+  z.product = Op::CrossDot;
+  z.n = (int)n; z.prec = precision; z.in_stride = pitch; z.out_stride = pitch; z.nrows = nrows; z.valid = (int)valid;
+  z.scale = 1.0 / ((double)n * (double)n);
+  MFFT_TRY(launch_nlz(z, nullptr));
+  if (sync) MFFT_HIP(hipStreamSynchronize(nullptr));
+  return 0;
+}
+
 // The stage with the maxima of its six real rows (fft_nlz.h NlzAbsMax), synchronous: out as mfft_nlz_rows (dot = 0) or
 // mfft_nlz_dot_rows (dot = 1) leave it, out6 = [max |irfft(a_f)|, f = 0..2, max |irfft(b_f)|, f = 0..2] over all rows.
 int mfft_nlz_rows_absmax(const void* a, const void* b, void* out, int64_t nrows, int64_t n, int64_t pitch, int64_t valid, int precision,

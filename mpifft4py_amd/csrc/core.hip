@@ -528,7 +528,7 @@ int launch_c2r(const RealArgs& a, hipStream_t s) { return launch_real(FAM_C2R, a
 // fused nonlinear z stage (fft_nlz.h): out_f = rfft((irfft(a) x irfft(b))_f) along the contiguous axis, row by row
 bool nlz_supported(int64_t n, int prec, Op product, bool absmax) {
   if (absmax) return n >= 2 && n < 65536 && find_kernel(FAM_NLZ, (int)n, prec, 0, product, Build::AbsMax) != nullptr;
-  if (product == Op::Dot) return n >= 2 && n < 65536 && find_kernel(FAM_NLZ, (int)n, prec, 0, Op::Dot) != nullptr;
+  if (product == Op::Dot || product == Op::CrossDot) return n >= 2 && n < 65536 && find_kernel(FAM_NLZ, (int)n, prec, 0, product) != nullptr;
   return n >= 2 && n < 65536 && (find_kernel(FAM_NLZ, (int)n, prec, 0) != nullptr || find_kernel(FAM_NLZ, (int)n, prec, 0, Op::Plain, Build::Nlz3) != nullptr);
 }
 // waves of the Build::AbsMax launch over nrows rows = groups of NLM_SLOTS values it writes to NlzArgs::part (0: no such kernel)
@@ -541,6 +541,10 @@ template <typename T, class PT = NlzParams<T>>
 static int launch_nlz_t(const KernelEntry* e, const NlzArgs& a, void* tw, void* rt3, hipStream_t s) {
   PT P;
   if constexpr (std::is_same<PT, NlmParams<T>>::value) P.part = static_cast<T*>(a.part);
+  if constexpr (std::is_same<PT, NlcParams<T>>::value) {
+    for (int f = 0; f < 3; ++f) P.c[f] = static_cast<const cx<T>*>(a.c[f]);
+    P.outs = static_cast<cx<T>*>(a.out[3]);
+  }
   P.rt3 = static_cast<const cx<T>*>(rt3);
   for (int f = 0; f < 3; ++f) {
     P.a[f] = static_cast<const cx<T>*>(a.a[f]);
@@ -558,6 +562,16 @@ static int launch_nlz_t(const KernelEntry* e, const NlzArgs& a, void* tw, void* 
 }
 int launch_nlz(const NlzArgs& a, hipStream_t s) {
   const bool dot = a.product == Op::Dot;
+  if (a.product == Op::CrossDot) {               // (NlzFft only: MFFT_NLZ3 does not touch this route either, and it has no maxima)
+    const KernelEntry* ec = a.n >= 2 && a.n < 65536 && !a.part ? find_kernel(FAM_NLZ, a.n, a.prec, 0, Op::CrossDot) : nullptr;
+    if (!ec) return set_error(MFFT_ERR_UNSUPPORTED, "no fused nonlinear z-stage kernel of length %d (cross and dot product)%s", a.n, a.part ? " with maxima" : "");
+    for (int f = 0; f < 3; ++f)
+      if (!a.a[f] || !a.b[f] || !a.c[f] || !a.out[f]) return set_error(MFFT_ERR_INVALID, "null argument");
+    if (!a.out[3]) return set_error(MFFT_ERR_INVALID, "null argument");
+    void* twc = nullptr;
+    MFFT_TRY(prepare_kernel(ec, &twc));
+    return by_prec(a.prec, [&](auto t) { return launch_nlz_t<decltype(t), NlcParams<decltype(t)>>(ec, a, twc, nullptr, s); });
+  }
   if (a.part) {                                  // Build::AbsMax: the same rows, and the partial maxima of the six real fields
     const KernelEntry* em = a.n < 65536 ? find_kernel(FAM_NLZ, a.n, a.prec, 0, a.product, Build::AbsMax) : nullptr;
     if (!em) return set_error(MFFT_ERR_UNSUPPORTED, "no fused nonlinear z-stage kernel of length %d with maxima%s", a.n, dot ? " (dot product)" : "");

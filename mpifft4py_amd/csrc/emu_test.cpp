@@ -13,6 +13,7 @@
 #include <cstring>
 #include <cmath>
 #include <functional>
+#include <limits>
 #include <random>
 #include <vector>
 
@@ -1413,6 +1414,124 @@ template <class S> static void test_nld_all() {
   }
 }
 
+// ... with the cross AND the dot product (NlzFft::body_cross_dot, NlcParams): out[f] = rfft((irfft(a) x irfft(b))_f) and
+// outs = rfft(sum_f irfft(a_f) irfft(c_f)), four rows out per nine rows in.  alias: 0 out of place, 1 the cross product over a and
+// the scalar row over c_2, 2 the cross product over b and the scalar row over c_0 (row for row); every other input must come back
+// untouched.  poison: the buffers hold one more row than nrows (an odd count), full of NaNs -- the missing partner of the last
+// row must contribute nothing, whatever lies behind the last row.
+template <class S, typename T, int ROWS, bool TWLDS, bool SPLIT, bool WAVE = false>
+static void test_nlc(int valid, int alias, int valid_in = 0, bool poison = false) {
+  typedef NlzProd<NlzFft<S, T, ROWS, TWLDS, SPLIT, WAVE>, NlzProduct::CrossDot> K;
+  const int vin = valid_in > 0 ? valid_in : valid;
+  const int M = S::N;
+  const int nrows = 2 * ROWS + 3;                 // an odd count: the last pair has one row
+  const int pin = valid + 2, pout = alias ? pin : valid + 1;
+  const int extra = poison ? 1 : 0;
+  std::mt19937_64 rng(4224 + M + valid);
+  std::uniform_real_distribution<double> U(-1, 1);
+  const T nan = std::numeric_limits<T>::quiet_NaN();
+  std::vector<cx<T>> in[9], out[4];               // a, b, c
+  for (auto& f : in) {
+    f.resize((size_t)(nrows + extra) * pin);
+    for (auto& z : f) z = mk<T>((T)U(rng), (T)U(rng));
+    for (size_t i = (size_t)nrows * pin; i < f.size(); ++i) f[i] = mk<T>(nan, nan);
+  }
+  std::vector<cx<T>> keep[9];
+  for (int f = 0; f < 9; ++f) keep[f] = in[f];
+  for (auto& f : out) {
+    f.assign((size_t)(nrows + extra) * pout, mk<T>((T)7, (T)7));
+    for (size_t i = (size_t)nrows * pout; i < f.size(); ++i) f[i] = mk<T>(nan, nan);
+  }
+  // the input field each result lies over (-1: none)
+  int over[4] = {-1, -1, -1, -1};
+  if (alias == 1) { over[0] = 0; over[1] = 1; over[2] = 2; over[3] = 8; }
+  if (alias == 2) { over[0] = 3; over[1] = 4; over[2] = 5; over[3] = 6; }
+  auto tw = build_pass_twiddles<S, T>();
+  NlcParams<T> P;
+  for (int f = 0; f < 3; ++f) { P.a[f] = in[f].data(); P.b[f] = in[3 + f].data(); P.c[f] = in[6 + f].data(); }
+  cx<T>* res[4];
+  for (int c = 0; c < 4; ++c) res[c] = over[c] >= 0 ? in[over[c]].data() : out[c].data();
+  for (int f = 0; f < 3; ++f) P.out[f] = res[f];
+  P.outs = res[3];
+  P.tw = tw.data(); P.in_stride = pin; P.out_stride = pout; P.nrows = nrows; P.valid = valid; P.valid_in = vin;
+  P.scale = (T)(1.0 / ((double)M * (double)M));
+  P.rt3 = nullptr;
+  emu_launch((nrows + 2 * ROWS - 1) / (2 * ROWS), K::THREADS, K::LDS_BYTES, [&](int b, int t, char* lds) { K::body(P, b, t, lds); });
+  long double num = 0, den = 0;
+  for (int r = 0; r < nrows; ++r) {
+    std::vector<std::vector<long double>> re(9, std::vector<long double>(M));
+    for (int f = 0; f < 9; ++f) {
+      lvec X(M);
+      for (int p = 0; p < M; ++p) { X[p].x = 0; X[p].y = 0; }
+      for (int q = 0; q < vin; ++q) {
+        cx<T> z = keep[f][(size_t)r * pin + q];
+        long double zr = z.x, zi = z.y;
+        if (q == 0 || (M % 2 == 0 && q == M / 2)) zi = 0;
+        X[q].x = zr; X[q].y = zi;
+        if (q != 0 && q != M - q) { X[M - q].x = zr; X[M - q].y = -zi; }
+      }
+      lvec x = naive_dft(X, +1);
+      for (int p = 0; p < M; ++p) re[f][p] = x[p].x / M;
+    }
+    for (int c = 0; c < 4; ++c) {
+      const int c1 = (c + 1) % 3, c2 = (c + 2) % 3;
+      lvec x(M);
+      for (int p = 0; p < M; ++p) {
+        x[p].x = c < 3 ? re[c1][p] * re[3 + c2][p] - re[c2][p] * re[3 + c1][p]
+                       : re[0][p] * re[6][p] + re[1][p] * re[7][p] + re[2][p] * re[8][p];
+        x[p].y = 0;
+      }
+      lvec X = naive_dft(x, -1);
+      const cx<T>* g = res[c] + (size_t)r * pout;
+      for (int q = 0; q < valid; ++q) {
+        const long double d = (g[q].x - X[q].x) * (g[q].x - X[q].x) + (g[q].y - X[q].y) * (g[q].y - X[q].y);
+        num += d == d ? d : 1;                     // (a NaN must not vanish in the comparison below)
+        den += X[q].x * X[q].x + X[q].y * X[q].y;
+      }
+      for (int q = valid; q < pout; ++q) {         // nothing is stored beyond the valid bins
+        const cx<T> was = over[c] >= 0 ? keep[over[c]][(size_t)r * pin + q] : mk<T>((T)7, (T)7);
+        if (g[q].x != was.x || g[q].y != was.y) num += 1;
+      }
+    }
+  }
+  for (int c = 0; c < 4; ++c)                      // ... nor behind the last row
+    for (size_t i = (size_t)nrows * pout; i < (size_t)(nrows + extra) * pout; ++i)
+      if (res[c][i].x == res[c][i].x || res[c][i].y == res[c][i].y) num += 1;
+  for (int f = 0; f < 9; ++f) {                    // the inputs are preserved (but for those the results lie over)
+    bool taken = false;
+    for (int c = 0; c < 4; ++c) taken = taken || over[c] == f;
+    if (!taken && memcmp(in[f].data(), keep[f].data(), keep[f].size() * sizeof(cx<T>)) != 0) num += 1;
+  }
+  char name[80];
+  snprintf(name, sizeof name, "nlc r%d v%d/%d%s%s%s%s%s", ROWS, vin, valid, TWLDS ? " twlds" : "", SPLIT ? " split" : "",
+           alias == 1 ? " inpl a c2" : alias == 2 ? " inpl b c0" : "", poison ? " poison" : "", WAVE ? " wave" : "");
+  report(name, M, pname<T>(), (double)sqrtl(num / den), sizeof(T) == 8 ? 4e-14 : 2e-5);
+}
+template <class S> static void test_nlc_all() {
+  const int M = S::N;
+  const int full = M / 2 + 1, lim = M / 3 + 1;     // every bin / the bins of the un-padded mesh under the 3/2-rule
+  if constexpr (S::TPT <= 64 && 64 % S::TPT == 0) {      // the wave-synchronous build
+    test_nlc<S, double, 2, true, false, true>(lim, 1, 0, true);
+    test_nlc<S, double, 1, false, false, true>(full, 2);
+    test_nlc<S, float, 3, false, false, true>(full, 0);
+    test_nlc<S, float, 2, true, false, true>(lim, 2, 0, true);
+  }
+  test_nlc<S, double, 2, true, false>(full, 0);
+  test_nlc<S, double, 1, false, true>(lim, 1, 0, true);
+  test_nlc<S, double, 2, true, true>(full, 2);
+  test_nlc<S, double, 3, false, false>(lim, 0);
+  test_nlc<S, float, 3, false, false>(lim, 0);
+  test_nlc<S, float, 2, true, true>(full, 1, 0, true);
+  test_nlc<S, float, 1, false, true>(lim, 2);
+  test_nlc<S, float, 2, true, false>(full, 2);
+  if (lim < full) {                                 // pruned 2/3-rule: the kept kz bins in, every bin out
+    test_nlc<S, double, 2, true, false>(full, 1, lim);
+    test_nlc<S, double, 1, false, true>(full, 0, lim);
+    test_nlc<S, float, 3, false, false>(full, 0, (2 * full) / 3);
+    test_nlc<S, float, 2, true, true>(full, 2, (2 * full) / 3, true);
+  }
+}
+
 // ... with the real-space maxima (fft_nlz.h NlzAbsMax, Build::AbsMax): the same rows, bit for bit, as the plain body in this
 // emulator, and max |irfft(a_f)|, max |irfft(b_f)| over all rows against long-double transforms of the six rows.  A spike can
 // be planted at one z position of one row of one field (over small noise), a NaN in one input bin of one field.
@@ -1815,6 +1934,11 @@ int main() {
 #define MFFT_NLM(N, ...) test_nlm_all<Spec<N, __VA_ARGS__>>();
   MFFT_NLZPLANS_P2(MFFT_NLM) MFFT_NLZPLANS_3(MFFT_NLM) MFFT_NLZPLANS_9(MFFT_NLM)     // the fused nonlinear z stage with the real-space maxima
 #undef MFFT_NLM
+#endif
+#if EMU_HAS(20)      // (`make emu_nlc`, a binary of its own as well)
+#define MFFT_NLC(N, ...) test_nlc_all<Spec<N, __VA_ARGS__>>();
+  MFFT_NLZPLANS_P2(MFFT_NLC) MFFT_NLZPLANS_3(MFFT_NLC) MFFT_NLZPLANS_9(MFFT_NLC)     // the fused nonlinear z stage, cross and dot product
+#undef MFFT_NLC
 #endif
 #if EMU_HAS(1)
   // pair-row kernels (with plan group B, where the shipped 512 / 1024 plans are; tests/test_cabi.py fixes the number of parts): even and odd meshes (self-paired planes and rows), a partial last workgroup, the shipped shapes

@@ -50,6 +50,12 @@ struct NlmParams : NlzParams<T> {
   T* part;                     // (waves of the launch, 2 rows of a pair, [a, b], 3 fields) un-normalised maxima, every slot written
 };
 constexpr int NLM_SLOTS = 12;  // values per wave in NlmParams::part
+// ... of the kernel that forms a x b AND sum_f a_f c_f (NlzFft::body_cross_dot below): a third field in, a fourth row out
+template <typename T>
+struct NlcParams : NlzParams<T> {
+  const cx<T>* c[3];           // half-spectra rows of the third vector field, strides and valid_in as a[] / b[]
+  cx<T>* outs;                 // half-spectra rows of sum_f a_f c_f; may alias one a[] / b[] / c[] component out[] does not take
+};
 
 // Maximum that KEEPS a NaN (fmax drops it): a blown-up field must not report a finite maximum.  m is sticky once NaN.
 template <typename T> MFFT_D T nan_max(T m, T x) { return (x > m || x != x) ? x : m; }
@@ -129,15 +135,21 @@ struct NlzFft {
   // (STATS: non-finite input values are taken out, bad[0] of field a, bad[1] of field b: take_out_nonfinite)
   template <bool STATS = false>
   static MFFT_D void load_pair(cx<T> (&v)[E], const cx<T>* ra, const cx<T>* rb, int j, int valid, T* bad = nullptr) {
+    load_pair_rows<STATS>(v, ra, rb, j, valid, valid, bad);
+  }
+  // ... the two rows with bin counts of their own (0: the row reads as zeros and is not touched beyond its first element, which
+  // exists)
+  template <bool STATS = false>
+  static MFFT_D void load_pair_rows(cx<T> (&v)[E], const cx<T>* ra, const cx<T>* rb, int j, int valid_a, int valid_b, T* bad = nullptr) {
     if constexpr (STATS) bad[0] = bad[1] = (T)0;
 #pragma unroll
     for (int k = 0; k < E; ++k) {
       const int p = j + k * S::TPT;
       const bool mir = p > M / 2;                  // upper half: conj of bin M - p
       const int q = mir ? M - p : p;
-      const bool ok = q < valid;
+      const bool oka = q < valid_a, okb = q < valid_b;
       // unconditional loads of a clamped position (fft_core.h keep_bits): all 2 E of them in flight together
-      cx<T> xa = keep_bits(ra[ok ? q : 0], ok), xb = keep_bits(rb[ok ? q : 0], ok);
+      cx<T> xa = keep_bits(ra[oka ? q : 0], oka), xb = keep_bits(rb[okb ? q : 0], okb);
       if (q == 0 || (M % 2 == 0 && q == M / 2)) {  // imaginary parts of the k = 0 and k = M/2 bins are ignored (as c2r does)
         xa.y = (T)0;
         xb.y = (T)0;
@@ -357,16 +369,98 @@ struct NlzFft {
       }
     }
   }
+
+  // The stage of a velocity that carries a scalar: out[f] = rfft((irfft(a) x irfft(b))_f) AND outs = rfft(sum_f irfft(a_f)
+  // irfft(c_f)) -- u x omega and u . grad(theta) with irfft(a_f) computed ONCE.  Ten real rows in, four out: 6.5 complex transforms
+  // of length M per row, the minimum for thirteen real ones.  The pairs are chosen so that products fall out of ONE transform:
+  //     before the pair of rows   b_2[row 0] + i b_2[row 1]      (the odd tenth row: E reals of row 1 wait for their turn)
+  //     per row                   a_f + i c_f, f = 0..2          s += a_f c_f at once, a_f parked (3 E reals + E)
+  //                               b_0 + i b_1                    -> r_0, r_1, r_2 from the parked a and the row's b_2
+  //                               forward r_0 + i r_1            -> out[0], out[1]
+  //                               forward r_2 + i s              -> out[2], outs
+  // Both results of every forward transform belong to the row, so nothing waits for the partner row on the forward side.  Parked
+  // next to a transform's working set: 6 E reals across the fourth inverse transform (a, s, b_2 of both rows), 3 E across the first
+  // forward one (r_2, s, b_2 of the partner), where the cross body parks 5 E.
+  // Every load of a row, and the early b_2 load of its partner, precedes the row's first store: out[] may lie over a[] or b[], and
+  // outs over any one component they leave alone.  A row past nrows reads as zeros -- it does NOT read the last row again, which
+  // an in-place caller has overwritten by then -- and stores nothing.
+  template <class PP>
+  static MFFT_D void body_cross_dot(const PP& P, int bid, int tid, char* lds) {
+    cx<T>* ltw = reinterpret_cast<cx<T>*>(lds);
+    const int rl = tid / S::TPT;
+    const int j = row_thread_index<S>(tid);
+    XE* xb = reinterpret_cast<XE*>(lds + TW_BYTES) + rl * PLEN;
+    if constexpr (TWLDS && S::NP > 1) {
+      stage_twiddles<S, T>(ltw, P.tw, tid, THREADS);
+      if constexpr (WAVE) MFFT_BARRIER();
+    }
+    const cx<T>* tw = (TWLDS && S::NP > 1) ? (const cx<T>*)ltw : P.tw;
+    Xch xc{xb, PadSlot<PD>{}};
+    const i64 unit = (i64)bid * ROWS + rl;         // a pair of rows
+    const i64 last = P.nrows - 1;
+    cx<T> v[E];
+    // (Seven transforms are inlined here, and hipcc keeps LDS addresses and twiddle indices of all of them live: every double-precision
+    // kernel sits at 256 VGPRs with scratch, profiles/nonlinear_cross_dot_regs.tsv.  Hiding the thread index at the head of each
+    // transform, as Nlz3Fft does, lowered the scratch -- and gave a WRONG cross product on the device for the 12-point plan in double
+    // precision, exact in the emulator, cause not found.  Not done.)
+    T b2[E], b2n[E];                               // irfft(b_2) of the row at hand and of its partner
+    {
+      const bool act0 = 2 * unit < P.nrows, act1 = 2 * unit + 1 < P.nrows;
+      load_pair_rows(v, P.b[2] + (act0 ? 2 * unit : last) * P.in_stride, P.b[2] + (act1 ? 2 * unit + 1 : last) * P.in_stride, j,
+                     act0 ? P.valid_in : 0, act1 ? P.valid_in : 0);
+      nlz_sync<WAVE>();
+      run_passes<S, 0, T>(v, j, tw, xc);
+#pragma unroll
+      for (int k = 0; k < E; ++k) { b2[k] = v[k].y; b2n[k] = v[k].x; }      // swapped results: .y the first row, .x the second
+    }
+#pragma unroll 1
+    for (int h = 0; h < 2; ++h) {
+      const i64 row = 2 * unit + h;
+      const bool active = row < P.nrows;
+      const i64 io = (active ? row : last) * P.in_stride;
+      const int vin = active ? P.valid_in : 0;
+      T a0[E], a1[E], a2[E], s[E];
+      inverse_pair(v, P.a[0] + io, P.c[0] + io, j, vin, tw, xc);
+#pragma unroll
+      for (int k = 0; k < E; ++k) { a0[k] = v[k].y; s[k] = v[k].y * v[k].x; }
+      inverse_pair(v, P.a[1] + io, P.c[1] + io, j, vin, tw, xc);
+#pragma unroll
+      for (int k = 0; k < E; ++k) { a1[k] = v[k].y; s[k] += v[k].y * v[k].x; }
+      inverse_pair(v, P.a[2] + io, P.c[2] + io, j, vin, tw, xc);
+#pragma unroll
+      for (int k = 0; k < E; ++k) { a2[k] = v[k].y; s[k] += v[k].y * v[k].x; }
+      inverse_pair(v, P.b[0] + io, P.b[1] + io, j, vin, tw, xc);
+      T r2[E];
+#pragma unroll
+      for (int k = 0; k < E; ++k) {
+        const T b0 = v[k].y, b1 = v[k].x;
+        v[k] = mk<T>((a1[k] * b2[k] - a2[k] * b1) * P.scale, (a2[k] * b0 - a0[k] * b2[k]) * P.scale);
+        r2[k] = (a0[k] * b1 - a1[k] * b0) * P.scale;
+      }
+      const i64 oo = row * P.out_stride;
+      forward_pair(v, j, tw, xc, xb, P.out[0] + oo, P.out[1] + oo, active, active, P.valid);
+#pragma unroll
+      for (int k = 0; k < E; ++k) v[k] = mk<T>(r2[k], s[k] * P.scale);
+      forward_pair(v, j, tw, xc, xb, P.out[2] + oo, P.outs + oo, active, active, P.valid);
+#pragma unroll
+      for (int k = 0; k < E; ++k) b2[k] = b2n[k];
+    }
+  }
 };
 
 // The product of the stage as a parameter of the kernel: NlzProd<K, NlzProduct::Dot> is K's rows, exchanges and transforms
 // around the dot product.  (A wrapper, not a seventh parameter of NlzFft: that would rename every cross-product kernel's
 // symbol, and scripts/kernel_regs.py --diff could no longer show that they are what they were.)
-enum class NlzProduct { Cross = 0, Dot = 1 };
+enum class NlzProduct { Cross = 0, Dot = 1, CrossDot = 2 };
 template <class K, NlzProduct PRODUCT = NlzProduct::Cross> struct NlzProd : K {};
 template <class K> struct NlzProd<K, NlzProduct::Dot> {
   static constexpr int THREADS = K::THREADS, LDS_BYTES = K::LDS_BYTES;
   template <class P> static MFFT_D void body(const P& p, int bid, int tid, char* lds) { K::body_dot(p, bid, tid, lds); }
+};
+
+template <class K> struct NlzProd<K, NlzProduct::CrossDot> {      // (takes NlcParams)
+  static constexpr int THREADS = K::THREADS, LDS_BYTES = K::LDS_BYTES;
+  template <class P> static MFFT_D void body(const P& p, int bid, int tid, char* lds) { K::body_cross_dot(p, bid, tid, lds); }
 };
 
 // The stage that also emits the six maxima (Build::AbsMax): K's body with STATS on and NlmParams.  A wrapper again, for the

@@ -113,18 +113,21 @@ int launch_c2r(const RealArgs& a, hipStream_t s);
 bool pair_rows_supported(int64_t n, int prec);     // both pair-row kernels of real length n exist
 
 // fused nonlinear z stage (fft_nlz.h): rows of half-spectra of two vector fields in, rows of the half-spectra of their
-// cross product out (may alias the inputs row for row) -- or, product = Op::Dot, the ONE row out[0] of their dot product
+// cross product out (may alias the inputs row for row) -- or, product = Op::Dot, the ONE row out[0] of their dot product -- or,
+// product = Op::CrossDot, the cross product AND the row out[3] of the dot product of a with a third field c
 struct NlzArgs {
   const void* a[3] = {nullptr, nullptr, nullptr};
   const void* b[3] = {nullptr, nullptr, nullptr};
-  void* out[3] = {nullptr, nullptr, nullptr};
+  const void* c[3] = {nullptr, nullptr, nullptr};   // Op::CrossDot only
+  void* out[4] = {nullptr, nullptr, nullptr, nullptr};
   int n = 0;             // REAL length of a z row
   int prec = MFFT_DOUBLE;
   int64_t in_stride = 0, out_stride = 0, nrows = 0;   // complex elements
   int valid = 0;         // bins per row present in memory (0 = all n/2+1)
   int valid_in = 0;      // bins per INPUT row, where fewer than `valid` exist (pruned 2/3-rule); 0 = valid
   double scale = 1.0;    // applied to the product (1 / n^2: both inverse transforms normalised)
-  Op product = Op::Plain;  // Op::Plain: a x b into out[0..2];  Op::Dot: sum_f a_f b_f into out[0], out[1..2] unused
+  Op product = Op::Plain;  // Op::Plain: a x b into out[0..2];  Op::Dot: sum_f a_f b_f into out[0], out[1..2] unused;
+                           // Op::CrossDot: a x b into out[0..2] and sum_f a_f c_f into out[3]
   void* part = nullptr;    // not null: the Build::AbsMax kernel runs and writes nlz_absmax_waves() groups of 12 un-normalised
                            // partial maxima here, in the rows' precision: [wave][row of the pair][a, b][field] (fft_nlz.h NlmParams)
 };

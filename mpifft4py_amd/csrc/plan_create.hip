@@ -352,6 +352,16 @@ int mfft_nonlinear_dot(mfft_plan_t p, const void* a_hat, const void* b_hat, void
   return p->nonlinear_dot(a_hat, b_hat, out_hat, dealias);
 }
 
+// out = fftn(ifftn(a) x ifftn(b)) AND s = fftn(sum_f ifftn(a_f) ifftn(c_f)) in one pass: a, b, c, out vector fields, s ONE
+// component; out may be a or b, s any one component of c.  See include/mpifft4py_amd.h.
+int mfft_nonlinear_cross_dot(mfft_plan_t p, const void* a_hat, const void* b_hat, const void* c_hat, void* out_hat, void* s_hat, int dealias) {
+  MFFT_TRY(check_ready(p, a_hat, b_hat));
+  if (!c_hat || !out_hat || !s_hat) return set_error(MFFT_ERR_INVALID, "null argument");
+  if (dealias != MFFT_DEALIAS_NONE && dealias != MFFT_DEALIAS_2_3 && dealias != MFFT_DEALIAS_3_2)
+    return set_error(MFFT_ERR_INVALID, "unknown dealias mode %d", dealias);
+  return p->nonlinear_cross_dot(a_hat, b_hat, c_hat, out_hat, s_hat, dealias);
+}
+
 // ... and the same two with statistics: the call also leaves the six real-space maxima in the plan (mfft_plan_nonlinear_absmax)
 static int nonlinear_stats(mfft_plan_t p, const void* a_hat, const void* b_hat, void* out_hat, int dealias, Op product) {
   MFFT_TRY(check_ready(p, a_hat, b_hat));
@@ -396,6 +406,9 @@ int mfft_plan_get_info(mfft_plan_t p, const char* key, int64_t* value) {
   else if (k == "nonlinear_dot_fused_none") *value = p->nonlinear_fusable(MFFT_DEALIAS_NONE, Op::Dot) ? 1 : 0;
   else if (k == "nonlinear_dot_fused_2_3") *value = p->nonlinear_fusable(MFFT_DEALIAS_2_3, Op::Dot) ? 1 : 0;
   else if (k == "nonlinear_dot_fused_3_2") *value = p->nonlinear_fusable(MFFT_DEALIAS_3_2, Op::Dot) ? 1 : 0;
+  else if (k == "nonlinear_cross_dot_fused_none") *value = p->nonlinear_fusable(MFFT_DEALIAS_NONE, Op::CrossDot) ? 1 : 0;
+  else if (k == "nonlinear_cross_dot_fused_2_3") *value = p->nonlinear_fusable(MFFT_DEALIAS_2_3, Op::CrossDot) ? 1 : 0;
+  else if (k == "nonlinear_cross_dot_fused_3_2") *value = p->nonlinear_fusable(MFFT_DEALIAS_3_2, Op::CrossDot) ? 1 : 0;
   else if (k == "nonlinear_absmax_fused_none") *value = p->nonlinear_fusable(MFFT_DEALIAS_NONE, Op::Plain, true) ? 1 : 0;
   else if (k == "nonlinear_absmax_fused_2_3") *value = p->nonlinear_fusable(MFFT_DEALIAS_2_3, Op::Plain, true) ? 1 : 0;
   else if (k == "nonlinear_absmax_fused_3_2") *value = p->nonlinear_fusable(MFFT_DEALIAS_3_2, Op::Plain, true) ? 1 : 0;

@@ -487,10 +487,13 @@ struct mfft_plan_s {
   int64_t local_real_count(bool padded) const;
   int nonlinear_cross(const void* a, const void* b, void* out, int dealias);
   int nonlinear_dot(const void* a, const void* b, void* out, int dealias);      // out: ONE component; may alias one of a's or b's
-  int nonlinear(const void* a, const void* b, void* out, int dealias, mfft::Op product, bool stats = false);
-  int nonlinear_fused(const void* a, const void* b, void* out, int dealias, mfft::Op product, bool stats);
-  int nonlinear_fused_ranks(const void* a, const void* b, void* out, int dealias, mfft::Op product, bool stats);
-  int nonlinear_composed(const void* a, const void* b, void* out, int dealias, mfft::Op product, bool stats);
+  // (mfft::Op::CrossDot: a x b into out AND sum_f a_f c_f of a third field c into the ONE component outs; no statistics.  out
+  // may be a or b, outs any one component of c)
+  int nonlinear_cross_dot(const void* a, const void* b, const void* c, void* out, void* outs, int dealias);
+  int nonlinear(const void* a, const void* b, void* out, int dealias, mfft::Op product, bool stats = false, const void* c = nullptr, void* outs = nullptr);
+  int nonlinear_fused(const void* a, const void* b, void* out, int dealias, mfft::Op product, bool stats, const void* c = nullptr, void* outs = nullptr);
+  int nonlinear_fused_ranks(const void* a, const void* b, void* out, int dealias, mfft::Op product, bool stats, const void* c = nullptr, void* outs = nullptr);
+  int nonlinear_composed(const void* a, const void* b, void* out, int dealias, mfft::Op product, bool stats, const void* c = nullptr, void* outs = nullptr);
   int nonlinear_absmax(double out6[6]);                                   // this rank's maxima of the last statistics call
   int absmax_sweep(const void* x, int ncomp, size_t n, double* acc);      // absmax.hip
 };

@@ -13,7 +13,15 @@ extern "C" int mfft_ew_dot(mfft_plan_t plan, const void* a, const void* b, void*
 // Two products share every route below: Op::Plain, the cross product (three result components), and Op::Dot, the dot product
 // sum_f ifftn(a_f) ifftn(b_f) of a transported scalar's u . grad(theta) (ONE result component: nout = 1 -- one forward y pass,
 // one forward exchange, one forward x pass; seven work arrays instead of nine in the composition).
-static int nl_nout(Op product) { return product == Op::Dot ? 1 : 3; }
+// Op::CrossDot: both at once for a velocity that carries a scalar, a x b AND sum_f a_f c_f with a third field c -- NINE fields in
+// (nin), FOUR results (the scalar one, `outs`, is the fourth): ifftn(a) is computed once where the two calls compute it twice.
+static int nl_nout(Op product) { return product == Op::Dot ? 1 : product == Op::CrossDot ? 4 : 3; }
+static int nl_nin(Op product) { return product == Op::CrossDot ? 9 : 6; }
+// component f of the operation's inputs (a, b, then c) and results (out, then outs), C elements of es bytes per component
+static const void* nl_src(const void* a, const void* b, const void* c, int f, int64_t C, size_t es) {
+  return static_cast<const char*>(f < 3 ? a : f < 6 ? b : c) + (size_t)((f % 3) * C) * es;
+}
+static void* nl_dst(void* out, void* outs, int f, int64_t C, size_t es) { return f < 3 ? static_cast<char*>(out) + (size_t)(f * C) * es : outs; }
 
 int64_t mfft_plan_s::local_real_count(bool padded) const {
   if (d.line2d) return 0;
@@ -22,26 +30,37 @@ int64_t mfft_plan_s::local_real_count(bool padded) const {
 }
 
 // Composed route (every decomposition and length): the transforms the caller would run, on nine (dot product: seven) work
-// arrays of the plan.
-int mfft_plan_s::nonlinear_composed(const void* a, const void* b, void* out, int dealias, Op product, bool stats) {
-  const int nout = nl_nout(product);
+// arrays of the plan: the nin real fields, then the results.
+// Op::CrossDot: twelve -- the dot product of a and c goes over c_0 (mfft_ew_dot allows it), the cross product into three more
+// arrays (mfft_ew_cross does not alias).
+int mfft_plan_s::nonlinear_composed(const void* a, const void* b, void* out, int dealias, Op product, bool stats, const void* c, void* outs) {
+  const int nout = nl_nout(product), nin = nl_nin(product);
+  const bool both = product == Op::CrossDot;
   const bool pad = dealias == MFFT_DEALIAS_3_2, masked = dealias == MFFT_DEALIAS_2_3;
   const int64_t nr = local_real_count(pad), nc = local_complex_alloc();       // (pitched arrays: a component is that much larger)
-  if (nr <= 0 || !r2c) return set_error(MFFT_ERR_UNSUPPORTED, "nonlinear_%s needs a 3-D real-to-complex plan", nout == 1 ? "dot" : "cross");
-  MFFT_TRY(ensure(nlr, (size_t)((6 + nout) * nr) * rs));
+  if (nr <= 0 || !r2c) return set_error(MFFT_ERR_UNSUPPORTED, "nonlinear_%s needs a 3-D real-to-complex plan", both ? "cross_dot" : nout == 1 ? "dot" : "cross");
+  const int narr = both ? 12 : nin + nout;
+  MFFT_TRY(ensure(nlr, (size_t)(narr * nr) * rs));
   char* R = static_cast<char*>(nlr.p);
+  auto arr = [&](int k) { return R + (size_t)(k * nr) * rs; };
   auto back = [&](const void* in, void* o) { return exec(false, in, o, dealias); };
   auto fwd = [&](const void* in, void* o) { return exec(true, in, o, masked ? (int)MFFT_DEALIAS_NONE : dealias); };
-  for (int f = 0; f < 3; ++f) {
-    MFFT_TRY(back(static_cast<const char*>(a) + (size_t)(f * nc) * es, R + (size_t)(f * nr) * rs));
-    MFFT_TRY(back(static_cast<const char*>(b) + (size_t)(f * nc) * es, R + (size_t)((3 + f) * nr) * rs));
-  }
+  for (int f = 0; f < 3; ++f)                      // (component by component, as before: a_f, b_f, then c_f)
+    for (int g = 0; g < nin / 3; ++g) MFFT_TRY(back(nl_src(a, b, c, 3 * g + f, nc, es), arr(3 * g + f)));
   // statistics: the six real arrays exist here, one streaming sweep over them (absmax.hip) into the same accumulator
   if (stats) MFFT_TRY(stage("nl_absmax", 6.0 * (double)nr * rs, [&] { return absmax_sweep(R, 6, (size_t)nr, static_cast<double*>(nlmacc.p)); }));
-  MFFT_TRY(stage(nout == 1 ? "nl_dot" : "nl_cross", (6.0 + nout) * (double)nr * rs, [&] {
-    return (nout == 1 ? mfft_ew_dot : mfft_ew_cross)(this, R, R + (size_t)(3 * nr) * rs, R + (size_t)(6 * nr) * rs, (size_t)nr, prec);
-  }));
-  for (int f = 0; f < nout; ++f) MFFT_TRY(fwd(R + (size_t)((6 + f) * nr) * rs, static_cast<char*>(out) + (size_t)(f * nc) * es));
+  // the element-wise products and where their results lie: res[f] is the work array forward transform f starts from
+  int res[4] = {6, 7, 8, 0};
+  if (both) {
+    MFFT_TRY(stage("nl_dot", 7.0 * (double)nr * rs, [&] { return mfft_ew_dot(this, arr(0), arr(6), arr(6), (size_t)nr, prec); }));
+    MFFT_TRY(stage("nl_cross", 9.0 * (double)nr * rs, [&] { return mfft_ew_cross(this, arr(0), arr(3), arr(9), (size_t)nr, prec); }));
+    res[0] = 9; res[1] = 10; res[2] = 11; res[3] = 6;
+  } else {
+    MFFT_TRY(stage(nout == 1 ? "nl_dot" : "nl_cross", (6.0 + nout) * (double)nr * rs, [&] {
+      return (nout == 1 ? mfft_ew_dot : mfft_ew_cross)(this, arr(0), arr(3), arr(6), (size_t)nr, prec);
+    }));
+  }
+  for (int f = 0; f < nout; ++f) MFFT_TRY(fwd(arr(res[f]), nl_dst(out, outs, f, nc, es)));
   return 0;
 }
 
@@ -54,7 +73,7 @@ static int64_t nlz_batch_planes(size_t plane6, int64_t planes) {
 }
 
 // the fused z stage on a batch: rows of the six fields in Y (yelems apart, pitch Za) in, the three rows of the cross product
-// (the one row of the dot product) out, in place on the first three (the first)
+// (the one row of the dot product) out, in place on the first three (the first); Op::CrossDot: nine fields in, four rows out
 // (stats: the Build::AbsMax kernel, its partial maxima into nlm, folded into the plan's accumulator with 1 / L2 -- the kernel's
 // inverse transforms are un-normalised -- after the launch: the maxima accumulate over the batches)
 static int nlz_rows(mfft_plan_s* p, char* Y, size_t yelems, int64_t L2, int64_t Za, int64_t nrows, int valid_in, Op product, bool stats) {
@@ -69,8 +88,9 @@ static int nlz_rows(mfft_plan_s* p, char* Y, size_t yelems, int64_t L2, int64_t 
   for (int f = 0; f < 3; ++f) {
     z.a[f] = Y + (size_t)f * yelems * p->es;
     z.b[f] = Y + (size_t)(3 + f) * yelems * p->es;
-    if (f < nl_nout(product)) z.out[f] = Y + (size_t)f * yelems * p->es;
+    if (product == Op::CrossDot) z.c[f] = Y + (size_t)(6 + f) * yelems * p->es;
   }
+  for (int f = 0; f < nl_nout(product); ++f) z.out[f] = Y + (size_t)f * yelems * p->es;      // (Op::CrossDot: the scalar row over b_0)
   z.product = product;
   z.n = (int)L2; z.prec = p->prec; z.in_stride = Za; z.out_stride = Za; z.nrows = nrows; z.valid = (int)p->Nf;
   z.valid_in = valid_in;
@@ -106,8 +126,10 @@ bool mfft_plan_s::nonlinear_fusable(int dealias, Op product, bool stats) const {
 // composed route needs 9 x 29 GB of real work arrays).
 // Op::Dot: the same with ONE result -- the z kernel writes the rows of the dot product in place on the first field, one forward
 // y pass per batch, one forward x pass.
-int mfft_plan_s::nonlinear_fused(const void* a, const void* b, void* out, int dealias, Op product, bool stats) {
-  const int nout = nl_nout(product);
+// Op::CrossDot: nine fields through the inverse passes, the z kernel's four result rows in place on the first four (the cross
+// product over a, the scalar row over b_0), four forward passes.
+int mfft_plan_s::nonlinear_fused(const void* a, const void* b, void* out, int dealias, Op product, bool stats, const void* c, void* outs) {
+  const int nout = nl_nout(product), nin = nl_nin(product);
   const bool pad = dealias == MFFT_DEALIAS_3_2, masked = dealias == MFFT_DEALIAS_2_3;
   const int64_t L0 = pad ? M0 : N0, L1 = pad ? M1 : N1, L2 = pad ? M2 : N2;
   const int64_t line = (int64_t)(128 / es);
@@ -122,9 +144,9 @@ int mfft_plan_s::nonlinear_fused(const void* a, const void* b, void* out, int de
   // gain nothing from it and pay for their short launches: profiles/r06_dns_batch.txt), so: batches of 16 GiB -- ONE batch up to
   // 512^3 with the 3/2-rule (14.9 GB), four at 768^3, eight at 1024^3 (14.7 GB of batch buffers beside 78.5 GB of x-pass
   // buffers).  MFFT_NLZ_BATCH_MB overrides.
-  const size_t plane6 = (size_t)(6 * L1 * Za) * es;
+  const size_t plane6 = (size_t)(nin * L1 * Za) * es;      // (the bytes of a plane of every input field: six, or nine)
   const int64_t mb = std::min(std::max<int64_t>(nlz_batch_planes(plane6, L0), 1), L0);
-  MFFT_TRY(ensure(nlx, 6 * xelems * es));
+  MFFT_TRY(ensure(nlx, (size_t)nin * xelems * es));
   MFFT_TRY(ensure(nly, (size_t)mb * plane6));
   char* X = static_cast<char*>(nlx.p);
   char* Y = static_cast<char*>(nly.p);
@@ -141,9 +163,9 @@ int mfft_plan_s::nonlinear_fused(const void* a, const void* b, void* out, int de
   const bool pruned = masked && band_ok && prune_enabled();
   double keep0 = 1.0, keep1 = 1.0, keep2 = 1.0;
   if (pruned) band_keep(&keep0, &keep1, &keep2);
-  MFFT_TRY(stage("nl_x_inv", 6 * (Cb * keep0 + Xb) * keep1 * keep2, [&] {
-    for (int f = 0; f < 6; ++f) {
-      const void* src = static_cast<const char*>(f < 3 ? a : b) + (size_t)((f % 3) * C) * es;
+  MFFT_TRY(stage("nl_x_inv", nin * (Cb * keep0 + Xb) * keep1 * keep2, [&] {
+    for (int f = 0; f < nin; ++f) {
+      const void* src = nl_src(a, b, c, f, C, es);
       void* dst = X + (size_t)f * xelems * es;
       if (pruned) {                                // one outer batch per ky, the kept kz columns of it
         ColArgs::Band bx;
@@ -167,8 +189,8 @@ int mfft_plan_s::nonlinear_fused(const void* a, const void* b, void* out, int de
   for (int64_t i0 = 0; i0 < L0; i0 += mb) {
     const int64_t m = std::min(mb, L0 - i0);
     const double frac = (double)m / (double)L0;
-    MFFT_TRY(stage("nl_y_inv", 6 * (Xb * keep1 + Yb) * keep2 * frac, [&] {
-      for (int f = 0; f < 6; ++f) {
+    MFFT_TRY(stage("nl_y_inv", nin * (Xb * keep1 + Yb) * keep2 * frac, [&] {
+      for (int f = 0; f < nin; ++f) {
         const void* src = X + ((size_t)f * xelems + (size_t)(i0 * N1 * Za)) * es;
         void* dst = Y + (size_t)f * yelems * es;
         if (pruned) {
@@ -181,7 +203,7 @@ int mfft_plan_s::nonlinear_fused(const void* a, const void* b, void* out, int de
       }
       return 0;
     }));
-    MFFT_TRY(stage("nl_z", (6 * keep2 + nout) * Yb * frac, [&] {
+    MFFT_TRY(stage("nl_z", (nin * keep2 + nout) * Yb * frac, [&] {
       return nlz_rows(this, Y, yelems, L2, Za, m * L1, pruned ? ba2 : 0, product, stats);
     }));
     MFFT_TRY(stage("nl_y_fwd", nout * (Xb + Yb) * frac, [&] {
@@ -194,7 +216,7 @@ int mfft_plan_s::nonlinear_fused(const void* a, const void* b, void* out, int de
   MFFT_TRY(stage("nl_x_fwd", nout * (Cb + Xb), [&] {
     for (int f = 0; f < nout; ++f) {
       const void* src = X + (size_t)f * xelems * es;
-      void* dst = static_cast<char*>(out) + (size_t)(f * C) * es;
+      void* dst = nl_dst(out, outs, f, C, es);
       if (Zi == Za && Za != Nf)                    // pitched result
         MFFT_TRY(col_pad(src, dst, L0, false, pad ? Op::TruncStore : Op::Plain, pad, 1, N1 * Za, 0, plain(N1 * Za), 0, plain(N1 * Za), 1.0 / sc3));
       else if (Za != Nf)                           // tiles of the compact result; input column (y, z) sits at y * Za + z
@@ -212,8 +234,9 @@ int mfft_plan_s::nonlinear_fused(const void* a, const void* b, void* out, int de
 // two-level row map (transpose_Uc fused, maths.pyx:21-31), the fused z kernel, forward y passes writing the packed send
 // layout (slab.py:403) -- three all-to-alls, three forward x passes.  Nine exchanges as in the composition, no real arrays.
 // (Op::Dot: six inverse exchanges and one forward exchange.)
-int mfft_plan_s::nonlinear_fused_ranks(const void* a, const void* b, void* out, int dealias, Op product, bool stats) {
-  const int nout = nl_nout(product);
+// (Op::CrossDot: nine inverse exchanges and four forward ones.)
+int mfft_plan_s::nonlinear_fused_ranks(const void* a, const void* b, void* out, int dealias, Op product, bool stats, const void* c, void* outs) {
+  const int nout = nl_nout(product), nin = nl_nin(product);
   const bool pad = dealias == MFFT_DEALIAS_3_2, masked = dealias == MFFT_DEALIAS_2_3;
   const int64_t L0 = pad ? M0 : N0, L1 = pad ? M1 : N1, L2 = pad ? M2 : N2, Lp0 = L0 / P;
   const int64_t line = (int64_t)(128 / es);
@@ -221,10 +244,10 @@ int mfft_plan_s::nonlinear_fused_ranks(const void* a, const void* b, void* out, 
   const int64_t S = Np1 * Nf + (pad ? 0 : xplane_pad(true));      // x-row pitch of the forward exchange's layout (sched())
   const int64_t C = N0 * Np1 * Nf;                                 // one component of the caller's arrays
   const size_t xelems = (size_t)(L0 * S);                          // one field in any of the exchanged layouts
-  const size_t plane6 = (size_t)(6 * L1 * Za) * es;
+  const size_t plane6 = (size_t)(nin * L1 * Za) * es;      // (the bytes of a plane of every input field: six, or nine)
   const int64_t mb = nlz_batch_planes(plane6, Lp0);
-  MFFT_TRY(ensure(nlw[0], 6 * xelems * es));
-  MFFT_TRY(ensure(nlw[1], 6 * xelems * es));
+  MFFT_TRY(ensure(nlw[0], (size_t)nin * xelems * es));
+  MFFT_TRY(ensure(nlw[1], (size_t)nin * xelems * es));
   MFFT_TRY(ensure(nly, (size_t)mb * plane6));
   char *X = static_cast<char*>(nlw[0].p), *R = static_cast<char*>(nlw[1].p), *Y = static_cast<char*>(nly.p);
   const size_t yelems = (size_t)(mb * L1 * Za);
@@ -237,8 +260,8 @@ int mfft_plan_s::nonlinear_fused_ranks(const void* a, const void* b, void* out, 
   const int64_t a2 = ba2, ap = (a2 + line - 1) / line * line;      // rows of the pruned layout start on cache lines
   const bool pruned = masked && band_ok && ap <= Nf && prune_enabled();
   MFFT_TRY(stage("nl_x_inv", 0, [&] {
-    for (int f = 0; f < 6; ++f) {
-      const void* src = static_cast<const char*>(f < 3 ? a : b) + (size_t)((f % 3) * C) * es;
+    for (int f = 0; f < nin; ++f) {
+      const void* src = nl_src(a, b, c, f, C, es);
       void* dst = X + (size_t)f * xelems * es;
       if (pruned) {
         if (band_allzero) {                        // nothing of this rank's spectrum survives the mask
@@ -259,7 +282,7 @@ int mfft_plan_s::nonlinear_fused_ranks(const void* a, const void* b, void* out, 
     return 0;
   }));
   MFFT_TRY(stage("nl_a2a_inv", 0, [&] {
-    for (int f = 0; f < 6; ++f) {
+    for (int f = 0; f < nin; ++f) {
       if (pruned) MFFT_TRY(exchange_equal(world, X + (size_t)f * xelems * es, R + (size_t)f * xelems * es, (size_t)(Np0 * Np1 * ap) * es));
       else MFFT_TRY(xchg(0, false, pad, X + (size_t)f * xelems * es, R + (size_t)f * xelems * es));
     }
@@ -268,7 +291,7 @@ int mfft_plan_s::nonlinear_fused_ranks(const void* a, const void* b, void* out, 
   for (int64_t i0 = 0; i0 < Lp0; i0 += mb) {
     const int64_t m = std::min(mb, Lp0 - i0);
     MFFT_TRY(stage("nl_y_inv", 0, [&] {
-      for (int f = 0; f < 6; ++f) {
+      for (int f = 0; f < nin; ++f) {
         if (pruned)
           MFFT_TRY(col(R + ((size_t)f * xelems + (size_t)(i0 * Np1 * ap)) * es, Y + (size_t)f * yelems * es, N1, true, m, a2, Np1 * ap,
                        two_level(Np1, Np0 * Np1 * ap, ap), L1 * Za, plain(Za)));
@@ -294,7 +317,7 @@ int mfft_plan_s::nonlinear_fused_ranks(const void* a, const void* b, void* out, 
   }));
   MFFT_TRY(stage("nl_x_fwd", 0, [&] {
     for (int f = 0; f < nout; ++f)
-      MFFT_TRY(col_pad(R + (size_t)f * xelems * es, static_cast<char*>(out) + (size_t)(f * C) * es, L0, false, pad ? Op::TruncStore : Op::Plain, pad, 1,
+      MFFT_TRY(col_pad(R + (size_t)f * xelems * es, nl_dst(out, outs, f, C, es), L0, false, pad ? Op::TruncStore : Op::Plain, pad, 1,
                        Np1 * Nf, 0, plain(S), 0, plain(Np1 * Nf), 1.0 / sc3));
     return 0;
   }));
@@ -305,7 +328,8 @@ int mfft_plan_s::nonlinear_fused_ranks(const void* a, const void* b, void* out, 
 // the product is formed on (the padded one under the 3/2-rule) in the plan's accumulator, nlmacc[0..5] = [a, b][f]: cleared on
 // the stream here, raised by every batch's fold (or the composed route's sweep), read by nonlinear_absmax.  A call without
 // stats does not touch it.
-int mfft_plan_s::nonlinear(const void* a, const void* b, void* out, int dealias, Op product, bool stats) {
+int mfft_plan_s::nonlinear(const void* a, const void* b, void* out, int dealias, Op product, bool stats, const void* c, void* outs) {
+  if (product == Op::CrossDot && (stats || !c || !outs)) return set_error(MFFT_ERR_INVALID, "nonlinear_cross_dot: a third field, a scalar result, no statistics");
   if (dealias == MFFT_DEALIAS_2_3) MFFT_TRY(require_mask());
   if (stats) {
     MFFT_TRY(ensure(nlmacc, 12 * sizeof(double)));
@@ -313,8 +337,8 @@ int mfft_plan_s::nonlinear(const void* a, const void* b, void* out, int dealias,
     nlm_valid = false;          // cleared, and partial until every batch has folded: valid only once the route has enqueued it all
   }
   const int rc = nonlinear_fusable(dealias, product, stats)
-                     ? (P == 1 ? nonlinear_fused(a, b, out, dealias, product, stats) : nonlinear_fused_ranks(a, b, out, dealias, product, stats))
-                     : nonlinear_composed(a, b, out, dealias, product, stats);
+                     ? (P == 1 ? nonlinear_fused(a, b, out, dealias, product, stats, c, outs) : nonlinear_fused_ranks(a, b, out, dealias, product, stats, c, outs))
+                     : nonlinear_composed(a, b, out, dealias, product, stats, c, outs);
   if (stats && rc == 0) nlm_valid = true;
   return rc;
 }
@@ -326,3 +350,6 @@ int mfft_plan_s::nonlinear_absmax(double out6[6]) {
 }
 int mfft_plan_s::nonlinear_cross(const void* a, const void* b, void* out, int dealias) { return nonlinear(a, b, out, dealias, Op::Plain); }
 int mfft_plan_s::nonlinear_dot(const void* a, const void* b, void* out, int dealias) { return nonlinear(a, b, out, dealias, Op::Dot); }
+int mfft_plan_s::nonlinear_cross_dot(const void* a, const void* b, const void* c, void* out, void* outs, int dealias) {
+  return nonlinear(a, b, out, dealias, Op::CrossDot, false, c, outs);
+}

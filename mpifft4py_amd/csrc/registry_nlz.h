@@ -106,6 +106,20 @@ void register_nlm(const char* name) {
   }
 }
 
+// Op::CrossDot: the cross product of a and b AND the dot product of a and a third field c in one pass over the rows (fft_nlz.h
+// body_cross_dot, NlcParams; kernels_nlc*.hip).  Rows, twiddle placement, exchange, wave-synchronous build and the two-waves-per-SIMD
+// cap are the cross kernels' (nlz_rows, nlz_twlds, nlz_split, nlz_wave, MFFT_NLZ_OCC): the body parks 6 E reals where the cross body
+// parks 5 E, and inlines seven transforms where it inlines five: every double-precision kernel takes all 256 VGPRs of the cap AND
+// scratch, where the 8-values twins take 166 - 244 and none (profiles/nonlinear_cross_dot_regs.tsv).  No other cap was measured.
+template <class S, typename T>
+void register_nlc(const char* name) {
+  auto& reg = kernel_registry();
+  constexpr int R = nlz_rows<S, T>();
+  constexpr int W = MFFT_NLZ_OCC > 1 ? 16 + MFFT_NLZ_OCC : 0;
+  typedef NlzProd<NlzFft<S, T, R, nlz_twlds<S, T>(), nlz_split<S, T>(), nlz_wave<S, T>()>, NlzProduct::CrossDot> K;
+  reg.push_back(make_entry<K, NlcParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::CrossDot, Build::Default, R, name));
+}
+
 // ... and its pruned 3/2-rule flavour (Nlz3Fft: Build::Nlz3, entry.n = M = 3 L): three thread groups of SL::TPT threads per row
 template <class SL, typename T> constexpr int nlz3_rows() { return 256 / (3 * SL::TPT) > 0 ? 256 / (3 * SL::TPT) : 1; }
 template <class SL, typename T>

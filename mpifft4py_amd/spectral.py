@@ -132,6 +132,30 @@ def dot_transform(FFT, a_hat, b_hat, out_hat, dealias=None, absmax=False):
     return out_hat
 
 
+def cross_dot_transform(FFT, a_hat, b_hat, c_hat, out_hat, s_hat, dealias=None):
+    """out_hat = fftn(ifftn(a_hat) x ifftn(b_hat)) AND s_hat = fftn(sum_f ifftn(a_hat[f]) * ifftn(c_hat[f])) as ONE operation
+    of the plan (mfft_nonlinear_cross_dot): u x omega and u . grad(theta) of a velocity that carries a scalar, =
+    `cross_transform(FFT, a_hat, b_hat, out_hat)` and `dot_transform(FFT, a_hat, c_hat, s_hat)` with ifftn(a_hat) computed
+    once -- nine inverse and four forward transforms instead of twelve and four.  a_hat, b_hat, c_hat and out_hat are
+    DeviceArrays of shape (3,) + FFT.complex_shape(), s_hat has FFT.complex_shape().  out_hat may be a_hat or b_hat, s_hat
+    may be any one component of c_hat (`c_hat.component(1)`); the inputs are otherwise preserved.  On slab plans with radix
+    kernels on every axis the z stages are one fused kernel and no real-space work array exists
+    (`FFT.plan_info("nonlinear_cross_dot_fused_3_2")`); elsewhere the plan composes it on twelve work arrays of its own.
+    There is no `absmax` here: take the maxima of a CFL step from one `cross_transform(.., absmax=True)`."""
+    from ._base import _DEALIAS
+    assert dealias in ('3/2-rule', '2/3-rule', 'None', None)
+    cs = tuple(int(s) for s in FFT.complex_shape())
+    for x, shape in ((a_hat, (3,) + cs), (b_hat, (3,) + cs), (c_hat, (3,) + cs), (out_hat, (3,) + cs), (s_hat, cs)):
+        assert x.shape == shape and x.dtype == np.dtype(FFT.complex), (x.shape, x.dtype, shape)
+        FFT._check_pitch(x, FFT.complex_pitch)
+    code = _DEALIAS[dealias]
+    FFT.comm.use_device()
+    if code == _lib.DEALIAS_2_3:
+        FFT._ensure_mask()
+    _lib.call("mfft_nonlinear_cross_dot", FFT._plan, a_hat.ptr, b_hat.ptr, c_hat.ptr, out_hat.ptr, s_hat.ptr, code)
+    return out_hat, s_hat
+
+
 def _max_over_ranks(FFT, v):
     """Maximum over FFT.comm that keeps NaNs: the NaN flags are reduced beside the values and the NaNs put back."""
     from .comm import MAX
