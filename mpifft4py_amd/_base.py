@@ -326,7 +326,9 @@ class DistFFTBase(object):
 
     def plan_info(self, key):
         """What the plan decided (mfft_plan_get_info): "pruned_route", "comm_cus", "kz_slices", "row_batches", "zfuse",
-        "plane_pad", "split_last", "complex_pitch", "complex_pitch_native", "nonlinear_fused_3_2" / "_none" / "_2_3", "nonlinear_bytes"."""
+        "plane_pad", "split_last", "complex_pitch", "complex_pitch_native", "nonlinear_bytes" and, for the fused route of the
+        nonlinear term, "nonlinear[_dot|_cross_dot][_absmax]_fused_3_2" / "_none" / "_2_3": unnamed the cross product, "_dot" and
+        "_cross_dot" the other two (spectral.py), "_absmax" the call that records the maxima (none for "_cross_dot")."""
         v = ctypes.c_int64(0)
         _lib.call("mfft_plan_get_info", self._plan, key.encode(), ctypes.byref(v))
         return int(v.value)

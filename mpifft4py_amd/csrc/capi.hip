@@ -252,41 +252,42 @@ int mfft_c2r_last(const void* in, void* out, const int64_t rshape[3], int precis
   return 0;
 }
 
+// the rows of one product for launch_nlz: a, b (and c) are (3, nrows, pitch) complex, out the product's vector result (nullptr:
+// none), s its scalar row (nrows, pitch), the row after the vector's
+static NlzArgs nlz_args(Op product, const void* a, const void* b, const void* c, void* out, void* s, int64_t nrows, int64_t n, int64_t pitch,
+                        int64_t valid, int precision) {
+  const size_t comp = (size_t)(nrows * pitch) * elem_bytes(precision, true);
+  NlzArgs z;
+  for (int f = 0; f < 3; ++f) {
+    z.a[f] = static_cast<const char*>(a) + f * comp;
+    z.b[f] = static_cast<const char*>(b) + f * comp;
+    if (c) z.c[f] = static_cast<const char*>(c) + f * comp;
+    if (out) z.out[f] = static_cast<char*>(out) + f * comp;
+  }
+  z.out[out ? 3 : 0] = s;
+  z.product = product;
+  z.n = (int)n; z.prec = precision; z.in_stride = pitch; z.out_stride = pitch; z.nrows = nrows; z.valid = (int)valid;
+  z.scale = 1.0 / ((double)n * (double)n);
+  return z;
+}
+static int nlz_run(const NlzArgs& z, int sync) {
+  MFFT_TRY(launch_nlz(z, nullptr));
+  if (sync) MFFT_HIP(hipStreamSynchronize(nullptr));
+  return 0;
+}
+
 // fused nonlinear z stage on rows (csrc/fft_nlz.h): a, b, out are (3, nrows, pitch) complex, `valid` bins per row exist
 int mfft_nlz_rows(const void* a, const void* b, void* out, int64_t nrows, int64_t n, int64_t pitch, int64_t valid, int precision,
                   int sync) {
   if (!a || !b || !out || nrows < 1 || n < 2 || pitch < valid || valid < 1) return set_error(MFFT_ERR_INVALID, "bad argument");
-  const size_t es = elem_bytes(precision, true);
-  NlzArgs z;
-  for (int f = 0; f < 3; ++f) {
-    z.a[f] = static_cast<const char*>(a) + (size_t)(f * nrows * pitch) * es;
-    z.b[f] = static_cast<const char*>(b) + (size_t)(f * nrows * pitch) * es;
-    z.out[f] = static_cast<char*>(out) + (size_t)(f * nrows * pitch) * es;
-  }
-  z.n = (int)n; z.prec = precision; z.in_stride = pitch; z.out_stride = pitch; z.nrows = nrows; z.valid = (int)valid;
-  z.scale = 1.0 / ((double)n * (double)n);
-  MFFT_TRY(launch_nlz(z, nullptr));
-  if (sync) MFFT_HIP(hipStreamSynchronize(nullptr));
-  return 0;
+  return nlz_run(nlz_args(Op::Plain, a, b, nullptr, out, nullptr, nrows, n, pitch, valid, precision), sync);
 }
 
 // ... and with the dot product: a, b (3, nrows, pitch), out (nrows, pitch); out may be any one component of a or b
 int mfft_nlz_dot_rows(const void* a, const void* b, void* out, int64_t nrows, int64_t n, int64_t pitch, int64_t valid, int precision,
                       int sync) {
   if (!a || !b || !out || nrows < 1 || n < 2 || pitch < valid || valid < 1) return set_error(MFFT_ERR_INVALID, "bad argument");
-  const size_t es = elem_bytes(precision, true);
-  NlzArgs z;
-  for (int f = 0; f < 3; ++f) {
-    z.a[f] = static_cast<const char*>(a) + (size_t)(f * nrows * pitch) * es;
-    z.b[f] = static_cast<const char*>(b) + (size_t)(f * nrows * pitch) * es;
-  }
-  z.out[0] = out;
-  z.product = Op::Dot;
-  z.n = (int)n; z.prec = precision; z.in_stride = pitch; z.out_stride = pitch; z.nrows = nrows; z.valid = (int)valid;
-  z.scale = 1.0 / ((double)n * (double)n);
-  MFFT_TRY(launch_nlz(z, nullptr));
-  if (sync) MFFT_HIP(hipStreamSynchronize(nullptr));
-  return 0;
+  return nlz_run(nlz_args(Op::Dot, a, b, nullptr, nullptr, out, nrows, n, pitch, valid, precision), sync);
 }
 
 // ... and with both products (fft_nlz.h body_cross_dot): a, b, c, out (3, nrows, pitch), s (nrows, pitch); out may be a or b, s any
@@ -294,21 +295,7 @@ int mfft_nlz_dot_rows(const void* a, const void* b, void* out, int64_t nrows, in
 int mfft_nlz_cross_dot_rows(const void* a, const void* b, const void* c, void* out, void* s, int64_t nrows, int64_t n, int64_t pitch,
                             int64_t valid, int precision, int sync) {
   if (!a || !b || !c || !out || !s || nrows < 1 || n < 2 || pitch < valid || valid < 1) return set_error(MFFT_ERR_INVALID, "bad argument");
-  const size_t es = elem_bytes(precision, true);
-  NlzArgs z;
-  for (int f = 0; f < 3; ++f) {
-    z.a[f] = static_cast<const char*>(a) + (size_t)(f * nrows * pitch) * es;
-    z.b[f] = static_cast<const char*>(b) + (size_t)(f * nrows * pitch) * es;
-    z.c[f] = static_cast<const char*>(c) + (size_t)(f * nrows * pitch) * es;
-    z.out[f] = static_cast<char*>(out) + (size_t)(f * nrows * pitch) * es;
-  }
-  z.out[3] = s;
-  z.product = Op::CrossDot;
-  z.n = (int)n; z.prec = precision; z.in_stride = pitch; z.out_stride = pitch; z.nrows = nrows; z.valid = (int)valid;
-  z.scale = 1.0 / ((double)n * (double)n);
-  MFFT_TRY(launch_nlz(z, nullptr));
-  if (sync) MFFT_HIP(hipStreamSynchronize(nullptr));
-  return 0;
+  return nlz_run(nlz_args(Op::CrossDot, a, b, c, out, s, nrows, n, pitch, valid, precision), sync);
 }
 
 // The stage with the maxima of its six real rows (fft_nlz.h NlzAbsMax), synchronous: out as mfft_nlz_rows (dot = 0) or
@@ -318,16 +305,8 @@ int mfft_nlz_rows_absmax(const void* a, const void* b, void* out, int64_t nrows,
   if (!a || !b || !out || !out6 || nrows < 1 || n < 2 || pitch < valid || valid < 1) return set_error(MFFT_ERR_INVALID, "bad argument");
   if (precision != MFFT_DOUBLE && precision != MFFT_SINGLE) return set_error(MFFT_ERR_INVALID, "unknown precision %d", precision);
   const size_t es = elem_bytes(precision, true);
-  NlzArgs z;
-  for (int f = 0; f < 3; ++f) {
-    z.a[f] = static_cast<const char*>(a) + (size_t)(f * nrows * pitch) * es;
-    z.b[f] = static_cast<const char*>(b) + (size_t)(f * nrows * pitch) * es;
-    if (!dot) z.out[f] = static_cast<char*>(out) + (size_t)(f * nrows * pitch) * es;
-  }
-  if (dot) z.out[0] = out;
-  z.product = dot ? Op::Dot : Op::Plain;
-  z.n = (int)n; z.prec = precision; z.in_stride = pitch; z.out_stride = pitch; z.nrows = nrows; z.valid = (int)valid;
-  z.scale = 1.0 / ((double)n * (double)n);
+  NlzArgs z = dot ? nlz_args(Op::Dot, a, b, nullptr, nullptr, out, nrows, n, pitch, valid, precision)
+                  : nlz_args(Op::Plain, a, b, nullptr, out, nullptr, nrows, n, pitch, valid, precision);
   const int64_t waves = nlz_absmax_waves(n, precision, z.product, nrows);
   if (waves < 1) return set_error(MFFT_ERR_UNSUPPORTED, "no fused nonlinear z-stage kernel of length %lld with maxima", (long long)n);
   const size_t head = absmax_fold_scratch_bytes() + 6 * sizeof(double);

@@ -526,14 +526,20 @@ int launch_r2c(const RealArgs& a, hipStream_t s) { return launch_real(FAM_R2C, a
 int launch_c2r(const RealArgs& a, hipStream_t s) { return launch_real(FAM_C2R, a, s); }
 
 // fused nonlinear z stage (fft_nlz.h): out_f = rfft((irfft(a) x irfft(b))_f) along the contiguous axis, row by row
+// the kernel of one product in one build; a z row has 2 <= n < 65536 (no kernel exists outside that), and the table of
+// products (mfft_internal.h) says which builds a product has
+static const KernelEntry* find_nlz(int64_t n, int prec, Op product, Build build = Build::Default) {
+  const NlProduct& q = nl_product(product);
+  if (n < 2 || n >= 65536 || (build == Build::AbsMax && !q.absmax) || (build == Build::Nlz3 && !q.nlz3)) return nullptr;
+  return find_kernel(FAM_NLZ, (int)n, prec, 0, product, build);
+}
 bool nlz_supported(int64_t n, int prec, Op product, bool absmax) {
-  if (absmax) return n >= 2 && n < 65536 && find_kernel(FAM_NLZ, (int)n, prec, 0, product, Build::AbsMax) != nullptr;
-  if (product == Op::Dot || product == Op::CrossDot) return n >= 2 && n < 65536 && find_kernel(FAM_NLZ, (int)n, prec, 0, product) != nullptr;
-  return n >= 2 && n < 65536 && (find_kernel(FAM_NLZ, (int)n, prec, 0) != nullptr || find_kernel(FAM_NLZ, (int)n, prec, 0, Op::Plain, Build::Nlz3) != nullptr);
+  if (absmax) return find_nlz(n, prec, product, Build::AbsMax) != nullptr;
+  return find_nlz(n, prec, product) != nullptr || find_nlz(n, prec, product, Build::Nlz3) != nullptr;
 }
 // waves of the Build::AbsMax launch over nrows rows = groups of NLM_SLOTS values it writes to NlzArgs::part (0: no such kernel)
 int64_t nlz_absmax_waves(int64_t n, int prec, Op product, int64_t nrows) {
-  const KernelEntry* e = n >= 2 && n < 65536 ? find_kernel(FAM_NLZ, (int)n, prec, 0, product, Build::AbsMax) : nullptr;
+  const KernelEntry* e = find_nlz(n, prec, product, Build::AbsMax);
   if (!e || nrows < 1) return 0;
   return (nrows + 2 * e->tile - 1) / (2 * e->tile) * ((e->threads + 63) / 64);
 }
@@ -561,42 +567,32 @@ static int launch_nlz_t(const KernelEntry* e, const NlzArgs& a, void* tw, void* 
   return launch_rows(e, P, a.nrows, 2 * e->tile, s);      // a thread group works through a PAIR of rows
 }
 int launch_nlz(const NlzArgs& a, hipStream_t s) {
-  const bool dot = a.product == Op::Dot;
-  if (a.product == Op::CrossDot) {               // (NlzFft only: MFFT_NLZ3 does not touch this route either, and it has no maxima)
-    const KernelEntry* ec = a.n >= 2 && a.n < 65536 && !a.part ? find_kernel(FAM_NLZ, a.n, a.prec, 0, Op::CrossDot) : nullptr;
-    if (!ec) return set_error(MFFT_ERR_UNSUPPORTED, "no fused nonlinear z-stage kernel of length %d (cross and dot product)%s", a.n, a.part ? " with maxima" : "");
-    for (int f = 0; f < 3; ++f)
-      if (!a.a[f] || !a.b[f] || !a.c[f] || !a.out[f]) return set_error(MFFT_ERR_INVALID, "null argument");
-    if (!a.out[3]) return set_error(MFFT_ERR_INVALID, "null argument");
-    void* twc = nullptr;
-    MFFT_TRY(prepare_kernel(ec, &twc));
-    return by_prec(a.prec, [&](auto t) { return launch_nlz_t<decltype(t), NlcParams<decltype(t)>>(ec, a, twc, nullptr, s); });
-  }
-  if (a.part) {                                  // Build::AbsMax: the same rows, and the partial maxima of the six real fields
-    const KernelEntry* em = a.n < 65536 ? find_kernel(FAM_NLZ, a.n, a.prec, 0, a.product, Build::AbsMax) : nullptr;
-    if (!em) return set_error(MFFT_ERR_UNSUPPORTED, "no fused nonlinear z-stage kernel of length %d with maxima%s", a.n, dot ? " (dot product)" : "");
-    for (int f = 0; f < 3; ++f)
-      if (!a.a[f] || !a.b[f] || !a.out[dot ? 0 : f]) return set_error(MFFT_ERR_INVALID, "null argument");
-    void* twm = nullptr;
-    MFFT_TRY(prepare_kernel(em, &twm));
-    return by_prec(a.prec, [&](auto t) { return launch_nlz_t<decltype(t), NlmParams<decltype(t)>>(em, a, twm, nullptr, s); });
-  }
-  const KernelEntry* e = a.n < 65536 ? find_kernel(FAM_NLZ, a.n, a.prec, 0, a.product) : nullptr;
+  const NlProduct& q = nl_product(a.product);
+  // a.part: Build::AbsMax, the same rows and the partial maxima of the six real fields
+  const KernelEntry* e = find_nlz(a.n, a.prec, a.product, a.part ? Build::AbsMax : Build::Default);
   // 3/2-rule rows (n = 3 L with the L + 1 bins of the un-padded mesh) also have the pruned kernel (fft_nlz.h Nlz3Fft: three
   // sub-transforms of length L in three thread groups, a third of the registers).  Measured EVEN with NlzFft at 768 (1.36 ms per
   // 73,728 rows both) and behind at 1536 (1.80 - 1.91 against 1.59 ms per 36,864 rows): profiles/r06_nlz_variants.txt -- its
   // staging and combination cost what the skipped radix-3 pass saves.  MFFT_NLZ3=1 takes it; where NlzFft has no plan it runs anyway.
+  // (Nlz3Fft has the cross product only and no maxima: MFFT_NLZ3 touches neither the other products nor a statistics call)
   static const int nlz3_on = getenv("MFFT_NLZ3") ? atoi(getenv("MFFT_NLZ3")) : 0;
-  const bool rows3 = a.n % 3 == 0 && a.valid == a.n / 3 + 1 && a.n < 65536;
-  if ((nlz3_on || !e) && rows3 && !dot)          // (Nlz3Fft has the cross product only: MFFT_NLZ3 does not touch the dot route)
-    if (const KernelEntry* e3 = find_kernel(FAM_NLZ, a.n, a.prec, 0, Op::Plain, Build::Nlz3)) e = e3;
-  if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused nonlinear z-stage kernel of length %d%s", a.n, dot ? " (dot product)" : "");
+  const bool rows3 = a.n % 3 == 0 && a.valid == a.n / 3 + 1;
+  if ((nlz3_on || !e) && rows3 && !a.part)
+    if (const KernelEntry* e3 = find_nlz(a.n, a.prec, a.product, Build::Nlz3)) e = e3;
+  if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused nonlinear z-stage kernel of length %d%s (%s product)", a.n, a.part ? " with maxima" : "", q.name);
   for (int f = 0; f < 3; ++f)
-    if (!a.a[f] || !a.b[f] || !a.out[dot ? 0 : f]) return set_error(MFFT_ERR_INVALID, "null argument");
+    if (!a.a[f] || !a.b[f] || (q.nin > 6 && !a.c[f])) return set_error(MFFT_ERR_INVALID, "null argument");
+  for (int f = 0; f < q.nout; ++f)
+    if (!a.out[f]) return set_error(MFFT_ERR_INVALID, "null argument");
   void *tw = nullptr, *rt3 = nullptr;
   MFFT_TRY(prepare_kernel(e, &tw));
   if (e->build == Build::Nlz3) MFFT_TRY(nlz3_twiddles(a.n / 3, a.prec, &rt3));
-  return by_prec(a.prec, [&](auto t) { return launch_nlz_t<decltype(t)>(e, a, tw, rt3, s); });
+  return by_prec(a.prec, [&](auto t) {
+    using T = decltype(t);
+    if (a.part) return launch_nlz_t<T, NlmParams<T>>(e, a, tw, rt3, s);
+    if (q.nin > 6) return launch_nlz_t<T, NlcParams<T>>(e, a, tw, rt3, s);      // (a third field in, a fourth row out)
+    return launch_nlz_t<T>(e, a, tw, rt3, s);
+  });
 }
 
 // ---------------------------------------------------------------------------

@@ -1266,6 +1266,69 @@ static void test_col3() {
 }
 
 // ---------------------------------------------------------------------------
+// The long-double reference the tests of the fused nonlinear z stage (fft_nlz.h) share.
+// The real row a stored half-spectrum row z stands for: its first vin bins, extended to the Hermitian spectrum of M points (the
+// imaginary parts of the self-conjugate bins dropped), inverse DFT, real part / M.  nan_as_zero: a NaN real part reads as 0.
+typedef std::vector<long double> lreal;
+template <typename T> static lreal nl_real_row(const cx<T>* z, int vin, int M, bool nan_as_zero = false) {
+  lvec X(M);
+  for (int p = 0; p < M; ++p) { X[p].x = 0; X[p].y = 0; }
+  for (int q = 0; q < vin; ++q) {
+    long double zr = z[q].x, zi = z[q].y;
+    if (nan_as_zero && zr != zr) zr = 0;
+    if (q == 0 || (M % 2 == 0 && q == M / 2)) zi = 0;
+    X[q].x = zr; X[q].y = zi;
+    if (q != 0 && q != M - q) { X[M - q].x = zr; X[M - q].y = -zi; }
+  }
+  lvec x = naive_dft(X, +1);
+  lreal re(M);
+  for (int p = 0; p < M; ++p) re[p] = x[p].x / M;
+  return re;
+}
+// row r (pitch pin) of each of nf stored fields
+template <typename T> static std::vector<lreal> nl_real_rows(const std::vector<cx<T>>* keep, int nf, int r, int pin, int vin, int M) {
+  std::vector<lreal> re(nf);
+  for (int f = 0; f < nf; ++f) re[f] = nl_real_row(keep[f].data() + (size_t)r * pin, vin, M);
+  return re;
+}
+// spectra of the products of real rows: component c of a x b, and sum_f a_f b_f (a, b: three rows each)
+static lvec nl_cross_spectrum(const lreal* a, const lreal* b, int c) {
+  const int c1 = (c + 1) % 3, c2 = (c + 2) % 3, M = (int)a[0].size();
+  lvec x(M);
+  for (int p = 0; p < M; ++p) { x[p].x = a[c1][p] * b[c2][p] - a[c2][p] * b[c1][p]; x[p].y = 0; }
+  return naive_dft(x, -1);
+}
+static lvec nl_dot_spectrum(const lreal* a, const lreal* b) {
+  const int M = (int)a[0].size();
+  lvec x(M);
+  for (int p = 0; p < M; ++p) { x[p].x = a[0][p] * b[0][p] + a[1][p] * b[1][p] + a[2][p] * b[2][p]; x[p].y = 0; }
+  return naive_dft(x, -1);
+}
+// a result row g against its reference X over the valid bins: num += |g - X|^2, den += |X|^2
+template <typename T> static void nl_accumulate(const cx<T>* g, const lvec& X, int valid, long double& num, long double& den) {
+  for (int q = 0; q < valid; ++q) {
+    const long double d = (g[q].x - X[q].x) * (g[q].x - X[q].x) + (g[q].y - X[q].y) * (g[q].y - X[q].y);
+    num += d == d ? d : 1;                         // (a NaN must not vanish in the comparison with the tolerance)
+    den += X[q].x * X[q].x + X[q].y * X[q].y;
+  }
+}
+// nothing is stored beyond the valid bins of a result row g: bins [valid, pout) hold what they held -- the bins of `was`, the row
+// of the input the result lies over, or (null) the 7s the tests fill their own result rows with
+template <typename T> static void nl_tail_kept(const cx<T>* g, const cx<T>* was, int valid, int pout, long double& num) {
+  for (int q = valid; q < pout; ++q) {
+    const cx<T> w = was ? was[q] : mk<T>((T)7, (T)7);
+    if (g[q].x != w.x || g[q].y != w.y) num += 1;
+  }
+}
+// the inputs are preserved, but for those a result lies over (over[0..nres): the field, or -1)
+template <typename T> static void nl_inputs_kept(const std::vector<cx<T>>* in, const std::vector<cx<T>>* keep, int nf, const int* over, int nres, long double& num) {
+  for (int f = 0; f < nf; ++f) {
+    bool taken = false;
+    for (int c = 0; c < nres; ++c) taken = taken || over[c] == f;
+    if (!taken && memcmp(in[f].data(), keep[f].data(), keep[f].size() * sizeof(cx<T>)) != 0) num += 1;
+  }
+}
+
 // fused nonlinear z stage (fft_nlz.h): out_f = rfft((irfft(a) x irfft(b))_f), rows of `valid` bins, against long-double DFTs
 template <class S, typename T, int ROWS, bool TWLDS, bool SPLIT, bool WAVE = false>
 static void test_nlz(int valid, bool inplace, int valid_in = 0) {      // valid_in: fewer input bins than stored ones (pruned 2/3-rule)
@@ -1292,33 +1355,11 @@ static void test_nlz(int valid, bool inplace, int valid_in = 0) {      // valid_
   emu_launch((nrows + 2 * ROWS - 1) / (2 * ROWS), K::THREADS, K::LDS_BYTES, [&](int b, int t, char* lds) { K::body(P, b, t, lds); });
   long double num = 0, den = 0;
   for (int r = 0; r < nrows; ++r) {
-    std::vector<std::vector<long double>> re(6, std::vector<long double>(M));
-    for (int f = 0; f < 6; ++f) {
-      lvec X(M);
-      for (int p = 0; p < M; ++p) { X[p].x = 0; X[p].y = 0; }
-      for (int q = 0; q < vin; ++q) {
-        cx<T> z = keep[f][(size_t)r * pin + q];
-        long double zr = z.x, zi = z.y;
-        if (q == 0 || (M % 2 == 0 && q == M / 2)) zi = 0;
-        X[q].x = zr; X[q].y = zi;
-        if (q != 0 && q != M - q) { X[M - q].x = zr; X[M - q].y = -zi; }
-      }
-      lvec x = naive_dft(X, +1);
-      for (int p = 0; p < M; ++p) re[f][p] = x[p].x / M;
-    }
+    const std::vector<lreal> re = nl_real_rows(keep, 6, r, pin, vin, M);
     for (int c = 0; c < 3; ++c) {
-      const int c1 = (c + 1) % 3, c2 = (c + 2) % 3;
-      lvec x(M);
-      for (int p = 0; p < M; ++p) { x[p].x = re[c1][p] * re[3 + c2][p] - re[c2][p] * re[3 + c1][p]; x[p].y = 0; }
-      lvec X = naive_dft(x, -1);
       const cx<T>* g = (inplace ? in[c].data() : out[c].data()) + (size_t)r * pout;
-      for (int q = 0; q < valid; ++q) {
-        num += (g[q].x - X[q].x) * (g[q].x - X[q].x) + (g[q].y - X[q].y) * (g[q].y - X[q].y);
-        den += X[q].x * X[q].x + X[q].y * X[q].y;
-      }
-      if (!inplace)
-        for (int q = valid; q < pout; ++q)
-          if (g[q].x != (T)7 || g[q].y != (T)7) { num += 1; }      // nothing is stored beyond the valid bins
+      nl_accumulate(g, nl_cross_spectrum(&re[0], &re[3], c), valid, num, den);
+      if (!inplace) nl_tail_kept<T>(g, nullptr, valid, pout, num);
     }
   }
   char name[64];
@@ -1355,35 +1396,12 @@ static void test_nld(int valid, int alias, int valid_in = 0) {
   emu_launch((nrows + 2 * ROWS - 1) / (2 * ROWS), K::THREADS, K::LDS_BYTES, [&](int b, int t, char* lds) { K::body(P, b, t, lds); });
   long double num = 0, den = 0;
   for (int r = 0; r < nrows; ++r) {
-    std::vector<std::vector<long double>> re(6, std::vector<long double>(M));
-    for (int f = 0; f < 6; ++f) {
-      lvec X(M);
-      for (int p = 0; p < M; ++p) { X[p].x = 0; X[p].y = 0; }
-      for (int q = 0; q < vin; ++q) {
-        cx<T> z = keep[f][(size_t)r * pin + q];
-        long double zr = z.x, zi = z.y;
-        if (q == 0 || (M % 2 == 0 && q == M / 2)) zi = 0;
-        X[q].x = zr; X[q].y = zi;
-        if (q != 0 && q != M - q) { X[M - q].x = zr; X[M - q].y = -zi; }
-      }
-      lvec x = naive_dft(X, +1);
-      for (int p = 0; p < M; ++p) re[f][p] = x[p].x / M;
-    }
-    lvec x(M);
-    for (int p = 0; p < M; ++p) { x[p].x = re[0][p] * re[3][p] + re[1][p] * re[4][p] + re[2][p] * re[5][p]; x[p].y = 0; }
-    lvec X = naive_dft(x, -1);
+    const std::vector<lreal> re = nl_real_rows(keep, 6, r, pin, vin, M);
     const cx<T>* g = P.out[0] + (size_t)r * pout;
-    for (int q = 0; q < valid; ++q) {
-      num += (g[q].x - X[q].x) * (g[q].x - X[q].x) + (g[q].y - X[q].y) * (g[q].y - X[q].y);
-      den += X[q].x * X[q].x + X[q].y * X[q].y;
-    }
-    for (int q = valid; q < pout; ++q) {           // nothing is stored beyond the valid bins
-      const cx<T> was = af >= 0 ? keep[af][(size_t)r * pin + q] : mk<T>((T)7, (T)7);
-      if (g[q].x != was.x || g[q].y != was.y) num += 1;
-    }
+    nl_accumulate(g, nl_dot_spectrum(&re[0], &re[3]), valid, num, den);
+    nl_tail_kept<T>(g, af >= 0 ? keep[af].data() + (size_t)r * pin : nullptr, valid, pout, num);
   }
-  for (int f = 0; f < 6; ++f)                      // the inputs are preserved (but for the one the result lies over)
-    if (f != af && memcmp(in[f].data(), keep[f].data(), keep[f].size() * sizeof(cx<T>)) != 0) num += 1;
+  nl_inputs_kept(in, keep, 6, &af, 1, num);
   char name[72];
   snprintf(name, sizeof name, "nld r%d v%d/%d%s%s%s%s", ROWS, vin, valid, TWLDS ? " twlds" : "", SPLIT ? " split" : "",
            alias == 1 ? " over a0" : alias == 2 ? " over b1" : "", WAVE ? " wave" : "");
@@ -1459,49 +1477,17 @@ static void test_nlc(int valid, int alias, int valid_in = 0, bool poison = false
   emu_launch((nrows + 2 * ROWS - 1) / (2 * ROWS), K::THREADS, K::LDS_BYTES, [&](int b, int t, char* lds) { K::body(P, b, t, lds); });
   long double num = 0, den = 0;
   for (int r = 0; r < nrows; ++r) {
-    std::vector<std::vector<long double>> re(9, std::vector<long double>(M));
-    for (int f = 0; f < 9; ++f) {
-      lvec X(M);
-      for (int p = 0; p < M; ++p) { X[p].x = 0; X[p].y = 0; }
-      for (int q = 0; q < vin; ++q) {
-        cx<T> z = keep[f][(size_t)r * pin + q];
-        long double zr = z.x, zi = z.y;
-        if (q == 0 || (M % 2 == 0 && q == M / 2)) zi = 0;
-        X[q].x = zr; X[q].y = zi;
-        if (q != 0 && q != M - q) { X[M - q].x = zr; X[M - q].y = -zi; }
-      }
-      lvec x = naive_dft(X, +1);
-      for (int p = 0; p < M; ++p) re[f][p] = x[p].x / M;
-    }
+    const std::vector<lreal> re = nl_real_rows(keep, 9, r, pin, vin, M);
     for (int c = 0; c < 4; ++c) {
-      const int c1 = (c + 1) % 3, c2 = (c + 2) % 3;
-      lvec x(M);
-      for (int p = 0; p < M; ++p) {
-        x[p].x = c < 3 ? re[c1][p] * re[3 + c2][p] - re[c2][p] * re[3 + c1][p]
-                       : re[0][p] * re[6][p] + re[1][p] * re[7][p] + re[2][p] * re[8][p];
-        x[p].y = 0;
-      }
-      lvec X = naive_dft(x, -1);
       const cx<T>* g = res[c] + (size_t)r * pout;
-      for (int q = 0; q < valid; ++q) {
-        const long double d = (g[q].x - X[q].x) * (g[q].x - X[q].x) + (g[q].y - X[q].y) * (g[q].y - X[q].y);
-        num += d == d ? d : 1;                     // (a NaN must not vanish in the comparison below)
-        den += X[q].x * X[q].x + X[q].y * X[q].y;
-      }
-      for (int q = valid; q < pout; ++q) {         // nothing is stored beyond the valid bins
-        const cx<T> was = over[c] >= 0 ? keep[over[c]][(size_t)r * pin + q] : mk<T>((T)7, (T)7);
-        if (g[q].x != was.x || g[q].y != was.y) num += 1;
-      }
+      nl_accumulate(g, c < 3 ? nl_cross_spectrum(&re[0], &re[3], c) : nl_dot_spectrum(&re[0], &re[6]), valid, num, den);
+      nl_tail_kept<T>(g, over[c] >= 0 ? keep[over[c]].data() + (size_t)r * pin : nullptr, valid, pout, num);
     }
   }
   for (int c = 0; c < 4; ++c)                      // ... nor behind the last row
     for (size_t i = (size_t)nrows * pout; i < (size_t)(nrows + extra) * pout; ++i)
       if (res[c][i].x == res[c][i].x || res[c][i].y == res[c][i].y) num += 1;
-  for (int f = 0; f < 9; ++f) {                    // the inputs are preserved (but for those the results lie over)
-    bool taken = false;
-    for (int c = 0; c < 4; ++c) taken = taken || over[c] == f;
-    if (!taken && memcmp(in[f].data(), keep[f].data(), keep[f].size() * sizeof(cx<T>)) != 0) num += 1;
-  }
+  nl_inputs_kept(in, keep, 9, over, 4, num);
   char name[80];
   snprintf(name, sizeof name, "nlc r%d v%d/%d%s%s%s%s%s", ROWS, vin, valid, TWLDS ? " twlds" : "", SPLIT ? " split" : "",
            alias == 1 ? " inpl a c2" : alias == 2 ? " inpl b c0" : "", poison ? " poison" : "", WAVE ? " wave" : "");
@@ -1597,20 +1583,8 @@ static double run_nlm(const NlmCase& c) {          // the worst relative error o
   long double want[6];
   for (int f = 0; f < 6; ++f) {
     want[f] = 0;
-    for (int r = 0; r < nrows; ++r) {
-      lvec X(M);
-      for (int p = 0; p < M; ++p) { X[p].x = 0; X[p].y = 0; }
-      for (int q = 0; q < vin; ++q) {
-        cx<T> z = in[f][(size_t)r * pin + q];
-        long double zr = z.x, zi = z.y;
-        if (zr != zr) zr = 0;                        // (the NaN field's expectation is NaN: no reference needed)
-        if (q == 0 || (M % 2 == 0 && q == M / 2)) zi = 0;
-        X[q].x = zr; X[q].y = zi;
-        if (q != 0 && q != M - q) { X[M - q].x = zr; X[M - q].y = -zi; }
-      }
-      lvec x = naive_dft(X, +1);
-      for (int p = 0; p < M; ++p) want[f] = std::max(want[f], fabsl(x[p].x / M));
-    }
+    for (int r = 0; r < nrows; ++r)                  // (a NaN reads as 0: the NaN field's expectation is NaN, no reference needed)
+      for (long double v : nl_real_row(in[f].data() + (size_t)r * pin, vin, M, true)) want[f] = std::max(want[f], fabsl(v));
   }
   for (int f = 0; f < 6; ++f) {
     const double g = (double)got[f] / M;             // the kernel's inverse transforms are un-normalised
@@ -1714,33 +1688,11 @@ static void test_nlz3(bool inplace) {
   emu_launch((nrows + 2 * ROWS - 1) / (2 * ROWS), K::THREADS, K::LDS_BYTES, [&](int b, int t, char* lds) { K::body(P, b, t, lds); });
   long double num = 0, den = 0;
   for (int r = 0; r < nrows; ++r) {
-    std::vector<std::vector<long double>> re(6, std::vector<long double>(M));
-    for (int f = 0; f < 6; ++f) {
-      lvec X(M);
-      for (int p = 0; p < M; ++p) { X[p].x = 0; X[p].y = 0; }
-      for (int q = 0; q < valid; ++q) {
-        cx<T> z = keep[f][(size_t)r * pin + q];
-        long double zr = z.x, zi = z.y;
-        if (q == 0) zi = 0;
-        X[q].x = zr; X[q].y = zi;
-        if (q != 0) { X[M - q].x = zr; X[M - q].y = -zi; }
-      }
-      lvec x = naive_dft(X, +1);
-      for (int p = 0; p < M; ++p) re[f][p] = x[p].x / M;
-    }
+    const std::vector<lreal> re = nl_real_rows(keep, 6, r, pin, valid, M);      // (L + 1 bins of 3 L points: bin 0 alone is its own conjugate)
     for (int c = 0; c < 3; ++c) {
-      const int c1 = (c + 1) % 3, c2 = (c + 2) % 3;
-      lvec x(M);
-      for (int p = 0; p < M; ++p) { x[p].x = re[c1][p] * re[3 + c2][p] - re[c2][p] * re[3 + c1][p]; x[p].y = 0; }
-      lvec X = naive_dft(x, -1);
       const cx<T>* g = (inplace ? in[c].data() : out[c].data()) + (size_t)r * pout;
-      for (int q = 0; q < valid; ++q) {
-        num += (g[q].x - X[q].x) * (g[q].x - X[q].x) + (g[q].y - X[q].y) * (g[q].y - X[q].y);
-        den += X[q].x * X[q].x + X[q].y * X[q].y;
-      }
-      if (!inplace)
-        for (int q = valid; q < pout; ++q)
-          if (g[q].x != (T)7 || g[q].y != (T)7) { num += 1; }
+      nl_accumulate(g, nl_cross_spectrum(&re[0], &re[3], c), valid, num, den);
+      if (!inplace) nl_tail_kept<T>(g, nullptr, valid, pout, num);
     }
   }
   char name[64];

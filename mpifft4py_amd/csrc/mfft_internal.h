@@ -131,6 +131,24 @@ struct NlzArgs {
   void* part = nullptr;    // not null: the Build::AbsMax kernel runs and writes nlz_absmax_waves() groups of 12 un-normalised
                            // partial maxima here, in the rows' precision: [wave][row of the pair][a, b][field] (fft_nlz.h NlmParams)
 };
+// What a product of the nonlinear term is, written down ONCE: every route, entry point, key and message reads this table.
+struct NlProduct {
+  Op op;
+  const char* name;      // in error texts; in plan_info keys "nonlinear[_<name>][_absmax]_fused_<mode>", the cross product unnamed
+  int nin, nout;         // fields in (a, b, then c), rows / components out (out, then the scalar one)
+  bool absmax;           // a Build::AbsMax kernel family exists (the call with real-space maxima)
+  bool nlz3;             // Build::Nlz3, the pruned 3/2-rule kernel, may stand in
+};
+constexpr NlProduct NL_PRODUCTS[] = {
+    {Op::Plain, "cross", 6, 3, true, true},
+    {Op::Dot, "dot", 6, 1, true, false},
+    {Op::CrossDot, "cross_dot", 9, 4, false, false},
+};
+inline const NlProduct& nl_product(Op op) {
+  for (const NlProduct& q : NL_PRODUCTS)
+    if (q.op == op) return q;
+  return NL_PRODUCTS[0];
+}
 bool nlz_supported(int64_t n, int prec, Op product = Op::Plain, bool absmax = false);
 int64_t nlz_absmax_waves(int64_t n, int prec, Op product, int64_t nrows);
 int launch_nlz(const NlzArgs& a, hipStream_t s);

@@ -332,49 +332,40 @@ int mfft_backward(mfft_plan_t p, const void* fu, void* u, int dealias) {
   return run_direct(p, false, fu, u, dealias);
 }
 
+// The five entries to the nonlinear term: the plan on its device, exactly the pointers the product needs, a known dealias mode.
+static int run_nonlinear(mfft_plan_t p, Op product, bool stats, const NlFields& u, int dealias) {
+  const NlProduct& q = nl_product(product);
+  MFFT_TRY(check_ready(p, u.a, u.b));
+  if (!u.out || (q.nin > 6 && !u.c) || (q.nout > 3 && !u.outs)) return set_error(MFFT_ERR_INVALID, "null argument");
+  if (dealias != MFFT_DEALIAS_NONE && dealias != MFFT_DEALIAS_2_3 && dealias != MFFT_DEALIAS_3_2)
+    return set_error(MFFT_ERR_INVALID, "unknown dealias mode %d", dealias);
+  return p->nonlinear(u, dealias, product, stats);
+}
+
 // out = fftn(ifftn(a) x ifftn(b)) with the plan's transforms under the given dealias mode: a, b, out are vector fields of
 // shape (3,) + the local complex shape, component-major; out may be a or b.  See include/mpifft4py_amd.h.
 int mfft_nonlinear_cross(mfft_plan_t p, const void* a_hat, const void* b_hat, void* out_hat, int dealias) {
-  MFFT_TRY(check_ready(p, a_hat, b_hat));
-  if (!out_hat) return set_error(MFFT_ERR_INVALID, "null argument");
-  if (dealias != MFFT_DEALIAS_NONE && dealias != MFFT_DEALIAS_2_3 && dealias != MFFT_DEALIAS_3_2)
-    return set_error(MFFT_ERR_INVALID, "unknown dealias mode %d", dealias);
-  return p->nonlinear_cross(a_hat, b_hat, out_hat, dealias);
+  return run_nonlinear(p, Op::Plain, false, {a_hat, b_hat, nullptr, out_hat, nullptr}, dealias);
 }
 
 // out = fftn(sum_f ifftn(a_f) ifftn(b_f)): a, b as above, out ONE component (the local complex shape); out may be any one
 // component of a or b.  See include/mpifft4py_amd.h.
 int mfft_nonlinear_dot(mfft_plan_t p, const void* a_hat, const void* b_hat, void* out_hat, int dealias) {
-  MFFT_TRY(check_ready(p, a_hat, b_hat));
-  if (!out_hat) return set_error(MFFT_ERR_INVALID, "null argument");
-  if (dealias != MFFT_DEALIAS_NONE && dealias != MFFT_DEALIAS_2_3 && dealias != MFFT_DEALIAS_3_2)
-    return set_error(MFFT_ERR_INVALID, "unknown dealias mode %d", dealias);
-  return p->nonlinear_dot(a_hat, b_hat, out_hat, dealias);
+  return run_nonlinear(p, Op::Dot, false, {a_hat, b_hat, nullptr, out_hat, nullptr}, dealias);
 }
 
 // out = fftn(ifftn(a) x ifftn(b)) AND s = fftn(sum_f ifftn(a_f) ifftn(c_f)) in one pass: a, b, c, out vector fields, s ONE
 // component; out may be a or b, s any one component of c.  See include/mpifft4py_amd.h.
 int mfft_nonlinear_cross_dot(mfft_plan_t p, const void* a_hat, const void* b_hat, const void* c_hat, void* out_hat, void* s_hat, int dealias) {
-  MFFT_TRY(check_ready(p, a_hat, b_hat));
-  if (!c_hat || !out_hat || !s_hat) return set_error(MFFT_ERR_INVALID, "null argument");
-  if (dealias != MFFT_DEALIAS_NONE && dealias != MFFT_DEALIAS_2_3 && dealias != MFFT_DEALIAS_3_2)
-    return set_error(MFFT_ERR_INVALID, "unknown dealias mode %d", dealias);
-  return p->nonlinear_cross_dot(a_hat, b_hat, c_hat, out_hat, s_hat, dealias);
+  return run_nonlinear(p, Op::CrossDot, false, {a_hat, b_hat, c_hat, out_hat, s_hat}, dealias);
 }
 
-// ... and the same two with statistics: the call also leaves the six real-space maxima in the plan (mfft_plan_nonlinear_absmax)
-static int nonlinear_stats(mfft_plan_t p, const void* a_hat, const void* b_hat, void* out_hat, int dealias, Op product) {
-  MFFT_TRY(check_ready(p, a_hat, b_hat));
-  if (!out_hat) return set_error(MFFT_ERR_INVALID, "null argument");
-  if (dealias != MFFT_DEALIAS_NONE && dealias != MFFT_DEALIAS_2_3 && dealias != MFFT_DEALIAS_3_2)
-    return set_error(MFFT_ERR_INVALID, "unknown dealias mode %d", dealias);
-  return p->nonlinear(a_hat, b_hat, out_hat, dealias, product, true);
-}
+// ... and the first two with statistics: the call also leaves the six real-space maxima in the plan (mfft_plan_nonlinear_absmax)
 int mfft_nonlinear_cross_absmax(mfft_plan_t p, const void* a_hat, const void* b_hat, void* out_hat, int dealias) {
-  return nonlinear_stats(p, a_hat, b_hat, out_hat, dealias, Op::Plain);
+  return run_nonlinear(p, Op::Plain, true, {a_hat, b_hat, nullptr, out_hat, nullptr}, dealias);
 }
 int mfft_nonlinear_dot_absmax(mfft_plan_t p, const void* a_hat, const void* b_hat, void* out_hat, int dealias) {
-  return nonlinear_stats(p, a_hat, b_hat, out_hat, dealias, Op::Dot);
+  return run_nonlinear(p, Op::Dot, true, {a_hat, b_hat, nullptr, out_hat, nullptr}, dealias);
 }
 int mfft_plan_nonlinear_absmax(mfft_plan_t p, double out6[6]) {
   if (!p || !out6) return set_error(MFFT_ERR_INVALID, "null argument");
@@ -386,6 +377,22 @@ int mfft_plan_sync(mfft_plan_t p) {
   if (p->cstream) MFFT_HIP(hipStreamSynchronize(p->cstream));
   MFFT_HIP(hipStreamSynchronize(p->stream));
   return 0;
+}
+
+// "nonlinear[_dot|_cross_dot][_absmax]_fused_{none,2_3,3_2}": does the fused route take that product (with statistics) under that
+// dealias mode?  One key per product, build it has and mode -- a product without a maxima build has no such key.
+static bool nonlinear_fused_key(mfft_plan_t p, const std::string& k, int64_t* value) {
+  static const struct { const char* name; int mode; } modes[] = {{"none", MFFT_DEALIAS_NONE}, {"2_3", MFFT_DEALIAS_2_3}, {"3_2", MFFT_DEALIAS_3_2}};
+  for (const NlProduct& q : NL_PRODUCTS) {
+    const std::string named = q.op == Op::Plain ? "nonlinear" : std::string("nonlinear_") + q.name;      // (the cross product's keys go unnamed)
+    for (int stats = 0; stats <= (q.absmax ? 1 : 0); ++stats)
+      for (const auto& m : modes)
+        if (k == named + (stats ? "_absmax" : "") + "_fused_" + m.name) {
+          *value = p->nonlinear_fusable(m.mode, q.op, stats != 0) ? 1 : 0;
+          return true;
+        }
+  }
+  return false;
 }
 
 int mfft_plan_get_info(mfft_plan_t p, const char* key, int64_t* value) {
@@ -400,21 +407,7 @@ int mfft_plan_get_info(mfft_plan_t p, const char* key, int64_t* value) {
   else if (k == "ranks") *value = p->P;
   else if (k == "complex_pitch") *value = p->pitched() ? p->Zp : 0;        // row pitch of the caller's spectrum (elements), 0 = compact
   else if (k == "complex_pitch_native") *value = p->nat_pitch() ? 1 : 0;  // 1: the routes run on the pitched rows themselves
-  else if (k == "nonlinear_fused_none") *value = p->nonlinear_fusable(MFFT_DEALIAS_NONE) ? 1 : 0;
-  else if (k == "nonlinear_fused_2_3") *value = p->nonlinear_fusable(MFFT_DEALIAS_2_3) ? 1 : 0;
-  else if (k == "nonlinear_fused_3_2") *value = p->nonlinear_fusable(MFFT_DEALIAS_3_2) ? 1 : 0;
-  else if (k == "nonlinear_dot_fused_none") *value = p->nonlinear_fusable(MFFT_DEALIAS_NONE, Op::Dot) ? 1 : 0;
-  else if (k == "nonlinear_dot_fused_2_3") *value = p->nonlinear_fusable(MFFT_DEALIAS_2_3, Op::Dot) ? 1 : 0;
-  else if (k == "nonlinear_dot_fused_3_2") *value = p->nonlinear_fusable(MFFT_DEALIAS_3_2, Op::Dot) ? 1 : 0;
-  else if (k == "nonlinear_cross_dot_fused_none") *value = p->nonlinear_fusable(MFFT_DEALIAS_NONE, Op::CrossDot) ? 1 : 0;
-  else if (k == "nonlinear_cross_dot_fused_2_3") *value = p->nonlinear_fusable(MFFT_DEALIAS_2_3, Op::CrossDot) ? 1 : 0;
-  else if (k == "nonlinear_cross_dot_fused_3_2") *value = p->nonlinear_fusable(MFFT_DEALIAS_3_2, Op::CrossDot) ? 1 : 0;
-  else if (k == "nonlinear_absmax_fused_none") *value = p->nonlinear_fusable(MFFT_DEALIAS_NONE, Op::Plain, true) ? 1 : 0;
-  else if (k == "nonlinear_absmax_fused_2_3") *value = p->nonlinear_fusable(MFFT_DEALIAS_2_3, Op::Plain, true) ? 1 : 0;
-  else if (k == "nonlinear_absmax_fused_3_2") *value = p->nonlinear_fusable(MFFT_DEALIAS_3_2, Op::Plain, true) ? 1 : 0;
-  else if (k == "nonlinear_dot_absmax_fused_none") *value = p->nonlinear_fusable(MFFT_DEALIAS_NONE, Op::Dot, true) ? 1 : 0;
-  else if (k == "nonlinear_dot_absmax_fused_2_3") *value = p->nonlinear_fusable(MFFT_DEALIAS_2_3, Op::Dot, true) ? 1 : 0;
-  else if (k == "nonlinear_dot_absmax_fused_3_2") *value = p->nonlinear_fusable(MFFT_DEALIAS_3_2, Op::Dot, true) ? 1 : 0;
+  else if (nonlinear_fused_key(p, k, value)) return 0;
   else if (k == "nonlinear_bytes") *value = (int64_t)(p->nlx.bytes + p->nly.bytes + p->nlr.bytes + p->nlw[0].bytes + p->nlw[1].bytes);
   else if (k == "split_last") *value = p->split_last_route() ? 1 : 0;   // the one-rank route that splits real / complex last (decides whether the work buffer fits, if no call has yet)
   else if (k == "plane_pad") *value = (p->P == 1 && p->d.decomp == MFFT_SLAB) ? p->p1_plane_pad() : 0;   // elements added to the intermediate's plane pitch

@@ -74,6 +74,16 @@ struct Buf {                   // a device buffer of the plan that only grows (m
   size_t bytes = 0;
 };
 
+// The caller's arrays of one nonlinear operation (plan_nonlinear.hip): vector fields a, b and -- where the product has one -- c
+// in, the result out (three components, or the ONE of the dot product) and, of the product with both, the scalar result outs.
+struct NlFields {
+  const void *a, *b, *c;
+  void *out, *outs;
+  // component f of the inputs (a, b, then c) / of the results (out, then outs), C elements of es bytes per component
+  const void* src(int f, int64_t C, size_t es) const { return static_cast<const char*>(f < 3 ? a : f < 6 ? b : c) + (size_t)((f % 3) * C) * es; }
+  void* dst(int f, int64_t C, size_t es) const { return f < 3 ? static_cast<char*>(out) + (size_t)(f * C) * es : outs; }
+};
+
 // host-only part of plan construction: decomposition bookkeeping (no HIP call; plan_sched.hip)
 int decomp_init(mfft_plan_s* p, const mfft_plan_desc* desc, int nranks, int rank);
 
@@ -480,20 +490,16 @@ struct mfft_plan_s {
   int exec(bool forward, const void* in, void* out, int dealias);       // one transform, pitched callers' arrays converted where needed
 
   // ---- round 6: the nonlinear term a x b of a pseudo-spectral step as one operation (fft_nlz.h; plan_nonlinear.hip) ----
-  // (product: mfft::Op::Plain the cross product, three result components; mfft::Op::Dot the dot product, one)
+  // (product: one of mfft::NL_PRODUCTS -- the cross product, three result components; the dot product, one; both at once with a
+  // third field, four)
   // (stats: also the six real-space maxima, into nlmacc -- the Build::AbsMax z kernel on the fused routes, a sweep over the
   // real work arrays on the composed one)
   bool nonlinear_fusable(int dealias, mfft::Op product = mfft::Op::Plain, bool stats = false) const;
   int64_t local_real_count(bool padded) const;
-  int nonlinear_cross(const void* a, const void* b, void* out, int dealias);
-  int nonlinear_dot(const void* a, const void* b, void* out, int dealias);      // out: ONE component; may alias one of a's or b's
-  // (mfft::Op::CrossDot: a x b into out AND sum_f a_f c_f of a third field c into the ONE component outs; no statistics.  out
-  // may be a or b, outs any one component of c)
-  int nonlinear_cross_dot(const void* a, const void* b, const void* c, void* out, void* outs, int dealias);
-  int nonlinear(const void* a, const void* b, void* out, int dealias, mfft::Op product, bool stats = false, const void* c = nullptr, void* outs = nullptr);
-  int nonlinear_fused(const void* a, const void* b, void* out, int dealias, mfft::Op product, bool stats, const void* c = nullptr, void* outs = nullptr);
-  int nonlinear_fused_ranks(const void* a, const void* b, void* out, int dealias, mfft::Op product, bool stats, const void* c = nullptr, void* outs = nullptr);
-  int nonlinear_composed(const void* a, const void* b, void* out, int dealias, mfft::Op product, bool stats, const void* c = nullptr, void* outs = nullptr);
+  int nonlinear(const mfft::NlFields& u, int dealias, mfft::Op product, bool stats);
+  int nonlinear_fused(const mfft::NlFields& u, int dealias, mfft::Op product, bool stats);
+  int nonlinear_fused_ranks(const mfft::NlFields& u, int dealias, mfft::Op product, bool stats);
+  int nonlinear_composed(const mfft::NlFields& u, int dealias, mfft::Op product, bool stats);
   int nonlinear_absmax(double out6[6]);                                   // this rank's maxima of the last statistics call
   int absmax_sweep(const void* x, int ncomp, size_t n, double* acc);      // absmax.hip
 };

@@ -10,18 +10,13 @@ using namespace mfft;
 // ===========================================================================
 extern "C" int mfft_ew_cross(mfft_plan_t plan, const void* a, const void* b, void* out, size_t n, int precision);
 extern "C" int mfft_ew_dot(mfft_plan_t plan, const void* a, const void* b, void* out, size_t n, int precision);
-// Two products share every route below: Op::Plain, the cross product (three result components), and Op::Dot, the dot product
-// sum_f ifftn(a_f) ifftn(b_f) of a transported scalar's u . grad(theta) (ONE result component: nout = 1 -- one forward y pass,
-// one forward exchange, one forward x pass; seven work arrays instead of nine in the composition).
-// Op::CrossDot: both at once for a velocity that carries a scalar, a x b AND sum_f a_f c_f with a third field c -- NINE fields in
-// (nin), FOUR results (the scalar one, `outs`, is the fourth): ifftn(a) is computed once where the two calls compute it twice.
-static int nl_nout(Op product) { return product == Op::Dot ? 1 : product == Op::CrossDot ? 4 : 3; }
-static int nl_nin(Op product) { return product == Op::CrossDot ? 9 : 6; }
-// component f of the operation's inputs (a, b, then c) and results (out, then outs), C elements of es bytes per component
-static const void* nl_src(const void* a, const void* b, const void* c, int f, int64_t C, size_t es) {
-  return static_cast<const char*>(f < 3 ? a : f < 6 ? b : c) + (size_t)((f % 3) * C) * es;
-}
-static void* nl_dst(void* out, void* outs, int f, int64_t C, size_t es) { return f < 3 ? static_cast<char*>(out) + (size_t)(f * C) * es : outs; }
+// Three products (mfft_internal.h NL_PRODUCTS) share every route below: the cross product (three result components); the dot
+// product sum_f ifftn(a_f) ifftn(b_f) of a transported scalar's u . grad(theta) (ONE result component: nout = 1 -- one forward y
+// pass, one forward exchange, one forward x pass; seven work arrays instead of nine in the composition); and both at once for a
+// velocity that carries a scalar, a x b AND sum_f a_f c_f with a third field c -- NINE fields in (nin), FOUR results (the scalar
+// one, `outs`, is the fourth): ifftn(a) is computed once where the two calls compute it twice.
+// The routes read nin and nout from the table of products (mfft_internal.h NlProduct) and the caller's arrays through NlFields
+// (plan_impl.h); only the composed route, which chooses the element-wise products, names a product.
 
 int64_t mfft_plan_s::local_real_count(bool padded) const {
   if (d.line2d) return 0;
@@ -31,14 +26,15 @@ int64_t mfft_plan_s::local_real_count(bool padded) const {
 
 // Composed route (every decomposition and length): the transforms the caller would run, on nine (dot product: seven) work
 // arrays of the plan: the nin real fields, then the results.
-// Op::CrossDot: twelve -- the dot product of a and c goes over c_0 (mfft_ew_dot allows it), the cross product into three more
+// Both products: twelve -- the dot product of a and c goes over c_0 (mfft_ew_dot allows it), the cross product into three more
 // arrays (mfft_ew_cross does not alias).
-int mfft_plan_s::nonlinear_composed(const void* a, const void* b, void* out, int dealias, Op product, bool stats, const void* c, void* outs) {
-  const int nout = nl_nout(product), nin = nl_nin(product);
-  const bool both = product == Op::CrossDot;
+int mfft_plan_s::nonlinear_composed(const NlFields& u, int dealias, Op product, bool stats) {
+  const NlProduct& q = nl_product(product);
+  const int nout = q.nout, nin = q.nin;
+  const bool both = product == Op::CrossDot, dot = product == Op::Dot;
   const bool pad = dealias == MFFT_DEALIAS_3_2, masked = dealias == MFFT_DEALIAS_2_3;
   const int64_t nr = local_real_count(pad), nc = local_complex_alloc();       // (pitched arrays: a component is that much larger)
-  if (nr <= 0 || !r2c) return set_error(MFFT_ERR_UNSUPPORTED, "nonlinear_%s needs a 3-D real-to-complex plan", both ? "cross_dot" : nout == 1 ? "dot" : "cross");
+  if (nr <= 0 || !r2c) return set_error(MFFT_ERR_UNSUPPORTED, "nonlinear_%s needs a 3-D real-to-complex plan", q.name);
   const int narr = both ? 12 : nin + nout;
   MFFT_TRY(ensure(nlr, (size_t)(narr * nr) * rs));
   char* R = static_cast<char*>(nlr.p);
@@ -46,7 +42,7 @@ int mfft_plan_s::nonlinear_composed(const void* a, const void* b, void* out, int
   auto back = [&](const void* in, void* o) { return exec(false, in, o, dealias); };
   auto fwd = [&](const void* in, void* o) { return exec(true, in, o, masked ? (int)MFFT_DEALIAS_NONE : dealias); };
   for (int f = 0; f < 3; ++f)                      // (component by component, as before: a_f, b_f, then c_f)
-    for (int g = 0; g < nin / 3; ++g) MFFT_TRY(back(nl_src(a, b, c, 3 * g + f, nc, es), arr(3 * g + f)));
+    for (int g = 0; g < nin / 3; ++g) MFFT_TRY(back(u.src(3 * g + f, nc, es), arr(3 * g + f)));
   // statistics: the six real arrays exist here, one streaming sweep over them (absmax.hip) into the same accumulator
   if (stats) MFFT_TRY(stage("nl_absmax", 6.0 * (double)nr * rs, [&] { return absmax_sweep(R, 6, (size_t)nr, static_cast<double*>(nlmacc.p)); }));
   // the element-wise products and where their results lie: res[f] is the work array forward transform f starts from
@@ -56,11 +52,11 @@ int mfft_plan_s::nonlinear_composed(const void* a, const void* b, void* out, int
     MFFT_TRY(stage("nl_cross", 9.0 * (double)nr * rs, [&] { return mfft_ew_cross(this, arr(0), arr(3), arr(9), (size_t)nr, prec); }));
     res[0] = 9; res[1] = 10; res[2] = 11; res[3] = 6;
   } else {
-    MFFT_TRY(stage(nout == 1 ? "nl_dot" : "nl_cross", (6.0 + nout) * (double)nr * rs, [&] {
-      return (nout == 1 ? mfft_ew_dot : mfft_ew_cross)(this, arr(0), arr(3), arr(6), (size_t)nr, prec);
+    MFFT_TRY(stage(dot ? "nl_dot" : "nl_cross", (6.0 + nout) * (double)nr * rs, [&] {
+      return (dot ? mfft_ew_dot : mfft_ew_cross)(this, arr(0), arr(3), arr(6), (size_t)nr, prec);
     }));
   }
-  for (int f = 0; f < nout; ++f) MFFT_TRY(fwd(arr(res[f]), nl_dst(out, outs, f, nc, es)));
+  for (int f = 0; f < nout; ++f) MFFT_TRY(fwd(arr(res[f]), u.dst(f, nc, es)));
   return 0;
 }
 
@@ -73,7 +69,7 @@ static int64_t nlz_batch_planes(size_t plane6, int64_t planes) {
 }
 
 // the fused z stage on a batch: rows of the six fields in Y (yelems apart, pitch Za) in, the three rows of the cross product
-// (the one row of the dot product) out, in place on the first three (the first); Op::CrossDot: nine fields in, four rows out
+// (the one row of the dot product) out, in place on the first three (the first); both products: nine fields in, four rows out
 // (stats: the Build::AbsMax kernel, its partial maxima into nlm, folded into the plan's accumulator with 1 / L2 -- the kernel's
 // inverse transforms are un-normalised -- after the launch: the maxima accumulate over the batches)
 static int nlz_rows(mfft_plan_s* p, char* Y, size_t yelems, int64_t L2, int64_t Za, int64_t nrows, int valid_in, Op product, bool stats) {
@@ -85,12 +81,14 @@ static int nlz_rows(mfft_plan_s* p, char* Y, size_t yelems, int64_t L2, int64_t 
     MFFT_TRY(p->ensure(p->nlm, absmax_fold_scratch_bytes() + (size_t)waves * NLM_SLOTS * p->rs));
     z.part = static_cast<char*>(p->nlm.p) + absmax_fold_scratch_bytes();
   }
+  const NlProduct& q = nl_product(product);
+  auto Yf = [&](int f) { return Y + (size_t)f * yelems * p->es; };
   for (int f = 0; f < 3; ++f) {
-    z.a[f] = Y + (size_t)f * yelems * p->es;
-    z.b[f] = Y + (size_t)(3 + f) * yelems * p->es;
-    if (product == Op::CrossDot) z.c[f] = Y + (size_t)(6 + f) * yelems * p->es;
+    z.a[f] = Yf(f);
+    z.b[f] = Yf(3 + f);
+    if (q.nin > 6) z.c[f] = Yf(6 + f);
   }
-  for (int f = 0; f < nl_nout(product); ++f) z.out[f] = Y + (size_t)f * yelems * p->es;      // (Op::CrossDot: the scalar row over b_0)
+  for (int f = 0; f < q.nout; ++f) z.out[f] = Yf(f);      // (four results: the scalar row over b_0)
   z.product = product;
   z.n = (int)L2; z.prec = p->prec; z.in_stride = Za; z.out_stride = Za; z.nrows = nrows; z.valid = (int)p->Nf;
   z.valid_in = valid_in;
@@ -124,13 +122,14 @@ bool mfft_plan_s::nonlinear_fusable(int dealias, Op product, bool stats) const {
 // planes of that batch are free by then.  Three forward x passes finish.  The real-space arrays never exist; the batch
 // buffers are at most 16 GiB (1024^3 with the 3/2-rule: 6 x 13.1 GB of x-pass buffers + 14.7 GB of batch buffers, where the
 // composed route needs 9 x 29 GB of real work arrays).
-// Op::Dot: the same with ONE result -- the z kernel writes the rows of the dot product in place on the first field, one forward
+// The dot product: the same with ONE result -- the z kernel writes the rows of the dot product in place on the first field, one forward
 // y pass per batch, one forward x pass.
-// Op::CrossDot: nine fields through the inverse passes, the z kernel's four result rows in place on the first four (the cross
+// Both products: nine fields through the inverse passes, the z kernel's four result rows in place on the first four (the cross
 // product over a, the scalar row over b_0), four forward passes.
-int mfft_plan_s::nonlinear_fused(const void* a, const void* b, void* out, int dealias, Op product, bool stats, const void* c, void* outs) {
-  const int nout = nl_nout(product), nin = nl_nin(product);
+int mfft_plan_s::nonlinear_fused(const NlFields& u, int dealias, Op product, bool stats) {
+  const int nout = nl_product(product).nout, nin = nl_product(product).nin;
   const bool pad = dealias == MFFT_DEALIAS_3_2, masked = dealias == MFFT_DEALIAS_2_3;
+  const Op ld = pad ? Op::PadLoad : Op::Plain, st = pad ? Op::TruncStore : Op::Plain;      // the 3/2-rule's passes pad on load, truncate on store
   const int64_t L0 = pad ? M0 : N0, L1 = pad ? M1 : N1, L2 = pad ? M2 : N2;
   const int64_t line = (int64_t)(128 / es);
   static const int align_mode = (int)env_int("MFFT_NLZ_ALIGN", -1);     // 0 compact rows, 1 aligned, unset: rows of 2 KiB and more
@@ -148,9 +147,11 @@ int mfft_plan_s::nonlinear_fused(const void* a, const void* b, void* out, int de
   const int64_t mb = std::min(std::max<int64_t>(nlz_batch_planes(plane6, L0), 1), L0);
   MFFT_TRY(ensure(nlx, (size_t)nin * xelems * es));
   MFFT_TRY(ensure(nly, (size_t)mb * plane6));
-  char* X = static_cast<char*>(nlx.p);
-  char* Y = static_cast<char*>(nly.p);
   const size_t yelems = (size_t)(mb * L1 * Za);
+  // field f of the x-pass buffers from element `off` of it on, of the batch buffers; where the batch of planes from i0 on starts
+  auto Xf = [&, X = static_cast<char*>(nlx.p)](int f, size_t off = 0) { return X + ((size_t)f * xelems + off) * es; };
+  auto Yf = [&, Y = static_cast<char*>(nly.p)](int f) { return Y + (size_t)f * yelems * es; };
+  auto batch = [&](int64_t i0) { return (size_t)(i0 * N1 * Za); };
   const double sc3 = pad ? padscale() : 1.0;
   const double Cb = (double)C * es, Xb = (double)(L0 * N1 * Nf) * es, Yb = (double)(L0 * L1 * Nf) * es;
   MaskScope mask_scope{this};
@@ -165,8 +166,8 @@ int mfft_plan_s::nonlinear_fused(const void* a, const void* b, void* out, int de
   if (pruned) band_keep(&keep0, &keep1, &keep2);
   MFFT_TRY(stage("nl_x_inv", nin * (Cb * keep0 + Xb) * keep1 * keep2, [&] {
     for (int f = 0; f < nin; ++f) {
-      const void* src = nl_src(a, b, c, f, C, es);
-      void* dst = X + (size_t)f * xelems * es;
+      const void* src = u.src(f, C, es);
+      void* dst = Xf(f);
       if (pruned) {                                // one outer batch per ky, the kept kz columns of it
         ColArgs::Band bx;
         bx.row_lo = ba0; bx.row_hi = bb0; bx.g_off = 0; bx.g_step = 1; bx.g_lo = ba1; bx.g_hi = bb1;
@@ -176,12 +177,12 @@ int mfft_plan_s::nonlinear_fused(const void* a, const void* b, void* out, int de
         MFFT_TRY(col(src, dst, N0, true, N1, Nf, Zi, plain(N1 * Zi), Za, plain(N1 * Za)));
         mask_src = nullptr;
       } else if (Zi == Za && Za != Nf) {           // pitched caller rows: whole planes of N1 * Za columns
-        MFFT_TRY(col_pad(src, dst, L0, true, pad ? Op::PadLoad : Op::Plain, false, 1, N1 * Za, 0, plain(N1 * Za), 0, plain(N1 * Za), sc3 / (double)L0));
+        MFFT_TRY(col_pad(src, dst, L0, true, ld, false, 1, N1 * Za, 0, plain(N1 * Za), 0, plain(N1 * Za), sc3 / (double)L0));
       } else if (Za != Nf) {                       // one outer batch per y row: compact rows in, pitched rows out
-        MFFT_TRY(col_pad(src, dst, L0, true, pad ? Op::PadLoad : Op::Plain, false, N1, Nf, Nf, plain(N1 * Nf), Za, plain(N1 * Za), sc3 / (double)L0,
+        MFFT_TRY(col_pad(src, dst, L0, true, ld, false, N1, Nf, Nf, plain(N1 * Nf), Za, plain(N1 * Za), sc3 / (double)L0,
                          0, 0, 1));
       } else {
-        MFFT_TRY(col_pad(src, dst, L0, true, pad ? Op::PadLoad : Op::Plain, false, 1, N1 * Nf, 0, plain(N1 * Nf), 0, plain(N1 * Nf), sc3 / (double)L0));
+        MFFT_TRY(col_pad(src, dst, L0, true, ld, false, 1, N1 * Nf, 0, plain(N1 * Nf), 0, plain(N1 * Nf), sc3 / (double)L0));
       }
     }
     return 0;
@@ -191,38 +192,37 @@ int mfft_plan_s::nonlinear_fused(const void* a, const void* b, void* out, int de
     const double frac = (double)m / (double)L0;
     MFFT_TRY(stage("nl_y_inv", nin * (Xb * keep1 + Yb) * keep2 * frac, [&] {
       for (int f = 0; f < nin; ++f) {
-        const void* src = X + ((size_t)f * xelems + (size_t)(i0 * N1 * Za)) * es;
-        void* dst = Y + (size_t)f * yelems * es;
+        const void* src = Xf(f, batch(i0));
+        void* dst = Yf(f);
         if (pruned) {
           ColArgs::Band by;
           by.row_lo = ba1; by.row_hi = bb1; by.c_lim = ba2;
           MFFT_TRY(col_band(src, dst, N1, m, ba2, N1 * Za, plain(Za), L1 * Za, plain(Za), by));
         } else {
-          MFFT_TRY(col_pad(src, dst, L1, true, pad ? Op::PadLoad : Op::Plain, false, m, Nf, N1 * Za, plain(Za), L1 * Za, plain(Za), 1.0 / (double)L1));
+          MFFT_TRY(col_pad(src, dst, L1, true, ld, false, m, Nf, N1 * Za, plain(Za), L1 * Za, plain(Za), 1.0 / (double)L1));
         }
       }
       return 0;
     }));
     MFFT_TRY(stage("nl_z", (nin * keep2 + nout) * Yb * frac, [&] {
-      return nlz_rows(this, Y, yelems, L2, Za, m * L1, pruned ? ba2 : 0, product, stats);
+      return nlz_rows(this, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0, product, stats);
     }));
     MFFT_TRY(stage("nl_y_fwd", nout * (Xb + Yb) * frac, [&] {
       for (int f = 0; f < nout; ++f)
-        MFFT_TRY(col_pad(Y + (size_t)f * yelems * es, X + ((size_t)f * xelems + (size_t)(i0 * N1 * Za)) * es, L1, false, pad ? Op::TruncStore : Op::Plain,
-                         pad, m, Nf, L1 * Za, plain(Za), N1 * Za, plain(Za), 1.0));
+        MFFT_TRY(col_pad(Yf(f), Xf(f, batch(i0)), L1, false, st, pad, m, Nf, L1 * Za, plain(Za), N1 * Za, plain(Za), 1.0));
       return 0;
     }));
   }
   MFFT_TRY(stage("nl_x_fwd", nout * (Cb + Xb), [&] {
     for (int f = 0; f < nout; ++f) {
-      const void* src = X + (size_t)f * xelems * es;
-      void* dst = nl_dst(out, outs, f, C, es);
+      const void* src = Xf(f);
+      void* dst = u.dst(f, C, es);
       if (Zi == Za && Za != Nf)                    // pitched result
-        MFFT_TRY(col_pad(src, dst, L0, false, pad ? Op::TruncStore : Op::Plain, pad, 1, N1 * Za, 0, plain(N1 * Za), 0, plain(N1 * Za), 1.0 / sc3));
+        MFFT_TRY(col_pad(src, dst, L0, false, st, pad, 1, N1 * Za, 0, plain(N1 * Za), 0, plain(N1 * Za), 1.0 / sc3));
       else if (Za != Nf)                           // tiles of the compact result; input column (y, z) sits at y * Za + z
-        MFFT_TRY(col_pad(src, dst, L0, false, pad ? Op::TruncStore : Op::Plain, pad, 1, N1 * Nf, 0, plain(N1 * Za), 0, plain(N1 * Nf), 1.0 / sc3, Nf, Za - Nf));
+        MFFT_TRY(col_pad(src, dst, L0, false, st, pad, 1, N1 * Nf, 0, plain(N1 * Za), 0, plain(N1 * Nf), 1.0 / sc3, Nf, Za - Nf));
       else
-        MFFT_TRY(col_pad(src, dst, L0, false, pad ? Op::TruncStore : Op::Plain, pad, 1, N1 * Nf, 0, plain(N1 * Nf), 0, plain(N1 * Nf), 1.0 / sc3));
+        MFFT_TRY(col_pad(src, dst, L0, false, st, pad, 1, N1 * Nf, 0, plain(N1 * Nf), 0, plain(N1 * Nf), 1.0 / sc3));
     }
     return 0;
   }));
@@ -233,11 +233,12 @@ int mfft_plan_s::nonlinear_fused(const void* a, const void* b, void* out, int de
 // passes, six all-to-alls, then batches of the rank's x planes -- inverse y passes reading the receive layout through the
 // two-level row map (transpose_Uc fused, maths.pyx:21-31), the fused z kernel, forward y passes writing the packed send
 // layout (slab.py:403) -- three all-to-alls, three forward x passes.  Nine exchanges as in the composition, no real arrays.
-// (Op::Dot: six inverse exchanges and one forward exchange.)
-// (Op::CrossDot: nine inverse exchanges and four forward ones.)
-int mfft_plan_s::nonlinear_fused_ranks(const void* a, const void* b, void* out, int dealias, Op product, bool stats, const void* c, void* outs) {
-  const int nout = nl_nout(product), nin = nl_nin(product);
+// (The dot product: six inverse exchanges and one forward exchange.)
+// (Both products: nine inverse exchanges and four forward ones.)
+int mfft_plan_s::nonlinear_fused_ranks(const NlFields& u, int dealias, Op product, bool stats) {
+  const int nout = nl_product(product).nout, nin = nl_product(product).nin;
   const bool pad = dealias == MFFT_DEALIAS_3_2, masked = dealias == MFFT_DEALIAS_2_3;
+  const Op ld = pad ? Op::PadLoad : Op::Plain, st = pad ? Op::TruncStore : Op::Plain;      // the 3/2-rule's passes pad on load, truncate on store
   const int64_t L0 = pad ? M0 : N0, L1 = pad ? M1 : N1, L2 = pad ? M2 : N2, Lp0 = L0 / P;
   const int64_t line = (int64_t)(128 / es);
   const int64_t Za = Nf * (int64_t)es >= 2048 ? (Nf + line - 1) / line * line : Nf;        // batch buffers: line-aligned rows
@@ -249,8 +250,13 @@ int mfft_plan_s::nonlinear_fused_ranks(const void* a, const void* b, void* out, 
   MFFT_TRY(ensure(nlw[0], (size_t)nin * xelems * es));
   MFFT_TRY(ensure(nlw[1], (size_t)nin * xelems * es));
   MFFT_TRY(ensure(nly, (size_t)mb * plane6));
-  char *X = static_cast<char*>(nlw[0].p), *R = static_cast<char*>(nlw[1].p), *Y = static_cast<char*>(nly.p);
   const size_t yelems = (size_t)(mb * L1 * Za);
+  // field f of the two exchange buffers from element `off` of it on, of the batch buffers; where the batch of planes from i0 on
+  // starts in a layout of x rows `pitch` apart
+  auto Xf = [&, X = static_cast<char*>(nlw[0].p)](int f, size_t off = 0) { return X + ((size_t)f * xelems + off) * es; };
+  auto Rf = [&, R = static_cast<char*>(nlw[1].p)](int f, size_t off = 0) { return R + ((size_t)f * xelems + off) * es; };
+  auto Yf = [&, Y = static_cast<char*>(nly.p)](int f) { return Y + (size_t)f * yelems * es; };
+  auto batch = [&](int64_t i0, int64_t pitch) { return (size_t)(i0 * pitch); };
   const double sc3 = pad ? padscale() : 1.0;
   MaskScope mask_scope{this};
   lband_use = false;
@@ -261,8 +267,8 @@ int mfft_plan_s::nonlinear_fused_ranks(const void* a, const void* b, void* out, 
   const bool pruned = masked && band_ok && ap <= Nf && prune_enabled();
   MFFT_TRY(stage("nl_x_inv", 0, [&] {
     for (int f = 0; f < nin; ++f) {
-      const void* src = nl_src(a, b, c, f, C, es);
-      void* dst = X + (size_t)f * xelems * es;
+      const void* src = u.src(f, C, es);
+      void* dst = Xf(f);
       if (pruned) {
         if (band_allzero) {                        // nothing of this rank's spectrum survives the mask
           MFFT_TRY(zero(dst, (size_t)(N0 * Np1 * ap) * es));
@@ -276,15 +282,15 @@ int mfft_plan_s::nonlinear_fused_ranks(const void* a, const void* b, void* out, 
         MFFT_TRY(col(src, dst, N0, true, 1, Np1 * Nf, 0, plain(Np1 * Nf), 0, plain(Np1 * Nf)));
         mask_src = nullptr;
       } else {
-        MFFT_TRY(col_pad(src, dst, L0, true, pad ? Op::PadLoad : Op::Plain, false, 1, Np1 * Nf, 0, plain(Np1 * Nf), 0, plain(Np1 * Nf), sc3 / (double)L0));
+        MFFT_TRY(col_pad(src, dst, L0, true, ld, false, 1, Np1 * Nf, 0, plain(Np1 * Nf), 0, plain(Np1 * Nf), sc3 / (double)L0));
       }
     }
     return 0;
   }));
   MFFT_TRY(stage("nl_a2a_inv", 0, [&] {
     for (int f = 0; f < nin; ++f) {
-      if (pruned) MFFT_TRY(exchange_equal(world, X + (size_t)f * xelems * es, R + (size_t)f * xelems * es, (size_t)(Np0 * Np1 * ap) * es));
-      else MFFT_TRY(xchg(0, false, pad, X + (size_t)f * xelems * es, R + (size_t)f * xelems * es));
+      if (pruned) MFFT_TRY(exchange_equal(world, Xf(f), Rf(f), (size_t)(Np0 * Np1 * ap) * es));
+      else MFFT_TRY(xchg(0, false, pad, Xf(f), Rf(f)));
     }
     return 0;
   }));
@@ -293,32 +299,29 @@ int mfft_plan_s::nonlinear_fused_ranks(const void* a, const void* b, void* out, 
     MFFT_TRY(stage("nl_y_inv", 0, [&] {
       for (int f = 0; f < nin; ++f) {
         if (pruned)
-          MFFT_TRY(col(R + ((size_t)f * xelems + (size_t)(i0 * Np1 * ap)) * es, Y + (size_t)f * yelems * es, N1, true, m, a2, Np1 * ap,
-                       two_level(Np1, Np0 * Np1 * ap, ap), L1 * Za, plain(Za)));
+          MFFT_TRY(col(Rf(f, batch(i0, Np1 * ap)), Yf(f), N1, true, m, a2, Np1 * ap, two_level(Np1, Np0 * Np1 * ap, ap), L1 * Za, plain(Za)));
         else
-          MFFT_TRY(col_pad(R + ((size_t)f * xelems + (size_t)(i0 * Np1 * Nf)) * es, Y + (size_t)f * yelems * es, L1, true, pad ? Op::PadLoad : Op::Plain,
-                           false, m, Nf, Np1 * Nf, two_level(Np1, Lp0 * Np1 * Nf, Nf), L1 * Za, plain(Za), 1.0 / (double)L1));
+          MFFT_TRY(col_pad(Rf(f, batch(i0, Np1 * Nf)), Yf(f), L1, true, ld, false, m, Nf, Np1 * Nf, two_level(Np1, Lp0 * Np1 * Nf, Nf), L1 * Za,
+                           plain(Za), 1.0 / (double)L1));
       }
       return 0;
     }));
     MFFT_TRY(stage("nl_z", 0, [&] {
-      return nlz_rows(this, Y, yelems, L2, Za, m * L1, pruned ? (int)a2 : 0, product, stats);
+      return nlz_rows(this, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0, product, stats);
     }));
     MFFT_TRY(stage("nl_y_fwd", 0, [&] {      // truncate + fold in y, straight into the packed (P, Lp0, S) send layout
       for (int f = 0; f < nout; ++f)
-        MFFT_TRY(col_pad(Y + (size_t)f * yelems * es, X + ((size_t)f * xelems + (size_t)(i0 * S)) * es, L1, false, pad ? Op::TruncStore : Op::Plain, pad, m,
-                         Nf, L1 * Za, plain(Za), S, two_level(Np1, Lp0 * S, Nf), 1.0));
+        MFFT_TRY(col_pad(Yf(f), Xf(f, batch(i0, S)), L1, false, st, pad, m, Nf, L1 * Za, plain(Za), S, two_level(Np1, Lp0 * S, Nf), 1.0));
       return 0;
     }));
   }
   MFFT_TRY(stage("nl_a2a_fwd", 0, [&] {
-    for (int f = 0; f < nout; ++f) MFFT_TRY(xchg(0, true, pad, X + (size_t)f * xelems * es, R + (size_t)f * xelems * es));
+    for (int f = 0; f < nout; ++f) MFFT_TRY(xchg(0, true, pad, Xf(f), Rf(f)));
     return 0;
   }));
   MFFT_TRY(stage("nl_x_fwd", 0, [&] {
     for (int f = 0; f < nout; ++f)
-      MFFT_TRY(col_pad(R + (size_t)f * xelems * es, nl_dst(out, outs, f, C, es), L0, false, pad ? Op::TruncStore : Op::Plain, pad, 1,
-                       Np1 * Nf, 0, plain(S), 0, plain(Np1 * Nf), 1.0 / sc3));
+      MFFT_TRY(col_pad(Rf(f), u.dst(f, C, es), L0, false, st, pad, 1, Np1 * Nf, 0, plain(S), 0, plain(Np1 * Nf), 1.0 / sc3));
     return 0;
   }));
   return 0;
@@ -328,8 +331,10 @@ int mfft_plan_s::nonlinear_fused_ranks(const void* a, const void* b, void* out, 
 // the product is formed on (the padded one under the 3/2-rule) in the plan's accumulator, nlmacc[0..5] = [a, b][f]: cleared on
 // the stream here, raised by every batch's fold (or the composed route's sweep), read by nonlinear_absmax.  A call without
 // stats does not touch it.
-int mfft_plan_s::nonlinear(const void* a, const void* b, void* out, int dealias, Op product, bool stats, const void* c, void* outs) {
-  if (product == Op::CrossDot && (stats || !c || !outs)) return set_error(MFFT_ERR_INVALID, "nonlinear_cross_dot: a third field, a scalar result, no statistics");
+int mfft_plan_s::nonlinear(const NlFields& u, int dealias, Op product, bool stats) {
+  const NlProduct& q = nl_product(product);
+  if ((stats && !q.absmax) || (q.nin > 6 && !u.c) || (q.nout > 3 && !u.outs))
+    return set_error(MFFT_ERR_INVALID, "nonlinear_%s: %d fields in, %d components out, %s", q.name, q.nin, q.nout, q.absmax ? "statistics" : "no statistics");
   if (dealias == MFFT_DEALIAS_2_3) MFFT_TRY(require_mask());
   if (stats) {
     MFFT_TRY(ensure(nlmacc, 12 * sizeof(double)));
@@ -337,8 +342,8 @@ int mfft_plan_s::nonlinear(const void* a, const void* b, void* out, int dealias,
     nlm_valid = false;          // cleared, and partial until every batch has folded: valid only once the route has enqueued it all
   }
   const int rc = nonlinear_fusable(dealias, product, stats)
-                     ? (P == 1 ? nonlinear_fused(a, b, out, dealias, product, stats, c, outs) : nonlinear_fused_ranks(a, b, out, dealias, product, stats, c, outs))
-                     : nonlinear_composed(a, b, out, dealias, product, stats, c, outs);
+                     ? (P == 1 ? nonlinear_fused(u, dealias, product, stats) : nonlinear_fused_ranks(u, dealias, product, stats))
+                     : nonlinear_composed(u, dealias, product, stats);
   if (stats && rc == 0) nlm_valid = true;
   return rc;
 }
@@ -347,9 +352,4 @@ int mfft_plan_s::nonlinear_absmax(double out6[6]) {
   MFFT_HIP(hipMemcpyAsync(out6, nlmacc.p, 6 * sizeof(double), hipMemcpyDeviceToHost, stream));
   MFFT_HIP(hipStreamSynchronize(stream));
   return 0;
-}
-int mfft_plan_s::nonlinear_cross(const void* a, const void* b, void* out, int dealias) { return nonlinear(a, b, out, dealias, Op::Plain); }
-int mfft_plan_s::nonlinear_dot(const void* a, const void* b, void* out, int dealias) { return nonlinear(a, b, out, dealias, Op::Dot); }
-int mfft_plan_s::nonlinear_cross_dot(const void* a, const void* b, const void* c, void* out, void* outs, int dealias) {
-  return nonlinear(a, b, out, dealias, Op::CrossDot, false, c, outs);
 }

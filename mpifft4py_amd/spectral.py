@@ -66,6 +66,23 @@ def ns_rhs(FFT, K, dU, U_hat, nu):
     return dU
 
 
+def _nonlinear(FFT, name, fields, dealias):
+    """One nonlinear operation of the plan, mfft_<name>: `fields` are its (DeviceArray, is_vector) pairs in the order of the
+    call's arguments, each of shape FFT.complex_shape() -- (3,) + that for a vector field -- and of the plan's pitch."""
+    from ._base import _DEALIAS
+    assert dealias in ('3/2-rule', '2/3-rule', 'None', None)
+    cs = tuple(int(s) for s in FFT.complex_shape())
+    for x, is_vector in fields:
+        shape = (3,) + cs if is_vector else cs
+        assert x.shape == shape and x.dtype == np.dtype(FFT.complex), (x.shape, x.dtype, shape)
+        FFT._check_pitch(x, FFT.complex_pitch)
+    code = _DEALIAS[dealias]
+    FFT.comm.use_device()
+    if code == _lib.DEALIAS_2_3:
+        FFT._ensure_mask()
+    _lib.call("mfft_" + name, FFT._plan, *[x.ptr for x, _ in fields], code)
+
+
 def cross_transform(FFT, a_hat, b_hat, out_hat, dealias=None, absmax=False):
     """out_hat = fftn(ifftn(a_hat) x ifftn(b_hat)), the nonlinear term of a pseudo-spectral step as ONE operation of the
     plan (mfft_nonlinear_cross): what the reference demo composes from six `FFT.ifftn(.., dealias)`, a cross product of
@@ -74,17 +91,7 @@ def cross_transform(FFT, a_hat, b_hat, out_hat, dealias=None, absmax=False):
     and no real-space work array exists (`FFT.plan_info("nonlinear_fused_3_2")`); elsewhere the plan composes it.
     With `absmax` the call also records max |ifftn(a_hat[f])| and max |ifftn(b_hat[f])| -- velocity and vorticity -- on the
     device (mfft_nonlinear_cross_absmax); `nonlinear_absmax(FFT)` fetches them."""
-    from ._base import _DEALIAS
-    assert dealias in ('3/2-rule', '2/3-rule', 'None', None)
-    shape = (3,) + tuple(int(s) for s in FFT.complex_shape())
-    for x in (a_hat, b_hat, out_hat):
-        assert x.shape == shape and x.dtype == np.dtype(FFT.complex), (x.shape, x.dtype, shape)
-        FFT._check_pitch(x, FFT.complex_pitch)
-    code = _DEALIAS[dealias]
-    FFT.comm.use_device()
-    if code == _lib.DEALIAS_2_3:
-        FFT._ensure_mask()
-    _lib.call("mfft_nonlinear_cross_absmax" if absmax else "mfft_nonlinear_cross", FFT._plan, a_hat.ptr, b_hat.ptr, out_hat.ptr, code)
+    _nonlinear(FFT, "nonlinear_cross_absmax" if absmax else "nonlinear_cross", [(a_hat, True), (b_hat, True), (out_hat, True)], dealias)
     return out_hat
 
 
@@ -118,17 +125,7 @@ def dot_transform(FFT, a_hat, b_hat, out_hat, dealias=None, absmax=False):
     stages are one fused kernel and no real-space work array exists (`FFT.plan_info("nonlinear_dot_fused_3_2")`);
     elsewhere the plan composes it on seven work arrays of its own.  With `absmax` the call also records
     max |ifftn(a_hat[f])| and max |ifftn(b_hat[f])| (mfft_nonlinear_dot_absmax; see `nonlinear_absmax`)."""
-    from ._base import _DEALIAS
-    assert dealias in ('3/2-rule', '2/3-rule', 'None', None)
-    cs = tuple(int(s) for s in FFT.complex_shape())
-    for x, shape in ((a_hat, (3,) + cs), (b_hat, (3,) + cs), (out_hat, cs)):
-        assert x.shape == shape and x.dtype == np.dtype(FFT.complex), (x.shape, x.dtype, shape)
-        FFT._check_pitch(x, FFT.complex_pitch)
-    code = _DEALIAS[dealias]
-    FFT.comm.use_device()
-    if code == _lib.DEALIAS_2_3:
-        FFT._ensure_mask()
-    _lib.call("mfft_nonlinear_dot_absmax" if absmax else "mfft_nonlinear_dot", FFT._plan, a_hat.ptr, b_hat.ptr, out_hat.ptr, code)
+    _nonlinear(FFT, "nonlinear_dot_absmax" if absmax else "nonlinear_dot", [(a_hat, True), (b_hat, True), (out_hat, False)], dealias)
     return out_hat
 
 
@@ -142,17 +139,7 @@ def cross_dot_transform(FFT, a_hat, b_hat, c_hat, out_hat, s_hat, dealias=None):
     kernels on every axis the z stages are one fused kernel and no real-space work array exists
     (`FFT.plan_info("nonlinear_cross_dot_fused_3_2")`); elsewhere the plan composes it on twelve work arrays of its own.
     There is no `absmax` here: take the maxima of a CFL step from one `cross_transform(.., absmax=True)`."""
-    from ._base import _DEALIAS
-    assert dealias in ('3/2-rule', '2/3-rule', 'None', None)
-    cs = tuple(int(s) for s in FFT.complex_shape())
-    for x, shape in ((a_hat, (3,) + cs), (b_hat, (3,) + cs), (c_hat, (3,) + cs), (out_hat, (3,) + cs), (s_hat, cs)):
-        assert x.shape == shape and x.dtype == np.dtype(FFT.complex), (x.shape, x.dtype, shape)
-        FFT._check_pitch(x, FFT.complex_pitch)
-    code = _DEALIAS[dealias]
-    FFT.comm.use_device()
-    if code == _lib.DEALIAS_2_3:
-        FFT._ensure_mask()
-    _lib.call("mfft_nonlinear_cross_dot", FFT._plan, a_hat.ptr, b_hat.ptr, c_hat.ptr, out_hat.ptr, s_hat.ptr, code)
+    _nonlinear(FFT, "nonlinear_cross_dot", [(a_hat, True), (b_hat, True), (c_hat, True), (out_hat, True), (s_hat, False)], dealias)
     return out_hat, s_hat
 
 

@@ -4,18 +4,18 @@ composes from six FFT.ifftn, numpy products and three FFT.fftn (demo/spectral_dn
 seeded spectra, through the C ABI."""
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-from gpu_util import L, TOL, cdtype, have_gpu, orc, rdtype, run_ranks
+import nonlinear_util as nl
+from gpu_util import L, TOL, cdtype, have_gpu, orc, run_ranks
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "examples"))
-INFO = {"3/2-rule": "nonlinear_fused_3_2", "2/3-rule": "nonlinear_fused_2_3", None: "nonlinear_fused_none"}
+INFO = {d: nl.info_key("cross", d) for d in nl.RULE}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -25,31 +25,12 @@ def _need_gpu():
 
 
 def _spectra(F, N, prec, seed, hermitian):
-    """Two vector fields in spectral space: transforms of random real fields (what a solver holds), or arbitrary complex
-    numbers (the transforms' conventions for the bins a real field would not have: c2r ignores Im of kz = 0, N/2)."""
-    rng = np.random.default_rng(seed)
-    cs = tuple(F.complex_shape())
-    if hermitian:
-        a = np.stack([np.fft.rfftn(rng.random(tuple(N)) - 0.5) for _ in range(3)])
-        b = np.stack([np.fft.rfftn(rng.random(tuple(N)) - 0.5) for _ in range(3)])
-    else:
-        a = rng.random((3,) + cs) - 0.5 + 1j * (rng.random((3,) + cs) - 0.5)
-        b = rng.random((3,) + cs) - 0.5 + 1j * (rng.random((3,) + cs) - 0.5)
-    return a.astype(cdtype(prec)), b.astype(cdtype(prec))
+    return nl.spectra(tuple(F.complex_shape()), N, prec, seed, hermitian)
 
 
 def _oracle_cross(a, b, N, prec, dealias, mask=None):
     """fftn(ifftn(a) x ifftn(b)) with the oracle's one-rank transforms in the mode `dealias`."""
-    if dealias == "3/2-rule":
-        back = lambda x: orc.slab_r2c_backward_padded([x], N, prec)[0]
-        fwd = lambda x: orc.slab_r2c_forward_padded([x], N, prec)[0]
-    else:
-        back = lambda x: orc.slab_r2c_backward([x if mask is None else orc.apply_mask(x, mask)], N, prec)[0]
-        fwd = lambda x: orc.slab_r2c_forward([x], N, prec)[0]
-    ua = [np.asarray(back(a[i]), dtype=np.float64) for i in range(3)]
-    ub = [np.asarray(back(b[i]), dtype=np.float64) for i in range(3)]
-    r = np.cross(np.stack(ua), np.stack(ub), axis=0).astype(rdtype(prec))
-    return np.stack([fwd(r[i]) for i in range(3)])
+    return nl.oracle("cross", (a, b), N, prec, dealias, mask)
 
 
 @pytest.mark.parametrize("prec", ["double", "single"])
@@ -87,28 +68,7 @@ def test_nonlinear_cross_one_rank(N, fused, dealias, prec, hermitian):
 def test_nonlinear_cross_batches(batch_mb, align):
     """Several batches of x planes (the last one ragged) and both row pitches of the intermediates: a fresh process,
     the switches are read once."""
-    code = """
-import sys, numpy as np
-sys.path.insert(0, %r); sys.path.insert(0, %r)
-from gpu_util import L, orc
-from mpifft4py_amd import DeviceArray, SelfComm, Slab_R2C, spectral
-import test_gpu_nonlinear as t
-for N, dealias in (([40, 32, 64], '3/2-rule'), ([24, 64, 128], None)):
-    N = np.array(N)
-    F = Slab_R2C(N, L, SelfComm(0), 'double')
-    a, b = t._spectra(F, N, 'double', 3, True)
-    want = t._oracle_cross(a, b, N, 'double', dealias)
-    out = DeviceArray.empty(a.shape, a.dtype)
-    spectral.cross_transform(F, DeviceArray.from_numpy(a), DeviceArray.from_numpy(b), out, dealias)
-    F.sync()
-    assert F.plan_info(t.INFO[dealias]) == 1
-    e = orc.rel_l2(out.get(), want)
-    assert e < 4e-10, e
-print('ok')
-""" % (ROOT, os.path.join(ROOT, "tests"))
-    env = dict(os.environ, MFFT_NLZ_BATCH_MB=batch_mb, MFFT_NLZ_ALIGN=align)
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
+    nl.check_cases_in_child("cross", (([40, 32, 64], '3/2-rule'), ([24, 64, 128], None)), 1, 4e-10, MFFT_NLZ_BATCH_MB=batch_mb, MFFT_NLZ_ALIGN=align)
 
 
 @pytest.mark.parametrize("dealias", ["3/2-rule", "2/3-rule", None])

@@ -13,16 +13,16 @@ import sys
 import numpy as np
 import pytest
 
+import nonlinear_util as nl
 from gpu_util import L, TOL, cdtype, have_gpu, orc, rdtype, run_ranks
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "examples"))
-RULE = {"3/2-rule": "3_2", "2/3-rule": "2_3", None: "none"}
 
 
 def INFO(dealias, dot):
-    return "nonlinear_%sabsmax_fused_%s" % ("dot_" if dot else "", RULE[dealias])
+    return nl.info_key("dot" if dot else "cross", dealias, absmax=True)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -139,27 +139,16 @@ def _reference(N, prec, dealias):
     if key not in _REF:
         from mpifft4py_amd import LayoutComm
         from mpifft4py_amd.slab import R2C
-        import test_gpu_nonlinear_dot as t
         N = np.array(N)
         F = R2C(N, L, LayoutComm(1, 0), prec)
-        a, b = t._spectra(F, N, prec, 11 + int(N[2]), True)
+        a, b = nl.spectra(tuple(F.complex_shape()), N, prec, 11 + int(N[2]), True)
         mask = F.get_dealias_filter() if dealias == "2/3-rule" else None
-        if dealias == "3/2-rule":
-            back = lambda x: orc.slab_r2c_backward_padded([x], N, prec)[0]
-        else:
-            back = lambda x: orc.slab_r2c_backward([x if mask is None else orc.apply_mask(x, mask)], N, prec)[0]
-        ua = np.stack([np.asarray(back(a[i]), dtype=np.float64) for i in range(3)])
-        ub = np.stack([np.asarray(back(b[i]), dtype=np.float64) for i in range(3)])
-        _REF[key] = (a, b, ua, ub)
+        _REF[key] = (a, b, nl.oracle_back(a, N, prec, dealias, mask), nl.oracle_back(b, N, prec, dealias, mask))
     return _REF[key]
 
 
 def _oracle_out(ua, ub, N, prec, dealias, dot):
-    fwd = (lambda x: orc.slab_r2c_forward_padded([x], N, prec)[0]) if dealias == "3/2-rule" else (lambda x: orc.slab_r2c_forward([x], N, prec)[0])
-    if dot:
-        return fwd(np.sum(ua * ub, 0).astype(rdtype(prec)))
-    r = np.cross(ua, ub, axis=0).astype(rdtype(prec))
-    return np.stack([fwd(r[i]) for i in range(3)])
+    return nl.oracle_product("dot" if dot else "cross", (ua, ub), N, prec, dealias)
 
 
 def _want6(ua, ub):
@@ -243,19 +232,9 @@ def test_nonlinear_absmax_semantics():
 
 
 # ---- batches, composed route: fresh processes (the switches are read once) ------------------------------------------------
-_CHILD = """
-import sys, numpy as np
-sys.path.insert(0, %r); sys.path.insert(0, %r)
-from gpu_util import L, TOL, orc
-from mpifft4py_amd import SelfComm, Slab_R2C, spectral
-import test_gpu_nonlinear_absmax as t
-""" % (ROOT, os.path.join(ROOT, "tests"))
-
-
 def _child(code, **env):
-    r = subprocess.run([sys.executable, "-c", _CHILD + code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=280)
-    assert r.returncode == 0 and "ok" in r.stdout.splitlines()[-1:], r.stdout[-3000:] + r.stderr[-3000:]
-    return r.stdout
+    """(the cases and their checks are this module's own: the child imports it beside nonlinear_util)"""
+    return nl.run_child("import test_gpu_nonlinear_absmax as t\n" + code, timeout=280, **env)
 
 
 @pytest.mark.parametrize("align", ["0", "1"])

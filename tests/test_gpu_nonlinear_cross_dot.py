@@ -4,18 +4,18 @@ caller composes from nine FFT.ifftn, np.cross, np.sum(ua * uc, 0) and four FFT.f
 ABI; against cross_transform + dot_transform of the same plan over several ranks and at 512^3; its z stage on its own against
 numpy; and the Boussinesq example, one operation per stage against two calls."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-from gpu_util import L, TOL, cdtype, have_gpu, orc, rdtype, run_ranks
+import nonlinear_util as nl
+from gpu_util import L, TOL, cdtype, have_gpu, orc, run_ranks
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "examples"))
-INFO = {"3/2-rule": "nonlinear_cross_dot_fused_3_2", "2/3-rule": "nonlinear_cross_dot_fused_2_3", None: "nonlinear_cross_dot_fused_none"}
+INFO = {d: nl.info_key("cross_dot", d) for d in nl.RULE}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -25,28 +25,12 @@ def _need_gpu():
 
 
 def _spectra(cs, N, prec, seed, hermitian):
-    """Three vector fields in spectral space: transforms of random real fields (what a solver holds), or arbitrary complex
-    numbers (the transforms' conventions for the bins a real field would not have: c2r ignores Im of kz = 0, N/2)."""
-    rng = np.random.default_rng(seed)
-    if hermitian:
-        f = [np.stack([np.fft.rfftn(rng.random(tuple(N)) - 0.5) for _ in range(3)]) for _ in range(3)]
-    else:
-        f = [rng.random((3,) + cs) - 0.5 + 1j * (rng.random((3,) + cs) - 0.5) for _ in range(3)]
-    return tuple(x.astype(cdtype(prec)) for x in f)
+    return nl.spectra(cs, N, prec, seed, hermitian, 3)
 
 
 def _oracle(a, b, c, N, prec, dealias, mask=None):
     """(fftn(ifftn(a) x ifftn(b)), fftn(sum_f ifftn(a_f) ifftn(c_f))) with the oracle's one-rank transforms in the mode `dealias`."""
-    if dealias == "3/2-rule":
-        back = lambda x: orc.slab_r2c_backward_padded([x], N, prec)[0]
-        fwd = lambda x: orc.slab_r2c_forward_padded([x], N, prec)[0]
-    else:
-        back = lambda x: orc.slab_r2c_backward([x if mask is None else orc.apply_mask(x, mask)], N, prec)[0]
-        fwd = lambda x: orc.slab_r2c_forward([x], N, prec)[0]
-    ua, ub, uc = (np.stack([np.asarray(back(x[i]), dtype=np.float64) for i in range(3)]) for x in (a, b, c))
-    r = np.cross(ua, ub, axis=0).astype(rdtype(prec))
-    s = np.sum(ua * uc, 0).astype(rdtype(prec))
-    return np.stack([fwd(r[i]) for i in range(3)]), fwd(s)
+    return nl.oracle("cross_dot", (a, b, c), N, prec, dealias, mask)
 
 
 def _nlz_lengths():
@@ -126,43 +110,18 @@ def test_nonlinear_cross_dot_pitched_plan():
         _one_rank([32, 64, 128], True, dealias, "double", True, complex_pitch="auto")
 
 
-_CHILD = """
-import sys, numpy as np
-sys.path.insert(0, %r); sys.path.insert(0, %r)
-from gpu_util import L, TOL, orc
-from mpifft4py_amd import SelfComm, Slab_R2C, spectral
-import test_gpu_nonlinear_cross_dot as t
-for N, dealias in %s:
-    N = np.array(N)
-    F = Slab_R2C(N, L, SelfComm(0), 'double')
-    a, b, c, want, swant = t._reference(F, N, 'double', dealias, True, 3)
-    out, s = F.empty_complex(3), F.empty_complex()
-    spectral.cross_dot_transform(F, F.empty_complex(3).set(a), F.empty_complex(3).set(b), F.empty_complex(3).set(c), out, s, dealias)
-    F.sync()
-    assert F.plan_info(t.INFO[dealias]) == %d
-    e, es = orc.rel_l2(out.get(), want), orc.rel_l2(s.get(), swant)
-    print(list(N), dealias, e, es)
-    assert e < 4 * TOL['double'] and es < 4 * TOL['double'], (e, es)
-print('ok')
-"""
-
-
 @pytest.mark.parametrize("batch_mb,align", [("1", "0"), ("1", "1"), ("3", "-1")])
 def test_nonlinear_cross_dot_batches(batch_mb, align):
     """Several batches of x planes and both row pitches of the intermediates: a fresh process, the switches are read once.
     (Nine fields of [24, 64, 128] are 14.4 MB: twelve batches of two planes at 1 MB, five of five planes at 3 MB -- the last one
     ragged, four planes.)"""
-    code = _CHILD % (ROOT, os.path.join(ROOT, "tests"), "(([40, 32, 64], '3/2-rule'), ([24, 64, 128], None))", 1)
-    env = dict(os.environ, MFFT_NLZ_BATCH_MB=batch_mb, MFFT_NLZ_ALIGN=align)
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
+    nl.check_cases_in_child("cross_dot", (([40, 32, 64], '3/2-rule'), ([24, 64, 128], None)), 1, 4 * TOL["double"],
+                            MFFT_NLZ_BATCH_MB=batch_mb, MFFT_NLZ_ALIGN=align)
 
 
 def test_nonlinear_cross_dot_kill_switch():
     """MFFT_NO_NLZ=1 (read once per process: a fresh one): the same call, the plan's composition, the same answer."""
-    code = _CHILD % (ROOT, os.path.join(ROOT, "tests"), "(([32, 64, 128], '3/2-rule'), ([32, 64, 128], '2/3-rule'), ([32, 64, 128], None))", 0)
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, MFFT_NO_NLZ="1"), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
+    nl.check_cases_in_child("cross_dot", [([32, 64, 128], d) for d in ('3/2-rule', '2/3-rule', None)], 0, 4 * TOL["double"], MFFT_NO_NLZ="1")
 
 
 _RANKS_REF = {}
@@ -239,6 +198,19 @@ def test_nonlinear_cross_dot_ranks(decomp, P, dealias):
 
     errs = run_ranks(P, work)
     assert max(errs) < 1e-13, errs
+
+
+def test_plan_info_fused_keys():
+    """The smallest mesh the fused route takes: every "nonlinear[_dot|_cross_dot][_absmax]_fused_<mode>" key the plan has -- three
+    products and the two with maxima, three modes each, fifteen -- answers 0 or 1; both products with maxima is no key."""
+    from mpifft4py_amd import SelfComm, Slab_R2C, _lib
+    F = Slab_R2C(np.array([8, 16, 32]), L, SelfComm(0), "double")
+    keys = nl.fused_keys()
+    assert len(set(keys)) == 15, keys
+    for key in keys:
+        assert F.plan_info(key) in (0, 1), key
+    with pytest.raises(_lib.MfftError):
+        F.plan_info("nonlinear_cross_dot_absmax_fused_none")
 
 
 # ---- stage level ----------------------------------------------------------------------------------------------------

@@ -4,18 +4,18 @@ np.sum(ua * ub, 0) and one FFT.fftn -- on the same seeded spectra, through the C
 and the passive-scalar example against the exact RK4 answer of a uniform velocity."""
 import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import nonlinear_util as nl
 from gpu_util import L, TOL, cdtype, have_gpu, orc, rdtype, run_ranks
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "examples"))
-INFO = {"3/2-rule": "nonlinear_dot_fused_3_2", "2/3-rule": "nonlinear_dot_fused_2_3", None: "nonlinear_dot_fused_none"}
+INFO = {d: nl.info_key("dot", d) for d in nl.RULE}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -25,31 +25,12 @@ def _need_gpu():
 
 
 def _spectra(F, N, prec, seed, hermitian):
-    """Two vector fields in spectral space: transforms of random real fields (what a solver holds), or arbitrary complex
-    numbers (the transforms' conventions for the bins a real field would not have: c2r ignores Im of kz = 0, N/2)."""
-    rng = np.random.default_rng(seed)
-    cs = tuple(F.complex_shape())
-    if hermitian:
-        a = np.stack([np.fft.rfftn(rng.random(tuple(N)) - 0.5) for _ in range(3)])
-        b = np.stack([np.fft.rfftn(rng.random(tuple(N)) - 0.5) for _ in range(3)])
-    else:
-        a = rng.random((3,) + cs) - 0.5 + 1j * (rng.random((3,) + cs) - 0.5)
-        b = rng.random((3,) + cs) - 0.5 + 1j * (rng.random((3,) + cs) - 0.5)
-    return a.astype(cdtype(prec)), b.astype(cdtype(prec))
+    return nl.spectra(tuple(F.complex_shape()), N, prec, seed, hermitian)
 
 
 def _oracle_dot(a, b, N, prec, dealias, mask=None):
     """fftn(sum_f ifftn(a_f) ifftn(b_f)) with the oracle's one-rank transforms in the mode `dealias`."""
-    if dealias == "3/2-rule":
-        back = lambda x: orc.slab_r2c_backward_padded([x], N, prec)[0]
-        fwd = lambda x: orc.slab_r2c_forward_padded([x], N, prec)[0]
-    else:
-        back = lambda x: orc.slab_r2c_backward([x if mask is None else orc.apply_mask(x, mask)], N, prec)[0]
-        fwd = lambda x: orc.slab_r2c_forward([x], N, prec)[0]
-    ua = [np.asarray(back(a[i]), dtype=np.float64) for i in range(3)]
-    ub = [np.asarray(back(b[i]), dtype=np.float64) for i in range(3)]
-    r = np.sum(np.stack(ua) * np.stack(ub), 0).astype(rdtype(prec))
-    return fwd(r)
+    return nl.oracle("dot", (a, b), N, prec, dealias, mask)
 
 
 def _one_rank(N, fused, dealias, prec, hermitian, complex_pitch=None):
@@ -106,53 +87,12 @@ def test_nonlinear_dot_pitched_plan():
 def test_nonlinear_dot_batches(batch_mb, align):
     """Several batches of x planes (the last one ragged) and both row pitches of the intermediates: a fresh process,
     the switches are read once."""
-    code = """
-import sys, numpy as np
-sys.path.insert(0, %r); sys.path.insert(0, %r)
-from gpu_util import L, orc
-from mpifft4py_amd import DeviceArray, SelfComm, Slab_R2C, spectral
-import test_gpu_nonlinear_dot as t
-for N, dealias in (([40, 32, 64], '3/2-rule'), ([24, 64, 128], None)):
-    N = np.array(N)
-    F = Slab_R2C(N, L, SelfComm(0), 'double')
-    a, b = t._spectra(F, N, 'double', 3, True)
-    want = t._oracle_dot(a, b, N, 'double', dealias)
-    out = DeviceArray.empty(want.shape, a.dtype)
-    spectral.dot_transform(F, DeviceArray.from_numpy(a), DeviceArray.from_numpy(b), out, dealias)
-    F.sync()
-    assert F.plan_info(t.INFO[dealias]) == 1
-    e = orc.rel_l2(out.get(), want)
-    assert e < 4e-10, e
-print('ok')
-""" % (ROOT, os.path.join(ROOT, "tests"))
-    env = dict(os.environ, MFFT_NLZ_BATCH_MB=batch_mb, MFFT_NLZ_ALIGN=align)
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
+    nl.check_cases_in_child("dot", (([40, 32, 64], '3/2-rule'), ([24, 64, 128], None)), 1, 4e-10, MFFT_NLZ_BATCH_MB=batch_mb, MFFT_NLZ_ALIGN=align)
 
 
 def test_nonlinear_dot_kill_switch():
     """MFFT_NO_NLZ=1 (read once per process: a fresh one): the same call, the plan's composition, the same answer."""
-    code = """
-import sys, numpy as np
-sys.path.insert(0, %r); sys.path.insert(0, %r)
-from gpu_util import L, orc
-from mpifft4py_amd import DeviceArray, SelfComm, Slab_R2C, spectral
-import test_gpu_nonlinear_dot as t
-for dealias in ('3/2-rule', '2/3-rule', None):
-    N = np.array([32, 64, 128])
-    F = Slab_R2C(N, L, SelfComm(0), 'double')
-    a, b = t._spectra(F, N, 'double', 3, True)
-    want = t._oracle_dot(a, b, N, 'double', dealias, F.get_dealias_filter() if dealias == '2/3-rule' else None)
-    out = DeviceArray.empty(want.shape, a.dtype)
-    spectral.dot_transform(F, DeviceArray.from_numpy(a), DeviceArray.from_numpy(b), out, dealias)
-    F.sync()
-    assert F.plan_info(t.INFO[dealias]) == 0
-    e = orc.rel_l2(out.get(), want)
-    assert e < 4e-10, e
-print('ok')
-""" % (ROOT, os.path.join(ROOT, "tests"))
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, MFFT_NO_NLZ="1"), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
+    nl.check_cases_in_child("dot", [([32, 64, 128], d) for d in ('3/2-rule', '2/3-rule', None)], 0, 4e-10, MFFT_NO_NLZ="1")
 
 
 @pytest.mark.parametrize("dealias", ["3/2-rule", None])
