@@ -29,7 +29,8 @@ def _zero(a):
 
 
 def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double", nu=0.000625, dt=0.01, steps=10,
-          report=None, fused=True, timing=False, complex_pitch="default", edge=None, spectrum=False, cfl=None, dt_max=None):
+          report=None, fused=True, timing=False, complex_pitch="default", edge=None, spectrum=False, cfl=None, dt_max=None,
+          stats=False):
     """fused=True (round 6): the nonlinear term is ONE plan operation (spectral.cross_transform: no real-space work
     arrays, the z stages one kernel) and a Runge-Kutta stage's projection, viscous term, both updates and the next
     curl are ONE sweep (spectral.ns_rk_stage).  fused=False: the composition of rounds 3 - 5 (nine transforms, cross,
@@ -39,7 +40,10 @@ def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double
     cfl=C (fused loop): an advective time step.  The first Runge-Kutta stage of a step runs with absmax=True, so the
     fused z kernel also leaves max |u_f| and max |omega_f| on the device; dt = min(dt_max, C / sum_f max|u_f| N_f / L_f)
     is fetched right after it -- ONE synchronisation of the plan's stream per step -- and the step's four stages use
-    it.  report["dt"] lists the steps' dt, report["wmax"] their max |omega|; rank 0 prints both."""
+    it.  report["dt"] lists the steps' dt, report["wmax"] their max |omega|; rank 0 prints both.
+    stats=True (fused loop): report["stats"] holds the one-point statistics of the final state -- spectral.Moments of the three
+    longitudinal derivatives du_f/dx_f ("grad"), and of u and omega together ("u_omega": six fields) -- from
+    spectral.real_moments: the fields exist as spectra only, no real array is written for them."""
     if complex_pitch == "default":       # the fused loop on ONE rank keeps its spectra pitched (rows a whole number of cache lines
         # apart: every pass runs on them); several ranks and the composition of rounds 3 - 5 keep compact rows
         complex_pitch = "auto" if (fused and comm.Get_size() == 1) else None
@@ -47,6 +51,8 @@ def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double
     L = np.array([2 * np.pi] * 3, dtype=float)
     if cfl is not None and not fused:
         raise ValueError("cfl needs the fused loop: the composition has no statistics call")
+    if stats and not fused:
+        raise ValueError("stats needs the fused loop: the composition holds no curl of the final state")
     if decomposition == 'slab':
         FFT = Slab_R2C(N, L, comm, precision, complex_pitch=complex_pitch)
     else:
@@ -104,7 +110,7 @@ def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double
         FFT.sync()
         wall = time.perf_counter() - t0
         if report is not None:
-            report["ms_per_step"] = 1e3 * wall / steps
+            report["ms_per_step"] = 1e3 * wall / max(steps, 1)
             report["fused_nonlinear"] = FFT.plan_info({"3/2-rule": "nonlinear_fused_3_2", "2/3-rule": "nonlinear_fused_2_3"}.get(
                 dealias, "nonlinear_fused_none"))
             report["work_bytes"] = FFT.plan_info("nonlinear_bytes") + FFT.workspace_bytes()
@@ -114,6 +120,11 @@ def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double
             E = spectral.energy_spectrum(FFT, K, U_hat)         # (collective: every rank calls it)
             if report is not None:
                 report["spectrum"] = E
+        if stats:                                               # (collective too; dU holds the curl of the final state)
+            uw = spectral.real_moments(FFT, U_hat, dU, dealias)
+            grad = spectral.real_moments(FFT, spectral.diag_grad_hat(FFT, K, U_hat, FFT.empty_complex(3)), None, dealias)
+            if report is not None:
+                report["stats"] = {"u_omega": uw, "grad": grad}
         for i in range(3):
             FFT.ifftn(U_hat.component(i), U.component(i))
         return FFT.comm.reduce(spectral.sumsq(FFT, U) / float(N[0]) / float(N[1]) / float(N[2]) / 2)
@@ -183,6 +194,8 @@ def main():
     ap.add_argument("--cfl", type=float, default=None, help="advective time step dt = CFL / sum_f max|u_f| N_f / L_f from the fused nonlinear term's "
                     "real-space maxima (one stream synchronisation per step) instead of the fixed dt = 0.01; prints dt and max|omega| per step")
     ap.add_argument("--dt-max", type=float, default=None, help="with --cfl: dt = min(DT_MAX, advective dt)")
+    ap.add_argument("--stats", action="store_true", help="print skewness and flatness of du_f/dx_f and of u_f and min / max of omega_f of the final "
+                    "state, from the spectra (spectral.real_moments: no real-space array)")
     args = ap.parse_args()
     dealias = None if args.dealias == "None" else args.dealias
     from mpifft4py_amd import LocalGroup, SelfComm
@@ -191,11 +204,11 @@ def main():
         ks = LocalGroup(args.ranks).run(lambda c: solve(c, args.M, dealias, steps=args.steps, precision=args.precision,
                                                         report=rep if c.Get_rank() == 0 else None, fused=not args.composed,
                                                         timing=args.stages, complex_pitch=None if args.compact else "default",
-                                                        edge=args.N or None, spectrum=args.spectrum, cfl=args.cfl, dt_max=args.dt_max))
+                                                        edge=args.N or None, spectrum=args.spectrum, cfl=args.cfl, dt_max=args.dt_max, stats=args.stats))
     else:
         ks = [solve(SelfComm(), args.M, dealias, steps=args.steps, precision=args.precision, report=rep,
                     fused=not args.composed, timing=args.stages, complex_pitch=None if args.compact else "default",
-                    edge=args.N or None, spectrum=args.spectrum, cfl=args.cfl, dt_max=args.dt_max)]
+                    edge=args.N or None, spectrum=args.spectrum, cfl=args.cfl, dt_max=args.dt_max, stats=args.stats)]
     print("N = %d^3, %d RK4 steps, %.3f ms per step (%s, device-resident; plan work buffers %.2f GB)"
           % (args.N or 2 ** args.M, args.steps, rep.get("ms_per_step", float("nan")),
              "composed: 36 transforms + element-wise kernels" if args.composed else
@@ -213,6 +226,12 @@ def main():
         if args.precision == "double":
             assert abs(E.sum() - ks[0]) <= 1e-12 * ks[0], (E.sum(), ks[0])
             print("sum of E(k) equals k to 1e-12")
+    if args.stats:
+        fmt = lambda v: "[" + " ".join("%.9f" % float(x) for x in v) + "]"
+        uw, grad = rep["stats"]["u_omega"], rep["stats"]["grad"]
+        print("du_f/dx_f: skewness = %s  flatness = %s" % (fmt(grad.skewness()), fmt(grad.flatness())))
+        print("u: skewness = %s  flatness = %s" % (fmt(uw.skewness()[:3]), fmt(uw.flatness()[:3])))
+        print("omega: min = %s  max = %s" % (fmt(uw.min[3:]), fmt(uw.max[3:])))
     if args.M == 5 and not args.N and args.steps == 10 and args.precision == "double" and args.cfl is None:
         assert round(ks[0] - 0.124953117517, 7) == 0
         print("matches the reference demo's known answer 0.124953117517")

@@ -256,6 +256,18 @@ MFFT_API int mfft_nlz_cross_dot_rows(const void* a, const void* b, const void* c
  * mfft_nonlinear_dot_absmax on its own, for tests. */
 MFFT_API int mfft_nlz_rows_absmax(const void* a, const void* b, void* out, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
                                   int precision, int dot, double out6[6]);
+/* The z stage that ends in a reduction (csrc/fft_nlz.h body_moments), synchronous: the one-point statistics of the real rows
+ * irfft(row, n) without the real rows.  nfields = 1: a is (nrows, pitch) complex; 2: a and b are; 3: a is (3, nrows, pitch), b
+ * NULL; 6: a and b are.  `valid` bins per row exist, the first valid_in of them are read (0: all).  Per field, over all rows and
+ * all n points (numpy's normalisation):  out[f * 6 + 0] = min, [1] = max, [2 + p - 1] = sum (x - center[f])^p, p = 1..4 (center
+ * NULL: zeros); fields in the order a_0.., then b_0...  Powers and sums in double in both precisions.  A NaN or Inf bin of a field
+ * gives NaN sums and NaN / +-Inf extremes for THAT field; the others stay right.  Bitwise reproducible run to run on one device.
+ * MFFT_ERR_UNSUPPORTED for lengths without a kernel, MFFT_ERR_INVALID for valid > n / 2 + 1.  The z stage of mfft_real_moments on
+ * its own, for tests.
+ * mfft_nlz_moments_groups: the workgroups of that launch (it strides over the rows; 0: no kernel of that length). */
+MFFT_API int mfft_nlz_moments_rows(const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
+                                   int64_t valid_in, int precision, const double* center, double* out);
+MFFT_API int64_t mfft_nlz_moments_groups(int64_t nrows, int64_t n, int precision);
 /* slab pack / unpack (slab.py:403; cython/maths.pyx:21-31 transpose_Uc) */
 MFFT_API int mfft_slab_pack(const void* uc_hatT, void* u_mpi, int P, int64_t np0, int64_t np1, int64_t nf, int precision);
 MFFT_API int mfft_slab_unpack(const void* u_mpi, void* uc_hatT, int P, int64_t np0, int64_t np1, int64_t nf, int precision);
@@ -296,6 +308,11 @@ MFFT_API int mfft_ew_dot(mfft_plan_t plan, const void* a, const void* b, void* o
  * 1j * K * s_hat. */
 MFFT_API int mfft_ew_grad_hat(mfft_plan_t plan, const void* s_hat, void* out, const void* kx, const void* ky, const void* kz,
                               const int64_t shape[3], int precision);
+/* out_f = i K_f U_hat_f, the three LONGITUDINAL derivatives du_f / dx_f of a vector field in spectral space (the field whose
+ * skewness a DNS is judged by): U_hat and out are (3,) + shape; the rest as mfft_ew_grad_hat.  What a caller writes as
+ * 1j * K * U_hat. */
+MFFT_API int mfft_ew_diag_grad_hat(mfft_plan_t plan, const void* U_hat, void* out, const void* kx, const void* ky, const void* kz,
+                                   const int64_t shape[3], int precision);
 MFFT_API int mfft_ew_ns_rhs(mfft_plan_t plan, void* dU, const void* U_hat, const void* kx, const void* ky, const void* kz,
                             const int64_t shape[3], double nu, int precision);                          /* demo:73-77 */
 MFFT_API int mfft_ew_axpbz(mfft_plan_t plan, void* y, const void* x, const void* z, double alpha, double beta, size_t n_real,
@@ -314,6 +331,26 @@ MFFT_API int mfft_ew_sumsq(mfft_plan_t plan, const void* x, size_t n_real, int p
  * One sweep, 16 bytes per lane, no atomics; a NaN in a component gives NaN for it; bitwise reproducible.  The plan must not be
  * null (partial maxima live in a buffer of the plan); synchronises the plan's stream. */
 MFFT_API int mfft_ew_absmax(mfft_plan_t plan, const void* x, int ncomp, size_t n, int precision, double* out_host);
+
+/* out_host[c * 6 + {0: min, 1: max, 2..5: S1..S4}] of a real device array (ncomp, n), ncomp = 1, 2, 3 or 6, in the plan's
+ * precision; S_p = sum (x[c, :] - center[c])^p, center NULL: zeros.  The companion of mfft_ew_absmax / mfft_ew_sumsq: one
+ * sweep, 16 bytes per lane, powers and sums in double, no atomics, bitwise reproducible; a NaN in a component gives NaN in all six
+ * of its statistics.  The plan must not be null; synchronises the plan's stream. */
+MFFT_API int mfft_ew_moments(mfft_plan_t plan, const void* x, int ncomp, size_t n, int precision, const double* center, double* out_host);
+
+/* One-point statistics of fields that exist as spectra only: for the ncomp (1 or 3) components of a_hat and, where b_hat is not
+ * NULL, of b_hat -- 1, 2, 3 or 6 fields, in that order --
+ *     out[f * 6 + 0] = min x,  [1] = max x,  [2 + p - 1] = sum (x - center[f])^p, p = 1..4,     x = ifftn(field f, dealias)
+ * over THIS RANK's part of the real-space grid (the padded grid under the 3/2-rule, the masked field under the 2/3-rule, as
+ * mfft_nonlinear_cross_absmax), *count = the points summed.  center NULL: zeros; a centre near the mean keeps the digits of the
+ * central moments (about 0 they cancel as (mean / sigma)^p).  The routes are those of mfft_nonlinear_cross (mfft_plan_get_info
+ * "nonlinear_moments_fused_3_2" / "_none" / "_2_3"): on slab R2C plans with radix kernels on every axis the inverse x and y passes
+ * and ONE z kernel per batch of x planes that ends in a reduction (csrc/fft_nlz.h body_moments) -- no real-space array exists;
+ * every other plan transforms one field at a time into ONE real work array and sweeps it (mfft_ew_moments).  Powers and sums in
+ * double in both precisions, no atomics: bitwise reproducible run to run on one plan and device.  A NaN or Inf bin gives NaN sums
+ * and NaN / +-Inf extremes for its field.  The inputs are preserved.  Synchronises the plan's stream. */
+MFFT_API int mfft_real_moments(mfft_plan_t plan, const void* a_hat, const void* b_hat, int ncomp, int dealias, const double* center,
+                               double* out, int64_t* count);
 
 /* The nonlinear term of a pseudo-spectral step as ONE operation:
  *     out_hat = fftn(ifftn(a_hat) x ifftn(b_hat))        (cross product in real space, component by component)

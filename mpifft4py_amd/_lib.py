@@ -93,6 +93,9 @@ _SIGNATURES = {
     "mfft_nlz_dot_rows": ([c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int], c_int),
     "mfft_nlz_cross_dot_rows": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int], c_int),
     "mfft_nlz_rows_absmax": ([c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, POINTER(c_double)], c_int),
+    "mfft_nlz_moments_rows": ([c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, POINTER(c_double),
+                               POINTER(c_double)], c_int),
+    "mfft_nlz_moments_groups": ([c_int64, c_int64, c_int], c_int64),
     "mfft_slab_pack": ([c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int], c_int),
     "mfft_slab_unpack": ([c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int], c_int),
     "mfft_dealias_filter": ([c_void_p, c_void_p, c_size_t, c_int], c_int),
@@ -110,12 +113,15 @@ _SIGNATURES = {
     "mfft_ew_curl_hat": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_int], c_int),
     "mfft_ew_dot": ([c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int], c_int),
     "mfft_ew_grad_hat": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_int], c_int),
+    "mfft_ew_diag_grad_hat": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_int], c_int),
     "mfft_ew_ns_rhs": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_double, c_int], c_int),
     "mfft_ew_axpbz": ([c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_size_t, c_int], c_int),
     "mfft_ew_ns_rk_stage": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int64),
                              c_double, c_double, c_double, c_int, c_int], c_int),
     "mfft_ew_sumsq": ([c_void_p, c_void_p, c_size_t, c_int, POINTER(c_double)], c_int),
     "mfft_ew_absmax": ([c_void_p, c_void_p, c_int, c_size_t, c_int, POINTER(c_double)], c_int),
+    "mfft_ew_moments": ([c_void_p, c_void_p, c_int, c_size_t, c_int, POINTER(c_double), POINTER(c_double)], c_int),
+    "mfft_real_moments": ([c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_double), POINTER(c_double), POINTER(c_int64)], c_int),
     "mfft_ew_dft_bins": ([c_void_p, c_void_p, c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), c_int, c_int,
                           POINTER(c_int64), c_int, POINTER(c_double)], c_int),
     "mfft_ew_shell_sums": ([c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -127,7 +133,8 @@ _SIGNATURES = {
 }
 
 # functions whose int result is a count, not a status
-_COUNT_RESULT = {"mfft_version", "mfft_length_supported", "mfft_length_route", "mfft_length_route_precision", "mfft_plan_timing_get"}
+_COUNT_RESULT = {"mfft_version", "mfft_length_supported", "mfft_length_route", "mfft_length_route_precision", "mfft_plan_timing_get",
+                 "mfft_nlz_moments_groups"}
 
 _lib = None
 

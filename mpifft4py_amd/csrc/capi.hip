@@ -323,6 +323,59 @@ int mfft_nlz_rows_absmax(const void* a, const void* b, void* out, int64_t nrows,
   return rc;
 }
 
+// The stage that ends in a reduction (fft_nlz.h body_moments), synchronous.  nfields = 1: a is (nrows, pitch); 2: a and b are;
+// 3: a is (3, nrows, pitch); 6: a and b are.  `valid` bins per row exist, the first valid_in of them are read (0: all of them).
+// out[f * 6 + {0: min, 1: max, 2..5: S1..S4}] of irfft(row, n) over all rows, fields in the order a_0.., then b_0..;
+// S_p = sum (x - center[f])^p (center null: zeros).
+int mfft_nlz_moments_rows(const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
+                          int64_t valid_in, int precision, const double* center, double* out) {
+  if (!a || !out || nrows < 1 || n < 2 || n >= 65536 || pitch < valid || valid < 1 || valid > n / 2 + 1 || valid_in < 0 || valid_in > valid)
+    return set_error(MFFT_ERR_INVALID, "bad argument");
+  if (precision != MFFT_DOUBLE && precision != MFFT_SINGLE) return set_error(MFFT_ERR_INVALID, "unknown precision %d", precision);
+  if ((nfields != 1 && nfields != 2 && nfields != 3 && nfields != 6) || ((nfields % 2 == 0) != (b != nullptr)))
+    return set_error(MFFT_ERR_INVALID, "nfields must be 1 or 3 (a alone) or 2 or 6 (a and b), not %d", nfields);
+  const size_t es = elem_bytes(precision, true);
+  const int ncomp = b ? nfields / 2 : nfields;
+  NlsArgs z;
+  int slot_of[6] = {0, 0, 0, 0, 0, 0};
+  for (int f = 0; f < nfields; ++f) {
+    const int slot = b ? (f < ncomp ? 2 * f : 2 * (f - ncomp) + 1) : f;
+    const char* base = static_cast<const char*>(f < ncomp ? a : b) + (size_t)((f % ncomp) * nrows * pitch) * es;
+    (slot % 2 ? z.b : z.a)[slot / 2] = base;
+    z.center[slot] = center ? center[f] : 0.0;
+    slot_of[f] = slot;
+  }
+  z.npairs = (nfields + 1) / 2;
+  z.n = (int)n; z.prec = precision; z.in_stride = pitch; z.nrows = nrows; z.valid = (int)valid; z.valid_in = (int)valid_in;
+  z.norm = 1.0 / (double)n;
+  int ngroups = 0;
+  int64_t waves = 0;
+  MFFT_TRY(nls_launch_shape(n, precision, nrows, &ngroups, &waves));
+  z.ngroups = ngroups;
+  char* buf = nullptr;
+  MFFT_HIP(hipMalloc(reinterpret_cast<void**>(&buf), (size_t)(waves + 1) * NLS_SLOTS * sizeof(double)));
+  double* acc = reinterpret_cast<double*>(buf);
+  z.part = acc + NLS_SLOTS;
+  int rc = moments_clear(acc, NLS_SLOTS, nullptr);
+  if (!rc) rc = launch_nls(z, nullptr);
+  if (!rc) rc = moments_fold(static_cast<const double*>(z.part), (size_t)waves, NLS_SLOTS, acc, nullptr);
+  double host[NLS_SLOTS];
+  if (!rc && hipMemcpy(host, acc, sizeof host, hipMemcpyDeviceToHost) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemcpy failed");
+  if (hipStreamSynchronize(nullptr) != hipSuccess && !rc) rc = set_error(MFFT_ERR_HIP, "hipStreamSynchronize failed");
+  (void)hipFree(buf);
+  if (!rc)
+    for (int f = 0; f < nfields; ++f)
+      for (int k = 0; k < NLS_STATS; ++k) out[f * NLS_STATS + k] = host[slot_of[f] * NLS_STATS + k];
+  return rc;
+}
+// workgroups of that launch: a caller that wants more rows than one pass of the grid asks here (0: no kernel of that length)
+int64_t mfft_nlz_moments_groups(int64_t nrows, int64_t n, int precision) {
+  int ngroups = 0;
+  int64_t waves = 0;
+  if (nls_launch_shape(n, precision, nrows, &ngroups, &waves) != 0) return 0;
+  return ngroups;
+}
+
 // U_mpi[p, i, j, k] = Uc_hatT[i, p*Np1 + j, k]   (slab.py:403)
 int mfft_slab_pack(const void* uc_hatT, void* u_mpi, int P, int64_t np0, int64_t np1, int64_t nf, int precision) {
   if (!uc_hatT || !u_mpi || P < 1) return set_error(MFFT_ERR_INVALID, "bad argument");

@@ -595,6 +595,79 @@ int launch_nlz(const NlzArgs& a, hipStream_t s) {
   });
 }
 
+// The stage that ends in a reduction (fft_nlz.h body_moments, Op::Moments).  Its grid does not follow the rows: the workgroups
+// that are resident at once, CUs x min(what the runtime says fits, NLS_WG_PER_CU), asked once per device and kernel, and never
+// more than there are pairs of rows to start on.
+constexpr int NLS_WG_PER_CU = 4;
+static int nls_resident(const KernelEntry* e, int* cap) {
+  struct Key { int dev; const void* fn; int cap; };
+  static std::mutex mu;
+  static std::vector<Key> known;
+  int dev = 0;
+  MFFT_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(mu);
+  for (const Key& k : known)
+    if (k.dev == dev && k.fn == e->func) { *cap = k.cap; return 0; }
+  int ncu = 0, occ = 0;
+  MFFT_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+  MFFT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, e->func, e->threads, (size_t)e->lds_bytes));
+  if (occ < 1 || ncu < 1) return set_error(MFFT_ERR_INTERNAL, "%s: no resident workgroup (%d CUs, %d per CU)", e->name, ncu, occ);
+  *cap = ncu * (occ < NLS_WG_PER_CU ? occ : NLS_WG_PER_CU);
+  known.push_back(Key{dev, e->func, *cap});
+  return 0;
+}
+// workgroups and waves (= groups of NLS_SLOTS doubles written to NlsArgs::part) of the launch over nrows rows
+int nls_launch_shape(int64_t n, int prec, int64_t nrows, int* ngroups, int64_t* waves) {
+  const KernelEntry* e = find_nlz(n, prec, Op::Moments);
+  if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused z-stage kernel with moments of length %lld", (long long)n);
+  if (nrows < 1) return set_error(MFFT_ERR_INVALID, "no rows");
+  void* tw = nullptr;
+  MFFT_TRY(prepare_kernel(e, &tw));                // (the LDS attribute is set before the occupancy is asked for)
+  int cap = 0;
+  MFFT_TRY(nls_resident(e, &cap));
+  const int64_t units = (nrows + 2 * e->tile - 1) / (2 * e->tile);
+  *ngroups = (int)std::min<int64_t>(units, cap);
+  *waves = (int64_t)*ngroups * ((e->threads + 63) / 64);
+  return 0;
+}
+template <typename T>
+static int launch_nls_t(const KernelEntry* e, const NlsArgs& a, int ngroups, void* tw, hipStream_t s) {
+  NlsParams<T> P;
+  for (int f = 0; f < 3; ++f) {
+    P.a[f] = static_cast<const cx<T>*>(f < a.npairs ? a.a[f] : nullptr);
+    P.b[f] = static_cast<const cx<T>*>(f < a.npairs ? a.b[f] : nullptr);
+    P.out[f] = nullptr;
+  }
+  P.tw = static_cast<const cx<T>*>(tw);
+  P.rt3 = nullptr;
+  P.in_stride = a.in_stride;
+  P.out_stride = 0;
+  P.nrows = a.nrows;
+  P.valid = a.valid > 0 && a.valid < a.n / 2 + 1 ? a.valid : a.n / 2 + 1;
+  P.valid_in = a.valid_in > 0 && a.valid_in < P.valid ? a.valid_in : P.valid;
+  P.scale = (T)1;
+  P.part = static_cast<double*>(a.part);
+  for (int i = 0; i < 2 * NLS_PAIRS; ++i) P.center[i] = a.center[i];
+  P.norm = a.norm;
+  P.npairs = a.npairs;
+  P.ngroups = ngroups;
+  e->launch(&P, ngroups, s);
+  MFFT_HIP(hipGetLastError());
+  return 0;
+}
+int launch_nls(const NlsArgs& a, hipStream_t s) {
+  const KernelEntry* e = find_nlz(a.n, a.prec, Op::Moments);
+  if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused z-stage kernel with moments of length %d", a.n);
+  const int64_t units = (a.nrows + 2 * e->tile - 1) / (2 * e->tile);
+  if (a.npairs < 1 || a.npairs > NLS_PAIRS || !a.part || a.nrows < 1 || a.ngroups < 1 || a.ngroups > units)
+    return set_error(MFFT_ERR_INVALID, "bad argument");
+  for (int p = 0; p < a.npairs; ++p)
+    if (!a.a[p]) return set_error(MFFT_ERR_INVALID, "null argument");
+  void* tw = nullptr;
+  MFFT_TRY(prepare_kernel(e, &tw));
+  return by_prec(a.prec, [&](auto t) { return launch_nls_t<decltype(t)>(e, a, a.ngroups, tw, s); });
+}
+
 // ---------------------------------------------------------------------------
 // data-movement kernels
 // ---------------------------------------------------------------------------

@@ -1663,6 +1663,128 @@ template <class S> static void test_nlm_all() {
   }
 }
 
+// The stage that ends in a reduction (fft_nlz.h body_moments, Op::Moments): [min, max, S1 .. S4] of up to six real fields over all
+// rows against long-double transforms of the rows.  The launch has `ngroups` workgroups whatever the row count, so the loop over
+// the rows iterates and ends unevenly; the waves' slots are added up on the host in the order of the fold kernel.
+struct NlsCase {
+  int valid = 0, valid_in = 0, nrows = 0, nfields = 1, ngroups = 1;
+  bool center = false;
+  int bad_field = -1;
+  bool inf = false;
+};
+template <class S, typename T, int ROWS, bool TWLDS, bool SPLIT, bool WAVE>
+static double run_nls(const NlsCase& c, double tol) {      // the worst error in units of its bound, times tol; 1e30 for a broken contract
+  typedef NlzMoments<NlzFft<S, T, ROWS, TWLDS, SPLIT, WAVE>> K;
+  const int M = S::N, valid = c.valid, vin = c.valid_in > 0 ? c.valid_in : c.valid, nrows = c.nrows, nf = c.nfields;
+  const int pin = valid + 2;
+  const bool two = nf % 2 == 0;                      // a and b: field f of a rides with field f of b
+  const int ncomp = two ? nf / 2 : nf;
+  std::mt19937_64 rng(4242 + M + valid + 13 * nf + nrows);
+  std::uniform_real_distribution<double> U(-1.0, 1.0);
+  std::vector<cx<T>> in[6];
+  for (int f = 0; f < nf; ++f) {
+    in[f].resize((size_t)nrows * pin);
+    for (auto& z : in[f]) z = mk<T>((T)U(rng), (T)U(rng));
+    for (int r = 0; r < nrows; ++r) in[f][(size_t)r * pin].x += (T)(0.5 * M * (f + 1));      // a mean of (f + 1) / 2
+  }
+  if (c.bad_field >= 0) in[c.bad_field][(size_t)(nrows / 2) * pin + 1].x = c.inf ? (T)INFINITY : (T)NAN;
+  auto tw = build_pass_twiddles<S, T>();
+  const int units = (nrows + 2 * ROWS - 1) / (2 * ROWS);
+  const int grid = std::min(units, c.ngroups);
+  NlsParams<T> P;
+  int slot_of[6];
+  for (int p = 0; p < 3; ++p) { P.a[p] = nullptr; P.b[p] = nullptr; P.out[p] = nullptr; }
+  for (int i = 0; i < 6; ++i) P.center[i] = 0.0;
+  for (int f = 0; f < nf; ++f) {
+    const int slot = two ? (f < ncomp ? 2 * f : 2 * (f - ncomp) + 1) : f;
+    (slot % 2 ? P.b : P.a)[slot / 2] = in[f].data();
+    P.center[slot] = c.center ? 0.5 * (f + 1) + 0.125 : 0.0;
+    slot_of[f] = slot;
+  }
+  P.tw = tw.data(); P.in_stride = pin; P.out_stride = 0; P.nrows = nrows; P.valid = valid; P.valid_in = vin;
+  P.scale = (T)1; P.rt3 = nullptr;
+  P.norm = 1.0 / (double)M; P.npairs = (nf + 1) / 2; P.ngroups = grid;
+  std::vector<double> part((size_t)grid * K::WAVES * NLS_SLOTS, -7.0);
+  P.part = part.data();
+  std::vector<cx<T>> keep[6];
+  for (int f = 0; f < nf; ++f) keep[f] = in[f];
+  emu_launch(grid, K::THREADS, K::LDS_BYTES, [&](int b, int t, char* lds) { K::body(P, b, t, lds); });
+  double bad = 0;
+  for (int f = 0; f < nf; ++f)                       // the inputs are preserved (NaNs: compare the bytes)
+    if (memcmp(in[f].data(), keep[f].data(), keep[f].size() * sizeof(cx<T>)) != 0) bad = 1e30;
+  for (double v : part)
+    if (v == -7.0) bad = 1e30;                       // a slot nobody wrote
+  const long double eps = 2.220446049250313e-16L;
+  for (int f = 0; f < nf; ++f) {
+    double got[6] = {INFINITY, -INFINITY, 0, 0, 0, 0};
+    for (size_t w = 0; w < part.size() / NLS_SLOTS; ++w) {
+      const double* q = part.data() + w * NLS_SLOTS + slot_of[f] * NLS_STATS;
+      got[0] = (q[0] < got[0] || q[0] != q[0]) ? q[0] : got[0];
+      got[1] = emu_nan_max(got[1], q[1]);
+      for (int k = 2; k < 6; ++k) got[k] += q[k];
+    }
+    if (f == c.bad_field) {                          // NaN sums; NaN extremes, or for an Inf bin -Inf / +Inf or NaN
+      for (int k = 2; k < 6; ++k) if (got[k] == got[k]) bad = 1e30;
+      if (!c.inf && (got[0] == got[0] || got[1] == got[1])) bad = 1e30;
+      if (c.inf && !((got[0] != got[0] || got[0] == -INFINITY) && (got[1] != got[1] || got[1] == INFINITY))) bad = 1e30;
+      continue;
+    }
+    const long double ctr = P.center[slot_of[f]];
+    long double mn = INFINITY, mx = -INFINITY, sp[5] = {0, 0, 0, 0, 0}, sa[5] = {0, 0, 0, 0, 0}, s2p[5] = {0, 0, 0, 0, 0}, sx2 = 0, amax = 0;
+    for (int r = 0; r < nrows; ++r)
+      for (long double x : nl_real_row(in[f].data() + (size_t)r * pin, vin, M)) {
+        mn = std::min(mn, x); mx = std::max(mx, x); amax = std::max(amax, fabsl(x)); sx2 += x * x;
+        const long double d = x - ctr;
+        long double dp = 1;
+        for (int p = 1; p <= 4; ++p) { s2p[p] += dp * dp; dp *= d; sp[p] += dp; sa[p] += fabsl(dp); }      // s2p[p] = sum d^(2 (p - 1))
+      }
+    const long double cnt = (long double)nrows * M;
+    for (int k = 0; k < 6; ++k)
+      if (got[k] != got[k]) bad = 1e30;              // a clean field next to a bad one stays finite
+    bad = std::max(bad, (double)(fabsl(got[0] - mn) / amax));
+    bad = std::max(bad, (double)(fabsl(got[1] - mx) / amax));
+    for (int p = 1; p <= 4; ++p) {                    // the transform's relative-L2 error pushed through x -> (x - c)^p, plus a double sum in any order
+      const long double bound = tol * p * sqrtl(s2p[p] * sx2) + (cnt + 8) * eps * sa[p];
+      bad = std::max(bad, (double)(fabsl(got[1 + p] - sp[p]) / bound * tol));
+    }
+  }
+  return bad;
+}
+template <class S, typename T, int ROWS, bool TWLDS, bool SPLIT, bool WAVE>
+static void test_nls(int nfields, int valid, int valid_in, int nrows, int ngroups, bool center, int bad_kind = 0) {
+  NlsCase c;
+  c.valid = valid; c.valid_in = valid_in; c.nrows = nrows; c.nfields = nfields; c.ngroups = ngroups; c.center = center;
+  const double tol = sizeof(T) == 8 ? 4e-14 : 2e-5;
+  const int vin = valid_in > 0 ? valid_in : valid;
+  char name[128];
+  snprintf(name, sizeof name, "nls f%d r%d n%d g%d v%d/%d%s%s%s%s", nfields, ROWS, nrows, ngroups, vin, valid, center ? " centre" : "",
+           TWLDS ? " twlds" : "", SPLIT ? " split" : "", WAVE ? " wave" : "");
+  report(name, S::N, pname<T>(), run_nls<S, T, ROWS, TWLDS, SPLIT, WAVE>(c, tol), tol);
+  if (!bad_kind) return;
+  c.bad_field = (S::N + ROWS) % nfields;
+  c.inf = bad_kind == 2;
+  snprintf(name, sizeof name, "nls f%d r%d %s in field %d%s%s", nfields, ROWS, c.inf ? "inf" : "nan", c.bad_field, SPLIT ? " split" : "", WAVE ? " wave" : "");
+  report(name, S::N, pname<T>(), run_nls<S, T, ROWS, TWLDS, SPLIT, WAVE>(c, tol), tol);
+}
+template <class S> static void test_nls_all() {
+  const int M = S::N;
+  const int full = M / 2 + 1, lim = M / 3 + 1;
+  if constexpr (S::TPT <= 64 && 64 % S::TPT == 0) {      // the wave-synchronous build
+    test_nls<S, double, 2, true, false, true>(6, lim, 0, 7, 1, true, 1);
+    test_nls<S, float, 3, false, false, true>(1, full, 0, 1, 4, false, 2);
+  }
+  test_nls<S, double, 2, true, false, false>(3, full, 0, 7, 2, false, 2);
+  test_nls<S, double, 1, false, true, false>(2, lim, 0, 1, 1, true, 1);
+  test_nls<S, float, 2, true, true, false>(6, full, 0, 5, 1, false, 1);
+  test_nls<S, float, 3, false, false, false>(3, lim, 0, 2 * 6 + 3, 1, true, 2);          // two passes of the one workgroup and a ragged rest
+  test_nls<S, float, 2, true, false, false>(2, full, 0, 1, 1, false, 0);
+  test_nls<S, double, 1, false, true, false>(1, full, 0, 3 * 4 + 3, 2, false, 0);         // three passes of two workgroups and a ragged rest
+  if (lim < full) {                                 // pruned 2/3-rule: the kept kz bins are read
+    test_nls<S, double, 2, true, false, false>(2, full, lim, 7, 1, false, 0);
+    test_nls<S, float, 1, false, true, false>(1, full, (2 * full) / 3, 3, 1, true, 0);
+  }
+}
+
 // the pruned 3/2-rule flavour (Nlz3Fft): M = 3 L, L + 1 bins per row, three sub-transforms per row
 template <class SL, typename T, int ROWS, bool TWLDS>
 static void test_nlz3(bool inplace) {
@@ -1891,6 +2013,11 @@ int main() {
 #define MFFT_NLC(N, ...) test_nlc_all<Spec<N, __VA_ARGS__>>();
   MFFT_NLZPLANS_P2(MFFT_NLC) MFFT_NLZPLANS_3(MFFT_NLC) MFFT_NLZPLANS_9(MFFT_NLC)     // the fused nonlinear z stage, cross and dot product
 #undef MFFT_NLC
+#endif
+#if EMU_HAS(21)      // (`make emu_nls`, a binary of its own as well)
+#define MFFT_NLS(N, ...) test_nls_all<Spec<N, __VA_ARGS__>>();
+  MFFT_NLZPLANS_P2(MFFT_NLS) MFFT_NLZPLANS_3(MFFT_NLS) MFFT_NLZPLANS_9(MFFT_NLS)     // the fused z stage that ends in a reduction
+#undef MFFT_NLS
 #endif
 #if EMU_HAS(1)
   // pair-row kernels (with plan group B, where the shipped 512 / 1024 plans are; tests/test_cabi.py fixes the number of parts): even and odd meshes (self-paired planes and rows), a partial last workgroup, the shipped shapes

@@ -143,6 +143,7 @@ constexpr NlProduct NL_PRODUCTS[] = {
     {Op::Plain, "cross", 6, 3, true, true},
     {Op::Dot, "dot", 6, 1, true, false},
     {Op::CrossDot, "cross_dot", 9, 4, false, false},
+    {Op::Moments, "moments", 6, 0, false, false},      // (up to six fields: the call says how many, NlFields::nfields)
 };
 inline const NlProduct& nl_product(Op op) {
   for (const NlProduct& q : NL_PRODUCTS)
@@ -152,6 +153,28 @@ inline const NlProduct& nl_product(Op op) {
 bool nlz_supported(int64_t n, int prec, Op product = Op::Plain, bool absmax = false);
 int64_t nlz_absmax_waves(int64_t n, int prec, Op product, int64_t nrows);
 int launch_nlz(const NlzArgs& a, hipStream_t s);
+// The z stage that ends in a reduction (fft_nlz.h body_moments): pair p is the rows a[p] + i b[p] (b[p] may be null), p < npairs
+// <= 3; [min, max, S1 .. S4] of the 2 npairs real fields, x = norm * (the un-normalised inverse transform), S_p about center[].
+struct NlsArgs {
+  const void* a[3] = {nullptr, nullptr, nullptr};
+  const void* b[3] = {nullptr, nullptr, nullptr};
+  int npairs = 0;
+  int n = 0;             // REAL length of a z row
+  int prec = MFFT_DOUBLE;
+  int64_t in_stride = 0, nrows = 0;   // complex elements
+  int valid = 0;         // bins per row present in memory (0 = all n/2+1)
+  int valid_in = 0;      // bins per row that are read, where fewer (pruned 2/3-rule); 0 = valid
+  double norm = 1.0;
+  double center[6] = {0, 0, 0, 0, 0, 0};   // [pair][a, b]
+  int ngroups = 0;       // workgroups of the launch, from nls_launch_shape() of (n, prec, nrows): the caller asks once and sizes `part` by it
+  void* part = nullptr;  // `waves` of nls_launch_shape() groups of 36 doubles, [wave][pair][a, b][statistic]: moments_fold adds them up
+};
+int nls_launch_shape(int64_t n, int prec, int64_t nrows, int* ngroups, int64_t* waves);
+int launch_nls(const NlsArgs& a, hipStream_t s);
+// Statistics [min, max, S1 .. S4] per slot (moments.hip).  acc: device doubles, nvals = 6 * slots of them.  moments_clear: the
+// identity (+Inf, -Inf, zeros); moments_fold: acc[v] = merge(acc[v], the groups' part[g * nvals + v] in a fixed order), NaNs kept.
+int moments_clear(double* acc, int nvals, hipStream_t s);
+int moments_fold(const double* part, size_t groups, int nvals, double* acc, hipStream_t s);
 // max |x| reductions (absmax.hip): acc[s] = max(acc[s], scale * max_g part[g * period + s]), NaNs kept; `scratch` holds
 // absmax_fold_scratch_bytes(), `part` is in precision `prec`, acc in double
 size_t absmax_fold_scratch_bytes();

@@ -76,11 +76,17 @@ struct Buf {                   // a device buffer of the plan that only grows (m
 
 // The caller's arrays of one nonlinear operation (plan_nonlinear.hip): vector fields a, b and -- where the product has one -- c
 // in, the result out (three components, or the ONE of the dot product) and, of the product with both, the scalar result outs.
+// An operation whose number of fields belongs to the call (Op::Moments): nfields of them, ncomp components of a, then of b.
 struct NlFields {
   const void *a, *b, *c;
   void *out, *outs;
+  int ncomp = 3;               // components per field
+  int nfields = 0;             // 0: what the table of products says (NlProduct::nin)
+  int nin(const NlProduct& q) const { return nfields > 0 ? nfields : q.nin; }
   // component f of the inputs (a, b, then c) / of the results (out, then outs), C elements of es bytes per component
-  const void* src(int f, int64_t C, size_t es) const { return static_cast<const char*>(f < 3 ? a : f < 6 ? b : c) + (size_t)((f % 3) * C) * es; }
+  const void* src(int f, int64_t C, size_t es) const {
+    return static_cast<const char*>(f < ncomp ? a : f < 2 * ncomp ? b : c) + (size_t)((f % ncomp) * C) * es;
+  }
   void* dst(int f, int64_t C, size_t es) const { return f < 3 ? static_cast<char*>(out) + (size_t)(f * C) * es : outs; }
 };
 
@@ -127,6 +133,9 @@ struct mfft_plan_s {
   // maxima of the last statistics call, the result of mfft_ew_absmax); no captured sequence holds them either.
   Buf work[3] = {{true, true}, {true, true}, {true, true}}, work3{true, false}, nlw[2] = {{true, true}, {true, true}};
   Buf nlx{false, true}, nly{false, true}, nlr{false, true}, pcomp{false, true}, shl{false, false}, nlm{false, false}, nlmacc{false, false};
+  // mfft_real_moments / mfft_ew_moments (moments.hip): 36 statistics in slot order, then the six centres; the partials go to nlm
+  Buf nlsacc{false, false};
+  double nls_center[6] = {0, 0, 0, 0, 0, 0};
   bool nlm_valid = false;       // a statistics call has run: nlmacc[0..5] hold max |ifftn(a_f)|, max |ifftn(b_f)| of this rank
   uint8_t* mask = nullptr;
   size_t mask_count = 0;
@@ -502,6 +511,13 @@ struct mfft_plan_s {
   int nonlinear_composed(const mfft::NlFields& u, int dealias, mfft::Op product, bool stats);
   int nonlinear_absmax(double out6[6]);                                   // this rank's maxima of the last statistics call
   int absmax_sweep(const void* x, int ncomp, size_t n, double* acc);      // absmax.hip
+  // One-point statistics of up to six fields given as spectra (plan_nonlinear.hip; the z stage fft_nlz.h body_moments on the
+  // fused routes, one inverse transform and one sweep per field on the composed one), and the sweep itself (moments.hip)
+  int real_moments(const mfft::NlFields& u, int dealias, const double* center, double* out, int64_t* count);
+  int moments_composed(const mfft::NlFields& u, int dealias);
+  int moments_sweep(const void* x, int ncomp, size_t n, const double* center, double* acc);
+  int moments_begin(const double center_slots[6]);
+  int moments_end(double host[36]);
 };
 
 namespace mfft {

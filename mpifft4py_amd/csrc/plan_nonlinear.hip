@@ -100,6 +100,33 @@ static int nlz_rows(mfft_plan_s* p, char* Y, size_t yelems, int64_t L2, int64_t 
   return 0;
 }
 
+// Where field f of a moments call (ncomp components of a, then of b) rides: slot 2 p is the first half of pair p, 2 p + 1 the
+// second.  With two fields a_f and b_f share a transform, as in the products; with one the components pair up among themselves.
+static int nls_slot(const NlFields& u, int f) { return u.b ? (f < u.ncomp ? 2 * f : 2 * (f - u.ncomp) + 1) : f; }
+
+// the z stage that ends in a reduction, on a batch: rows of the call's fields in Y (yelems apart, pitch Za) in, the partial
+// statistics of the launch's waves into nlm, folded into the plan's accumulator (moments_begin) after the launch: the statistics
+// accumulate over the batches.  The inverse z transform is un-normalised: norm = 1 / L2.
+static int nls_rows(mfft_plan_s* p, const NlFields& u, char* Y, size_t yelems, int64_t L2, int64_t Za, int64_t nrows, int valid_in) {
+  NlsArgs z;
+  int ngroups = 0;
+  int64_t waves = 0;
+  MFFT_TRY(nls_launch_shape(L2, p->prec, nrows, &ngroups, &waves));
+  MFFT_TRY(p->ensure(p->nlm, (size_t)waves * NLS_SLOTS * sizeof(double)));
+  for (int f = 0; f < u.nfields; ++f) {
+    const int slot = nls_slot(u, f);
+    (slot % 2 ? z.b : z.a)[slot / 2] = Y + (size_t)f * yelems * p->es;
+    z.center[slot] = p->nls_center[slot];
+  }
+  z.npairs = (u.nfields + 1) / 2;
+  z.n = (int)L2; z.prec = p->prec; z.in_stride = Za; z.nrows = nrows; z.valid = (int)p->Nf; z.valid_in = valid_in;
+  z.norm = 1.0 / (double)L2;
+  z.ngroups = ngroups;
+  z.part = p->nlm.p;
+  MFFT_TRY(launch_nls(z, p->stream));
+  return moments_fold(static_cast<const double*>(z.part), (size_t)waves, NLS_SLOTS, static_cast<double*>(p->nlsacc.p), p->stream);
+}
+
 // Fused route: one rank, slab, real data, radix kernels on every axis.
 bool mfft_plan_s::nonlinear_fusable(int dealias, Op product, bool stats) const {
   static const bool off = env_on("MFFT_NO_NLZ"), ranks_off = env_on("MFFT_NO_NLZ_RANKS");      // read once per process
@@ -127,7 +154,7 @@ bool mfft_plan_s::nonlinear_fusable(int dealias, Op product, bool stats) const {
 // Both products: nine fields through the inverse passes, the z kernel's four result rows in place on the first four (the cross
 // product over a, the scalar row over b_0), four forward passes.
 int mfft_plan_s::nonlinear_fused(const NlFields& u, int dealias, Op product, bool stats) {
-  const int nout = nl_product(product).nout, nin = nl_product(product).nin;
+  const int nout = nl_product(product).nout, nin = u.nin(nl_product(product));
   const bool pad = dealias == MFFT_DEALIAS_3_2, masked = dealias == MFFT_DEALIAS_2_3;
   const Op ld = pad ? Op::PadLoad : Op::Plain, st = pad ? Op::TruncStore : Op::Plain;      // the 3/2-rule's passes pad on load, truncate on store
   const int64_t L0 = pad ? M0 : N0, L1 = pad ? M1 : N1, L2 = pad ? M2 : N2;
@@ -205,15 +232,16 @@ int mfft_plan_s::nonlinear_fused(const NlFields& u, int dealias, Op product, boo
       return 0;
     }));
     MFFT_TRY(stage("nl_z", (nin * keep2 + nout) * Yb * frac, [&] {
+      if (product == Op::Moments) return nls_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0);
       return nlz_rows(this, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0, product, stats);
     }));
-    MFFT_TRY(stage("nl_y_fwd", nout * (Xb + Yb) * frac, [&] {
+    if (nout) MFFT_TRY(stage("nl_y_fwd", nout * (Xb + Yb) * frac, [&] {
       for (int f = 0; f < nout; ++f)
         MFFT_TRY(col_pad(Yf(f), Xf(f, batch(i0)), L1, false, st, pad, m, Nf, L1 * Za, plain(Za), N1 * Za, plain(Za), 1.0));
       return 0;
     }));
   }
-  MFFT_TRY(stage("nl_x_fwd", nout * (Cb + Xb), [&] {
+  if (nout) MFFT_TRY(stage("nl_x_fwd", nout * (Cb + Xb), [&] {
     for (int f = 0; f < nout; ++f) {
       const void* src = Xf(f);
       void* dst = u.dst(f, C, es);
@@ -236,7 +264,7 @@ int mfft_plan_s::nonlinear_fused(const NlFields& u, int dealias, Op product, boo
 // (The dot product: six inverse exchanges and one forward exchange.)
 // (Both products: nine inverse exchanges and four forward ones.)
 int mfft_plan_s::nonlinear_fused_ranks(const NlFields& u, int dealias, Op product, bool stats) {
-  const int nout = nl_product(product).nout, nin = nl_product(product).nin;
+  const int nout = nl_product(product).nout, nin = u.nin(nl_product(product));
   const bool pad = dealias == MFFT_DEALIAS_3_2, masked = dealias == MFFT_DEALIAS_2_3;
   const Op ld = pad ? Op::PadLoad : Op::Plain, st = pad ? Op::TruncStore : Op::Plain;      // the 3/2-rule's passes pad on load, truncate on store
   const int64_t L0 = pad ? M0 : N0, L1 = pad ? M1 : N1, L2 = pad ? M2 : N2, Lp0 = L0 / P;
@@ -307,19 +335,20 @@ int mfft_plan_s::nonlinear_fused_ranks(const NlFields& u, int dealias, Op produc
       return 0;
     }));
     MFFT_TRY(stage("nl_z", 0, [&] {
+      if (product == Op::Moments) return nls_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0);
       return nlz_rows(this, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0, product, stats);
     }));
-    MFFT_TRY(stage("nl_y_fwd", 0, [&] {      // truncate + fold in y, straight into the packed (P, Lp0, S) send layout
+    if (nout) MFFT_TRY(stage("nl_y_fwd", 0, [&] {      // truncate + fold in y, straight into the packed (P, Lp0, S) send layout
       for (int f = 0; f < nout; ++f)
         MFFT_TRY(col_pad(Yf(f), Xf(f, batch(i0, S)), L1, false, st, pad, m, Nf, L1 * Za, plain(Za), S, two_level(Np1, Lp0 * S, Nf), 1.0));
       return 0;
     }));
   }
-  MFFT_TRY(stage("nl_a2a_fwd", 0, [&] {
+  if (nout) MFFT_TRY(stage("nl_a2a_fwd", 0, [&] {
     for (int f = 0; f < nout; ++f) MFFT_TRY(xchg(0, true, pad, Xf(f), Rf(f)));
     return 0;
   }));
-  MFFT_TRY(stage("nl_x_fwd", 0, [&] {
+  if (nout) MFFT_TRY(stage("nl_x_fwd", 0, [&] {
     for (int f = 0; f < nout; ++f)
       MFFT_TRY(col_pad(Rf(f), u.dst(f, C, es), L0, false, st, pad, 1, Np1 * Nf, 0, plain(S), 0, plain(Np1 * Nf), 1.0 / sc3));
     return 0;
@@ -351,5 +380,40 @@ int mfft_plan_s::nonlinear_absmax(double out6[6]) {
   if (!nlm_valid) return set_error(MFFT_ERR_INVALID, "no nonlinear operation with statistics has run on this plan");
   MFFT_HIP(hipMemcpyAsync(out6, nlmacc.p, 6 * sizeof(double), hipMemcpyDeviceToHost, stream));
   MFFT_HIP(hipStreamSynchronize(stream));
+  return 0;
+}
+
+// One-point statistics of the real-space fields of up to six spectra: [min, max, S1 .. S4] per field, S_p = sum (x - center)^p over
+// this rank's part of the grid a product would be formed on (the padded one under the 3/2-rule, the masked field under the
+// 2/3-rule), x = ifftn(field, dealias).  Fused routes: the inverse passes of the products and the z stage that ends in a reduction,
+// no real array.  Composed route (pencils, lengths without a kernel, MFFT_NO_NLZ): the statistics are per field, so ONE real work
+// array serves them in turn -- inverse transform, sweep (moments.hip), next field.  Synchronises the plan's stream.
+int mfft_plan_s::moments_composed(const NlFields& u, int dealias) {
+  const bool pad = dealias == MFFT_DEALIAS_3_2;
+  const int64_t nr = local_real_count(pad), nc = local_complex_alloc();
+  if (nr <= 0 || !r2c) return set_error(MFFT_ERR_UNSUPPORTED, "real_moments needs a 3-D real-to-complex plan");
+  MFFT_TRY(ensure(nlr, (size_t)nr * rs));
+  double* acc = static_cast<double*>(nlsacc.p);
+  for (int f = 0; f < u.nfields; ++f) {
+    const int slot = nls_slot(u, f);
+    MFFT_TRY(exec(false, u.src(f, nc, es), nlr.p, dealias));
+    MFFT_TRY(stage("nl_moments", (double)nr * rs, [&] { return moments_sweep(nlr.p, 1, (size_t)nr, acc + NLS_SLOTS + slot, acc + slot * NLS_STATS); }));
+  }
+  return 0;
+}
+int mfft_plan_s::real_moments(const NlFields& u, int dealias, const double* center, double* out, int64_t* count) {
+  if (dealias == MFFT_DEALIAS_2_3) MFFT_TRY(require_mask());
+  double c6[6] = {0, 0, 0, 0, 0, 0};
+  for (int f = 0; center && f < u.nfields; ++f) c6[nls_slot(u, f)] = center[f];
+  MFFT_TRY(moments_begin(c6));
+  const bool pad = dealias == MFFT_DEALIAS_3_2;
+  MFFT_TRY(nonlinear_fusable(dealias, Op::Moments, false)
+               ? (P == 1 ? nonlinear_fused(u, dealias, Op::Moments, false) : nonlinear_fused_ranks(u, dealias, Op::Moments, false))
+               : moments_composed(u, dealias));
+  double host[NLS_SLOTS];
+  MFFT_TRY(moments_end(host));
+  for (int f = 0; f < u.nfields; ++f)
+    for (int k = 0; k < NLS_STATS; ++k) out[f * NLS_STATS + k] = host[nls_slot(u, f) * NLS_STATS + k];
+  *count = local_real_count(pad);
   return 0;
 }

@@ -120,6 +120,20 @@ void register_nlc(const char* name) {
   reg.push_back(make_entry<K, NlcParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::CrossDot, Build::Default, R, name));
 }
 
+// Op::Moments: the stage that ends in a reduction (fft_nlz.h body_moments, NlsParams; kernels_nls*.hip).  Rows, twiddle placement,
+// exchange, wave-synchronous build and the two-waves-per-SIMD cap are the cross kernels': the body inlines ONE transform where
+// the cross body inlines five and parks no row, but holds 36 doubles of accumulators for the whole launch: no scratch in single
+// precision, 36 - 196 bytes in the double-precision 12-values plans from 192 on (profiles/real_moments_regs.tsv).  No other cap
+// was measured.
+template <class S, typename T>
+void register_nls(const char* name) {
+  auto& reg = kernel_registry();
+  constexpr int R = nlz_rows<S, T>();
+  constexpr int W = MFFT_NLZ_OCC > 1 ? 16 + MFFT_NLZ_OCC : 0;
+  typedef NlzMoments<NlzFft<S, T, R, nlz_twlds<S, T>(), nlz_split<S, T>(), nlz_wave<S, T>()>> K;
+  reg.push_back(make_entry<K, NlsParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::Moments, Build::Default, R, name));
+}
+
 // ... and its pruned 3/2-rule flavour (Nlz3Fft: Build::Nlz3, entry.n = M = 3 L): three thread groups of SL::TPT threads per row
 template <class SL, typename T> constexpr int nlz3_rows() { return 256 / (3 * SL::TPT) > 0 ? 256 / (3 * SL::TPT) : 1; }
 template <class SL, typename T>

@@ -54,6 +54,21 @@ __global__ __launch_bounds__(EW_BLOCK) void grad_kernel(const cx<T>* __restrict_
   }
 }
 
+// out_f = i K_f U_f   (spectral space: the three longitudinal derivatives du_f / dx_f of a vector field)
+template <typename T>
+__global__ __launch_bounds__(EW_BLOCK) void diag_grad_kernel(const cx<T>* __restrict__ U, cx<T>* __restrict__ out,
+                                                            const T* __restrict__ kx, const T* __restrict__ ky,
+                                                            const T* __restrict__ kz, int64_t s1, int64_t s2, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const int64_t k = (int64_t)(i % s2), j = (int64_t)((i / s2) % s1), l = (int64_t)(i / (s2 * s1));
+    const T K0 = kx[l], K1 = ky[j], K2 = kz[k];
+    const cx<T> u0 = U[i], u1 = U[n + i], u2 = U[2 * n + i];
+    out[i] = mk<T>(-K0 * u0.y, K0 * u0.x);
+    out[n + i] = mk<T>(-K1 * u1.y, K1 * u1.x);
+    out[2 * n + i] = mk<T>(-K2 * u2.y, K2 * u2.x);
+  }
+}
+
 // out = i K x U   (spectral space, demo:60-64)
 template <typename T>
 __global__ __launch_bounds__(EW_BLOCK) void curl_kernel(const cx<T>* __restrict__ U, cx<T>* __restrict__ out,
@@ -290,6 +305,22 @@ int mfft_ew_grad_hat(mfft_plan_t plan, const void* s_hat, void* out, const void*
                        (cx<double>*)out, (const double*)kx, (const double*)ky, (const double*)kz, shape[1], shape[2], n);
   else
     hipLaunchKernelGGL(grad_kernel<float>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, st, (const cx<float>*)s_hat,
+                       (cx<float>*)out, (const float*)kx, (const float*)ky, (const float*)kz, shape[1], shape[2], n);
+  MFFT_HIP(hipGetLastError());
+  return 0;
+}
+
+// out[f] = i K[f] U_hat[f]: the sibling of mfft_ew_grad_hat for a vector field
+int mfft_ew_diag_grad_hat(mfft_plan_t plan, const void* U_hat, void* out, const void* kx, const void* ky, const void* kz,
+                          const int64_t shape[3], int precision) {
+  hipStream_t st = plan_stream(plan);
+  if (!U_hat || !out || !kx || !ky || !kz || !shape) return set_error(MFFT_ERR_INVALID, "null argument");
+  const size_t n = (size_t)(shape[0] * shape[1] * shape[2]);
+  if (precision == MFFT_DOUBLE)
+    hipLaunchKernelGGL(diag_grad_kernel<double>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, st, (const cx<double>*)U_hat,
+                       (cx<double>*)out, (const double*)kx, (const double*)ky, (const double*)kz, shape[1], shape[2], n);
+  else
+    hipLaunchKernelGGL(diag_grad_kernel<float>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, st, (const cx<float>*)U_hat,
                        (cx<float>*)out, (const float*)kx, (const float*)ky, (const float*)kz, shape[1], shape[2], n);
   MFFT_HIP(hipGetLastError());
   return 0;

@@ -66,9 +66,10 @@ def ns_rhs(FFT, K, dU, U_hat, nu):
     return dU
 
 
-def _nonlinear(FFT, name, fields, dealias):
+def _nonlinear(FFT, name, fields, dealias, head=None, tail=()):
     """One nonlinear operation of the plan, mfft_<name>: `fields` are its (DeviceArray, is_vector) pairs in the order of the
-    call's arguments, each of shape FFT.complex_shape() -- (3,) + that for a vector field -- and of the plan's pitch."""
+    call's arguments, each of shape FFT.complex_shape() -- (3,) + that for a vector field -- and of the plan's pitch.
+    `head`: the arguments before the dealias code where they are not just the fields' pointers; `tail`: those after it."""
     from ._base import _DEALIAS
     assert dealias in ('3/2-rule', '2/3-rule', 'None', None)
     cs = tuple(int(s) for s in FFT.complex_shape())
@@ -80,7 +81,7 @@ def _nonlinear(FFT, name, fields, dealias):
     FFT.comm.use_device()
     if code == _lib.DEALIAS_2_3:
         FFT._ensure_mask()
-    _lib.call("mfft_" + name, FFT._plan, *[x.ptr for x, _ in fields], code)
+    _lib.call("mfft_" + name, FFT._plan, *(tuple(x.ptr for x, _ in fields) if head is None else head), code, *tail)
 
 
 def cross_transform(FFT, a_hat, b_hat, out_hat, dealias=None, absmax=False):
@@ -112,6 +113,18 @@ def grad_hat(FFT, K, s_hat, out):
     assert s_hat.shape == cs and out.shape == (3,) + cs, (s_hat.shape, out.shape, cs)
     assert s_hat.dtype == out.dtype == np.dtype(FFT.complex) and s_hat.pitch == out.pitch, (s_hat.dtype, s_hat.pitch, out.pitch)
     _lib.call("mfft_ew_grad_hat", FFT._plan, s_hat.ptr, out.ptr, K.dev[0].ptr, K.dev[1].ptr, K.dev[2].ptr,
+              K.cshape, _prec(FFT))
+    return out
+
+
+def diag_grad_hat(FFT, K, U_hat, out):
+    """out[f] = i K[f] U_hat[f]: the three LONGITUDINAL derivatives du_f/dx_f of a vector field in spectral space
+    (mfft_ew_diag_grad_hat) -- the field whose skewness, about -0.5 in developed turbulence, a DNS is judged by
+    (`real_moments`).  U_hat and out are (3,) + FFT.complex_shape(); pitched spectra are swept as they lie in memory."""
+    cs = tuple(int(x) for x in FFT.complex_shape())
+    assert U_hat.shape == out.shape == (3,) + cs, (U_hat.shape, out.shape, cs)
+    assert U_hat.dtype == out.dtype == np.dtype(FFT.complex) and U_hat.pitch == out.pitch, (U_hat.dtype, U_hat.pitch, out.pitch)
+    _lib.call("mfft_ew_diag_grad_hat", FFT._plan, U_hat.ptr, out.ptr, K.dev[0].ptr, K.dev[1].ptr, K.dev[2].ptr,
               K.cshape, _prec(FFT))
     return out
 
@@ -181,6 +194,106 @@ def absmax(FFT, x, reduce=False):
     if reduce:
         out = _max_over_ranks(FFT, out)
     return float(out[0]) if len(x.shape) != 4 else out
+
+
+class Moments(object):
+    """Raw one-point statistics of `nfields` real fields over `count` points: `min`, `max` of shape (nfields,), `sums` of
+    shape (nfields, 4) with sums[f, p - 1] = sum (x - center[f])^p, and the `center` they were taken about.  The derived
+    numbers are formed on the host in np.longdouble from the raw sums, about the MEAN whatever the centre was."""
+
+    def __init__(self, count, mn, mx, sums, center):
+        self.count = int(count)
+        self.min = np.asarray(mn, dtype=np.float64)
+        self.max = np.asarray(mx, dtype=np.float64)
+        self.sums = np.asarray(sums, dtype=np.float64).reshape(-1, 4)
+        self.center = np.asarray(center, dtype=np.float64)
+
+    def _central(self):
+        """(delta, mu2, mu3, mu4): the mean minus the centre and the central moments, long double."""
+        m = self.sums.astype(np.longdouble) / np.longdouble(self.count)
+        d = m[:, 0]
+        mu2 = m[:, 1] - d * d
+        mu3 = m[:, 2] - 3 * d * m[:, 1] + 2 * d ** 3
+        mu4 = m[:, 3] - 4 * d * m[:, 2] + 6 * d * d * m[:, 1] - 3 * d ** 4
+        return d, mu2, mu3, mu4
+
+    def mean(self):
+        return self.center.astype(np.longdouble) + self._central()[0]
+
+    def variance(self):
+        return self._central()[1]
+
+    def skewness(self):
+        _, mu2, mu3, _ = self._central()
+        with np.errstate(divide="ignore", invalid="ignore"):      # (a field that is constant has none: nan)
+            return mu3 / mu2 ** np.longdouble(1.5)
+
+    def flatness(self):
+        _, mu2, _, mu4 = self._central()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return mu4 / (mu2 * mu2)
+
+
+def _moments_result(FFT, raw, count, center, reduce):
+    raw = np.asarray(raw, dtype=np.float64).reshape(-1, 6)
+    mn, mx, sums = raw[:, 0].copy(), raw[:, 1].copy(), raw[:, 2:].copy()
+    if reduce:
+        # sums and count: comm.allreduce adds in rank order, the same bits on every rank; the extremes keep their NaNs
+        tot = np.asarray(FFT.comm.allreduce(np.concatenate([sums.ravel(), [float(count)]])))
+        sums, count = tot[:-1].reshape(-1, 4), int(round(float(tot[-1])))
+        mx = _max_over_ranks(FFT, mx)
+        mn = -_max_over_ranks(FFT, -mn)
+    return Moments(count, mn, mx, sums, center)
+
+
+def _centers(center, nfields):
+    c = np.zeros(nfields, dtype=np.float64) if center is None else np.asarray(center, dtype=np.float64).reshape(-1) * np.ones(nfields)
+    assert c.shape == (nfields,), (c.shape, nfields)
+    return np.ascontiguousarray(c)
+
+
+def real_moments(FFT, a_hat, b_hat=None, dealias=None, center=None, reduce=True):
+    """One-point statistics of fields that exist as SPECTRA only (mfft_real_moments): minimum, maximum and the sums of the
+    first four powers of ifftn(a_hat[f], dealias) -- and of ifftn(b_hat[f], dealias) where b_hat is given -- without a real
+    array: on slab plans with radix kernels on every axis the z stage ends in a reduction
+    (`FFT.plan_info("nonlinear_moments_fused_3_2")`); elsewhere the plan transforms one field at a time into ONE work array
+    and sweeps it.  a_hat is a DeviceArray of FFT.complex_shape() or (3,) + that, b_hat None or of the same shape: 1, 2, 3 or
+    6 fields, a's first.  The grid is the one a product would be formed on (the padded one under the 3/2-rule, the masked
+    field under the 2/3-rule, as `nonlinear_absmax`).  Returns a `Moments`; with `reduce` over FFT.comm (every rank calls it,
+    every rank gets the same bits), else this rank's x planes.  `center` (a float or one per field): the sums are taken about
+    it.  Moments about a centre far from the mean lose digits as (mean / sigma)^p when the central moments are formed from
+    them -- a scalar of mean 3 and deviation 1e-3 keeps nothing of its flatness about 0 -- and that is what `center` is
+    for: pass the mean (a_hat[0, 0, 0] / N^3 on the rank that holds it).  A NaN or Inf anywhere in a field gives NaN sums for
+    that field; the values are bitwise reproducible.  Synchronises the plan's stream; the inputs are preserved."""
+    cs = tuple(int(s) for s in FFT.complex_shape())
+    assert a_hat.shape in (cs, (3,) + cs), (a_hat.shape, cs)
+    vec = len(a_hat.shape) == 4
+    fields = [(a_hat, vec)] + ([(b_hat, vec)] if b_hat is not None else [])
+    ncomp = 3 if vec else 1
+    nfields = ncomp * len(fields)
+    c = _centers(center, nfields)
+    out = np.zeros(nfields * 6, dtype=np.float64)
+    count = ctypes.c_int64(0)
+    dp = ctypes.POINTER(ctypes.c_double)
+    _nonlinear(FFT, "real_moments", fields, dealias, head=(a_hat.ptr, b_hat.ptr if b_hat is not None else None, ncomp),
+               tail=(c.ctypes.data_as(dp), out.ctypes.data_as(dp), ctypes.byref(count)))
+    return _moments_result(FFT, out, count.value, c, reduce)
+
+
+def moments(FFT, x, center=None, reduce=False):
+    """The same statistics of a real DeviceArray (mfft_ew_moments, the companion of `absmax` and `sumsq`): an array of the
+    real shape is one field, (3,) + the real shape three (any leading extent of 1, 2, 3 or 6 is taken as components).
+    Returns a `Moments`; with `reduce` over FFT.comm."""
+    if x.pitch is not None:
+        raise ValueError("moments of a pitched array would count the elements between its rows")
+    assert x.dtype == np.dtype(FFT.float), (x.dtype, FFT.float)
+    ncomp = int(x.shape[0]) if len(x.shape) == 4 else 1
+    c = _centers(center, ncomp)
+    FFT.comm.use_device()
+    out = np.zeros(36, dtype=np.float64)
+    dp = ctypes.POINTER(ctypes.c_double)
+    _lib.call("mfft_ew_moments", FFT._plan, x.ptr, ncomp, x.size // ncomp, _prec(FFT), c.ctypes.data_as(dp), out.ctypes.data_as(dp))
+    return _moments_result(FFT, out[:ncomp * 6], x.size // ncomp, c, reduce)
 
 
 def advective_dt(FFT, umax, cfl):

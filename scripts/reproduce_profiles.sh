@@ -111,6 +111,8 @@ run() {
     nonlinear_cross_dot_ab.txt) python scripts/nonlinear_cross_dot_ab.py --procs 3 --out out/nonlinear_cross_dot_ab.txt
       # its last section: the example's loop, one operation per stage against two calls
       for n in 256 512; do for dl in 3/2-rule 2/3-rule; do python examples/boussinesq_device.py --N $n --steps 5 --stages --dealias $dl; python examples/boussinesq_device.py --N $n --steps 5 --stages --dealias $dl --two-calls; done; done ;;
+    real_moments_regs.tsv) make -C mpifft4py_amd/csrc -j8 >/dev/null; python scripts/real_moments_regs.py ;;
+    real_moments_ab.txt) python scripts/real_moments_ab.py --procs 3 --out out/real_moments_ab.txt ;;
     shell_spectrum_ab.txt) python scripts/shell_spectrum_ab.py --procs 3 --out out/shell_spectrum_ab.txt
       # its last section: the kernels' trace statistics, and in a run of their own the LDS counters
       rocprofv3 --kernel-trace --stats --output-format csv -d out/shell_trace -- python scripts/shell_spectrum_ab.py --worker --cases 512:double,1024:double,1024:single
