@@ -209,7 +209,11 @@ MFFT_API int mfft_plan_set_dealias_mask(mfft_plan_t plan, const uint8_t* mask_ho
  * (pencils: z-chunk pack fused into the z transform), "ranks", "plane_pad" (one-rank slab plans: elements added to the
  * plane pitch of the intermediate because the mesh's own plane pitch is one the strided x pass reads slowly),
  * "split_last" (one-rank slab R2C plans: 1 = the plain transforms split real / complex at the spectrum end, MFFT_SPLIT_LAST;
- * asked before the first transform, the key decides then whether the route's work buffer fits).  Unknown keys are MFFT_ERR_INVALID. */
+ * asked before the first transform, the key decides then whether the route's work buffer fits), "split_last_yblock",
+ * "split_last_row_pitch", "split_last_block_pitch" (that route's work array: rows per y block, elements between the x rows of a
+ * block and between blocks; 0 where the plan does not take the route), "split_last_yfirst" (1: its y passes carry the caller's
+ * arrays, both x passes run in place on the work array), "work_bytes" (bytes of the first work buffer as allocated so far).
+ * Unknown keys are MFFT_ERR_INVALID. */
 MFFT_API int mfft_plan_get_info(mfft_plan_t plan, const char* key, int64_t* value);
 
 /* per-stage timing with HIP events on the plan's own streams (bench roofline) */

@@ -424,7 +424,7 @@ static int launch_real_t(const KernelEntry* e, const RealArgs& a, void* tw, void
 }
 // pair-row kernels (Op::PairRows): a workgroup holds tile / 2 of the (n0 / 2 + 1) * n1 pair slots (fft_kernels.h pair_row)
 template <typename T>
-static int launch_pair_t(const KernelEntry* e, const RealArgs& a, void* tw, void* rtw, hipStream_t s) {
+static int launch_pair_t(const KernelEntry* e, const RealArgs& a, int64_t real_stride, void* tw, void* rtw, hipStream_t s) {
   RealPairParams<T> P;
   P.in = a.in;
   P.out = a.out;
@@ -440,6 +440,7 @@ static int launch_pair_t(const KernelEntry* e, const RealArgs& a, void* tw, void
   P.pn1 = a.pair_n1;
   P.p_rplane = a.pair_rplane;
   P.p_cplane = a.pair_cplane;
+  P.p_ymap = make_rowmap(a.pair_rblock, real_stride, a.pair_yblock, a.pair_n1);
   return launch_rows(e, P, P.nrows, e->tile / 2, s);
 }
 
@@ -500,13 +501,15 @@ static int launch_real(int fam, const RealArgs& a, hipStream_t s) {
   if (a.pair_n0 > 0) {
     e = find_kernel(fam, a.n, a.prec, fam == FAM_C2R ? 1 : 0, Op::PairRows);
     const int64_t real_stride = fam == FAM_R2C ? a.in_stride : a.out_stride;
+    const bool blocked = a.pair_yblock > 0 && a.pair_yblock < a.pair_n1;      // (its fastdiv: rows and block below 2^16)
     if (!e || a.zs.nchunk || a.valid > 0 || real_stride % 2 != 0 || a.pair_rplane % 2 != 0 ||
-        a.nrows != (int64_t)a.pair_n0 * a.pair_n1 || a.nrows >= (int64_t)1 << 31)
+        a.nrows != (int64_t)a.pair_n0 * a.pair_n1 || a.nrows >= (int64_t)1 << 31 ||
+        (blocked && (a.pair_n1 >= 65536 || a.pair_n1 % a.pair_yblock != 0 || a.pair_rblock % 2 != 0)))
       return set_error(MFFT_ERR_UNSUPPORTED, "no pair-row real kernel of length %d for this layout", a.n);
     void *tw = nullptr, *rtw = nullptr;
     MFFT_TRY(prepare_kernel(e, &tw));
     MFFT_TRY(real_twiddles(a.n, a.prec, &rtw));
-    return by_prec(a.prec, [&](auto t) { return launch_pair_t<decltype(t)>(e, a, tw, rtw, s); });
+    return by_prec(a.prec, [&](auto t) { return launch_pair_t<decltype(t)>(e, a, real_stride, tw, rtw, s); });
   }
   MFFT_TRY(select_real(fam, a, &e));
   if (!e) return big_real(fam == FAM_C2R, a, s);

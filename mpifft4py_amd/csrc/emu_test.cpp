@@ -752,13 +752,23 @@ static void test_real() {
 // transforms of a real (n0, n1, N) field read as complex pairs go in, its half-spectrum must come out.  Inverse: an ARBITRARY
 // complex (n0, n1, N/2 + 1) array goes in (not the transform of a real field: the planes kz = 0 and N/2 are not Hermitian); the
 // inverse x and y transforms of what comes out, read as reals, must be numpy's irfftn of it (inverse c2c over x and y, then the
-// c2r that ignores the imaginary parts of bins 0 and N/2).  Rows and planes of both sides are pitched.
+// c2r that ignores the imaginary parts of bins 0 and N/2).  Rows and planes of both sides are pitched.  yb > 0: the real side is
+// blocked in y (RealPairParams::p_ymap): blocks of yb rows per x, pitched x rows inside a block, pitched blocks.
 template <class S, typename T, int ROWS, bool TWLDS>
-static void test_pair(int n0, int n1) {
+static void test_pair(int n0, int n1, int yb = 0) {
   const int M = S::N, N = 2 * M, Nf = M + 1;
   std::mt19937_64 rng(11 + N + 7 * n0 + n1);
   std::uniform_real_distribution<double> U(-1, 1);
-  const int wrow = M + 1, wplane = n1 * wrow + 3, crow = Nf + 2, cplane = n1 * crow + 5;      // complex elements
+  const int wrow = M + 1, wplane = (yb ? yb : n1) * wrow + 3, crow = Nf + 2, cplane = n1 * crow + 5;      // complex elements
+  const int wblock = n0 * wplane + 5;                       // blocked: complex elements between the y blocks
+  const size_t wsize = yb ? (size_t)(n1 / yb) * wblock : (size_t)n0 * wplane;
+  auto woff = [&](int x, int y) { return yb ? (size_t)(y / yb) * wblock + (size_t)x * wplane + (size_t)(y % yb) * wrow
+                                            : (size_t)x * wplane + (size_t)y * wrow; };
+  const RowMap ymap = make_rowmap(2 * (i64)wblock, 2 * wrow, yb, n1);
+  std::vector<long> wlog(wsize, -1);                        // element of W -> element of the logical (n0, n1, M) array, -1: a gap
+  for (int x = 0; x < n0; ++x)
+    for (int y = 0; y < n1; ++y)
+      for (int k = 0; k < M; ++k) wlog[woff(x, y) + k] = ((long)x * n1 + y) * M + k;
   auto tw = build_pass_twiddles<S, T>();
   auto rtw = build_real_twiddles<T>(N);
   // the long-double transform of axis `ax` (0: x, 1: y) of an (n0, n1, len) array
@@ -789,16 +799,16 @@ static void test_pair(int n0, int n1) {
     }
     xy(ref, Nf, 1, -1);
     xy(ref, Nf, 0, -1);
-    std::vector<cx<T>> W((size_t)n0 * wplane, mk<T>((T)9, (T)9)), fu((size_t)n0 * cplane, mk<T>((T)7, (T)7));
+    std::vector<cx<T>> W(wsize, mk<T>((T)9, (T)9)), fu((size_t)n0 * cplane, mk<T>((T)7, (T)7));
     for (int x = 0; x < n0; ++x)
       for (int y = 0; y < n1; ++y)
         for (int k = 0; k < M; ++k) {
           const cx<long double> z = w[((size_t)x * n1 + y) * M + k];
-          W[(size_t)x * wplane + (size_t)y * wrow + k] = mk<T>((T)z.x, (T)z.y);
+          W[woff(x, y) + k] = mk<T>((T)z.x, (T)z.y);
         }
     typedef R2CFft<S, T, ROWS, TWLDS, false, false, false, false, true> K;
     RealPairParams<T> P{{W.data(), fu.data(), tw.data(), rtw.data(), 2 * wrow, crow, slots, Nf, (T)1}};
-    P.pn0 = n0; P.pn1 = n1; P.p_rplane = 2 * wplane; P.p_cplane = cplane;
+    P.pn0 = n0; P.pn1 = n1; P.p_rplane = 2 * wplane; P.p_cplane = cplane; P.p_ymap = ymap;
     emu_launch(grid, K::THREADS, K::LDS_BYTES, [&](int b, int t, char* lds) { K::body(P, b, t, lds); });
     long double num = 0, den = 0;
     bool gaps = true;        // nothing outside the rows is written
@@ -812,13 +822,13 @@ static void test_pair(int n0, int n1) {
         gaps = false;
       }
     }
-    snprintf(name, sizeof name, "r2c pair r%d %dx%d%s", ROWS, n0, n1, TWLDS ? " twlds" : "");
+    snprintf(name, sizeof name, "r2c pair r%d %dx%d b%d%s", ROWS, n0, n1, yb, TWLDS ? " twlds" : "");
     report(name, N, pname<T>(), gaps ? (double)sqrtl(num / den) : 1.0, tol_of<T>());
   }
   {
     std::vector<cx<long double>> f((size_t)n0 * n1 * Nf);
     for (auto& z : f) { z.x = U(rng); z.y = U(rng); }
-    std::vector<cx<T>> fu((size_t)n0 * cplane, mk<T>((T)7, (T)7)), W((size_t)n0 * wplane, mk<T>((T)9, (T)9));
+    std::vector<cx<T>> fu((size_t)n0 * cplane, mk<T>((T)7, (T)7)), W(wsize, mk<T>((T)9, (T)9));
     for (int r = 0; r < n0 * n1; ++r)
       for (int k = 0; k < Nf; ++k) {
         const cx<T> z = mk<T>((T)f[(size_t)r * Nf + k].x, (T)f[(size_t)r * Nf + k].y);
@@ -842,13 +852,12 @@ static void test_pair(int n0, int n1) {
     }
     typedef C2RFft<S, T, ROWS, TWLDS, false, false, false, false, false, true> K;
     RealPairParams<T> P{{fu.data(), W.data(), tw.data(), rtw.data(), crow, 2 * wrow, slots, Nf, (T)(1.0 / N)}};
-    P.pn0 = n0; P.pn1 = n1; P.p_rplane = 2 * wplane; P.p_cplane = cplane;
+    P.pn0 = n0; P.pn1 = n1; P.p_rplane = 2 * wplane; P.p_cplane = cplane; P.p_ymap = ymap;
     emu_launch(grid, K::THREADS, K::LDS_BYTES, [&](int b, int t, char* lds) { K::body(P, b, t, lds); });
     bool gaps = true;
     std::vector<cx<long double>> w((size_t)n0 * n1 * M);
     for (size_t i = 0; i < W.size(); ++i) {
-      const int x = (int)(i / wplane), rem = (int)(i % wplane), y = rem / wrow, k = rem % wrow;
-      if (y < n1 && k < M) { w[((size_t)x * n1 + y) * M + k].x = W[i].x; w[((size_t)x * n1 + y) * M + k].y = W[i].y; }
+      if (wlog[i] >= 0) { w[wlog[i]].x = W[i].x; w[wlog[i]].y = W[i].y; }
       else if (W[i].x != (T)9 || W[i].y != (T)9) gaps = false;
     }
     xy(w, M, 1, +1);
@@ -859,7 +868,7 @@ static void test_pair(int n0, int n1) {
       num += a * a + b * b;
       den += ref[2 * i] * ref[2 * i] + ref[2 * i + 1] * ref[2 * i + 1];
     }
-    snprintf(name, sizeof name, "c2r pair r%d %dx%d%s", ROWS, n0, n1, TWLDS ? " twlds" : "");
+    snprintf(name, sizeof name, "c2r pair r%d %dx%d b%d%s", ROWS, n0, n1, yb, TWLDS ? " twlds" : "");
     report(name, N, pname<T>(), gaps ? (double)sqrtl(num / den) : 1.0, 4 * tol_of<T>());
   }
 }
@@ -2030,6 +2039,12 @@ int main() {
   test_pair<Spec<128, 16, 8>, double, 32, true>(12, 20);
   test_pair<Spec<512, 8, 8, 8>, double, 4, true>(3, 4);
   test_pair<Spec<1024, 16, 8, 8>, double, 2, false>(2, 3);
+  // the real side blocked in y: partner rows in another block, ky = n1 / 2 on a block start and inside one, one row per block
+  test_pair<Spec<32, 8, 4>, double, 4, true>(4, 6, 3);
+  test_pair<Spec<32, 8, 4>, double, 4, true>(4, 6, 2);
+  test_pair<Spec<32, 8, 4>, double, 64, true>(9, 15, 5);
+  test_pair<Spec<32, 8, 4>, double, 4, false>(5, 4, 1);
+  test_pair<Spec<128, 16, 8>, double, 32, true>(12, 20, 4);
 #endif
 #undef MFFT_PLAN
   printf("%s (%d failures)\n", g_fail ? "EMU TESTS FAILED" : "EMU TESTS PASSED", g_fail);

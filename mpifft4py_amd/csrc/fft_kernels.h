@@ -226,11 +226,14 @@ struct RealParams {            // r2c: in = real rows, out = complex rows; c2r t
 };
 // PAIR kernels: the rows are the (x, y) lines of a (pn0, pn1) mesh whose planes lie p_rplane reals (real side) and p_cplane
 // complex elements (complex side) apart, the strides of RealParams are the row pitches inside a plane, nrows counts row PAIRS
-// (a type of its own: the other kernels' arguments stay what they were)
+// (a type of its own: the other kernels' arguments stay what they were).  The real side may be blocked in y (plan_slab.hip, the
+// work array of the split-last route): row y of plane x then starts at (y / B) * hi + x * p_rplane + (y % B) * lo reals, which is
+// p_ymap with split = B (one group, hi = 0 and lo = the row pitch: the plain layout; pn1 < 2^16 for a real split).
 template <typename T>
 struct RealPairParams : RealParams<T> {
   int pn0, pn1;
   i64 p_rplane, p_cplane;
+  RowMap p_ymap;
 };
 
 // PAIR kernels (R2CFft / C2RFft): the real side holds, row by row, the x and y transforms of the real field read as complex
@@ -244,7 +247,7 @@ struct PairRow {
   bool live;                   // this (slot, side) stores a row
 };
 template <typename T>
-MFFT_D PairRow pair_row(const RealPairParams<T>& P, i64 q, int side, i64 real_pitch, i64 cplx_pitch) {
+MFFT_D PairRow pair_row(const RealPairParams<T>& P, i64 q, int side, i64 cplx_pitch) {
   const bool inrange = q < P.nrows;
   if (!inrange) q = P.nrows - 1;         // loads stay unconditional (see RowFft)
   const unsigned n0 = (unsigned)P.pn0, n1 = (unsigned)P.pn1;
@@ -254,7 +257,7 @@ MFFT_D PairRow pair_row(const RealPairParams<T>& P, i64 q, int side, i64 real_pi
   if (side && px == kx && py == ky) live = false;
   const unsigned x = side ? px : kx, y = side ? py : ky;
   PairRow r;
-  r.real_off = (i64)x * P.p_rplane + (i64)y * real_pitch;
+  r.real_off = (i64)x * P.p_rplane + row_off(P.p_ymap, y);
   r.cplx_off = (i64)x * P.p_cplane + (i64)y * cplx_pitch;
   r.live = live;
   return r;
@@ -846,7 +849,7 @@ struct R2CFft {
     XE* xch = reinterpret_cast<XE*>(lds + TW_BYTES) + rl * PLEN;
     const i64 row = (i64)bid * ROWS + rl;
     PairRow pr{};
-    if constexpr (PAIR) pr = pair_row<T>(P, (i64)bid * (ROWS / 2) + (rl >> 1), rl & 1, P.in_stride, P.out_stride);
+    if constexpr (PAIR) pr = pair_row<T>(P, (i64)bid * (ROWS / 2) + (rl >> 1), rl & 1, P.out_stride);
     const bool inrange = PAIR ? true : row < P.nrows;
     const bool active = PAIR ? pr.live : inrange && !dup;
     // a row of N reals read as N/2 complex (x[2n], x[2n+1])
@@ -1050,7 +1053,7 @@ struct C2RFft {
     XE* xch = reinterpret_cast<XE*>(lds + TW_BYTES) + rl * PLEN;
     const i64 row = (i64)bid * ROWS + rl;
     PairRow pr{};
-    if constexpr (PAIR) pr = pair_row<T>(P, (i64)bid * (ROWS / 2) + (rl >> 1), rl & 1, P.out_stride, P.in_stride);
+    if constexpr (PAIR) pr = pair_row<T>(P, (i64)bid * (ROWS / 2) + (rl >> 1), rl & 1, P.in_stride);
     const bool inrange = PAIR ? true : row < P.nrows;
     const bool active = PAIR ? pr.live : inrange && !dup;
     // rows past the end re-read the last row (unconditional loads: see RowFft) and store nothing

@@ -107,6 +107,10 @@ struct RealArgs {
   // strides above are the row pitches inside a plane and the planes lie pair_rplane reals / pair_cplane complex elements apart
   int pair_n0 = 0, pair_n1 = 0;      // 0: plain rows
   int64_t pair_rplane = 0, pair_cplane = 0;
+  // real side blocked in y: blocks of pair_yblock rows per plane, pair_rblock reals from block to block, pair_rplane from x row to
+  // x row INSIDE a block (fft_kernels.h RealPairParams::p_ymap); 0 or pair_n1: one block, the plain layout
+  int pair_yblock = 0;
+  int64_t pair_rblock = 0;
 };
 int launch_r2c(const RealArgs& a, hipStream_t s);
 int launch_c2r(const RealArgs& a, hipStream_t s);

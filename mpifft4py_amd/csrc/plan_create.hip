@@ -424,6 +424,13 @@ int mfft_plan_get_info(mfft_plan_t p, const char* key, int64_t* value) {
   else if (nonlinear_fused_key(p, k, value)) return 0;
   else if (k == "nonlinear_bytes") *value = (int64_t)(p->nlx.bytes + p->nly.bytes + p->nlr.bytes + p->nlw[0].bytes + p->nlw[1].bytes);
   else if (k == "split_last") *value = p->split_last_route() ? 1 : 0;   // the one-rank route that splits real / complex last (decides whether the work buffer fits, if no call has yet)
+  // layout of that route's work array (plan_impl.h SplitLastLayout; 0 where the plan does not take the route): rows per y block,
+  // elements between the x rows of a block and between blocks, the order (0 x first, 1 y first, 2 y first forward only); and the bytes of the work buffer as allocated
+  else if (k == "split_last_yblock") *value = p->split_last_route() ? p->split_last_layout().B : 0;
+  else if (k == "split_last_row_pitch") *value = p->split_last_route() ? p->split_last_layout().SR : 0;
+  else if (k == "split_last_block_pitch") *value = p->split_last_route() ? p->split_last_layout().SB : 0;
+  else if (k == "split_last_yfirst") *value = p->split_last_route() ? p->split_last_layout().yfirst : 0;
+  else if (k == "work_bytes") *value = (int64_t)p->work[0].bytes;
   else if (k == "plane_pad") *value = (p->P == 1 && p->d.decomp == MFFT_SLAB) ? p->p1_plane_pad() : 0;   // elements added to the intermediate's plane pitch
   else return set_error(MFFT_ERR_INVALID, "mfft_plan_get_info: unknown key '%s'", key);
   return 0;

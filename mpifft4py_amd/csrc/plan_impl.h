@@ -380,8 +380,26 @@ struct mfft_plan_s {
   int split_last = -1;          // MFFT_SPLIT_LAST, read when the plan is created: 0 never, 1 wherever the kernels exist, unset: by rule
   int split_last_fit = -1;      // the work buffer fits: decided at the first call
   int64_t split_last_pad() const { return plane_pad(N1 * (N2 / 2)); }
+  // The work array W of that route, logical shape (N0, N1, M = N2 / 2), may be blocked in y: element (x, y, m) lies at
+  // (y / B) * SB + x * SR + (y % B) * M + m.  B = N1 is the plain array (SR = its plane pitch), B = 1 the transposed one.
+  int split_last_yblock = -1;   // MFFT_SPLIT_LAST_YBLOCK, read when the plan is created: B; unset or not a divisor of N1: by rule
+  int split_last_yfirst = -1;   // MFFT_SPLIT_LAST_YFIRST: 1 = y, x, z forward and z, x, y inverse with both x passes in place on W,
+                                // 0 = x first (forward x and inverse x carry the caller's arrays), 2 = forward as 1, inverse as 0;
+                                // unset: by rule
+  int64_t split_last_pad_bytes = -1;   // MFFT_SPLIT_LAST_PAD: bytes added to B * M for SR (whole cache lines); unset: by rule
+  struct SplitLastLayout {
+    int64_t B, SR, SB, nblk;    // rows per block, elements from x row to x row of a block and from block to block, N1 / B
+    int yfirst;                 // 0, 1, 2 as split_last_yfirst
+    bool yfirst_fwd() const { return yfirst > 0; }
+    bool yfirst_bwd() const { return yfirst == 1; }
+    int64_t elems() const { return nblk * SB; }
+  };
+  SplitLastLayout split_last_layout() const;
   bool split_last_eligible() const;
   bool split_last_route();
+  int split_last_x(const SplitLastLayout& l, const void* user_in, void* user_out, void* W, bool inv);
+  int split_last_y(const SplitLastLayout& l, const void* user_in, void* user_out, void* W, bool inv);
+  int split_last_z(const SplitLastLayout& l, const void* in, void* out, bool inv);
   int slab_forward_split_last(const void* u, void* fu);
   int slab_backward_split_last(const void* fu, void* u);
   int slab_forward(const void* u, void* fu);

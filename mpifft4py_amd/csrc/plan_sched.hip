@@ -299,6 +299,9 @@ int mfft::decomp_init(mfft_plan_s* p, const mfft_plan_desc* desc, int nranks, in
   p->p1_xpad_lines = (int)env_int("MFFT_P1_XPAD", p->p1_xpad_lines);
   p->zpitch_on = !env_on("MFFT_NO_ZPITCH");
   if (getenv("MFFT_SPLIT_LAST")) p->split_last = env_on("MFFT_SPLIT_LAST") ? 1 : 0;
+  p->split_last_yblock = (int)env_int("MFFT_SPLIT_LAST_YBLOCK", p->split_last_yblock);
+  p->split_last_yfirst = (int)env_int("MFFT_SPLIT_LAST_YFIRST", p->split_last_yfirst);
+  p->split_last_pad_bytes = env_int("MFFT_SPLIT_LAST_PAD", p->split_last_pad_bytes);
   if (getenv("MFFT_PAD_ALIGN")) p->pad_align = env_on("MFFT_PAD_ALIGN") ? 1 : 0;
   p->pad_align_inv = (int)env_int("MFFT_PAD_ALIGN_INV", p->pad_align_inv);
   const int P = p->P;

@@ -32,6 +32,8 @@ bool mfft_plan_s::fwd_out_of_place(size_t cbytes) {
 // contiguous-axis kernels ever touch the caller's compact rows.  Same six launches, same bytes (2 * 6 R against 2 (R + 5 C)).
 // The inverse mirrors it: pair-merge z pass fu -> W, y in place on W, x out of place into u -- the pass that READS
 // power-of-two planes is the slow one (profiles/r02_power_of_two_stride.txt), so the padded W is what x reads.
+// (That is the order "x first"; split_last_layout below may pick y first -- y, x, z forward and z, x, y inverse, both x passes in
+// place on W -- and another layout of W.)
 // Results differ from the regular route's in the last bits (another order of the same sums).
 bool mfft_plan_s::split_last_eligible() const {
   if (d.decomp != MFFT_SLAB || P != 1 || !r2c || nat_pitch() || d.line2d || d.drop_nyquist || split_last == 0) return false;
@@ -41,10 +43,31 @@ bool mfft_plan_s::split_last_eligible() const {
   // large meshes with z rows of 8 KiB and more probably gain as well (same kernels, same strides in y); nobody has measured them.
   return prec == MFFT_DOUBLE && N0 == 1024 && N1 == 1024 && N2 == 1024;
 }
+// Layout of W and order of the passes.  By rule: the plain array (one block), planes plane_pad further apart, x first -- except on
+// the mesh the route is on for by itself (1024^3 in double precision), where the sweep of profiles/split_last_blocked_ab.txt picked
+// y first with the planes 16 KiB further apart (both x passes in place on W: 3.40 ms each against 3.81 / 3.46 with x first and one
+// line; no block came out ahead of that: small blocks bring the x passes to 3.03 - 3.11 ms and give it back in the y and z passes).
+// The switches of plan_impl.h choose another block, pad or order.  A block that does not divide N1 falls back to the plain array.  Blocked, SR and SB follow
+// the slow-pitch rules of the exchanged layouts (slow_pitch_pad: 64 KiB multiples, 2^a + 2^(a-7)); pads are whole cache lines, so
+// the non-temporal builds stay eligible.
+mfft_plan_s::SplitLastLayout mfft_plan_s::split_last_layout() const {
+  const int64_t M = N2 / 2;
+  SplitLastLayout l;
+  l.B = N1;
+  if (split_last_yblock > 0 && split_last_yblock < N1 && N1 % split_last_yblock == 0 && N1 < 65536) l.B = split_last_yblock;
+  l.nblk = N1 / l.B;
+  const bool rule_mesh = prec == MFFT_DOUBLE && N0 == 1024 && N1 == 1024 && N2 == 1024;
+  l.yfirst = split_last_yfirst >= 0 ? std::min(split_last_yfirst, 2) : rule_mesh ? 1 : 0;
+  int64_t pad_r = l.B == N1 ? (rule_mesh && l.yfirst > 0 ? (int64_t)(16384 / es) : split_last_pad()) : slow_pitch_pad(l.B * M);
+  if (split_last_pad_bytes >= 0 && split_last_pad_bytes % 128 == 0) pad_r = split_last_pad_bytes / (int64_t)es;
+  l.SR = l.B * M + pad_r;
+  l.SB = N0 * l.SR + (l.nblk > 1 ? slow_pitch_pad(N0 * l.SR) : 0);
+  return l;
+}
 bool mfft_plan_s::split_last_route() {
   if (!split_last_eligible()) return false;
   if (split_last_fit < 0) {      // the forward transform needs a work buffer now: as fwd_out_of_place decides
-    const size_t need = (size_t)(N0 * (N1 * (N2 / 2) + split_last_pad())) * es;
+    const size_t need = (size_t)split_last_layout().elems() * es;
     size_t fr = 0, tot = 0;
     if (work[0].bytes >= need) split_last_fit = 1;
     else if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); split_last_fit = 0; }
@@ -52,34 +75,57 @@ bool mfft_plan_s::split_last_route() {
   }
   return split_last_fit == 1;
 }
+// The two strided passes on W = (N1 / B blocks) x (N0 x rows) x (B y rows of M).  The x pass takes one outer batch per block, its
+// B * M columns contiguous on W's side (on the caller's side, x first, the same columns of the compact planes); the y pass one
+// outer batch per x, its rows on W's side two-level: B of them M apart, then the next block.  yfirst: y carries the caller's array
+// `user` (rows M apart: the fast case) and x runs in place on W; else x carries it and y runs in place.
+int mfft_plan_s::split_last_x(const SplitLastLayout& l, const void* user_in, void* user_out, void* W, bool inv) {
+  const int64_t M = N2 / 2;
+  const void* in = user_in ? user_in : W;
+  void* out = user_out ? user_out : W;
+  return col(in, out, N0, inv, l.nblk, l.B * M, user_in ? l.B * M : l.SB, plain(user_in ? N1 * M : l.SR),
+             user_out ? l.B * M : l.SB, plain(user_out ? N1 * M : l.SR));
+}
+int mfft_plan_s::split_last_y(const SplitLastLayout& l, const void* user_in, void* user_out, void* W, bool inv) {
+  const int64_t M = N2 / 2;
+  const void* in = user_in ? user_in : W;
+  void* out = user_out ? user_out : W;
+  const RowSpec wrows = two_level(l.B, l.SB, M);
+  return col(in, out, N1, inv, N0, M, user_in ? N1 * M : l.SR, user_in ? plain(M) : wrows, user_out ? N1 * M : l.SR,
+             user_out ? plain(M) : wrows);
+}
+int mfft_plan_s::split_last_z(const SplitLastLayout& l, const void* in, void* out, bool inv) {
+  RealArgs a = inv ? real_args(in, out, N0 * N1, N2, Nf, N2, 1.0 / (double)N2) : real_args(in, out, N0 * N1, N2, N2, Nf, 1.0);
+  a.pair_n0 = (int)N0; a.pair_n1 = (int)N1; a.pair_rplane = 2 * l.SR; a.pair_cplane = N1 * Nf;
+  a.pair_yblock = (int)l.B; a.pair_rblock = 2 * l.SB;
+  return inv ? mfft::launch_c2r(a, stream) : mfft::launch_r2c(a, stream);
+}
 int mfft_plan_s::slab_forward_split_last(const void* u, void* fu) {
-  const int64_t M = N2 / 2, pl = N1 * M + split_last_pad();
-  const double Wb = (double)(N0 * N1 * M) * es;
-  MFFT_TRY(ensure(work[0], (size_t)(N0 * pl) * es));
+  const SplitLastLayout l = split_last_layout();
+  const double Wb = (double)(N0 * N1 * (N2 / 2)) * es;
+  MFFT_TRY(ensure(work[0], (size_t)l.elems() * es));
   void* W = work[0].p;
-  // x first (out of place from u), y in place on W: the order the headline A/B was taken with (profiles/split_last_ab.txt
-  // section 1).  y first came out 0.1 - 0.25 ms ahead in two in-process rounds (section 2) but has no series of fresh
-  // processes against the parent behind it.
-  MFFT_TRY(stage("fwd_x", 2 * Wb, [&] { return col(u, W, N0, false, 1, N1 * M, 0, plain(N1 * M), 0, plain(pl)); }));
-  MFFT_TRY(stage("fwd_y", 2 * Wb, [&] { return col(W, W, N1, false, N0, M, pl, plain(M), pl, plain(M)); }));
-  return stage("fwd_z", Wb + (double)(N0 * N1 * Nf) * es, [&] {
-    RealArgs a = real_args(W, fu, N0 * N1, N2, N2, Nf, 1.0);
-    a.pair_n0 = (int)N0; a.pair_n1 = (int)N1; a.pair_rplane = 2 * pl; a.pair_cplane = N1 * Nf;
-    return mfft::launch_r2c(a, stream);
-  });
+  if (l.yfirst_fwd()) {
+    MFFT_TRY(stage("fwd_y", 2 * Wb, [&] { return split_last_y(l, u, nullptr, W, false); }));
+    MFFT_TRY(stage("fwd_x", 2 * Wb, [&] { return split_last_x(l, nullptr, nullptr, W, false); }));
+  } else {
+    MFFT_TRY(stage("fwd_x", 2 * Wb, [&] { return split_last_x(l, u, nullptr, W, false); }));
+    MFFT_TRY(stage("fwd_y", 2 * Wb, [&] { return split_last_y(l, nullptr, nullptr, W, false); }));
+  }
+  return stage("fwd_z", Wb + (double)(N0 * N1 * Nf) * es, [&] { return split_last_z(l, W, fu, false); });
 }
 int mfft_plan_s::slab_backward_split_last(const void* fu, void* u) {
-  const int64_t M = N2 / 2, pl = N1 * M + split_last_pad();
-  const double Wb = (double)(N0 * N1 * M) * es;
-  MFFT_TRY(ensure(work[0], (size_t)(N0 * pl) * es));
+  const SplitLastLayout l = split_last_layout();
+  const double Wb = (double)(N0 * N1 * (N2 / 2)) * es;
+  MFFT_TRY(ensure(work[0], (size_t)l.elems() * es));
   void* W = work[0].p;
-  MFFT_TRY(stage("bwd_z", Wb + (double)(N0 * N1 * Nf) * es, [&] {
-    RealArgs a = real_args(fu, W, N0 * N1, N2, Nf, N2, 1.0 / (double)N2);
-    a.pair_n0 = (int)N0; a.pair_n1 = (int)N1; a.pair_rplane = 2 * pl; a.pair_cplane = N1 * Nf;
-    return mfft::launch_c2r(a, stream);
-  }));
-  MFFT_TRY(stage("bwd_y", 2 * Wb, [&] { return col(W, W, N1, true, N0, M, pl, plain(M), pl, plain(M)); }));
-  return stage("bwd_x", 2 * Wb, [&] { return col(W, u, N0, true, 1, N1 * M, 0, plain(pl), 0, plain(N1 * M)); });
+  MFFT_TRY(stage("bwd_z", Wb + (double)(N0 * N1 * Nf) * es, [&] { return split_last_z(l, fu, W, true); }));
+  if (l.yfirst_bwd()) {
+    MFFT_TRY(stage("bwd_x", 2 * Wb, [&] { return split_last_x(l, nullptr, nullptr, W, true); }));
+    return stage("bwd_y", 2 * Wb, [&] { return split_last_y(l, nullptr, u, W, true); });
+  }
+  MFFT_TRY(stage("bwd_y", 2 * Wb, [&] { return split_last_y(l, nullptr, nullptr, W, true); }));
+  return stage("bwd_x", 2 * Wb, [&] { return split_last_x(l, nullptr, u, W, true); });
 }
 
 // ===========================================================================
