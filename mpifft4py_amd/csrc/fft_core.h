@@ -2,7 +2,7 @@
 //
 // Everything here is plain C++17 that compiles both as HIP device code (hipcc,
 // --offload-arch=gfx950) and as host code (g++), so that the exact same index
-// math can be exercised by the workgroup emulator in emu_test.cpp before a
+// math can be exercised by the workgroup emulator in emu/ before a
 // kernel ever reaches the GPU.  No CUDA-compat headers, no library FFT.
 //
 // Replaces (reference): the third-party per-rank FFT backends reached through

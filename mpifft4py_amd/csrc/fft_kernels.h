@@ -20,7 +20,7 @@
 //
 // The bodies are written once and compiled (a) by hipcc as __device__ code that
 // the __global__ wrappers in kernels.hip call, and (b) by g++ for the fibre-based
-// workgroup emulator (emu_test.cpp), where MFFT_BARRIER() yields to a scheduler.
+// workgroup emulator (emu/emu.h), where MFFT_BARRIER() yields to a scheduler.
 #pragma once
 #include <type_traits>
 #include "fft_core.h"
@@ -68,7 +68,7 @@ namespace mfft { void emu_barrier(); }
 #endif
 
 // Value of `x` in lane `src` of the caller's wave (64 lanes).  Device: one cross-lane read.  Host emulator: a round trip
-// through a per-workgroup slot array between two barriers (emu_test.cpp emu_shfl) -- every thread of the workgroup must
+// through a per-workgroup slot array between two barriers (emu/emu.h emu_shfl) -- every thread of the workgroup must
 // execute the same sequence of shuffles, which the kernels guarantee (they sit in fully unrolled, uniform loops) -- so
 // that the lane arithmetic of the shuffle paths is checked on the CPU as well.
 // WAVE_SHFL_DIRECT: the same on the device WITHOUT the function in between.  Through the `__forceinline__` template wrapper the

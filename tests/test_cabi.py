@@ -91,13 +91,45 @@ def test_fails_loudly_without_gpu(lib):
 
 def test_emulator_passes():
     """The fibre-based workgroup emulator runs the exact kernel bodies on the CPU
-    against a long-double DFT for every plan in plans.h."""
-    import glob
+    against a long-double DFT for every plan in plans.h: every group of csrc/emu/ passes, and no plan list of plans.h
+    is missing from what the groups print."""
+    import re
+    import tempfile
+    from emu_util import plan_lengths
     csrc = os.path.join(ROOT, "mpifft4py_amd", "csrc")
+    groups = subprocess.check_output(["make", "-s", "-C", csrc, "emu_list"]).decode().split()
+    assert groups
     subprocess.check_call(["make", "-C", csrc, "-j", "7", "emu"])
-    parts = sorted(glob.glob(os.path.join(csrc, "build", "emu_test_[0-9]")) + glob.glob(os.path.join(csrc, "build", "emu_test_[0-9][0-9]")))
-    assert len(parts) == 18, parts         # the plan list is split over eighteen binaries (Makefile: EMU_PARTS; 12 = the fused nonlinear z stage, 13 = radix 70, 14 - 17 = the 3/2-rule image plans of round 6)
-    procs = [subprocess.Popen([p], stdout=subprocess.PIPE) for p in parts]
-    for p, proc in zip(parts, procs):
-        out = proc.communicate()[0].decode()
+    parts = [os.path.join(csrc, "build", "emu_" + g) for g in groups]
+    assert all(os.path.exists(p) for p in parts), parts
+    outs = [tempfile.TemporaryFile() for p in parts]      # (not pipes: a group that fills its pipe would wait for its turn)
+    procs = [subprocess.Popen([p], stdout=f) for p, f in zip(parts, outs)]
+    lines = []
+    for p, proc, f in zip(parts, procs, outs):
+        proc.wait()
+        f.seek(0)
+        out = f.read().decode()
         assert proc.returncode == 0 and "EMU TESTS PASSED" in out, (p, out[-2000:])
+        lines += out.splitlines()
+
+    def seen(prefix):                      # the lengths N=<N> of the lines of one kernel family
+        return set(int(re.search(r" N=(\d+)\s", l).group(1)) for l in lines if l.startswith(prefix))
+
+    txt = open(os.path.join(csrc, "plans.h")).read().replace("\\\n", " ")
+    lists = []
+    for each in ("MFFT_FOR_EACH_PLAN", "MFFT_FOR_EACH_ROWPLAN"):
+        lists += re.findall(r"(MFFT_\w+)\(X\)", re.search(r"#define %s\(X\)(.*)" % each, txt).group(1))
+    assert len(lists) >= 22 + 7, lists
+    lists += ["MFFT_PLANS_S", "MFFT_ROWPLANS_F64_K"] + sorted(set(re.findall(r"#define (MFFT_COLPLANS_\w+)\(X\)", txt)))
+    col, row = seen("col "), seen("row ")
+    for name in lists:
+        lengths = plan_lengths(name)
+        assert lengths or "ROWPLANS" in name, name
+        for n in lengths:
+            assert n in col and n in row, (name, n)
+    col3 = [int(l) for l in re.findall(r"X\(\d+, (\d+),", re.search(r"#define MFFT_COL3PLANS_E\(X\)(.*)", txt).group(1))]
+    assert col3 and all(3 * l in col and 3 * l in row and 3 * l in seen("col3 ") for l in col3), col3
+    nlz = plan_lengths("MFFT_NLZPLANS_P2", "MFFT_NLZPLANS_3", "MFFT_NLZPLANS_9")
+    assert len(nlz) == 32 and set(nlz) <= seen("nlz "), sorted(set(nlz) - seen("nlz "))
+    nlz3 = plan_lengths("MFFT_NLZ3PLANS")
+    assert nlz3 and set(3 * l for l in nlz3) <= seen("nlz3 "), nlz3

@@ -10,42 +10,21 @@ to its own maximum).  Planted extremes: at every z position for rows of up to 64
 points, else at 0, 1, TPT - 1, TPT, M/2, M - 1, in the first row and in the last row of an odd count.  Then the five entry
 points of the feature in the header, the binding and the library, and advective_dt on a plan without a device.  A NaN in
 one input bin: NaN for that field only, NaNs in the product rows where the plain body has them."""
-import os
 import re
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mpifft4py_amd", "csrc")
+from emu_util import assert_entry_points, nlz_lengths, run_group
+
 NEW = ["mfft_nonlinear_cross_absmax", "mfft_nonlinear_dot_absmax", "mfft_plan_nonlinear_absmax", "mfft_nlz_rows_absmax",
        "mfft_ew_absmax"]
 
 
-def _nlz_lengths():
-    txt = open(os.path.join(CSRC, "plans.h")).read().replace("\\\n", " ")
-    out = []
-    for group in ("MFFT_NLZPLANS_P2", "MFFT_NLZPLANS_3", "MFFT_NLZPLANS_9"):
-        body = re.search(r"#define %s\(X\)(.*)" % group, txt).group(1)
-        out += [int(n) for n in re.findall(r"X\((\d+),", body)]
-    return out
-
-
-_RUN = []
-
-
-def _emu():
-    if not _RUN:                                       # one run serves both tests
-        subprocess.check_call(["make", "-C", CSRC, "emu_nlm"])
-        _RUN.append(subprocess.run([os.path.join(CSRC, "build", "emu_nlm")], stdout=subprocess.PIPE, text=True))
-    return _RUN[0]
-
-
 def test_absmax_bodies_in_the_emulator():
-    r = _emu()
+    r = run_group("nlm")
     assert r.returncode == 0 and "EMU TESTS PASSED" in r.stdout, r.stdout[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("nlm ")]
-    lengths = _nlz_lengths()
+    lengths = nlz_lengths()
     assert len(lengths) == 32
     for n in lengths:
         mine = [l for l in lines if re.search(r"N=%d\s" % n, l)]
@@ -80,7 +59,7 @@ def test_nan_in_one_field_gives_nan_for_that_field_only():
     it (fft_nlz.h take_out_nonfinite) and give them back to their own field after it: the emulator asserts NaN for field k,
     the other FIVE maxima against their long-double references, and NaNs in the product rows exactly where the plain body
     has them."""
-    r = _emu()
+    r = run_group("nlm")
     lines = [l for l in r.stdout.splitlines() if l.startswith("nlm ") and " nan in field" in l]
     fields = set(int(re.search(r"nan in field (\d)", l).group(1)) for l in lines)
     assert len(lines) >= 2 * 32 and min(fields) < 3 <= max(fields), (len(lines), fields)      # first-field and second-field cases
@@ -88,17 +67,7 @@ def test_nan_in_one_field_gives_nan_for_that_field_only():
 
 
 def test_new_entry_points_in_header_binding_and_library():
-    from mpifft4py_amd import _lib
-    header = open(os.path.join(ROOT, "include", "mpifft4py_amd.h")).read()
-    declared = set(re.findall(r"MFFT_API\s+[\w\s\*]+?\b(mfft_\w+)\s*\(", header))
-    if not os.path.exists(_lib.LIB_PATH):
-        subprocess.check_call(["make", "-C", CSRC, "-j8"])
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
-    exported = set(l.split()[-1] for l in nm.splitlines() if " T " in l)
-    for name in NEW:
-        assert name in declared, name
-        assert name in _lib.exported_symbols(), name
-        assert name in exported, name
+    assert_entry_points(NEW)
 
 
 def test_advective_dt_on_a_layout_plan():

@@ -3,31 +3,18 @@ against long-double DFTs of sum_f irfft(a_f) irfft(b_f) -- every plan of MFFT_NL
 wave-synchronous and barrier builds, whole-complex and split exchanges, with and without LDS twiddles, limited `valid`, pruned
 `valid_in`, out of place and over an input, an odd row count -- and the four entry points of the operation are in the header,
 the binding and the library."""
-import os
 import re
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mpifft4py_amd", "csrc")
+from emu_util import assert_entry_points, nlz_lengths, run_group
+
 NEW = ["mfft_nonlinear_dot", "mfft_nlz_dot_rows", "mfft_ew_dot", "mfft_ew_grad_hat"]
 
 
-def _nlz_lengths():
-    txt = open(os.path.join(CSRC, "plans.h")).read().replace("\\\n", " ")
-    out = []
-    for group in ("MFFT_NLZPLANS_P2", "MFFT_NLZPLANS_3", "MFFT_NLZPLANS_9"):
-        body = re.search(r"#define %s\(X\)(.*)" % group, txt).group(1)
-        out += [int(n) for n in re.findall(r"X\((\d+),", body)]
-    return out
-
-
 def test_dot_bodies_in_the_emulator():
-    subprocess.check_call(["make", "-C", CSRC, "emu_nld"])
-    exe = os.path.join(CSRC, "build", "emu_nld")
-    r = subprocess.run([exe], stdout=subprocess.PIPE, text=True)
+    r = run_group("nld")
     assert r.returncode == 0 and "EMU TESTS PASSED" in r.stdout, r.stdout[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("nld ")]
-    lengths = _nlz_lengths()
+    lengths = nlz_lengths()
     assert len(lengths) == 32
     for n in lengths:
         mine = [l for l in lines if re.search(r"N=%d\s" % n, l)]
@@ -41,14 +28,4 @@ def test_dot_bodies_in_the_emulator():
 
 
 def test_new_entry_points_in_header_binding_and_library():
-    from mpifft4py_amd import _lib
-    header = open(os.path.join(ROOT, "include", "mpifft4py_amd.h")).read()
-    declared = set(re.findall(r"MFFT_API\s+[\w\s\*]+?\b(mfft_\w+)\s*\(", header))
-    if not os.path.exists(_lib.LIB_PATH):
-        subprocess.check_call(["make", "-C", CSRC, "-j8"])
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
-    exported = set(l.split()[-1] for l in nm.splitlines() if " T " in l)
-    for name in NEW:
-        assert name in declared, name
-        assert name in _lib.exported_symbols(), name
-        assert name in exported, name
+    assert_entry_points(NEW)

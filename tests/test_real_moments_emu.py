@@ -6,34 +6,13 @@ centre, a NaN and an Inf in one bin of one field.  Per case min, max and the fou
 long-double transforms of the rows: extremes within tol * max|x|, S_p within tol * p * sqrt(sum d^(2(p-1)) * sum x^2) +
 (count + 8) * 2^-52 * sum |d|^p (d = x - centre; tol = 4e-14 / 2e-5, the tolerance emu_nld applies to rows).  Then the entry
 points of the feature in the header, the binding and the library, and the host arithmetic of `spectral.Moments`."""
-import os
 import re
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mpifft4py_amd", "csrc")
+from emu_util import assert_entry_points, nlz_lengths, run_group
+
 NEW = ["mfft_real_moments", "mfft_ew_moments", "mfft_nlz_moments_rows", "mfft_nlz_moments_groups", "mfft_ew_diag_grad_hat"]
-
-
-def _nlz_lengths():
-    txt = open(os.path.join(CSRC, "plans.h")).read().replace("\\\n", " ")
-    out = []
-    for group in ("MFFT_NLZPLANS_P2", "MFFT_NLZPLANS_3", "MFFT_NLZPLANS_9"):
-        body = re.search(r"#define %s\(X\)(.*)" % group, txt).group(1)
-        out += [int(n) for n in re.findall(r"X\((\d+),", body)]
-    return out
-
-
-_RUN = []
-
-
-def _emu():
-    if not _RUN:                                       # one run serves both tests
-        subprocess.check_call(["make", "-C", CSRC, "emu_nls"])
-        _RUN.append(subprocess.run([os.path.join(CSRC, "build", "emu_nls")], stdout=subprocess.PIPE, text=True))
-    return _RUN[0]
 
 
 def _case(l):
@@ -42,10 +21,10 @@ def _case(l):
 
 
 def test_moments_body_in_the_emulator():
-    r = _emu()
+    r = run_group("nls")
     assert r.returncode == 0 and "EMU TESTS PASSED" in r.stdout, r.stdout[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("nls ")]
-    lengths = _nlz_lengths()
+    lengths = nlz_lengths()
     assert len(lengths) == 32
     for n in lengths:
         mine = [l for l in lines if re.search(r"N=%d\s" % n, l)]
@@ -73,7 +52,7 @@ def test_nonfinite_bin_marks_its_field_only():
     """A NaN bin of one field: NaN in all six of its statistics; an Inf bin: NaN sums, extremes -Inf / +Inf or NaN.  The other
     fields -- the partner on the same complex transform among them -- against their long-double references as before
     (fft_nlz.h take_out_nonfinite): the "nan in field k" / "inf in field k" lines of the run."""
-    r = _emu()
+    r = run_group("nls")
     lines = [l for l in r.stdout.splitlines() if l.startswith("nls ") and " in field" in l]
     assert len(lines) >= 3 * 32, len(lines)
     assert r.returncode == 0 and all(l.rstrip().endswith("ok") for l in lines), r.stdout[-2000:]
@@ -82,17 +61,7 @@ def test_nonfinite_bin_marks_its_field_only():
 
 
 def test_new_entry_points_in_header_binding_and_library():
-    from mpifft4py_amd import _lib
-    header = open(os.path.join(ROOT, "include", "mpifft4py_amd.h")).read()
-    declared = set(re.findall(r"MFFT_API\s+[\w\s\*]+?\b(mfft_\w+)\s*\(", header))
-    if not os.path.exists(_lib.LIB_PATH):
-        subprocess.check_call(["make", "-C", CSRC, "-j8"])
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
-    exported = set(l.split()[-1] for l in nm.splitlines() if " T " in l)
-    for name in NEW:
-        assert name in declared, name
-        assert name in _lib.exported_symbols(), name
-        assert name in exported, name
+    assert_entry_points(NEW)
 
 
 def test_moments_object_host_arithmetic():
