@@ -30,7 +30,7 @@ def _zero(a):
 
 def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double", nu=0.000625, dt=0.01, steps=10,
           report=None, fused=True, timing=False, complex_pitch="default", edge=None, spectrum=False, cfl=None, dt_max=None,
-          stats=False):
+          stats=False, pdf=False):
     """fused=True (round 6): the nonlinear term is ONE plan operation (spectral.cross_transform: no real-space work
     arrays, the z stages one kernel) and a Runge-Kutta stage's projection, viscous term, both updates and the next
     curl are ONE sweep (spectral.ns_rk_stage).  fused=False: the composition of rounds 3 - 5 (nine transforms, cross,
@@ -43,7 +43,9 @@ def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double
     it.  report["dt"] lists the steps' dt, report["wmax"] their max |omega|; rank 0 prints both.
     stats=True (fused loop): report["stats"] holds the one-point statistics of the final state -- spectral.Moments of the three
     longitudinal derivatives du_f/dx_f ("grad"), and of u and omega together ("u_omega": six fields) -- from
-    spectral.real_moments: the fields exist as spectra only, no real array is written for them."""
+    spectral.real_moments: the fields exist as spectra only, no real array is written for them.
+    pdf=True (fused loop): report["pdf"] = (Histogram, mean, sigma) of du_0/dx_0 of the final state over +-8 of its standard deviations
+    in 32 bins, from spectral.real_histogram on the same spectrum (the z kernel ends in a histogram)."""
     if complex_pitch == "default":       # the fused loop on ONE rank keeps its spectra pitched (rows a whole number of cache lines
         # apart: every pass runs on them); several ranks and the composition of rounds 3 - 5 keep compact rows
         complex_pitch = "auto" if (fused and comm.Get_size() == 1) else None
@@ -53,6 +55,8 @@ def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double
         raise ValueError("cfl needs the fused loop: the composition has no statistics call")
     if stats and not fused:
         raise ValueError("stats needs the fused loop: the composition holds no curl of the final state")
+    if pdf and not fused:
+        raise ValueError("pdf needs the fused loop")
     if decomposition == 'slab':
         FFT = Slab_R2C(N, L, comm, precision, complex_pitch=complex_pitch)
     else:
@@ -125,6 +129,14 @@ def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double
             grad = spectral.real_moments(FFT, spectral.diag_grad_hat(FFT, K, U_hat, FFT.empty_complex(3)), None, dealias)
             if report is not None:
                 report["stats"] = {"u_omega": uw, "grad": grad}
+        if pdf:                                                 # (collective: a moments call for sigma, then the histogram)
+            G = spectral.diag_grad_hat(FFT, K, U_hat, FFT.empty_complex(3))
+            g0 = G.component(0)
+            m = spectral.real_moments(FFT, g0, None, dealias)
+            mean, sigma = float(m.mean()[0]), float(np.sqrt(m.variance()[0]))
+            h = spectral.real_histogram(FFT, g0, None, dealias, bins=32, range=(mean - 8 * sigma, mean + 8 * sigma))
+            if report is not None:
+                report["pdf"] = (h, mean, sigma)
         for i in range(3):
             FFT.ifftn(U_hat.component(i), U.component(i))
         return FFT.comm.reduce(spectral.sumsq(FFT, U) / float(N[0]) / float(N[1]) / float(N[2]) / 2)
@@ -196,6 +208,8 @@ def main():
     ap.add_argument("--dt-max", type=float, default=None, help="with --cfl: dt = min(DT_MAX, advective dt)")
     ap.add_argument("--stats", action="store_true", help="print skewness and flatness of du_f/dx_f and of u_f and min / max of omega_f of the final "
                     "state, from the spectra (spectral.real_moments: no real-space array)")
+    ap.add_argument("--pdf", action="store_true", help="print the PDF of du_0/dx_0 of the final state in units of its standard deviation, from "
+                    "the spectrum (spectral.real_histogram: no real-space array)")
     args = ap.parse_args()
     dealias = None if args.dealias == "None" else args.dealias
     from mpifft4py_amd import LocalGroup, SelfComm
@@ -204,11 +218,11 @@ def main():
         ks = LocalGroup(args.ranks).run(lambda c: solve(c, args.M, dealias, steps=args.steps, precision=args.precision,
                                                         report=rep if c.Get_rank() == 0 else None, fused=not args.composed,
                                                         timing=args.stages, complex_pitch=None if args.compact else "default",
-                                                        edge=args.N or None, spectrum=args.spectrum, cfl=args.cfl, dt_max=args.dt_max, stats=args.stats))
+                                                        edge=args.N or None, spectrum=args.spectrum, cfl=args.cfl, dt_max=args.dt_max, stats=args.stats, pdf=args.pdf))
     else:
         ks = [solve(SelfComm(), args.M, dealias, steps=args.steps, precision=args.precision, report=rep,
                     fused=not args.composed, timing=args.stages, complex_pitch=None if args.compact else "default",
-                    edge=args.N or None, spectrum=args.spectrum, cfl=args.cfl, dt_max=args.dt_max, stats=args.stats)]
+                    edge=args.N or None, spectrum=args.spectrum, cfl=args.cfl, dt_max=args.dt_max, stats=args.stats, pdf=args.pdf)]
     print("N = %d^3, %d RK4 steps, %.3f ms per step (%s, device-resident; plan work buffers %.2f GB)"
           % (args.N or 2 ** args.M, args.steps, rep.get("ms_per_step", float("nan")),
              "composed: 36 transforms + element-wise kernels" if args.composed else
@@ -232,6 +246,13 @@ def main():
         print("du_f/dx_f: skewness = %s  flatness = %s" % (fmt(grad.skewness()), fmt(grad.flatness())))
         print("u: skewness = %s  flatness = %s" % (fmt(uw.skewness()[:3]), fmt(uw.flatness()[:3])))
         print("omega: min = %s  max = %s" % (fmt(uw.min[3:]), fmt(uw.max[3:])))
+    if args.pdf:
+        h, mean, sigma = rep["pdf"]
+        width = (h.hi[0] - h.lo[0]) / h.nbins / sigma              # in units of sigma: the density below is that of (x - mean) / sigma
+        tails = float(h.below[0] + h.above[0] + h.nonfinite[0]) / h.count
+        print("PDF of du_0/dx_0 in units of its sigma = %.9e (%d points, bin width %.17g, outside the range: %.17g)" % (sigma, h.count, width, tails))
+        for c, p in zip((h.centers(0) - mean) / sigma, h.pdf(0) * sigma):
+            print("pdf %+.4f %.17g" % (c, p))
     if args.M == 5 and not args.N and args.steps == 10 and args.precision == "double" and args.cfl is None:
         assert round(ks[0] - 0.124953117517, 7) == 0
         print("matches the reference demo's known answer 0.124953117517")

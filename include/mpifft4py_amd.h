@@ -272,6 +272,27 @@ MFFT_API int mfft_nlz_rows_absmax(const void* a, const void* b, void* out, int64
 MFFT_API int mfft_nlz_moments_rows(const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
                                    int64_t valid_in, int precision, const double* center, double* out);
 MFFT_API int64_t mfft_nlz_moments_groups(int64_t nrows, int64_t n, int precision);
+/* Histograms: the slot rule that the host, the sweep, the fused kernel and the tests share.  For a real value x (numpy's
+ * normalisation, taken to double in both precisions), a field's lo < hi (both finite) and 1 <= nbins <= MFFT_HIST_MAXBINS:
+ *     inv  = nbins / (hi - lo)            formed once on the host, in double
+ *     t    = (x - lo) * inv               a subtraction, then a multiplication
+ *     slot = x != x      ? nbins + 2      not finite; tested first
+ *          : t <  0      ? 0              below lo (-Inf lands here)
+ *          : t >= nbins  ? nbins + 1      at or above hi (+Inf lands here); compared before the cast to int
+ *          :               1 + (int)t
+ * A result is nbins + 3 int64 counts per field; they always sum to the number of points. */
+#define MFFT_HIST_MAXBINS 512
+/* The z stage that ends in a histogram (csrc/fft_nlz.h body_hist), synchronous: the histograms of the real rows irfft(row, n)
+ * without the real rows.  Fields, rows, valid and valid_in as mfft_nlz_moments_rows; lo[f], hi[f] per field, in the order a_0..,
+ * then b_0..; out[f * (nbins + 3) + slot].  Counts are integers: bitwise reproducible, whatever the launch looks like.  A NaN or
+ * Inf bin of a field puts at least one count into THAT field's slot nbins + 2, its slots still sum to nrows * n; every other
+ * field, the partner on the same transform included, has exactly the counts of the run without the bad bin.
+ * MFFT_ERR_UNSUPPORTED for lengths without a kernel, MFFT_ERR_INVALID for nbins outside 1 .. MFFT_HIST_MAXBINS, hi <= lo and
+ * valid > n / 2 + 1.  The z stage of mfft_real_histogram on its own, for tests.
+ * mfft_nlz_hist_groups: the workgroups of that launch (it strides over the rows; 0: no kernel of that length). */
+MFFT_API int mfft_nlz_hist_rows(const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
+                                int64_t valid_in, int precision, const double* lo, const double* hi, int nbins, int64_t* out);
+MFFT_API int64_t mfft_nlz_hist_groups(int64_t nrows, int64_t n, int precision);
 /* slab pack / unpack (slab.py:403; cython/maths.pyx:21-31 transpose_Uc) */
 MFFT_API int mfft_slab_pack(const void* uc_hatT, void* u_mpi, int P, int64_t np0, int64_t np1, int64_t nf, int precision);
 MFFT_API int mfft_slab_unpack(const void* u_mpi, void* uc_hatT, int P, int64_t np0, int64_t np1, int64_t nf, int precision);
@@ -355,6 +376,24 @@ MFFT_API int mfft_ew_moments(mfft_plan_t plan, const void* x, int ncomp, size_t 
  * and NaN / +-Inf extremes for its field.  The inputs are preserved.  Synchronises the plan's stream. */
 MFFT_API int mfft_real_moments(mfft_plan_t plan, const void* a_hat, const void* b_hat, int ncomp, int dealias, const double* center,
                                double* out, int64_t* count);
+
+/* out_host[c * (nbins + 3) + slot]: the histogram of a real device array (ncomp, n), ncomp = 1, 2, 3 or 6, in the plan's
+ * precision, by the slot rule above with lo[c], hi[c].  The companion of mfft_ew_moments: one sweep, 16 bytes per lane, counts
+ * in a workgroup's LDS, plain stores, one fold in fixed order into int64; no global atomics.  The plan must not be null;
+ * synchronises the plan's stream. */
+MFFT_API int mfft_ew_histogram(mfft_plan_t plan, const void* x, int ncomp, size_t n, int precision, const double* lo, const double* hi,
+                               int nbins, int64_t* out_host);
+
+/* Histograms of fields that exist as spectra only: for the ncomp (1 or 3) components of a_hat and, where b_hat is not NULL, of
+ * b_hat -- 1, 2, 3 or 6 fields, in that order -- out[f * (nbins + 3) + slot] = the counts of x = ifftn(field f, dealias) by the
+ * slot rule above with lo[f], hi[f], over THIS RANK's part of the real-space grid (as mfft_real_moments), *count = the points
+ * counted (every field's slots sum to it).  The routes are those of mfft_real_moments (mfft_plan_get_info
+ * "nonlinear_histogram_fused_3_2" / "_none" / "_2_3"): fused, the z kernel ends in a histogram (csrc/fft_nlz.h body_hist) and no
+ * real-space array exists; every other plan transforms one field at a time into ONE real work array and sweeps it
+ * (mfft_ew_histogram).  Integers: bitwise reproducible run to run, and the same on every device and for every number of ranks of
+ * a fused slab plan.  The inputs are preserved.  Synchronises the plan's stream. */
+MFFT_API int mfft_real_histogram(mfft_plan_t plan, const void* a_hat, const void* b_hat, int ncomp, int dealias, const double* lo,
+                                 const double* hi, int nbins, int64_t* out, int64_t* count);
 
 /* The nonlinear term of a pseudo-spectral step as ONE operation:
  *     out_hat = fftn(ifftn(a_hat) x ifftn(b_hat))        (cross product in real space, component by component)

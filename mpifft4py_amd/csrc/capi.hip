@@ -376,6 +376,60 @@ int64_t mfft_nlz_moments_groups(int64_t nrows, int64_t n, int precision) {
   return ngroups;
 }
 
+// The stage that ends in a histogram (fft_nlz.h body_hist), synchronous.  Fields and rows as mfft_nlz_moments_rows;
+// out[f * (nbins + 3) + slot] = counts of irfft(row, n) over all rows, fields in the order a_0.., then b_0...
+int mfft_nlz_hist_rows(const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid, int64_t valid_in,
+                       int precision, const double* lo, const double* hi, int nbins, int64_t* out) {
+  if (!a || !out || !lo || !hi || nrows < 1 || n < 2 || n >= 65536 || pitch < valid || valid < 1 || valid > n / 2 + 1 || valid_in < 0 || valid_in > valid)
+    return set_error(MFFT_ERR_INVALID, "bad argument");
+  if (precision != MFFT_DOUBLE && precision != MFFT_SINGLE) return set_error(MFFT_ERR_INVALID, "unknown precision %d", precision);
+  if ((nfields != 1 && nfields != 2 && nfields != 3 && nfields != 6) || ((nfields % 2 == 0) != (b != nullptr)))
+    return set_error(MFFT_ERR_INVALID, "nfields must be 1 or 3 (a alone) or 2 or 6 (a and b), not %d", nfields);
+  const size_t es = elem_bytes(precision, true);
+  const int ncomp = b ? nfields / 2 : nfields;
+  NlhArgs z;
+  int slot_of[6] = {0, 0, 0, 0, 0, 0};
+  for (int f = 0; f < nfields; ++f) {
+    const int slot = b ? (f < ncomp ? 2 * f : 2 * (f - ncomp) + 1) : f;
+    const char* base = static_cast<const char*>(f < ncomp ? a : b) + (size_t)((f % ncomp) * nrows * pitch) * es;
+    (slot % 2 ? z.b : z.a)[slot / 2] = base;
+    MFFT_TRY(hist_range(lo[f], hi[f], nbins, &z.inv[slot]));
+    z.lo[slot] = lo[f];
+    slot_of[f] = slot;
+  }
+  z.npairs = (nfields + 1) / 2;
+  z.nbins = nbins;
+  z.n = (int)n; z.prec = precision; z.in_stride = pitch; z.nrows = nrows; z.valid = (int)valid; z.valid_in = (int)valid_in;
+  z.norm = 1.0 / (double)n;
+  int ngroups = 0;
+  int64_t max_rows = 0;
+  MFFT_TRY(nlh_launch_shape(n, precision, nrows, &ngroups, &max_rows));
+  const int nb3 = nbins + 3, nslots = 2 * z.npairs;
+  const size_t acc_bytes = (size_t)nslots * nb3 * sizeof(int64_t);
+  char* buf = nullptr;
+  MFFT_HIP(hipMalloc(reinterpret_cast<void**>(&buf), acc_bytes + hist_part_bytes(ngroups, nslots, nbins)));
+  int64_t* acc = reinterpret_cast<int64_t*>(buf);
+  z.part = buf + acc_bytes;
+  int rc = 0;
+  if (hipMemsetAsync(acc, 0, acc_bytes, nullptr) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemsetAsync failed");
+  if (!rc) rc = hist_rows(z, acc, nullptr);
+  std::vector<int64_t> host((size_t)nslots * nb3);
+  if (!rc && hipMemcpy(host.data(), acc, acc_bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemcpy failed");
+  if (hipStreamSynchronize(nullptr) != hipSuccess && !rc) rc = set_error(MFFT_ERR_HIP, "hipStreamSynchronize failed");
+  (void)hipFree(buf);
+  if (!rc)
+    for (int f = 0; f < nfields; ++f)
+      for (int k = 0; k < nb3; ++k) out[(size_t)f * nb3 + k] = host[(size_t)slot_of[f] * nb3 + k];
+  return rc;
+}
+// workgroups of that launch (0: no kernel of that length)
+int64_t mfft_nlz_hist_groups(int64_t nrows, int64_t n, int precision) {
+  int ngroups = 0;
+  int64_t max_rows = 0;
+  if (nlh_launch_shape(n, precision, nrows, &ngroups, &max_rows) != 0) return 0;
+  return ngroups;
+}
+
 // U_mpi[p, i, j, k] = Uc_hatT[i, p*Np1 + j, k]   (slab.py:403)
 int mfft_slab_pack(const void* uc_hatT, void* u_mpi, int P, int64_t np0, int64_t np1, int64_t nf, int precision) {
   if (!uc_hatT || !u_mpi || P < 1) return set_error(MFFT_ERR_INVALID, "bad argument");

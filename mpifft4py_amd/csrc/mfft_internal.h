@@ -148,6 +148,7 @@ constexpr NlProduct NL_PRODUCTS[] = {
     {Op::Dot, "dot", 6, 1, true, false},
     {Op::CrossDot, "cross_dot", 9, 4, false, false},
     {Op::Moments, "moments", 6, 0, false, false},      // (up to six fields: the call says how many, NlFields::nfields)
+    {Op::Histogram, "histogram", 6, 0, false, false},
 };
 inline const NlProduct& nl_product(Op op) {
   for (const NlProduct& q : NL_PRODUCTS)
@@ -179,6 +180,37 @@ int launch_nls(const NlsArgs& a, hipStream_t s);
 // identity (+Inf, -Inf, zeros); moments_fold: acc[v] = merge(acc[v], the groups' part[g * nvals + v] in a fixed order), NaNs kept.
 int moments_clear(double* acc, int nvals, hipStream_t s);
 int moments_fold(const double* part, size_t groups, int nvals, double* acc, hipStream_t s);
+// The z stage that ends in a histogram (fft_nlz.h body_hist): pairs as in NlsArgs; per field nbins + 3 counts of x = norm * (the
+// un-normalised inverse transform) -- below lo, the nbins bins of [lo, hi), at or above hi, not finite (fft_nlz.h hist_slot).
+struct NlhArgs {
+  const void* a[3] = {nullptr, nullptr, nullptr};
+  const void* b[3] = {nullptr, nullptr, nullptr};
+  int npairs = 0;
+  int n = 0;             // REAL length of a z row
+  int prec = MFFT_DOUBLE;
+  int64_t in_stride = 0, nrows = 0;   // complex elements
+  int valid = 0;         // bins per row present in memory (0 = all n/2+1)
+  int valid_in = 0;      // bins per row that are read, where fewer (pruned 2/3-rule); 0 = valid
+  double norm = 1.0;
+  double lo[6] = {0, 0, 0, 0, 0, 0}, inv[6] = {1, 1, 1, 1, 1, 1};   // [pair][a, b]: lower edge, nbins / (hi - lo)
+  int nbins = 0;
+  int ngroups = 0;       // workgroups of the launch, from nlh_launch_shape() of (n, prec, nrows)
+  void* part = nullptr;  // (ngroups, npairs, 2, nbins + 3) unsigned counts: hist_fold adds them up
+};
+// workgroups of the launch over nrows rows, and the rows ONE launch may take so that no workgroup counts 2^32 values (the caller
+// splits a longer run of rows into launches of at most that many)
+int nlh_launch_shape(int64_t n, int prec, int64_t nrows, int* ngroups, int64_t* max_rows);
+int launch_nlh(const NlhArgs& a, hipStream_t s);
+// all rows of z (ngroups not set; part holds hist_part_bytes() of the shape's ngroups): launches of at most max_rows rows, each
+// folded into acc (slot order, rows nbins + 3 apart) -- counts accumulate over launches and calls
+size_t hist_part_bytes(int ngroups, int nslots, int nbins);
+int hist_rows(const NlhArgs& z, int64_t* acc, hipStream_t s);
+// Histograms (hist.hip).  acc: device int64, (nfields, nbins + 3).  hist_fold: acc[f][s] += sum over the groups g, in fixed
+// order, of part[(g * nfields + f) * (nbins + 3) + s]; nfields <= 6.
+int hist_fold(const unsigned* part, size_t groups, int nfields, int nbins, int64_t* acc, hipStream_t s);
+// inv = nbins / (hi - lo) of a valid range; MFFT_ERR_INVALID for nbins outside 1 .. NLH_MAXBINS, hi <= lo, a range that is not finite
+int hist_range(double lo, double hi, int nbins, double* inv);
+int hist_max_bins();
 // max |x| reductions (absmax.hip): acc[s] = max(acc[s], scale * max_g part[g * period + s]), NaNs kept; `scratch` holds
 // absmax_fold_scratch_bytes(), `part` is in precision `prec`, acc in double
 size_t absmax_fold_scratch_bytes();

@@ -9,7 +9,7 @@ using namespace mfft;
 #endif
 
 mfft_plan_s::~mfft_plan_s() {
-  for (Buf* b : {&work[0], &work[1], &work[2], &work3, &nlw[0], &nlw[1], &nlx, &nly, &nlr, &pcomp, &shl, &nlm, &nlmacc, &nlsacc})
+  for (Buf* b : {&work[0], &work[1], &work[2], &work3, &nlw[0], &nlw[1], &nlx, &nly, &nlr, &pcomp, &shl, &nlm, &nlmacc, &nlsacc, &nlhacc})
     if (b->p) (void)(b->arena ? wfree(b->p) : dev_free(b->p));
   if (mask) (void)hipFree(mask);
   if (band_tiles) (void)hipFree(band_tiles);
@@ -384,6 +384,21 @@ int mfft_real_moments(mfft_plan_t p, const void* a_hat, const void* b_hat, int n
   u.ncomp = ncomp;
   u.nfields = b_hat ? 2 * ncomp : ncomp;
   return p->real_moments(u, dealias, center, out, count);
+}
+
+// counts of ifftn(field, dealias) in nbins equal bins per field, for the ncomp components of a and, where given, of b: see
+// include/mpifft4py_amd.h
+int mfft_real_histogram(mfft_plan_t p, const void* a_hat, const void* b_hat, int ncomp, int dealias, const double* lo, const double* hi,
+                        int nbins, int64_t* out, int64_t* count) {
+  if (!out || !count || !lo || !hi) return set_error(MFFT_ERR_INVALID, "null argument");
+  MFFT_TRY(check_ready(p, a_hat, a_hat));
+  if (ncomp != 1 && ncomp != 3) return set_error(MFFT_ERR_INVALID, "ncomp must be 1 or 3, not %d", ncomp);
+  if (dealias != MFFT_DEALIAS_NONE && dealias != MFFT_DEALIAS_2_3 && dealias != MFFT_DEALIAS_3_2)
+    return set_error(MFFT_ERR_INVALID, "unknown dealias mode %d", dealias);
+  NlFields u{a_hat, b_hat, nullptr, nullptr, nullptr};
+  u.ncomp = ncomp;
+  u.nfields = b_hat ? 2 * ncomp : ncomp;
+  return p->real_histogram(u, dealias, lo, hi, nbins, out, count);
 }
 
 int mfft_plan_sync(mfft_plan_t p) {

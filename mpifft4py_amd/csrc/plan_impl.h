@@ -136,6 +136,11 @@ struct mfft_plan_s {
   // mfft_real_moments / mfft_ew_moments (moments.hip): 36 statistics in slot order, then the six centres; the partials go to nlm
   Buf nlsacc{false, false};
   double nls_center[6] = {0, 0, 0, 0, 0, 0};
+  // mfft_real_histogram / mfft_ew_histogram (hist.hip): 6 x (NLH_MAXBINS + 3) int64 counts in slot order, rows nbins + 3 apart,
+  // cleared on the stream when a call starts; the workgroups' partial histograms go to nlm.  The call's ranges, in slot order.
+  Buf nlhacc{false, false};
+  double nlh_lo[6] = {0, 0, 0, 0, 0, 0}, nlh_inv[6] = {1, 1, 1, 1, 1, 1};
+  int nlh_bins = 0;
   bool nlm_valid = false;       // a statistics call has run: nlmacc[0..5] hold max |ifftn(a_f)|, max |ifftn(b_f)| of this rank
   uint8_t* mask = nullptr;
   size_t mask_count = 0;
@@ -536,6 +541,13 @@ struct mfft_plan_s {
   int moments_sweep(const void* x, int ncomp, size_t n, const double* center, double* acc);
   int moments_begin(const double center_slots[6]);
   int moments_end(double host[36]);
+  // Histograms of up to six fields given as spectra (plan_nonlinear.hip; the z stage fft_nlz.h body_hist on the fused routes, one
+  // inverse transform and one sweep per field on the composed one), and the sweep itself (hist.hip).  out: (nfields, nbins + 3)
+  int real_histogram(const mfft::NlFields& u, int dealias, const double* lo, const double* hi, int nbins, int64_t* out, int64_t* count);
+  int hist_composed(const mfft::NlFields& u, int dealias);
+  int hist_sweep(const void* x, int ncomp, size_t n, const double* lo, const double* inv, int nbins, int64_t* acc);
+  int hist_begin(const double lo_slots[6], const double inv_slots[6], int nbins);
+  int hist_end(int64_t* host, int nslots);
 };
 
 namespace mfft {

@@ -127,6 +127,27 @@ static int nls_rows(mfft_plan_s* p, const NlFields& u, char* Y, size_t yelems, i
   return moments_fold(static_cast<const double*>(z.part), (size_t)waves, NLS_SLOTS, static_cast<double*>(p->nlsacc.p), p->stream);
 }
 
+// the z stage that ends in a histogram, on a batch: rows of the call's fields in Y in, the workgroups' partial histograms into nlm,
+// folded into the plan's int64 accumulator (hist_begin) after each launch: the counts accumulate over the batches.
+static int nlh_rows(mfft_plan_s* p, const NlFields& u, char* Y, size_t yelems, int64_t L2, int64_t Za, int64_t nrows, int valid_in) {
+  NlhArgs z;
+  int ngroups = 0;
+  int64_t max_rows = 0;
+  MFFT_TRY(nlh_launch_shape(L2, p->prec, nrows, &ngroups, &max_rows));
+  z.npairs = (u.nfields + 1) / 2;
+  z.nbins = p->nlh_bins;
+  MFFT_TRY(p->ensure(p->nlm, hist_part_bytes(ngroups, 2 * z.npairs, z.nbins)));
+  for (int f = 0; f < u.nfields; ++f) {
+    const int slot = nls_slot(u, f);
+    (slot % 2 ? z.b : z.a)[slot / 2] = Y + (size_t)f * yelems * p->es;
+  }
+  for (int i = 0; i < 6; ++i) { z.lo[i] = p->nlh_lo[i]; z.inv[i] = p->nlh_inv[i]; }
+  z.n = (int)L2; z.prec = p->prec; z.in_stride = Za; z.nrows = nrows; z.valid = (int)p->Nf; z.valid_in = valid_in;
+  z.norm = 1.0 / (double)L2;
+  z.part = p->nlm.p;
+  return hist_rows(z, static_cast<int64_t*>(p->nlhacc.p), p->stream);
+}
+
 // Fused route: one rank, slab, real data, radix kernels on every axis.
 bool mfft_plan_s::nonlinear_fusable(int dealias, Op product, bool stats) const {
   static const bool off = env_on("MFFT_NO_NLZ"), ranks_off = env_on("MFFT_NO_NLZ_RANKS");      // read once per process
@@ -233,6 +254,7 @@ int mfft_plan_s::nonlinear_fused(const NlFields& u, int dealias, Op product, boo
     }));
     MFFT_TRY(stage("nl_z", (nin * keep2 + nout) * Yb * frac, [&] {
       if (product == Op::Moments) return nls_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0);
+      if (product == Op::Histogram) return nlh_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0);
       return nlz_rows(this, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0, product, stats);
     }));
     if (nout) MFFT_TRY(stage("nl_y_fwd", nout * (Xb + Yb) * frac, [&] {
@@ -336,6 +358,7 @@ int mfft_plan_s::nonlinear_fused_ranks(const NlFields& u, int dealias, Op produc
     }));
     MFFT_TRY(stage("nl_z", 0, [&] {
       if (product == Op::Moments) return nls_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0);
+      if (product == Op::Histogram) return nlh_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0);
       return nlz_rows(this, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0, product, stats);
     }));
     if (nout) MFFT_TRY(stage("nl_y_fwd", 0, [&] {      // truncate + fold in y, straight into the packed (P, Lp0, S) send layout
@@ -414,6 +437,48 @@ int mfft_plan_s::real_moments(const NlFields& u, int dealias, const double* cent
   MFFT_TRY(moments_end(host));
   for (int f = 0; f < u.nfields; ++f)
     for (int k = 0; k < NLS_STATS; ++k) out[f * NLS_STATS + k] = host[nls_slot(u, f) * NLS_STATS + k];
+  *count = local_real_count(pad);
+  return 0;
+}
+
+// Histograms of the real-space fields of up to six spectra: per field nbins + 3 counts (below lo, the nbins equal bins of [lo, hi),
+// at or above hi, not finite: fft_nlz.h hist_slot) of x = ifftn(field, dealias) over this rank's part of the grid a product would
+// be formed on.  The routes are real_moments': fused, the inverse passes of the products and the z stage that ends in a histogram
+// (no real array); composed, ONE real work array field by field -- inverse transform, sweep (hist.hip), next field.  Counts are
+// integers: the same bits on every route that computes the same values.  Synchronises the plan's stream.
+int mfft_plan_s::hist_composed(const NlFields& u, int dealias) {
+  const bool pad = dealias == MFFT_DEALIAS_3_2;
+  const int64_t nr = local_real_count(pad), nc = local_complex_alloc();
+  if (nr <= 0 || !r2c) return set_error(MFFT_ERR_UNSUPPORTED, "real_histogram needs a 3-D real-to-complex plan");
+  MFFT_TRY(ensure(nlr, (size_t)nr * rs));
+  int64_t* acc = static_cast<int64_t*>(nlhacc.p);
+  for (int f = 0; f < u.nfields; ++f) {
+    const int slot = nls_slot(u, f);
+    MFFT_TRY(exec(false, u.src(f, nc, es), nlr.p, dealias));
+    MFFT_TRY(stage("nl_histogram", (double)nr * rs, [&] {
+      return hist_sweep(nlr.p, 1, (size_t)nr, nlh_lo + slot, nlh_inv + slot, nlh_bins, acc + (size_t)slot * (nlh_bins + 3));
+    }));
+  }
+  return 0;
+}
+int mfft_plan_s::real_histogram(const NlFields& u, int dealias, const double* lo, const double* hi, int nbins, int64_t* out, int64_t* count) {
+  if (dealias == MFFT_DEALIAS_2_3) MFFT_TRY(require_mask());
+  double l6[6] = {0, 0, 0, 0, 0, 0}, i6[6] = {1, 1, 1, 1, 1, 1};
+  for (int f = 0; f < u.nfields; ++f) {
+    const int slot = nls_slot(u, f);
+    MFFT_TRY(hist_range(lo[f], hi[f], nbins, &i6[slot]));
+    l6[slot] = lo[f];
+  }
+  MFFT_TRY(hist_begin(l6, i6, nbins));
+  const bool pad = dealias == MFFT_DEALIAS_3_2;
+  MFFT_TRY(nonlinear_fusable(dealias, Op::Histogram, false)
+               ? (P == 1 ? nonlinear_fused(u, dealias, Op::Histogram, false) : nonlinear_fused_ranks(u, dealias, Op::Histogram, false))
+               : hist_composed(u, dealias));
+  const int nb3 = nbins + 3, nslots = 2 * ((u.nfields + 1) / 2);
+  std::vector<int64_t> host((size_t)nslots * nb3);
+  MFFT_TRY(hist_end(host.data(), nslots));
+  for (int f = 0; f < u.nfields; ++f)
+    memcpy(out + (size_t)f * nb3, host.data() + (size_t)nls_slot(u, f) * nb3, (size_t)nb3 * sizeof(int64_t));
   *count = local_real_count(pad);
   return 0;
 }

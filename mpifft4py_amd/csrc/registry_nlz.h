@@ -134,6 +134,24 @@ void register_nls(const char* name) {
   reg.push_back(make_entry<K, NlsParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::Moments, Build::Default, R, name));
 }
 
+// Op::Histogram: the stage that ends in a histogram (fft_nlz.h body_hist, NlhParams; kernels_nlh*.hip).  Rows, twiddle placement,
+// exchange, wave-synchronous build and the two-waves-per-SIMD cap are the cross kernels', as the moments kernels' are: the body
+// inlines ONE transform and keeps its counts in LDS, 2 x (NLH_MAXBINS + 3) x 4 = 4120 bytes behind the exchange buffers
+// (DESIGN.md 7 has the table of LDS bytes and resident workgroups per plan).
+// MFFT_NLH_MERGE=1 builds the variant that merges runs of equal slot inside the wave before the add (fft_nlz.h lds_count_runs;
+// `make nlh_variant`): measured against the plain add, profiles/real_histogram_ab.txt, and not shipped.
+#ifndef MFFT_NLH_MERGE
+#define MFFT_NLH_MERGE 0
+#endif
+template <class S, typename T>
+void register_nlh(const char* name) {
+  auto& reg = kernel_registry();
+  constexpr int R = nlz_rows<S, T>();
+  constexpr int W = MFFT_NLZ_OCC > 1 ? 16 + MFFT_NLZ_OCC : 0;
+  typedef NlzHist<NlzFft<S, T, R, nlz_twlds<S, T>(), nlz_split<S, T>(), nlz_wave<S, T>()>, MFFT_NLH_MERGE != 0> K;
+  reg.push_back(make_entry<K, NlhParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::Histogram, Build::Default, R, name));
+}
+
 // ... and its pruned 3/2-rule flavour (Nlz3Fft: Build::Nlz3, entry.n = M = 3 L): three thread groups of SL::TPT threads per row
 template <class SL, typename T> constexpr int nlz3_rows() { return 256 / (3 * SL::TPT) > 0 ? 256 / (3 * SL::TPT) : 1; }
 template <class SL, typename T>

@@ -296,6 +296,161 @@ def moments(FFT, x, center=None, reduce=False):
     return _moments_result(FFT, out[:ncomp * 6], x.size // ncomp, c, reduce)
 
 
+HIST_MAXBINS = 512      # bins per field of one call (MFFT_HIST_MAXBINS: what a workgroup's LDS histograms hold)
+
+
+def hist_slots(x, lo, hi, nbins):
+    """The slot rule of the histograms, in numpy float64 (include/mpifft4py_amd.h): 0 below lo, 1 .. nbins the equal bins of
+    [lo, hi), nbins + 1 at or above hi, nbins + 2 not a number.  The device evaluates the same expressions in the same order."""
+    x = np.asarray(x, dtype=np.float64)
+    inv = np.float64(nbins) / (np.float64(hi) - np.float64(lo))
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = (x - np.float64(lo)) * inv
+        inside = ~(x != x) & ~(t < 0) & ~(t >= nbins)
+        s = np.where(inside, 1 + np.where(inside, t, 0.0).astype(np.int64), 0)
+    s = np.where(t >= nbins, nbins + 1, s)
+    s = np.where(t < 0, 0, s)
+    return np.where(x != x, nbins + 2, s)
+
+
+class Histogram(object):
+    """Counts of `nfields` real fields over `count` points in `nbins` equal bins of [lo[f], hi[f]): `counts` of shape
+    (nfields, nbins), int64; `below` (x < lo), `above` (x >= hi) and `nonfinite` (NaN) of shape (nfields,).  For every field
+    counts[f].sum() + below[f] + above[f] + nonfinite[f] == count."""
+
+    def __init__(self, count, raw, lo, hi):
+        raw = np.asarray(raw, dtype=np.int64)
+        raw = raw.reshape(len(np.atleast_1d(lo)), -1)
+        self.count = int(count)
+        self.below = raw[:, 0].copy()
+        self.counts = raw[:, 1:-2].copy()
+        self.above = raw[:, -2].copy()
+        self.nonfinite = raw[:, -1].copy()
+        self.lo = np.atleast_1d(np.asarray(lo, dtype=np.float64)).copy()
+        self.hi = np.atleast_1d(np.asarray(hi, dtype=np.float64)).copy()
+
+    @property
+    def nbins(self):
+        return int(self.counts.shape[1])
+
+    def edges(self, f=0):
+        """The nbins + 1 edges of field f's bins."""
+        return self.lo[f] + (self.hi[f] - self.lo[f]) * (np.arange(self.nbins + 1, dtype=np.float64) / self.nbins)
+
+    def centers(self, f=0):
+        e = self.edges(f)
+        return 0.5 * (e[:-1] + e[1:])
+
+    def pdf(self, f=0):
+        """The density over [lo, hi), normalised by ALL `count` points: it integrates to 1 - (below + above + nonfinite) / count."""
+        return self.counts[f] / (float(self.count) * (self.hi[f] - self.lo[f]) / self.nbins)
+
+    def cdf(self, f=0):
+        """P(x < edge) at the nbins + 1 edges: below / count at lo, (count - above - nonfinite) / count at hi."""
+        c = np.concatenate([[self.below[f]], self.below[f] + np.cumsum(self.counts[f])])
+        return c / float(self.count)
+
+    def quantile(self, f, q):
+        """The x with cdf(x) = q, the counts taken as uniform inside their bin; nan where q lies in a tail outside [lo, hi)."""
+        c, e = self.cdf(f), self.edges(f)
+        q = np.asarray(q, dtype=np.float64)
+        j = np.clip(np.searchsorted(c, q, side="right") - 1, 0, self.nbins - 1)
+        d = c[j + 1] - c[j]
+        x = e[j] + np.where(d > 0, (q - c[j]) / np.where(d > 0, d, 1.0), 0.0) * (e[j + 1] - e[j])
+        return np.where((q < c[0]) | (q > c[-1]), np.nan, x)
+
+
+def _add_over_ranks(FFT, v):
+    """int64 counts added over FFT.comm exactly: the communicator adds doubles, so 24 low bits and the rest travel apart."""
+    v = np.asarray(v, dtype=np.int64)
+    if FFT.comm.Get_size() == 1:
+        return v.copy()
+    parts = np.concatenate([(v & 0xFFFFFF).ravel(), (v >> 24).ravel()]).astype(np.float64)
+    tot = np.rint(np.asarray(FFT.comm.allreduce(parts))).astype(np.int64)
+    return (tot[:v.size] + (tot[v.size:] << 24)).reshape(v.shape)
+
+
+def _hist_ranges(rng, nfields):
+    r = np.asarray(rng, dtype=np.float64)
+    if r.shape == (2,):
+        r = np.tile(r, (nfields, 1))
+    assert r.shape == (nfields, 2), (r.shape, nfields)
+    return np.ascontiguousarray(r[:, 0]), np.ascontiguousarray(r[:, 1])
+
+
+def _hist_check(lo, hi, bins):
+    if not 1 <= int(bins) <= HIST_MAXBINS:
+        raise ValueError("bins must be 1 .. %d, not %r" % (HIST_MAXBINS, bins))
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo < hi)):
+        raise ValueError("every range needs finite lo < hi, not %r .. %r" % (lo, hi))
+
+
+def real_histogram(FFT, a_hat, b_hat=None, dealias=None, bins=256, range=None, reduce=True):
+    """Histograms of fields that exist as SPECTRA only (mfft_real_histogram): the counts of ifftn(a_hat[f], dealias) -- and of
+    ifftn(b_hat[f], dealias) where b_hat is given -- in `bins` equal bins per field, without a real array: on slab plans with
+    radix kernels on every axis the z stage ends in a histogram (`FFT.plan_info("nonlinear_histogram_fused_3_2")`), elsewhere
+    the plan transforms one field at a time into ONE work array and sweeps it.  Fields and grid as `real_moments`.  `range` is
+    (lo, hi) for all fields or one pair per field; None: a `real_moments` call runs first and every field gets its own
+    [min, max] over FFT.comm, hi widened by (max - min) * 2^-20 so that the maximum falls inside (a constant field: a range
+    of width 1 about its value).  Returns a `Histogram`; with `reduce` the int64 counts are added over FFT.comm (every rank
+    calls it, every rank gets the same arrays).  Counts are integers: the result is the same bits run to run, on every device
+    and for every number of ranks that computes the same values.  Synchronises the plan's stream; the inputs are preserved."""
+    cs = tuple(int(s) for s in FFT.complex_shape())
+    assert a_hat.shape in (cs, (3,) + cs), (a_hat.shape, cs)
+    vec = len(a_hat.shape) == 4
+    fields = [(a_hat, vec)] + ([(b_hat, vec)] if b_hat is not None else [])
+    ncomp = 3 if vec else 1
+    nfields = ncomp * len(fields)
+    if range is None:
+        m = real_moments(FFT, a_hat, b_hat, dealias, reduce=True)
+        if not (np.all(np.isfinite(m.min)) and np.all(np.isfinite(m.max))):
+            raise ValueError("a field is not finite (min %r, max %r): give `range`" % (m.min, m.max))
+        lo, hi = m.min.copy(), np.maximum(m.max + (m.max - m.min) * 2.0 ** -20, np.nextafter(m.max, np.inf))
+        const = ~(m.min < m.max)
+        lo[const], hi[const] = m.min[const] - 0.5, m.min[const] + 0.5
+    else:
+        lo, hi = _hist_ranges(range, nfields)
+    _hist_check(lo, hi, bins)
+    out = np.zeros((nfields, int(bins) + 3), dtype=np.int64)
+    count = ctypes.c_int64(0)
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
+    _nonlinear(FFT, "real_histogram", fields, dealias, head=(a_hat.ptr, b_hat.ptr if b_hat is not None else None, ncomp),
+               tail=(lo.ctypes.data_as(dp), hi.ctypes.data_as(dp), int(bins), out.ctypes.data_as(ip), ctypes.byref(count)))
+    n = count.value
+    if reduce:
+        out, n = _add_over_ranks(FFT, out), int(_add_over_ranks(FFT, [n])[0])
+    return Histogram(n, out, lo, hi)
+
+
+def histogram(FFT, x, bins=256, range=None, reduce=False):
+    """The histogram of a real DeviceArray (mfft_ew_histogram, the companion of `moments`): an array of the real shape is one
+    field, a leading extent of 1, 2, 3 or 6 is taken as components.  `range` as in `real_histogram`; None: the components'
+    [min, max] from `moments` (over FFT.comm with `reduce`).  Returns a `Histogram`; with `reduce` over FFT.comm."""
+    if x.pitch is not None:
+        raise ValueError("a histogram of a pitched array would count the elements between its rows")
+    assert x.dtype == np.dtype(FFT.float), (x.dtype, FFT.float)
+    ncomp = int(x.shape[0]) if len(x.shape) == 4 else 1
+    if range is None:
+        m = moments(FFT, x, reduce=reduce)
+        if not (np.all(np.isfinite(m.min)) and np.all(np.isfinite(m.max))):
+            raise ValueError("a component is not finite (min %r, max %r): give `range`" % (m.min, m.max))
+        lo, hi = m.min.copy(), np.maximum(m.max + (m.max - m.min) * 2.0 ** -20, np.nextafter(m.max, np.inf))
+        const = ~(m.min < m.max)
+        lo[const], hi[const] = m.min[const] - 0.5, m.min[const] + 0.5
+    else:
+        lo, hi = _hist_ranges(range, ncomp)
+    _hist_check(lo, hi, bins)
+    FFT.comm.use_device()
+    out = np.zeros((ncomp, int(bins) + 3), dtype=np.int64)
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
+    _lib.call("mfft_ew_histogram", FFT._plan, x.ptr, ncomp, x.size // ncomp, _prec(FFT), lo.ctypes.data_as(dp), hi.ctypes.data_as(dp),
+              int(bins), out.ctypes.data_as(ip))
+    n = x.size // ncomp
+    if reduce:
+        out, n = _add_over_ranks(FFT, out), int(_add_over_ranks(FFT, [n])[0])
+    return Histogram(n, out, lo, hi)
+
+
 def advective_dt(FFT, umax, cfl):
     """cfl / sum_f umax[f] N[f] / L[f]: the advective (CFL) time step of a velocity whose components reach umax[f], on
     the mesh FFT.N of the box FFT.L -- the mesh of the run, not the padded one of a 3/2-rule product.  Pure host

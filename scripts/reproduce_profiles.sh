@@ -113,6 +113,12 @@ run() {
       for n in 256 512; do for dl in 3/2-rule 2/3-rule; do python examples/boussinesq_device.py --N $n --steps 5 --stages --dealias $dl; python examples/boussinesq_device.py --N $n --steps 5 --stages --dealias $dl --two-calls; done; done ;;
     real_moments_regs.tsv) make -C mpifft4py_amd/csrc -j8 >/dev/null; python scripts/real_moments_regs.py ;;
     real_moments_ab.txt) python scripts/real_moments_ab.py --procs 3 --out out/real_moments_ab.txt ;;
+    real_histogram_regs.tsv) make -C mpifft4py_amd/csrc -j8 >/dev/null; python scripts/real_histogram_regs.py ;;
+    real_histogram_ab.txt) make -C mpifft4py_amd/csrc -j8 nlh_variant >/dev/null      # the build that merges runs of equal slot, for section (a)
+      python scripts/real_histogram_ab.py --procs 3 --out out/real_histogram_ab.txt
+      # its last section: the LDS counters, in a counter run of their own
+      rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d out/hist_pmc -- python scripts/real_histogram_ab.py --pmc-worker
+      python scripts/real_histogram_ab.py --out out/real_histogram_ab.txt --append-pmc out/hist_pmc ;;
     shell_spectrum_ab.txt) python scripts/shell_spectrum_ab.py --procs 3 --out out/shell_spectrum_ab.txt
       # its last section: the kernels' trace statistics, and in a run of their own the LDS counters
       rocprofv3 --kernel-trace --stats --output-format csv -d out/shell_trace -- python scripts/shell_spectrum_ab.py --worker --cases 512:double,1024:double,1024:single
