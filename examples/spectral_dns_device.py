@@ -30,7 +30,7 @@ def _zero(a):
 
 def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double", nu=0.000625, dt=0.01, steps=10,
           report=None, fused=True, timing=False, complex_pitch="default", edge=None, spectrum=False, cfl=None, dt_max=None,
-          stats=False, pdf=False):
+          stats=False, pdf=False, dissipation=False):
     """fused=True (round 6): the nonlinear term is ONE plan operation (spectral.cross_transform: no real-space work
     arrays, the z stages one kernel) and a Runge-Kutta stage's projection, viscous term, both updates and the next
     curl are ONE sweep (spectral.ns_rk_stage).  fused=False: the composition of rounds 3 - 5 (nine transforms, cross,
@@ -45,7 +45,12 @@ def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double
     longitudinal derivatives du_f/dx_f ("grad"), and of u and omega together ("u_omega": six fields) -- from
     spectral.real_moments: the fields exist as spectra only, no real array is written for them.
     pdf=True (fused loop): report["pdf"] = (Histogram, mean, sigma) of du_0/dx_0 of the final state over +-8 of its standard deviations
-    in 32 bins, from spectral.real_histogram on the same spectrum (the z kernel ends in a histogram)."""
+    in 32 bins, from spectral.real_histogram on the same spectrum (the z kernel ends in a histogram).
+    dissipation=True (fused loop): before every step and of the final state, the statistics of the dissipation eps = 2 nu S_ij S_ij
+    and of the enstrophy density omega^2 -- quadratic forms of six and of three fields that exist as spectra only
+    (spectral.strain_hat, spectral.real_quadratic): report["dissipation"] lists (<eps>, <omega^2>, <eps^2> / <eps>^2,
+    <omega^4> / <omega^2>^2) and rank 0 prints them with nu <omega^2> / <eps>, which is 1 for a periodic solenoidal field; with pdf
+    also the two histograms of the final state, report["dissipation_pdf"]."""
     if complex_pitch == "default":       # the fused loop on ONE rank keeps its spectra pitched (rows a whole number of cache lines
         # apart: every pass runs on them); several ranks and the composition of rounds 3 - 5 keep compact rows
         complex_pitch = "auto" if (fused and comm.Get_size() == 1) else None
@@ -57,6 +62,8 @@ def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double
         raise ValueError("stats needs the fused loop: the composition holds no curl of the final state")
     if pdf and not fused:
         raise ValueError("pdf needs the fused loop")
+    if dissipation and not fused:
+        raise ValueError("dissipation needs the fused loop")
     if decomposition == 'slab':
         FFT = Slab_R2C(N, L, comm, precision, complex_pitch=complex_pitch)
     else:
@@ -97,7 +104,28 @@ def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double
         if timing:
             FFT.reset_timing()
         t0 = time.perf_counter()
+        def dissipation_report(label, bins=0):       # (collective: every rank calls it; three sweeps and two plan operations)
+            if not dis_work:
+                dis_work.extend(FFT.empty_complex(3) for _ in range(3))
+            diag, off, W = dis_work
+            spectral.strain_hat(FFT, K, U_hat, diag, off)
+            spectral.curl_hat(FFT, K, U_hat, W)
+            me, he = spectral.real_quadratic(FFT, diag, off, dealias, weights=2 * nu * np.array([1, 1, 1, 2, 2, 2.0]), bins=bins)
+            mw, hw = spectral.real_quadratic(FFT, W, None, dealias, bins=bins)
+            eps, w2 = float(me.sums[0, 0]) / me.count, float(mw.sums[0, 0]) / mw.count
+            fe, fw = float(me.sums[0, 1]) / me.count / eps ** 2, float(mw.sums[0, 1]) / mw.count / w2 ** 2
+            if report is not None:
+                report.setdefault("dissipation", []).append((eps, w2, fe, fw))
+                if bins:
+                    report["dissipation_pdf"] = (he, hw)
+            if comm.Get_rank() == 0:
+                print("%s: <eps> = %.15e  <omega^2> = %.15e  nu <omega^2> / <eps> = %.15f  flatness of eps = %.9f  of omega^2 = %.9f"
+                      % (label, eps, w2, nu * w2 / eps, fe, fw))
+
+        dis_work = []
         for step_ in range(steps):
+            if dissipation:
+                dissipation_report("step %d" % step_)
             for rk in range(4):
                 spectral.cross_transform(FFT, U_hat, dU, dU, dealias, absmax=(cfl is not None and rk == 0))      # dU = fftn(U x curl U)
                 if cfl is not None and rk == 0:      # max |u_f|, max |omega_f| of the state the step starts from (one stream synchronisation)
@@ -137,6 +165,8 @@ def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double
             h = spectral.real_histogram(FFT, g0, None, dealias, bins=32, range=(mean - 8 * sigma, mean + 8 * sigma))
             if report is not None:
                 report["pdf"] = (h, mean, sigma)
+        if dissipation:
+            dissipation_report("final", bins=32 if pdf else 0)
         for i in range(3):
             FFT.ifftn(U_hat.component(i), U.component(i))
         return FFT.comm.reduce(spectral.sumsq(FFT, U) / float(N[0]) / float(N[1]) / float(N[2]) / 2)
@@ -210,6 +240,9 @@ def main():
                     "state, from the spectra (spectral.real_moments: no real-space array)")
     ap.add_argument("--pdf", action="store_true", help="print the PDF of du_0/dx_0 of the final state in units of its standard deviation, from "
                     "the spectrum (spectral.real_histogram: no real-space array)")
+    ap.add_argument("--dissipation", action="store_true", help="print before every step and of the final state <eps>, <omega^2>, nu <omega^2> / <eps> "
+                    "(1 for a periodic solenoidal field) and the flatness <eps^2> / <eps>^2, <omega^4> / <omega^2>^2, from the spectra "
+                    "(spectral.real_quadratic: no real-space array); with --pdf also the two histograms of the final state")
     args = ap.parse_args()
     dealias = None if args.dealias == "None" else args.dealias
     from mpifft4py_amd import LocalGroup, SelfComm
@@ -218,11 +251,11 @@ def main():
         ks = LocalGroup(args.ranks).run(lambda c: solve(c, args.M, dealias, steps=args.steps, precision=args.precision,
                                                         report=rep if c.Get_rank() == 0 else None, fused=not args.composed,
                                                         timing=args.stages, complex_pitch=None if args.compact else "default",
-                                                        edge=args.N or None, spectrum=args.spectrum, cfl=args.cfl, dt_max=args.dt_max, stats=args.stats, pdf=args.pdf))
+                                                        edge=args.N or None, spectrum=args.spectrum, cfl=args.cfl, dt_max=args.dt_max, stats=args.stats, pdf=args.pdf, dissipation=args.dissipation))
     else:
         ks = [solve(SelfComm(), args.M, dealias, steps=args.steps, precision=args.precision, report=rep,
                     fused=not args.composed, timing=args.stages, complex_pitch=None if args.compact else "default",
-                    edge=args.N or None, spectrum=args.spectrum, cfl=args.cfl, dt_max=args.dt_max, stats=args.stats, pdf=args.pdf)]
+                    edge=args.N or None, spectrum=args.spectrum, cfl=args.cfl, dt_max=args.dt_max, stats=args.stats, pdf=args.pdf, dissipation=args.dissipation)]
     print("N = %d^3, %d RK4 steps, %.3f ms per step (%s, device-resident; plan work buffers %.2f GB)"
           % (args.N or 2 ** args.M, args.steps, rep.get("ms_per_step", float("nan")),
              "composed: 36 transforms + element-wise kernels" if args.composed else
@@ -253,6 +286,11 @@ def main():
         print("PDF of du_0/dx_0 in units of its sigma = %.9e (%d points, bin width %.17g, outside the range: %.17g)" % (sigma, h.count, width, tails))
         for c, p in zip((h.centers(0) - mean) / sigma, h.pdf(0) * sigma):
             print("pdf %+.4f %.17g" % (c, p))
+    if args.dissipation and args.pdf:
+        for name, h in zip(("eps", "omega2"), rep["dissipation_pdf"]):
+            print("PDF of %s over [%.9e, %.9e) (%d points)" % (name, h.lo[0], h.hi[0], h.count))
+            for c, p in zip(h.centers(0), h.pdf(0)):
+                print("pdf_%s %.9e %.17g" % (name, c, p))
     if args.M == 5 and not args.N and args.steps == 10 and args.precision == "double" and args.cfl is None:
         assert round(ks[0] - 0.124953117517, 7) == 0
         print("matches the reference demo's known answer 0.124953117517")

@@ -293,6 +293,27 @@ MFFT_API int64_t mfft_nlz_moments_groups(int64_t nrows, int64_t n, int precision
 MFFT_API int mfft_nlz_hist_rows(const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
                                 int64_t valid_in, int precision, const double* lo, const double* hi, int nbins, int64_t* out);
 MFFT_API int64_t mfft_nlz_hist_groups(int64_t nrows, int64_t n, int precision);
+/* Quadratic forms: the evaluation rule that the fused kernel, the sweeps, the emulator and the tests share.  For n = 1, 2, 3 or 6
+ * real fields r_f at a point and weights w_f (finite doubles of either sign):
+ *     r_f = (double)v * norm                          the transform's value in the plan's precision, taken to double, then
+ *                                                     normalised (a real array that is given as such: r_f = (double)x)
+ *     q   = 0
+ *     q   = q + (w_f * r_f) * r_f                     for each field in SLOT order (a alone: a_0, a_1, ..; a and b: a_0, b_0, a_1,
+ *                                                     b_1, a_2, b_2 -- the pairs that share a transform)
+ * Every product and every sum is rounded on its own, in double: nothing is contracted into a fused multiply-add, on the device
+ * or on the host.  q is a double in both precisions; its statistics are the six of mfft_real_moments about one centre, its counts
+ * follow the slot rule above with one lo < hi. */
+/* The z stage that ends in the statistics of a quadratic form (csrc/fft_nlz.h body_quad), synchronous: q over the real rows
+ * irfft(row, n) of the fields without the real rows.  Fields, rows, valid and valid_in as mfft_nlz_moments_rows; weights[f] in the
+ * order a_0.., then b_0..; out6 = [min, max, S1 .. S4] of q, S_p = sum (q - center)^p; counts[nbins + 3] by the slot rule (may be
+ * NULL where nbins == 0).  A NaN or Inf bin in ANY field makes q NaN where that bin was loaded: NaN sums, NaN min and max, counts
+ * in slot nbins + 2.  MFFT_ERR_INVALID for nbins outside 0 .. MFFT_HIST_MAXBINS, a weight or centre that is not finite, and with
+ * nbins > 0 hi <= lo; MFFT_ERR_UNSUPPORTED for lengths without a kernel; the outputs are untouched on error.  The z stage of
+ * mfft_real_quadratic on its own, for tests.  mfft_nlz_quad_groups: the workgroups of that launch (0: no kernel of that length). */
+MFFT_API int mfft_nlz_quad_rows(const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
+                                int64_t valid_in, int precision, const double* weights, double center, double lo, double hi, int nbins,
+                                double* out6, int64_t* counts);
+MFFT_API int64_t mfft_nlz_quad_groups(int64_t nrows, int64_t n, int precision);
 /* slab pack / unpack (slab.py:403; cython/maths.pyx:21-31 transpose_Uc) */
 MFFT_API int mfft_slab_pack(const void* uc_hatT, void* u_mpi, int P, int64_t np0, int64_t np1, int64_t nf, int precision);
 MFFT_API int mfft_slab_unpack(const void* u_mpi, void* uc_hatT, int P, int64_t np0, int64_t np1, int64_t nf, int precision);
@@ -338,6 +359,12 @@ MFFT_API int mfft_ew_grad_hat(mfft_plan_t plan, const void* s_hat, void* out, co
  * 1j * K * U_hat. */
 MFFT_API int mfft_ew_diag_grad_hat(mfft_plan_t plan, const void* U_hat, void* out, const void* kx, const void* ky, const void* kz,
                                    const int64_t shape[3], int precision);
+/* The strain-rate tensor S_ij = (du_i/dx_j + du_j/dx_i) / 2 of a vector field in spectral space, U_hat read ONCE: diag_f =
+ * i K_f U_hat_f (S_00, S_11, S_22) and off = (S_01, S_02, S_12) with S_ij = i (K_i U_hat_j + K_j U_hat_i) / 2; U_hat, diag and off
+ * are (3,) + shape and distinct; the rest as mfft_ew_grad_hat (pitched spectra are swept as they lie).  The dissipation is
+ * 2 nu S_ij S_ij = mfft_real_quadratic(diag, off, weights = 2 nu (1, 1, 1, 2, 2, 2)). */
+MFFT_API int mfft_ew_strain_hat(mfft_plan_t plan, const void* U_hat, void* diag, void* off, const void* kx, const void* ky, const void* kz,
+                                const int64_t shape[3], int precision);
 MFFT_API int mfft_ew_ns_rhs(mfft_plan_t plan, void* dU, const void* U_hat, const void* kx, const void* ky, const void* kz,
                             const int64_t shape[3], double nu, int precision);                          /* demo:73-77 */
 MFFT_API int mfft_ew_axpbz(mfft_plan_t plan, void* y, const void* x, const void* z, double alpha, double beta, size_t n_real,
@@ -394,6 +421,27 @@ MFFT_API int mfft_ew_histogram(mfft_plan_t plan, const void* x, int ncomp, size_
  * a fused slab plan.  The inputs are preserved.  Synchronises the plan's stream. */
 MFFT_API int mfft_real_histogram(mfft_plan_t plan, const void* a_hat, const void* b_hat, int ncomp, int dealias, const double* lo,
                                  const double* hi, int nbins, int64_t* out, int64_t* count);
+
+/* Statistics of q = sum_c weights[c] x[c, :]^2 of a real device array (ncomp, n), ncomp = 1, 2, 3 or 6, in the plan's precision,
+ * by the evaluation rule above: out6 = [min, max, S1 .. S4] about `center`, counts[nbins + 3] over [lo, hi) (NULL allowed where
+ * nbins == 0).  q is formed on the fly in ONE sweep, there is no q array; partials by plain stores, folds in fixed order, no global
+ * atomics.  The plan must not be null; synchronises the plan's stream. */
+MFFT_API int mfft_ew_quadratic(mfft_plan_t plan, const void* x, int ncomp, size_t n, int precision, const double* weights, double center,
+                               double lo, double hi, int nbins, double* out6, int64_t* counts);
+
+/* Statistics of a quadratic form of fields that exist as spectra only -- enstrophy, dissipation, energy density: for the ncomp (1 or
+ * 3) components of a_hat and, where b_hat is not NULL, of b_hat -- 1, 2, 3 or 6 fields, weights[f] in that order --
+ *     q(x) = sum_f weights[f] * ifftn(field f, dealias)(x)^2
+ * by the evaluation rule above, over THIS RANK's part of the grid a product would be formed on (as mfft_real_moments): out6 =
+ * [min, max, S1 .. S4] of q about `center`, counts[nbins + 3] by the slot rule over [lo, hi) (nbins == 0: no histogram, counts may
+ * be NULL, lo and hi are ignored), *count = the points.  Routes (mfft_plan_get_info "nonlinear_quadratic_fused_3_2" / "_none" /
+ * "_2_3"): fused, the z kernel accumulates q in registers across the inverse transforms of a row and ends in the reductions
+ * (csrc/fft_nlz.h body_quad), no real-space array exists; every other plan transforms one field at a time into ONE real work array,
+ * adds its term into ONE array of doubles and sweeps that once.  Bitwise reproducible run to run; the counts of a fused slab plan
+ * are the same for every number of ranks.  MFFT_ERR_INVALID as for mfft_nlz_quad_rows, the outputs untouched on error.  The
+ * inputs are preserved.  Synchronises the plan's stream. */
+MFFT_API int mfft_real_quadratic(mfft_plan_t plan, const void* a_hat, const void* b_hat, int ncomp, int dealias, const double* weights,
+                                 double center, double lo, double hi, int nbins, double* out6, int64_t* counts, int64_t* count);
 
 /* The nonlinear term of a pseudo-spectral step as ONE operation:
  *     out_hat = fftn(ifftn(a_hat) x ifftn(b_hat))        (cross product in real space, component by component)

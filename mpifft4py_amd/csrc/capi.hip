@@ -1,6 +1,7 @@
 // capi.hip -- the extern "C" surface of libmpifft4py_amd.so that is not the plan
 // executor (plan_*.hip): device/memory helpers, communicators, the stage-level
 // "serialFFT seam" entry points and HIP-event timers.
+#include <cmath>
 #include <cstring>
 #include "comm.h"
 #include "mfft_internal.h"
@@ -427,6 +428,63 @@ int64_t mfft_nlz_hist_groups(int64_t nrows, int64_t n, int precision) {
   int ngroups = 0;
   int64_t max_rows = 0;
   if (nlh_launch_shape(n, precision, nrows, &ngroups, &max_rows) != 0) return 0;
+  return ngroups;
+}
+
+// The stage that ends in the statistics of a quadratic form (fft_nlz.h body_quad), synchronous.  Fields and rows as
+// mfft_nlz_moments_rows; q = sum_f weights[f] irfft(row of field f, n)^2, fields in the order a_0.., then b_0..; out6 = [min, max,
+// S1 .. S4] of q about center over all rows, counts[nbins + 3] its histogram over [lo, hi) (null allowed where nbins == 0).
+int mfft_nlz_quad_rows(const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid, int64_t valid_in,
+                       int precision, const double* weights, double center, double lo, double hi, int nbins, double* out6, int64_t* counts) {
+  if (!a || !out6 || !weights || (nbins > 0 && !counts) || nrows < 1 || n < 2 || n >= 65536 || pitch < valid || valid < 1 || valid > n / 2 + 1 ||
+      valid_in < 0 || valid_in > valid || !std::isfinite(center))
+    return set_error(MFFT_ERR_INVALID, "bad argument");
+  if (precision != MFFT_DOUBLE && precision != MFFT_SINGLE) return set_error(MFFT_ERR_INVALID, "unknown precision %d", precision);
+  if ((nfields != 1 && nfields != 2 && nfields != 3 && nfields != 6) || ((nfields % 2 == 0) != (b != nullptr)))
+    return set_error(MFFT_ERR_INVALID, "nfields must be 1 or 3 (a alone) or 2 or 6 (a and b), not %d", nfields);
+  const size_t es = elem_bytes(precision, true);
+  const int ncomp = b ? nfields / 2 : nfields;
+  NlqArgs z;
+  MFFT_TRY(quad_check(weights, nfields, lo, hi, nbins, &z.inv));
+  for (int f = 0; f < nfields; ++f) {
+    const int slot = b ? (f < ncomp ? 2 * f : 2 * (f - ncomp) + 1) : f;
+    const char* base = static_cast<const char*>(f < ncomp ? a : b) + (size_t)((f % ncomp) * nrows * pitch) * es;
+    (slot % 2 ? z.b : z.a)[slot / 2] = base;
+    z.w[slot] = weights[f];
+  }
+  z.npairs = (nfields + 1) / 2;
+  z.nbins = nbins; z.lo = lo; z.center = center;
+  z.n = (int)n; z.prec = precision; z.in_stride = pitch; z.nrows = nrows; z.valid = (int)valid; z.valid_in = (int)valid_in;
+  z.norm = 1.0 / (double)n;
+  int ngroups = 0;
+  int64_t waves = 0, max_rows = 0;
+  MFFT_TRY(nlq_launch_shape(n, precision, nrows, &ngroups, &waves, &max_rows));
+  const int nb3 = nbins + 3;
+  const size_t macc_bytes = 128, hacc_bytes = ((size_t)nb3 * sizeof(int64_t) + 127) / 128 * 128;
+  char* buf = nullptr;
+  MFFT_HIP(hipMalloc(reinterpret_cast<void**>(&buf), macc_bytes + hacc_bytes + quad_mpart_bytes(waves) + quad_hpart_bytes(ngroups, nbins)));
+  double* macc = reinterpret_cast<double*>(buf);
+  int64_t* hacc = reinterpret_cast<int64_t*>(buf + macc_bytes);
+  int rc = moments_clear(macc, NLS_STATS, nullptr);
+  if (!rc && hipMemsetAsync(hacc, 0, hacc_bytes, nullptr) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemsetAsync failed");
+  if (!rc) rc = quad_rows(z, buf + macc_bytes + hacc_bytes, macc, hacc, nullptr);
+  double m6[NLS_STATS];
+  std::vector<int64_t> host((size_t)nb3);
+  if (!rc && hipMemcpy(m6, macc, sizeof m6, hipMemcpyDeviceToHost) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemcpy failed");
+  if (!rc && hipMemcpy(host.data(), hacc, (size_t)nb3 * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemcpy failed");
+  if (hipStreamSynchronize(nullptr) != hipSuccess && !rc) rc = set_error(MFFT_ERR_HIP, "hipStreamSynchronize failed");
+  (void)hipFree(buf);
+  if (!rc) {
+    for (int k = 0; k < NLS_STATS; ++k) out6[k] = m6[k];
+    for (int k = 0; nbins > 0 && k < nb3; ++k) counts[k] = host[k];
+  }
+  return rc;
+}
+// workgroups of that launch (0: no kernel of that length)
+int64_t mfft_nlz_quad_groups(int64_t nrows, int64_t n, int precision) {
+  int ngroups = 0;
+  int64_t waves = 0, max_rows = 0;
+  if (nlq_launch_shape(n, precision, nrows, &ngroups, &waves, &max_rows) != 0) return 0;
   return ngroups;
 }
 

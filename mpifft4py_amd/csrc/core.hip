@@ -738,6 +738,81 @@ int launch_nlh(const NlhArgs& a, hipStream_t s) {
   return by_prec(a.prec, [&](auto t) { return launch_nlh_t<decltype(t)>(e, a, tw, s); });
 }
 
+// The stage that ends in the statistics of a quadratic form (fft_nlz.h body_quad, Op::Quadratic): the grid of the moments stage by
+// the same query, the waves of nls_launch_shape (groups of NLS_STATS doubles in mpart) and the limit of nlh_launch_shape -- a
+// workgroup counts passes x 2 rows-per-workgroup x n values of q at the most, max_rows keeps that below 2^32.
+int nlq_launch_shape(int64_t n, int prec, int64_t nrows, int* ngroups, int64_t* waves, int64_t* max_rows) {
+  const KernelEntry* e = find_nlz(n, prec, Op::Quadratic);
+  if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused z-stage kernel with a quadratic form of length %lld", (long long)n);
+  if (nrows < 1) return set_error(MFFT_ERR_INVALID, "no rows");
+  void* tw = nullptr;
+  MFFT_TRY(prepare_kernel(e, &tw));                // (the LDS attribute is set before the occupancy is asked for)
+  int cap = 0;
+  MFFT_TRY(nls_resident(e, &cap));
+  const int64_t per_pass = 2 * (int64_t)e->tile * n;                   // values of one workgroup's pass
+  const int64_t passes = ((int64_t)1 << 32) / per_pass - 1;
+  if (passes < 1) return set_error(MFFT_ERR_INTERNAL, "%s: one pass of a workgroup counts 2^32 values", e->name);
+  *max_rows = passes * cap * 2 * e->tile;
+  const int64_t rows = std::min(nrows, *max_rows);
+  const int64_t units = (rows + 2 * e->tile - 1) / (2 * e->tile);
+  *ngroups = (int)std::min<int64_t>(units, cap);
+  *waves = (int64_t)*ngroups * ((e->threads + 63) / 64);
+  return 0;
+}
+template <typename T>
+static int launch_nlq_t(const KernelEntry* e, const NlqArgs& a, void* tw, hipStream_t s) {
+  NlqParams<T> P;
+  for (int f = 0; f < 3; ++f) {
+    P.a[f] = static_cast<const cx<T>*>(f < a.npairs ? a.a[f] : nullptr);
+    P.b[f] = static_cast<const cx<T>*>(f < a.npairs ? a.b[f] : nullptr);
+    P.out[f] = nullptr;
+  }
+  P.tw = static_cast<const cx<T>*>(tw);
+  P.rt3 = nullptr;
+  P.in_stride = a.in_stride;
+  P.out_stride = 0;
+  P.nrows = a.nrows;
+  P.valid = a.valid > 0 && a.valid < a.n / 2 + 1 ? a.valid : a.n / 2 + 1;
+  P.valid_in = a.valid_in > 0 && a.valid_in < P.valid ? a.valid_in : P.valid;
+  P.scale = (T)1;
+  P.mpart = static_cast<double*>(a.mpart);
+  P.hpart = static_cast<unsigned*>(a.hpart);
+  for (int i = 0; i < 2 * NLS_PAIRS; ++i) {        // (a slot without a field has weight 0)
+    const bool used = i / 2 < a.npairs && (i % 2 == 0 || a.b[i / 2]);
+    P.w[i] = used ? a.w[i] : 0.0;
+  }
+  P.center = a.center;
+  P.norm = a.norm;
+  P.lo = a.lo;
+  P.inv = a.inv;
+  P.nbins = a.nbins;
+  P.npairs = a.npairs;
+  P.ngroups = a.ngroups;
+  e->launch(&P, a.ngroups, s);
+  MFFT_HIP(hipGetLastError());
+  return 0;
+}
+int launch_nlq(const NlqArgs& a, hipStream_t s) {
+  const KernelEntry* e = find_nlz(a.n, a.prec, Op::Quadratic);
+  if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused z-stage kernel with a quadratic form of length %d", a.n);
+  const int64_t units = (a.nrows + 2 * e->tile - 1) / (2 * e->tile);
+  if (a.npairs < 1 || a.npairs > NLS_PAIRS || !a.mpart || !a.hpart || a.nrows < 1 || a.ngroups < 1 || a.ngroups > units || a.nbins < 0 ||
+      a.nbins > NLH_MAXBINS)
+    return set_error(MFFT_ERR_INVALID, "bad argument");
+  // what one workgroup counts stays below 2^32: passes x 2 x rows per workgroup x n
+  const int64_t passes = (units + a.ngroups - 1) / a.ngroups;
+  if (passes * 2 * e->tile * (int64_t)a.n >= ((int64_t)1 << 32))
+    return set_error(MFFT_ERR_INVALID, "%lld rows in one launch of %d workgroups: a count could wrap", (long long)a.nrows, a.ngroups);
+  for (int p = 0; p < a.npairs; ++p)
+    if (!a.a[p]) return set_error(MFFT_ERR_INVALID, "null argument");
+  for (int i = 0; i < 2 * a.npairs; ++i)
+    if (!std::isfinite(a.w[i])) return set_error(MFFT_ERR_INVALID, "a weight is not finite");
+  if (a.nbins > 0 && (!(a.inv > 0.0) || !std::isfinite(a.inv) || !std::isfinite(a.lo))) return set_error(MFFT_ERR_INVALID, "bad histogram range");
+  void* tw = nullptr;
+  MFFT_TRY(prepare_kernel(e, &tw));
+  return by_prec(a.prec, [&](auto t) { return launch_nlq_t<decltype(t)>(e, a, tw, s); });
+}
+
 // ---------------------------------------------------------------------------
 // data-movement kernels
 // ---------------------------------------------------------------------------

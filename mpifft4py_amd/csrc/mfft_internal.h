@@ -149,6 +149,7 @@ constexpr NlProduct NL_PRODUCTS[] = {
     {Op::CrossDot, "cross_dot", 9, 4, false, false},
     {Op::Moments, "moments", 6, 0, false, false},      // (up to six fields: the call says how many, NlFields::nfields)
     {Op::Histogram, "histogram", 6, 0, false, false},
+    {Op::Quadratic, "quadratic", 6, 0, false, false},
 };
 inline const NlProduct& nl_product(Op op) {
   for (const NlProduct& q : NL_PRODUCTS)
@@ -211,6 +212,37 @@ int hist_fold(const unsigned* part, size_t groups, int nfields, int nbins, int64
 // inv = nbins / (hi - lo) of a valid range; MFFT_ERR_INVALID for nbins outside 1 .. NLH_MAXBINS, hi <= lo, a range that is not finite
 int hist_range(double lo, double hi, int nbins, double* inv);
 int hist_max_bins();
+// The z stage that ends in the statistics of a quadratic form (fft_nlz.h body_quad): pairs as in NlsArgs; q = sum over the slots
+// of w[slot] r^2, r = norm * (the un-normalised inverse transform); [min, max, S1 .. S4] of q about `center` and, nbins > 0, the
+// nbins + 3 counts of q over [lo, lo + nbins / inv).
+struct NlqArgs {
+  const void* a[3] = {nullptr, nullptr, nullptr};
+  const void* b[3] = {nullptr, nullptr, nullptr};
+  int npairs = 0;
+  int n = 0;             // REAL length of a z row
+  int prec = MFFT_DOUBLE;
+  int64_t in_stride = 0, nrows = 0;   // complex elements
+  int valid = 0;         // bins per row present in memory (0 = all n/2+1)
+  int valid_in = 0;      // bins per row that are read, where fewer (pruned 2/3-rule); 0 = valid
+  double norm = 1.0;
+  double w[6] = {0, 0, 0, 0, 0, 0};   // [pair][a, b]
+  double center = 0.0, lo = 0.0, inv = 1.0;
+  int nbins = 0;         // 0: no histogram
+  int ngroups = 0;       // workgroups of the launch, from nlq_launch_shape() of (n, prec, nrows)
+  void* mpart = nullptr; // `waves` of nlq_launch_shape() groups of 6 doubles: moments_fold adds them up
+  void* hpart = nullptr; // (ngroups, nbins + 3) unsigned counts: hist_fold adds them up
+};
+// workgroups and waves of the launch over nrows rows, and the rows ONE launch may take so that no workgroup counts 2^32 values
+int nlq_launch_shape(int64_t n, int prec, int64_t nrows, int* ngroups, int64_t* waves, int64_t* max_rows);
+int launch_nlq(const NlqArgs& a, hipStream_t s);
+// bytes of mpart and of hpart for a launch of that shape, mpart first (hpart starts quad_mpart_bytes() behind it)
+size_t quad_mpart_bytes(int64_t waves);
+size_t quad_hpart_bytes(int ngroups, int nbins);
+// all rows of z (ngroups, mpart, hpart not set; `part` holds quad_mpart_bytes() + quad_hpart_bytes() of the shape of all rows):
+// launches of at most max_rows rows, each folded into macc (6 doubles) and, nbins > 0, hacc (nbins + 3 int64)
+int quad_rows(const NlqArgs& z, void* part, double* macc, int64_t* hacc, hipStream_t s);
+// finite weights, 0 <= nbins <= NLH_MAXBINS, and with nbins > 0 a valid range (hist_range); *inv = 1 where nbins == 0
+int quad_check(const double* weights, int nfields, double lo, double hi, int nbins, double* inv);
 // max |x| reductions (absmax.hip): acc[s] = max(acc[s], scale * max_g part[g * period + s]), NaNs kept; `scratch` holds
 // absmax_fold_scratch_bytes(), `part` is in precision `prec`, acc in double
 size_t absmax_fold_scratch_bytes();

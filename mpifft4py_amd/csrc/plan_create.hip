@@ -9,7 +9,7 @@ using namespace mfft;
 #endif
 
 mfft_plan_s::~mfft_plan_s() {
-  for (Buf* b : {&work[0], &work[1], &work[2], &work3, &nlw[0], &nlw[1], &nlx, &nly, &nlr, &pcomp, &shl, &nlm, &nlmacc, &nlsacc, &nlhacc})
+  for (Buf* b : {&work[0], &work[1], &work[2], &work3, &nlw[0], &nlw[1], &nlx, &nly, &nlr, &pcomp, &shl, &nlm, &nlmacc, &nlsacc, &nlhacc, &nlq})
     if (b->p) (void)(b->arena ? wfree(b->p) : dev_free(b->p));
   if (mask) (void)hipFree(mask);
   if (band_tiles) (void)hipFree(band_tiles);
@@ -401,6 +401,21 @@ int mfft_real_histogram(mfft_plan_t p, const void* a_hat, const void* b_hat, int
   return p->real_histogram(u, dealias, lo, hi, nbins, out, count);
 }
 
+// moments and counts of q = sum_f w_f ifftn(field f, dealias)^2 over the ncomp components of a and, where given, of b: see
+// include/mpifft4py_amd.h
+int mfft_real_quadratic(mfft_plan_t p, const void* a_hat, const void* b_hat, int ncomp, int dealias, const double* weights, double center,
+                        double lo, double hi, int nbins, double* out6, int64_t* counts, int64_t* count) {
+  if (!out6 || !count || !weights || (nbins > 0 && !counts)) return set_error(MFFT_ERR_INVALID, "null argument");
+  MFFT_TRY(check_ready(p, a_hat, a_hat));
+  if (ncomp != 1 && ncomp != 3) return set_error(MFFT_ERR_INVALID, "ncomp must be 1 or 3, not %d", ncomp);
+  if (dealias != MFFT_DEALIAS_NONE && dealias != MFFT_DEALIAS_2_3 && dealias != MFFT_DEALIAS_3_2)
+    return set_error(MFFT_ERR_INVALID, "unknown dealias mode %d", dealias);
+  NlFields u{a_hat, b_hat, nullptr, nullptr, nullptr};
+  u.ncomp = ncomp;
+  u.nfields = b_hat ? 2 * ncomp : ncomp;
+  return p->real_quadratic(u, dealias, weights, center, lo, hi, nbins, out6, counts, count);
+}
+
 int mfft_plan_sync(mfft_plan_t p) {
   if (!p) return set_error(MFFT_ERR_INVALID, "null plan");
   if (p->cstream) MFFT_HIP(hipStreamSynchronize(p->cstream));
@@ -437,7 +452,7 @@ int mfft_plan_get_info(mfft_plan_t p, const char* key, int64_t* value) {
   else if (k == "complex_pitch") *value = p->pitched() ? p->Zp : 0;        // row pitch of the caller's spectrum (elements), 0 = compact
   else if (k == "complex_pitch_native") *value = p->nat_pitch() ? 1 : 0;  // 1: the routes run on the pitched rows themselves
   else if (nonlinear_fused_key(p, k, value)) return 0;
-  else if (k == "nonlinear_bytes") *value = (int64_t)(p->nlx.bytes + p->nly.bytes + p->nlr.bytes + p->nlw[0].bytes + p->nlw[1].bytes);
+  else if (k == "nonlinear_bytes") *value = (int64_t)(p->nlx.bytes + p->nly.bytes + p->nlr.bytes + p->nlw[0].bytes + p->nlw[1].bytes + p->nlq.bytes);
   else if (k == "split_last") *value = p->split_last_route() ? 1 : 0;   // the one-rank route that splits real / complex last (decides whether the work buffer fits, if no call has yet)
   // layout of that route's work array (plan_impl.h SplitLastLayout; 0 where the plan does not take the route): rows per y block,
   // elements between the x rows of a block and between blocks, the order (0 x first, 1 y first, 2 y first forward only); and the bytes of the work buffer as allocated

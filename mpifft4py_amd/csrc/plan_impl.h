@@ -141,6 +141,12 @@ struct mfft_plan_s {
   Buf nlhacc{false, false};
   double nlh_lo[6] = {0, 0, 0, 0, 0, 0}, nlh_inv[6] = {1, 1, 1, 1, 1, 1};
   int nlh_bins = 0;
+  // mfft_real_quadratic / mfft_ew_quadratic (quad.hip): the statistics of q in slot 0 of nlsacc, its counts in the first nbins + 3
+  // of nlhacc, the partials in nlm; nlq is the ONE array of doubles the composed route adds the fields' terms into.  The call's
+  // weights (slot order), centre and range.
+  Buf nlq{false, false};
+  double nlq_w[6] = {0, 0, 0, 0, 0, 0}, nlq_center = 0.0, nlq_lo = 0.0, nlq_inv = 1.0;
+  int nlq_bins = 0;
   bool nlm_valid = false;       // a statistics call has run: nlmacc[0..5] hold max |ifftn(a_f)|, max |ifftn(b_f)| of this rank
   uint8_t* mask = nullptr;
   size_t mask_count = 0;
@@ -548,6 +554,16 @@ struct mfft_plan_s {
   int hist_sweep(const void* x, int ncomp, size_t n, const double* lo, const double* inv, int nbins, int64_t* acc);
   int hist_begin(const double lo_slots[6], const double inv_slots[6], int nbins);
   int hist_end(int64_t* host, int nslots);
+  // Statistics of q = sum_f w_f ifftn(field f)^2 over up to six fields given as spectra (plan_nonlinear.hip; the z stage fft_nlz.h
+  // body_quad on the fused routes; composed: one inverse transform per field into ONE real work array, its term added into nlq,
+  // one sweep of nlq), and the sweeps themselves (quad.hip).  out6: [min, max, S1 .. S4]; counts: nbins + 3, may be null if nbins == 0
+  int real_quadratic(const mfft::NlFields& u, int dealias, const double* weights, double center, double lo, double hi, int nbins, double* out6,
+                     int64_t* counts, int64_t* count);
+  int quad_composed(const mfft::NlFields& u, int dealias, const double w_slots[6]);
+  int quad_begin(double center, double lo, double inv, int nbins);
+  int quad_end(double out6[6], int64_t* counts);
+  int quad_sweep(const void* x, bool as_double, int ncomp, size_t stride, size_t n, const double* w, bool square);
+  int quad_accum(const void* r, double* q, size_t n, double w, bool first);
 };
 
 namespace mfft {

@@ -1,4 +1,5 @@
 // plan_nonlinear.hip -- the nonlinear term of a pseudo-spectral step as one plan-level operation.
+#include <cmath>
 #include "plan_impl.h"
 #include "fft_nlz.h"
 
@@ -148,6 +149,28 @@ static int nlh_rows(mfft_plan_s* p, const NlFields& u, char* Y, size_t yelems, i
   return hist_rows(z, static_cast<int64_t*>(p->nlhacc.p), p->stream);
 }
 
+// the z stage that ends in the statistics of a quadratic form, on a batch: rows of the call's fields in Y in, the waves' partial
+// statistics and the workgroups' partial histograms into nlm, folded into the plan's accumulators (quad_begin) after each launch:
+// both accumulate over the batches.
+static int nlq_rows(mfft_plan_s* p, const NlFields& u, char* Y, size_t yelems, int64_t L2, int64_t Za, int64_t nrows, int valid_in) {
+  NlqArgs z;
+  int ngroups = 0;
+  int64_t waves = 0, max_rows = 0;
+  MFFT_TRY(nlq_launch_shape(L2, p->prec, nrows, &ngroups, &waves, &max_rows));
+  z.npairs = (u.nfields + 1) / 2;
+  z.nbins = p->nlq_bins;
+  MFFT_TRY(p->ensure(p->nlm, quad_mpart_bytes(waves) + quad_hpart_bytes(ngroups, z.nbins)));
+  for (int f = 0; f < u.nfields; ++f) {
+    const int slot = nls_slot(u, f);
+    (slot % 2 ? z.b : z.a)[slot / 2] = Y + (size_t)f * yelems * p->es;
+  }
+  for (int i = 0; i < 6; ++i) z.w[i] = p->nlq_w[i];
+  z.center = p->nlq_center; z.lo = p->nlq_lo; z.inv = p->nlq_inv;
+  z.n = (int)L2; z.prec = p->prec; z.in_stride = Za; z.nrows = nrows; z.valid = (int)p->Nf; z.valid_in = valid_in;
+  z.norm = 1.0 / (double)L2;
+  return quad_rows(z, p->nlm.p, static_cast<double*>(p->nlsacc.p), static_cast<int64_t*>(p->nlhacc.p), p->stream);
+}
+
 // Fused route: one rank, slab, real data, radix kernels on every axis.
 bool mfft_plan_s::nonlinear_fusable(int dealias, Op product, bool stats) const {
   static const bool off = env_on("MFFT_NO_NLZ"), ranks_off = env_on("MFFT_NO_NLZ_RANKS");      // read once per process
@@ -255,6 +278,7 @@ int mfft_plan_s::nonlinear_fused(const NlFields& u, int dealias, Op product, boo
     MFFT_TRY(stage("nl_z", (nin * keep2 + nout) * Yb * frac, [&] {
       if (product == Op::Moments) return nls_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0);
       if (product == Op::Histogram) return nlh_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0);
+      if (product == Op::Quadratic) return nlq_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0);
       return nlz_rows(this, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0, product, stats);
     }));
     if (nout) MFFT_TRY(stage("nl_y_fwd", nout * (Xb + Yb) * frac, [&] {
@@ -359,6 +383,7 @@ int mfft_plan_s::nonlinear_fused_ranks(const NlFields& u, int dealias, Op produc
     MFFT_TRY(stage("nl_z", 0, [&] {
       if (product == Op::Moments) return nls_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0);
       if (product == Op::Histogram) return nlh_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0);
+      if (product == Op::Quadratic) return nlq_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0);
       return nlz_rows(this, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0, product, stats);
     }));
     if (nout) MFFT_TRY(stage("nl_y_fwd", 0, [&] {      // truncate + fold in y, straight into the packed (P, Lp0, S) send layout
@@ -479,6 +504,48 @@ int mfft_plan_s::real_histogram(const NlFields& u, int dealias, const double* lo
   MFFT_TRY(hist_end(host.data(), nslots));
   for (int f = 0; f < u.nfields; ++f)
     memcpy(out + (size_t)f * nb3, host.data() + (size_t)nls_slot(u, f) * nb3, (size_t)nb3 * sizeof(int64_t));
+  *count = local_real_count(pad);
+  return 0;
+}
+
+// Statistics of a quadratic form of the real-space fields of up to six spectra: q(x) = sum_f w_f r_f(x)^2, r_f = ifftn(field f,
+// dealias), by the one rule of include/mpifft4py_amd.h, over this rank's part of the grid a product would be formed on:
+// [min, max, S1 .. S4] of q about `center` and, nbins > 0, its nbins + 3 counts over [lo, hi).  The routes are real_moments': fused,
+// the inverse passes of the products and the z stage that ends in these statistics (fft_nlz.h body_quad; no real array);
+// composed, ONE real work array field by field in slot order -- inverse transform, its term added into the plan's ONE array of
+// doubles (quad.hip) -- and one sweep of that array.  Synchronises the plan's stream; the inputs are preserved.
+int mfft_plan_s::quad_composed(const NlFields& u, int dealias, const double w_slots[6]) {
+  const bool pad = dealias == MFFT_DEALIAS_3_2;
+  const int64_t nr = local_real_count(pad), nc = local_complex_alloc();
+  if (nr <= 0 || !r2c) return set_error(MFFT_ERR_UNSUPPORTED, "real_quadratic needs a 3-D real-to-complex plan");
+  MFFT_TRY(ensure(nlr, (size_t)nr * rs));
+  MFFT_TRY(ensure(nlq, (size_t)nr * sizeof(double)));
+  double* q = static_cast<double*>(nlq.p);
+  bool first = true;
+  for (int slot = 0; slot < 6; ++slot)             // (slot order: the order the fused kernel adds in)
+    for (int f = 0; f < u.nfields; ++f) {
+      if (nls_slot(u, f) != slot) continue;
+      MFFT_TRY(exec(false, u.src(f, nc, es), nlr.p, dealias));
+      MFFT_TRY(stage("nl_quadratic_add", (double)nr * (rs + 16), [&] { return quad_accum(nlr.p, q, (size_t)nr, w_slots[slot], first); }));
+      first = false;
+    }
+  const double one[1] = {1.0};
+  return stage("nl_quadratic", (double)nr * 8, [&] { return quad_sweep(q, true, 1, (size_t)nr, (size_t)nr, one, false); });
+}
+int mfft_plan_s::real_quadratic(const NlFields& u, int dealias, const double* weights, double center, double lo, double hi, int nbins, double* out6,
+                                int64_t* counts, int64_t* count) {
+  if (dealias == MFFT_DEALIAS_2_3) MFFT_TRY(require_mask());
+  if (!std::isfinite(center)) return set_error(MFFT_ERR_INVALID, "the centre is not finite");
+  double inv = 1.0;
+  MFFT_TRY(quad_check(weights, u.nfields, lo, hi, nbins, &inv));
+  for (int i = 0; i < 6; ++i) nlq_w[i] = 0.0;
+  for (int f = 0; f < u.nfields; ++f) nlq_w[nls_slot(u, f)] = weights[f];
+  MFFT_TRY(quad_begin(center, lo, inv, nbins));
+  const bool pad = dealias == MFFT_DEALIAS_3_2;
+  MFFT_TRY(nonlinear_fusable(dealias, Op::Quadratic, false)
+               ? (P == 1 ? nonlinear_fused(u, dealias, Op::Quadratic, false) : nonlinear_fused_ranks(u, dealias, Op::Quadratic, false))
+               : quad_composed(u, dealias, nlq_w));
+  MFFT_TRY(quad_end(out6, counts));
   *count = local_real_count(pad);
   return 0;
 }

@@ -152,6 +152,20 @@ void register_nlh(const char* name) {
   reg.push_back(make_entry<K, NlhParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::Histogram, Build::Default, R, name));
 }
 
+// Op::Quadratic: the stage that ends in the statistics of a quadratic form of its fields (fft_nlz.h body_quad, NlqParams;
+// kernels_nlq*.hip).  Rows, twiddle placement, exchange, wave-synchronous build and the two-waves-per-SIMD cap are those of
+// register_nls: the body inlines ONE transform, holds E doubles of running sum and 6 accumulators across it where body_moments holds
+// 36, and keeps ONE histogram in LDS, (NLH_MAXBINS + 3) x 4 = 2060 bytes behind the exchange buffers (DESIGN.md 7:
+// profiles/real_quadratic_regs.tsv, and the table of LDS bytes and resident workgroups).  No other cap was measured.
+template <class S, typename T>
+void register_nlq(const char* name) {
+  auto& reg = kernel_registry();
+  constexpr int R = nlz_rows<S, T>();
+  constexpr int W = MFFT_NLZ_OCC > 1 ? 16 + MFFT_NLZ_OCC : 0;
+  typedef NlzQuad<NlzFft<S, T, R, nlz_twlds<S, T>(), nlz_split<S, T>(), nlz_wave<S, T>()>> K;
+  reg.push_back(make_entry<K, NlqParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::Quadratic, Build::Default, R, name));
+}
+
 // ... and its pruned 3/2-rule flavour (Nlz3Fft: Build::Nlz3, entry.n = M = 3 L): three thread groups of SL::TPT threads per row
 template <class SL, typename T> constexpr int nlz3_rows() { return 256 / (3 * SL::TPT) > 0 ? 256 / (3 * SL::TPT) : 1; }
 template <class SL, typename T>

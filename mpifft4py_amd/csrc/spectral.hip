@@ -69,6 +69,29 @@ __global__ __launch_bounds__(EW_BLOCK) void diag_grad_kernel(const cx<T>* __rest
   }
 }
 
+// The strain-rate tensor S_ij = (du_i/dx_j + du_j/dx_i) / 2 of a vector field in spectral space, U read once:
+// diag_f = i K_f U_f (S_00, S_11, S_22), off = (S_01, S_02, S_12) with S_ij = i (K_i U_j + K_j U_i) / 2
+template <typename T>
+__global__ __launch_bounds__(EW_BLOCK) void strain_kernel(const cx<T>* __restrict__ U, cx<T>* __restrict__ diag, cx<T>* __restrict__ off,
+                                                         const T* __restrict__ kx, const T* __restrict__ ky,
+                                                         const T* __restrict__ kz, int64_t s1, int64_t s2, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const int64_t k = (int64_t)(i % s2), j = (int64_t)((i / s2) % s1), l = (int64_t)(i / (s2 * s1));
+    const T K0 = kx[l], K1 = ky[j], K2 = kz[k], h = (T)0.5;
+    const cx<T> u0 = U[i], u1 = U[n + i], u2 = U[2 * n + i];
+    // i * (a) = (-a.y, a.x)
+    diag[i] = mk<T>(-K0 * u0.y, K0 * u0.x);
+    diag[n + i] = mk<T>(-K1 * u1.y, K1 * u1.x);
+    diag[2 * n + i] = mk<T>(-K2 * u2.y, K2 * u2.x);
+    const cx<T> s01 = mk<T>(K0 * u1.x + K1 * u0.x, K0 * u1.y + K1 * u0.y);
+    const cx<T> s02 = mk<T>(K0 * u2.x + K2 * u0.x, K0 * u2.y + K2 * u0.y);
+    const cx<T> s12 = mk<T>(K1 * u2.x + K2 * u1.x, K1 * u2.y + K2 * u1.y);
+    off[i] = mk<T>(-h * s01.y, h * s01.x);
+    off[n + i] = mk<T>(-h * s02.y, h * s02.x);
+    off[2 * n + i] = mk<T>(-h * s12.y, h * s12.x);
+  }
+}
+
 // out = i K x U   (spectral space, demo:60-64)
 template <typename T>
 __global__ __launch_bounds__(EW_BLOCK) void curl_kernel(const cx<T>* __restrict__ U, cx<T>* __restrict__ out,
@@ -322,6 +345,24 @@ int mfft_ew_diag_grad_hat(mfft_plan_t plan, const void* U_hat, void* out, const 
   else
     hipLaunchKernelGGL(diag_grad_kernel<float>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, st, (const cx<float>*)U_hat,
                        (cx<float>*)out, (const float*)kx, (const float*)ky, (const float*)kz, shape[1], shape[2], n);
+  MFFT_HIP(hipGetLastError());
+  return 0;
+}
+
+// diag[f] = i K[f] U_hat[f], off = (S_01, S_02, S_12), S_ij = i (K[i] U_hat[j] + K[j] U_hat[i]) / 2: the six independent
+// components of the strain-rate tensor, U_hat read once; neither output may alias U_hat
+int mfft_ew_strain_hat(mfft_plan_t plan, const void* U_hat, void* diag, void* off, const void* kx, const void* ky, const void* kz,
+                       const int64_t shape[3], int precision) {
+  hipStream_t st = plan_stream(plan);
+  if (!U_hat || !diag || !off || !kx || !ky || !kz || !shape) return set_error(MFFT_ERR_INVALID, "null argument");
+  if (diag == U_hat || off == U_hat || diag == off) return set_error(MFFT_ERR_INVALID, "strain_hat: the arrays must be distinct");
+  const size_t n = (size_t)(shape[0] * shape[1] * shape[2]);
+  if (precision == MFFT_DOUBLE)
+    hipLaunchKernelGGL(strain_kernel<double>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, st, (const cx<double>*)U_hat, (cx<double>*)diag,
+                       (cx<double>*)off, (const double*)kx, (const double*)ky, (const double*)kz, shape[1], shape[2], n);
+  else
+    hipLaunchKernelGGL(strain_kernel<float>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, st, (const cx<float>*)U_hat, (cx<float>*)diag,
+                       (cx<float>*)off, (const float*)kx, (const float*)ky, (const float*)kz, shape[1], shape[2], n);
   MFFT_HIP(hipGetLastError());
   return 0;
 }

@@ -451,6 +451,128 @@ def histogram(FFT, x, bins=256, range=None, reduce=False):
     return Histogram(n, out, lo, hi)
 
 
+def quad_rule(r, weights):
+    """The evaluation rule of the quadratic forms, in numpy float64 (include/mpifft4py_amd.h): r of shape (n, ...) holds the
+    fields' values in SLOT order (`quad_slot_order`), q = 0, then q = q + (w_f * r_f) * r_f field by field -- every product
+    and sum rounded on its own (numpy never contracts), which is what the device computes."""
+    r = np.asarray(r, dtype=np.float64)
+    w = np.asarray(weights, dtype=np.float64)
+    assert r.shape[0] == w.shape[0], (r.shape, w.shape)
+    q = np.zeros(r.shape[1:], dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for f in range(r.shape[0]):
+            q = q + (w[f] * r[f]) * r[f]
+    return q
+
+
+def quad_slot_order(nfields, two):
+    """The order in which `real_quadratic` adds its fields: a's components as they come where a_hat stands alone; with b_hat,
+    a_f and b_f share a transform and the order is a_0, b_0, a_1, b_1, a_2, b_2 (indices into a's fields, then b's)."""
+    if not two:
+        return list(range(nfields))
+    ncomp = nfields // 2
+    return [i for f in range(ncomp) for i in (f, ncomp + f)]
+
+
+def _quad_args(weights, nfields, center, bins, rng):
+    w = np.ones(nfields, dtype=np.float64) if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+    if w.shape != (nfields,):
+        raise ValueError("%d weights for %d fields" % (w.size, nfields))
+    if not np.all(np.isfinite(w)):
+        raise ValueError("every weight must be finite, not %r" % (w,))
+    if not 0 <= int(bins) <= HIST_MAXBINS:
+        raise ValueError("bins must be 0 .. %d, not %r" % (HIST_MAXBINS, bins))
+    lo, hi = (0.0, 1.0) if rng is None else (float(rng[0]), float(rng[1]))
+    if int(bins) > 0 and not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise ValueError("the range needs finite lo < hi, not %r .. %r" % (lo, hi))
+    return w, float(center), lo, hi
+
+
+def _quad_range(m):
+    """[min, max] of a first call without bins, widened as in `real_histogram`."""
+    mn, mx = float(m.min[0]), float(m.max[0])
+    if not (np.isfinite(mn) and np.isfinite(mx)):
+        raise ValueError("q is not finite (min %r, max %r): give `range`" % (mn, mx))
+    if not mn < mx:
+        return mn - 0.5, mn + 0.5
+    return mn, float(max(mx + (mx - mn) * 2.0 ** -20, np.nextafter(mx, np.inf)))
+
+
+def _quad_result(FFT, out6, counts, n, center, bins, lo, hi, reduce):
+    m = _moments_result(FFT, out6, n, np.array([center]), reduce)
+    if not bins:
+        return m, None
+    if reduce:
+        counts, n = _add_over_ranks(FFT, counts), int(_add_over_ranks(FFT, [n])[0])
+    return m, Histogram(n, counts.reshape(1, -1), [lo], [hi])
+
+
+def real_quadratic(FFT, a_hat, b_hat=None, dealias=None, weights=None, center=0.0, bins=0, range=None, reduce=True):
+    """Statistics of a QUADRATIC FORM of fields that exist as spectra only (mfft_real_quadratic):
+        q(x) = sum_f weights[f] * ifftn(field f, dealias)(x)**2
+    over the components of a_hat and, where given, of b_hat (1, 2, 3 or 6 fields, a's first; `weights` None: all ones) --
+    enstrophy density (the curl, weights 1), dissipation (`strain_hat`, weights 2 nu (1, 1, 1, 2, 2, 2)), energy density --
+    whose moments and PDF do not follow from those of the single fields.  Returns (`Moments`, `Histogram` or None), each of ONE
+    field: min, max and the sums of (q - center)**p, p = 1..4, and with `bins` > 0 the counts of q in `bins` equal bins of
+    `range` = (lo, hi) by the slot rule of `real_histogram`.  bins > 0 with range None: a first call without bins gives
+    [min, max] over FFT.comm, widened as in `real_histogram`.  Fields, grid and routes as `real_moments`
+    (`FFT.plan_info("nonlinear_quadratic_fused_3_2")`): fused, the z kernel accumulates q in registers across the inverse
+    transforms of a row and no real array exists; elsewhere one field at a time goes through ONE work array into ONE array of
+    doubles.  q follows ONE rule on every route (`quad_rule`, fields in `quad_slot_order`).  A NaN or Inf in any field gives
+    NaN statistics and counts in the non-finite slot.  With `reduce` over FFT.comm; bitwise reproducible.  Synchronises the
+    plan's stream; the inputs are preserved."""
+    cs = tuple(int(s) for s in FFT.complex_shape())
+    assert a_hat.shape in (cs, (3,) + cs), (a_hat.shape, cs)
+    vec = len(a_hat.shape) == 4
+    fields = [(a_hat, vec)] + ([(b_hat, vec)] if b_hat is not None else [])
+    ncomp = 3 if vec else 1
+    nfields = ncomp * len(fields)
+    w, center, lo, hi = _quad_args(weights, nfields, center, bins, range)
+    if int(bins) > 0 and range is None:
+        lo, hi = _quad_range(real_quadratic(FFT, a_hat, b_hat, dealias, w, center, 0, None, True)[0])
+    out6 = np.zeros(6, dtype=np.float64)
+    counts = np.zeros(int(bins) + 3, dtype=np.int64)
+    count = ctypes.c_int64(0)
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
+    _nonlinear(FFT, "real_quadratic", fields, dealias, head=(a_hat.ptr, b_hat.ptr if b_hat is not None else None, ncomp),
+               tail=(w.ctypes.data_as(dp), center, lo, hi, int(bins), out6.ctypes.data_as(dp), counts.ctypes.data_as(ip), ctypes.byref(count)))
+    return _quad_result(FFT, out6, counts, count.value, center, int(bins), lo, hi, reduce)
+
+
+def quadratic(FFT, x, weights=None, center=0.0, bins=0, range=None, reduce=False):
+    """The same statistics of q = sum_c weights[c] * x[c]**2 of a real DeviceArray (mfft_ew_quadratic, the companion of `moments`
+    and `histogram`): an array of the real shape is one field, a leading extent of 1, 2, 3 or 6 is taken as components, added
+    in that order.  q is formed on the fly in one sweep; there is no q array.  Returns (`Moments`, `Histogram` or None)."""
+    if x.pitch is not None:
+        raise ValueError("a quadratic form of a pitched array would count the elements between its rows")
+    assert x.dtype == np.dtype(FFT.float), (x.dtype, FFT.float)
+    ncomp = int(x.shape[0]) if len(x.shape) == 4 else 1
+    w, center, lo, hi = _quad_args(weights, ncomp, center, bins, range)
+    if int(bins) > 0 and range is None:
+        lo, hi = _quad_range(quadratic(FFT, x, w, center, 0, None, reduce)[0])
+    FFT.comm.use_device()
+    out6 = np.zeros(6, dtype=np.float64)
+    counts = np.zeros(int(bins) + 3, dtype=np.int64)
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
+    _lib.call("mfft_ew_quadratic", FFT._plan, x.ptr, ncomp, x.size // ncomp, _prec(FFT), w.ctypes.data_as(dp), center, lo, hi, int(bins),
+              out6.ctypes.data_as(dp), counts.ctypes.data_as(ip))
+    return _quad_result(FFT, out6, counts, x.size // ncomp, center, int(bins), lo, hi, reduce)
+
+
+def strain_hat(FFT, K, U_hat, diag, off):
+    """The strain-rate tensor S_ij = (du_i/dx_j + du_j/dx_i) / 2 of a vector field in spectral space (mfft_ew_strain_hat), U_hat
+    read once: diag[f] = i K[f] U_hat[f] (S_00, S_11, S_22) and off = (S_01, S_02, S_12), S_ij = i (K[i] U_hat[j] + K[j] U_hat[i]) / 2.
+    All three are distinct arrays of shape (3,) + FFT.complex_shape(); pitched spectra are swept as they lie in memory.  The
+    dissipation 2 nu S_ij S_ij is `real_quadratic(FFT, diag, off, weights=2 * nu * np.array([1, 1, 1, 2, 2, 2]))`.
+    Returns (diag, off)."""
+    cs = tuple(int(x) for x in FFT.complex_shape())
+    assert U_hat.shape == diag.shape == off.shape == (3,) + cs, (U_hat.shape, diag.shape, off.shape, cs)
+    assert U_hat.dtype == diag.dtype == off.dtype == np.dtype(FFT.complex), (U_hat.dtype, diag.dtype, off.dtype)
+    assert U_hat.pitch == diag.pitch == off.pitch, (U_hat.pitch, diag.pitch, off.pitch)
+    _lib.call("mfft_ew_strain_hat", FFT._plan, U_hat.ptr, diag.ptr, off.ptr, K.dev[0].ptr, K.dev[1].ptr, K.dev[2].ptr, K.cshape, _prec(FFT))
+    return diag, off
+
+
 def advective_dt(FFT, umax, cfl):
     """cfl / sum_f umax[f] N[f] / L[f]: the advective (CFL) time step of a velocity whose components reach umax[f], on
     the mesh FFT.N of the box FFT.L -- the mesh of the run, not the padded one of a 3/2-rule product.  Pure host
