@@ -254,6 +254,13 @@ MFFT_API int mfft_nlz_dot_rows(const void* a, const void* b, void* out, int64_t 
  * FFT.ifftn + four FFT.fftn around a caller's np.cross(U, W) and np.sum(U * gradT, 0). */
 MFFT_API int mfft_nlz_cross_dot_rows(const void* a, const void* b, const void* c, void* out, void* s, int64_t nrows, int64_t n,
                                      int64_t pitch, int64_t valid, int precision, int sync);
+/* The same stage with the OUTER product (the z stages of mfft_nonlinear_outer): a, b are (3, nrows, pitch) as above, out is
+ * (9, nrows, pitch); out[3 i + j][row] = rfft(irfft(a[i, row]) irfft(b[j, row]))[:valid], all nine.  out's components 0..5 may be
+ * the six input components (a's three, then b's three), row for row -- every load of a row precedes its first store --;
+ * components 6..8 may not be an input.  MFFT_ERR_UNSUPPORTED for lengths without a kernel.  Replaces the z stages of six
+ * FFT.ifftn + nine FFT.fftn around a caller's A[:, None] * B[None, :]. */
+MFFT_API int mfft_nlz_outer_rows(const void* a, const void* b, void* out, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
+                                 int precision, int sync);
 /* Either stage with the maxima of its six real rows, synchronous: `out` as mfft_nlz_rows (dot = 0) or mfft_nlz_dot_rows
  * (dot = 1) leave it, and out6 = [max |irfft(a[f])|, f = 0..2, then max |irfft(b[f])|, f = 0..2] over all rows and all n
  * points (numpy's normalisation).  A NaN in a field gives NaN for that field.  The z stage of mfft_nonlinear_cross_absmax /
@@ -349,6 +356,17 @@ MFFT_API int mfft_ew_curl_hat(mfft_plan_t plan, const void* U_hat, void* out, co
 /* out = sum_f a_f b_f on real fields, a and b (3, n) component-major, out (n): what a caller writes as np.sum(a * b, 0);
  * out may be a component of a or b */
 MFFT_API int mfft_ew_dot(mfft_plan_t plan, const void* a, const void* b, void* out, size_t n, int precision);
+/* out = a b on real fields of n values: ONE product a_i b_j of the composed outer product; out may be a or b */
+MFFT_API int mfft_ew_mul(mfft_plan_t plan, const void* a, const void* b, void* out, size_t n, int precision);
+/* The right-hand sides of incompressible MHD in Elsasser variables z+- = u +- b in ONE sweep.  T_hat is (9,) + shape, the nine
+ * products T[3 i + j] = fftn(z+_i z-_j) of mfft_nonlinear_outer(Zp_hat, Zm_hat); Zp_hat, Zm_hat, dZp, dZm are (3,) + shape.  Per bin
+ *     N+_i = -i sum_j K_j T[3 i + j],   N-_i = -i sum_j K_j T[3 j + i],   each projected: N - K (K . N) / |K|^2 (0 at K = 0),
+ *     dZ+-_i = N+-_i - |K|^2 (np Z+-_i + nm Z-+_i),   np = (nu + eta) / 2,  nm = (nu - eta) / 2.
+ * dZp and dZm are arrays of their own (MFFT_ERR_INVALID where one is an input or the other).  kx / ky / kz and `shape` as for
+ * mfft_ew_curl_hat (pitched spectra: shape[2] = the row pitch, swept as they lie). */
+MFFT_API int mfft_ew_elsasser_rhs(mfft_plan_t plan, const void* T_hat, const void* Zp_hat, const void* Zm_hat, void* dZp, void* dZm,
+                                  const void* kx, const void* ky, const void* kz, const int64_t shape[3], double nu, double eta,
+                                  int precision);
 /* out_f = i K_f s_hat, the gradient of a scalar in spectral space: s_hat has `shape`, out is (3,) + shape; kx / ky / kz and
  * `shape` as for mfft_ew_curl_hat (pitched spectra: shape[2] = the row pitch, kz padded to it).  What a caller writes as
  * 1j * K * s_hat. */
@@ -477,6 +495,20 @@ MFFT_API int mfft_nonlinear_dot(mfft_plan_t plan, const void* a_hat, const void*
  * composes it on twelve work arrays of its own.  No statistics variant: take the maxima from mfft_nonlinear_cross_absmax. */
 MFFT_API int mfft_nonlinear_cross_dot(mfft_plan_t plan, const void* a_hat, const void* b_hat, const void* c_hat, void* out_hat,
                                       void* s_hat, int dealias);
+
+/* The OUTER product of two vector fields as ONE operation, all nine components:
+ *     out_hat[3 i + j] = fftn(ifftn(a_hat[i]) * ifftn(b_hat[j])),   i, j = 0..2
+ * -- the Elsasser products z+_i z-_j of incompressible MHD, a convective term in conservative form, a Reynolds or sub-grid
+ * stress u_i u_j, a scalar flux: six inverse and nine forward transforms, where three mfft_nonlinear_cross calls (u x omega,
+ * j x b, u x b) take eighteen and nine.  a_hat, b_hat: (3,) + local complex shape; out_hat: (9,) + local complex shape,
+ * component 3 i + j.  a_hat == b_hat is allowed and gives the symmetric tensor, all nine components computed.  out_hat may NOT
+ * overlap an input: MFFT_ERR_INVALID before anything is enqueued.  The inputs are preserved.  Dealias conventions are those of
+ * mfft_nonlinear_cross; routes (mfft_plan_get_info "nonlinear_outer_fused_3_2" / "_none" / "_2_3"): on slab R2C plans with
+ * radix kernels on every axis the z stages are ONE kernel (csrc/fft_nlz.h body_outer: 7.5 complex transforms per (x, y) row,
+ * the minimum for fifteen real rows; results 0..5 in place on the six inputs of the batch, 6..8 into three more fields) and
+ * no real-space array exists; every other plan -- pencils, z lengths without a kernel, MFFT_NO_NLZ=1 -- composes it on seven
+ * real work arrays of its own: six inverse transforms, then per (i, j) one product (mfft_ew_mul) and one forward transform. */
+MFFT_API int mfft_nonlinear_outer(mfft_plan_t plan, const void* a_hat, const void* b_hat, void* out_hat, int dealias);
 
 /* The two operations above WITH STATISTICS: the call also records, on the device,
  *     absmax[0][f] = max |ifftn(a_hat[f], dealias)|,   absmax[1][f] = max |ifftn(b_hat[f], dealias)|,   f = 0..2

@@ -91,6 +91,7 @@ _SIGNATURES = {
     "mfft_c2r_last": ([c_void_p, c_void_p, POINTER(c_int64), c_int], c_int),
     "mfft_nlz_rows": ([c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int], c_int),
     "mfft_nlz_dot_rows": ([c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int], c_int),
+    "mfft_nlz_outer_rows": ([c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int], c_int),
     "mfft_nlz_cross_dot_rows": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int], c_int),
     "mfft_nlz_rows_absmax": ([c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, POINTER(c_double)], c_int),
     "mfft_nlz_moments_rows": ([c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, POINTER(c_double),
@@ -111,12 +112,15 @@ _SIGNATURES = {
     "mfft_kernel_name": ([c_int, c_int64, c_int, c_int, c_int, c_void_p, c_size_t], c_int),
     "mfft_nonlinear_cross": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int], c_int),
     "mfft_nonlinear_dot": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int], c_int),
+    "mfft_nonlinear_outer": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int], c_int),
     "mfft_nonlinear_cross_dot": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int], c_int),
     "mfft_nonlinear_cross_absmax": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int], c_int),
     "mfft_nonlinear_dot_absmax": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int], c_int),
     "mfft_plan_nonlinear_absmax": ([c_void_p, POINTER(c_double)], c_int),
     "mfft_ew_cross": ([c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int], c_int),
     "mfft_ew_curl_hat": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_int], c_int),
+    "mfft_ew_mul": ([c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int], c_int),
+    "mfft_ew_elsasser_rhs": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_double, c_double, c_int], c_int),
     "mfft_ew_dot": ([c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int], c_int),
     "mfft_ew_grad_hat": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_int], c_int),
     "mfft_ew_diag_grad_hat": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_int], c_int),

@@ -299,6 +299,17 @@ int mfft_nlz_cross_dot_rows(const void* a, const void* b, const void* c, void* o
   return nlz_run(nlz_args(Op::CrossDot, a, b, c, out, s, nrows, n, pitch, valid, precision), sync);
 }
 
+// ... and with the outer product (fft_nlz.h body_outer): a, b (3, nrows, pitch), out (9, nrows, pitch), component 3 i + j the rows of
+// a_i b_j; out's components 0..5 may be the six input components (a's, then b's), row for row
+int mfft_nlz_outer_rows(const void* a, const void* b, void* out, int64_t nrows, int64_t n, int64_t pitch, int64_t valid, int precision,
+                        int sync) {
+  if (!a || !b || !out || nrows < 1 || n < 2 || pitch < valid || valid < 1) return set_error(MFFT_ERR_INVALID, "bad argument");
+  NlzArgs z = nlz_args(Op::Outer, a, b, nullptr, out, nullptr, nrows, n, pitch, valid, precision);
+  const size_t comp = (size_t)(nrows * pitch) * elem_bytes(precision, true);
+  for (int c = 3; c < 9; ++c) z.out[c] = static_cast<char*>(out) + c * comp;
+  return nlz_run(z, sync);
+}
+
 // The stage with the maxima of its six real rows (fft_nlz.h NlzAbsMax), synchronous: out as mfft_nlz_rows (dot = 0) or
 // mfft_nlz_dot_rows (dot = 1) leave it, out6 = [max |irfft(a_f)|, f = 0..2, max |irfft(b_f)|, f = 0..2] over all rows.
 int mfft_nlz_rows_absmax(const void* a, const void* b, void* out, int64_t nrows, int64_t n, int64_t pitch, int64_t valid, int precision,

@@ -555,6 +555,8 @@ static int launch_nlz_t(const KernelEntry* e, const NlzArgs& a, void* tw, void* 
     for (int f = 0; f < 3; ++f) P.c[f] = static_cast<const cx<T>*>(a.c[f]);
     P.outs = static_cast<cx<T>*>(a.out[3]);
   }
+  if constexpr (std::is_same<PT, NloParams<T>>::value)
+    for (int c = 0; c < 9; ++c) P.out9[c] = static_cast<cx<T>*>(a.out[c]);
   P.rt3 = static_cast<const cx<T>*>(rt3);
   for (int f = 0; f < 3; ++f) {
     P.a[f] = static_cast<const cx<T>*>(a.a[f]);
@@ -595,6 +597,7 @@ int launch_nlz(const NlzArgs& a, hipStream_t s) {
     using T = decltype(t);
     if (a.part) return launch_nlz_t<T, NlmParams<T>>(e, a, tw, rt3, s);
     if (q.nin > 6) return launch_nlz_t<T, NlcParams<T>>(e, a, tw, rt3, s);      // (a third field in, a fourth row out)
+    if (q.op == Op::Outer) return launch_nlz_t<T, NloParams<T>>(e, a, tw, rt3, s);      // (nine rows out)
     return launch_nlz_t<T>(e, a, tw, rt3, s);
   });
 }

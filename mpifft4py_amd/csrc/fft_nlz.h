@@ -56,6 +56,12 @@ struct NlcParams : NlzParams<T> {
   const cx<T>* c[3];           // half-spectra rows of the third vector field, strides and valid_in as a[] / b[]
   cx<T>* outs;                 // half-spectra rows of sum_f a_f c_f; may alias one a[] / b[] / c[] component out[] does not take
 };
+// ... of the kernel that forms all NINE products a_i b_j (NlzFft::body_outer below): six rows in, nine out -- the first product with
+// more rows out than in.  out[] is not used.
+template <typename T>
+struct NloParams : NlzParams<T> {
+  cx<T>* out9[9];              // half-spectra rows of a_i b_j at 3 i + j; [0..2] may alias a[0..2], [3..5] b[0..2], row for row
+};
 
 // ... of the kernel that ends in a REDUCTION instead of a product (NlzFft::body_moments below): min, max and the sums of the first
 // four powers of up to six real fields.  Pair p is a[p] + i b[p] on one complex transform, p < npairs; b[p] may be null (an odd
@@ -581,6 +587,89 @@ struct NlzFft {
     }
   }
 
+  // The stage with the OUTER product: out9[3 i + j] = rfft(irfft(a_i) irfft(b_j)), all nine -- the Elsasser products z+_i z-_j of
+  // incompressible MHD, a convective term in conservative form, a stress u_i u_j (a = b).  Six real rows in, nine out: three
+  // inverse transforms (a_f + i b_f) and four and a half forward ones per row, 7.5 transforms of length M, the minimum for fifteen
+  // real rows.  All six real values of a position sit in the thread after the third inverse transform; the products leave in the
+  // order that retires a_0 first,
+  //     (a0 b0, a0 b1)   (a0 b2, a1 b0)   (a1 b1, a1 b2)   (a2 b0, a2 b1)      each pair on ONE forward transform into the row's own outputs
+  //     a2 b2 of the TWO rows of a pair together on one more, as r2 / r2a of body_t.
+  // Parked next to the first forward transform's working set: a0 b2, a1, a2, b0, b1, b2 and the partner row's a2 b2 -- 7 E reals,
+  // where body_cross_dot parks 6 E; the later transforms park 6, 5 and 2 E.  The scale goes onto a once (3 E products instead of 9 E).
+  // Every load of a row precedes its first store, and the two rows of a pair are loaded and stored one after the other: out9[0..2]
+  // may lie over a[0..2] and out9[3..5] over b[0..2], row for row (the routes use exactly that); out9[6..8] are never inputs.
+  // A row past nrows reads as zeros and stores nothing (body_cross_dot's rule: the last row is NOT read again).
+  // (The thread index is not hidden at the head of the transforms: see body_cross_dot.)
+  template <class PP>
+  static MFFT_D void body_outer(const PP& P, int bid, int tid, char* lds) {
+    cx<T>* ltw = reinterpret_cast<cx<T>*>(lds);
+    const int rl = tid / S::TPT;
+    const int j = row_thread_index<S>(tid);
+    XE* xb = reinterpret_cast<XE*>(lds + TW_BYTES) + rl * PLEN;
+    if constexpr (TWLDS && S::NP > 1) {
+      stage_twiddles<S, T>(ltw, P.tw, tid, THREADS);
+      if constexpr (WAVE) MFFT_BARRIER();
+    }
+    const cx<T>* tw = (TWLDS && S::NP > 1) ? (const cx<T>*)ltw : P.tw;
+    Xch xc{xb, PadSlot<PD>{}};
+    const i64 unit = (i64)bid * ROWS + rl;         // a pair of rows
+    const i64 last = P.nrows - 1;
+    T w8a[E];                                      // a2 b2 of the first row of the pair
+#pragma unroll
+    for (int k = 0; k < E; ++k) w8a[k] = (T)0;
+    bool sa = false;
+    i64 rowa = 0;
+#pragma unroll 1
+    for (int h = 0; h < 2; ++h) {
+      const i64 row = 2 * unit + h;
+      const bool active = row < P.nrows;
+      const i64 io = (active ? row : last) * P.in_stride;
+      const int vin = active ? P.valid_in : 0;
+      cx<T> v[E];
+      T a0[E], a1[E], a2[E], b0[E], b1[E], b2[E];
+      // the results are swapped (inverse through the swap identity): .y = a_f, .x = b_f at position j + k TPT
+      inverse_pair(v, P.a[0] + io, P.b[0] + io, j, vin, tw, xc);
+#pragma unroll
+      for (int k = 0; k < E; ++k) { a0[k] = v[k].y * P.scale; b0[k] = v[k].x; }
+      inverse_pair(v, P.a[1] + io, P.b[1] + io, j, vin, tw, xc);
+#pragma unroll
+      for (int k = 0; k < E; ++k) { a1[k] = v[k].y * P.scale; b1[k] = v[k].x; }
+      inverse_pair(v, P.a[2] + io, P.b[2] + io, j, vin, tw, xc);
+#pragma unroll
+      for (int k = 0; k < E; ++k) { a2[k] = v[k].y * P.scale; b2[k] = v[k].x; }
+      const i64 oo = row * P.out_stride;
+      T p02[E];
+#pragma unroll
+      for (int k = 0; k < E; ++k) {
+        v[k] = mk<T>(a0[k] * b0[k], a0[k] * b1[k]);
+        p02[k] = a0[k] * b2[k];
+      }
+      forward_pair(v, j, tw, xc, xb, P.out9[0] + oo, P.out9[1] + oo, active, active, P.valid);
+#pragma unroll
+      for (int k = 0; k < E; ++k) v[k] = mk<T>(p02[k], a1[k] * b0[k]);
+      forward_pair(v, j, tw, xc, xb, P.out9[2] + oo, P.out9[3] + oo, active, active, P.valid);
+#pragma unroll
+      for (int k = 0; k < E; ++k) v[k] = mk<T>(a1[k] * b1[k], a1[k] * b2[k]);
+      forward_pair(v, j, tw, xc, xb, P.out9[4] + oo, P.out9[5] + oo, active, active, P.valid);
+#pragma unroll
+      for (int k = 0; k < E; ++k) {
+        v[k] = mk<T>(a2[k] * b0[k], a2[k] * b1[k]);
+        a2[k] = a2[k] * b2[k];
+      }
+      forward_pair(v, j, tw, xc, xb, P.out9[6] + oo, P.out9[7] + oo, active, active, P.valid);
+      if (h == 0) {
+#pragma unroll
+        for (int k = 0; k < E; ++k) w8a[k] = a2[k];
+        sa = active;
+        rowa = row;
+      } else {
+#pragma unroll
+        for (int k = 0; k < E; ++k) v[k] = mk<T>(w8a[k], a2[k]);
+        forward_pair(v, j, tw, xc, xb, P.out9[8] + rowa * P.out_stride, P.out9[8] + oo, sa, active, P.valid);
+      }
+    }
+  }
+
   // The stage that ends in a REDUCTION: min, max and S_p = sum (x - c)^p, p = 1..4, of up to six real fields over all rows and all
   // M positions -- the one-point statistics of a field that never exists in real space.  ceil(nfields / 2) inverse transforms per
   // row, nothing forward, nothing stored but the partials; nothing is parked next to a transform's working set but the
@@ -827,7 +916,7 @@ struct NlzFft {
 // The product of the stage as a parameter of the kernel: NlzProd<K, NlzProduct::Dot> is K's rows, exchanges and transforms
 // around the dot product.  (A wrapper, not a seventh parameter of NlzFft: that would rename every cross-product kernel's
 // symbol, and scripts/kernel_regs.py --diff could no longer show that they are what they were.)
-enum class NlzProduct { Cross = 0, Dot = 1, CrossDot = 2 };
+enum class NlzProduct { Cross = 0, Dot = 1, CrossDot = 2, Outer = 3 };
 template <class K, NlzProduct PRODUCT = NlzProduct::Cross> struct NlzProd : K {};
 template <class K> struct NlzProd<K, NlzProduct::Dot> {
   static constexpr int THREADS = K::THREADS, LDS_BYTES = K::LDS_BYTES;
@@ -837,6 +926,11 @@ template <class K> struct NlzProd<K, NlzProduct::Dot> {
 template <class K> struct NlzProd<K, NlzProduct::CrossDot> {      // (takes NlcParams)
   static constexpr int THREADS = K::THREADS, LDS_BYTES = K::LDS_BYTES;
   template <class P> static MFFT_D void body(const P& p, int bid, int tid, char* lds) { K::body_cross_dot(p, bid, tid, lds); }
+};
+
+template <class K> struct NlzProd<K, NlzProduct::Outer> {         // (takes NloParams)
+  static constexpr int THREADS = K::THREADS, LDS_BYTES = K::LDS_BYTES;
+  template <class P> static MFFT_D void body(const P& p, int bid, int tid, char* lds) { K::body_outer(p, bid, tid, lds); }
 };
 
 // The stage that also emits the six maxima (Build::AbsMax): K's body with STATS on and NlmParams.  A wrapper again, for the

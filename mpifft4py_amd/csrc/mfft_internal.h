@@ -123,7 +123,7 @@ struct NlzArgs {
   const void* a[3] = {nullptr, nullptr, nullptr};
   const void* b[3] = {nullptr, nullptr, nullptr};
   const void* c[3] = {nullptr, nullptr, nullptr};   // Op::CrossDot only
-  void* out[4] = {nullptr, nullptr, nullptr, nullptr};
+  void* out[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // (nine: Op::Outer)
   int n = 0;             // REAL length of a z row
   int prec = MFFT_DOUBLE;
   int64_t in_stride = 0, out_stride = 0, nrows = 0;   // complex elements
@@ -131,7 +131,8 @@ struct NlzArgs {
   int valid_in = 0;      // bins per INPUT row, where fewer than `valid` exist (pruned 2/3-rule); 0 = valid
   double scale = 1.0;    // applied to the product (1 / n^2: both inverse transforms normalised)
   Op product = Op::Plain;  // Op::Plain: a x b into out[0..2];  Op::Dot: sum_f a_f b_f into out[0], out[1..2] unused;
-                           // Op::CrossDot: a x b into out[0..2] and sum_f a_f c_f into out[3]
+                           // Op::CrossDot: a x b into out[0..2] and sum_f a_f c_f into out[3];
+                           // Op::Outer: a_i b_j into out[3 i + j]; out[0..2] may be a[0..2], out[3..5] b[0..2]
   void* part = nullptr;    // not null: the Build::AbsMax kernel runs and writes nlz_absmax_waves() groups of 12 un-normalised
                            // partial maxima here, in the rows' precision: [wave][row of the pair][a, b][field] (fft_nlz.h NlmParams)
 };
@@ -147,6 +148,7 @@ constexpr NlProduct NL_PRODUCTS[] = {
     {Op::Plain, "cross", 6, 3, true, true},
     {Op::Dot, "dot", 6, 1, true, false},
     {Op::CrossDot, "cross_dot", 9, 4, false, false},
+    {Op::Outer, "outer", 6, 9, false, false},
     {Op::Moments, "moments", 6, 0, false, false},      // (up to six fields: the call says how many, NlFields::nfields)
     {Op::Histogram, "histogram", 6, 0, false, false},
     {Op::Quadratic, "quadratic", 6, 0, false, false},

@@ -336,7 +336,7 @@ int mfft_backward(mfft_plan_t p, const void* fu, void* u, int dealias) {
 static int run_nonlinear(mfft_plan_t p, Op product, bool stats, const NlFields& u, int dealias) {
   const NlProduct& q = nl_product(product);
   MFFT_TRY(check_ready(p, u.a, u.b));
-  if (!u.out || (q.nin > 6 && !u.c) || (q.nout > 3 && !u.outs)) return set_error(MFFT_ERR_INVALID, "null argument");
+  if (!u.out || (q.nin > 6 && !u.c) || (q.nout > u.nres && !u.outs)) return set_error(MFFT_ERR_INVALID, "null argument");
   if (dealias != MFFT_DEALIAS_NONE && dealias != MFFT_DEALIAS_2_3 && dealias != MFFT_DEALIAS_3_2)
     return set_error(MFFT_ERR_INVALID, "unknown dealias mode %d", dealias);
   return p->nonlinear(u, dealias, product, stats);
@@ -358,6 +358,20 @@ int mfft_nonlinear_dot(mfft_plan_t p, const void* a_hat, const void* b_hat, void
 // component; out may be a or b, s any one component of c.  See include/mpifft4py_amd.h.
 int mfft_nonlinear_cross_dot(mfft_plan_t p, const void* a_hat, const void* b_hat, const void* c_hat, void* out_hat, void* s_hat, int dealias) {
   return run_nonlinear(p, Op::CrossDot, false, {a_hat, b_hat, c_hat, out_hat, s_hat}, dealias);
+}
+
+// out[3 i + j] = fftn(ifftn(a_i) ifftn(b_j)), all nine: a, b vector fields, out NINE components; a may be b (the symmetric tensor,
+// all nine computed); out may not overlap an input -- rejected before anything is enqueued.  See include/mpifft4py_amd.h.
+int mfft_nonlinear_outer(mfft_plan_t p, const void* a_hat, const void* b_hat, void* out_hat, int dealias) {
+  MFFT_TRY(check_ready(p, a_hat, b_hat));
+  if (!out_hat) return set_error(MFFT_ERR_INVALID, "null argument");
+  const size_t comp = (size_t)p->local_complex_alloc() * p->es;
+  const char *o = static_cast<const char*>(out_hat), *ins[2] = {static_cast<const char*>(a_hat), static_cast<const char*>(b_hat)};
+  for (const char* i : ins)
+    if (o < i + 3 * comp && i < o + 9 * comp) return set_error(MFFT_ERR_INVALID, "nonlinear_outer: out_hat overlaps an input");
+  NlFields u{a_hat, b_hat, nullptr, out_hat, nullptr};
+  u.nres = 9;
+  return run_nonlinear(p, Op::Outer, false, u, dealias);
 }
 
 // ... and the first two with statistics: the call also leaves the six real-space maxima in the plan (mfft_plan_nonlinear_absmax)

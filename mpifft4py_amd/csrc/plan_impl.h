@@ -75,19 +75,21 @@ struct Buf {                   // a device buffer of the plan that only grows (m
 };
 
 // The caller's arrays of one nonlinear operation (plan_nonlinear.hip): vector fields a, b and -- where the product has one -- c
-// in, the result out (three components, or the ONE of the dot product) and, of the product with both, the scalar result outs.
+// in, the result out (three components, the ONE of the dot product, or the NINE of the outer product) and, of the product with
+// both, the scalar result outs.
 // An operation whose number of fields belongs to the call (Op::Moments): nfields of them, ncomp components of a, then of b.
 struct NlFields {
   const void *a, *b, *c;
   void *out, *outs;
   int ncomp = 3;               // components per field
   int nfields = 0;             // 0: what the table of products says (NlProduct::nin)
+  int nres = 3;                // components `out` holds (nine: the outer product); results beyond them are outs
   int nin(const NlProduct& q) const { return nfields > 0 ? nfields : q.nin; }
   // component f of the inputs (a, b, then c) / of the results (out, then outs), C elements of es bytes per component
   const void* src(int f, int64_t C, size_t es) const {
     return static_cast<const char*>(f < ncomp ? a : f < 2 * ncomp ? b : c) + (size_t)((f % ncomp) * C) * es;
   }
-  void* dst(int f, int64_t C, size_t es) const { return f < 3 ? static_cast<char*>(out) + (size_t)(f * C) * es : outs; }
+  void* dst(int f, int64_t C, size_t es) const { return f < nres ? static_cast<char*>(out) + (size_t)(f * C) * es : outs; }
 };
 
 // host-only part of plan construction: decomposition bookkeeping (no HIP call; plan_sched.hip)

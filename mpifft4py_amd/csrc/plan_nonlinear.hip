@@ -11,11 +11,15 @@ using namespace mfft;
 // ===========================================================================
 extern "C" int mfft_ew_cross(mfft_plan_t plan, const void* a, const void* b, void* out, size_t n, int precision);
 extern "C" int mfft_ew_dot(mfft_plan_t plan, const void* a, const void* b, void* out, size_t n, int precision);
+extern "C" int mfft_ew_mul(mfft_plan_t plan, const void* a, const void* b, void* out, size_t n, int precision);
 // Three products (mfft_internal.h NL_PRODUCTS) share every route below: the cross product (three result components); the dot
 // product sum_f ifftn(a_f) ifftn(b_f) of a transported scalar's u . grad(theta) (ONE result component: nout = 1 -- one forward y
 // pass, one forward exchange, one forward x pass; seven work arrays instead of nine in the composition); and both at once for a
 // velocity that carries a scalar, a x b AND sum_f a_f c_f with a third field c -- NINE fields in (nin), FOUR results (the scalar
 // one, `outs`, is the fourth): ifftn(a) is computed once where the two calls compute it twice.
+// The outer product, all nine a_i b_j (the Elsasser products of MHD, a stress u_i u_j): six fields in, NINE results -- the first
+// product with nout > nin, so the fused routes size their buffers and batches by max(nin, nout) fields: the z kernel writes results
+// 0..5 in place on the six inputs and 6..8 into three more fields of the batch, nine forward passes follow.
 // The routes read nin and nout from the table of products (mfft_internal.h NlProduct) and the caller's arrays through NlFields
 // (plan_impl.h); only the composed route, which chooses the element-wise products, names a product.
 
@@ -29,6 +33,8 @@ int64_t mfft_plan_s::local_real_count(bool padded) const {
 // arrays of the plan: the nin real fields, then the results.
 // Both products: twelve -- the dot product of a and c goes over c_0 (mfft_ew_dot allows it), the cross product into three more
 // arrays (mfft_ew_cross does not alias).
+// The outer product: seven -- the six real fields and ONE more, which takes each product a_i b_j in turn (mfft_ew_mul) and is
+// transformed forward before the next.
 int mfft_plan_s::nonlinear_composed(const NlFields& u, int dealias, Op product, bool stats) {
   const NlProduct& q = nl_product(product);
   const int nout = q.nout, nin = q.nin;
@@ -36,7 +42,8 @@ int mfft_plan_s::nonlinear_composed(const NlFields& u, int dealias, Op product, 
   const bool pad = dealias == MFFT_DEALIAS_3_2, masked = dealias == MFFT_DEALIAS_2_3;
   const int64_t nr = local_real_count(pad), nc = local_complex_alloc();       // (pitched arrays: a component is that much larger)
   if (nr <= 0 || !r2c) return set_error(MFFT_ERR_UNSUPPORTED, "nonlinear_%s needs a 3-D real-to-complex plan", q.name);
-  const int narr = both ? 12 : nin + nout;
+  const bool outer = product == Op::Outer;
+  const int narr = both ? 12 : outer ? 7 : nin + nout;
   MFFT_TRY(ensure(nlr, (size_t)(narr * nr) * rs));
   char* R = static_cast<char*>(nlr.p);
   auto arr = [&](int k) { return R + (size_t)(k * nr) * rs; };
@@ -48,6 +55,13 @@ int mfft_plan_s::nonlinear_composed(const NlFields& u, int dealias, Op product, 
   if (stats) MFFT_TRY(stage("nl_absmax", 6.0 * (double)nr * rs, [&] { return absmax_sweep(R, 6, (size_t)nr, static_cast<double*>(nlmacc.p)); }));
   // the element-wise products and where their results lie: res[f] is the work array forward transform f starts from
   int res[4] = {6, 7, 8, 0};
+  if (outer) {
+    for (int c = 0; c < nout; ++c) {
+      MFFT_TRY(stage("nl_mul", 3.0 * (double)nr * rs, [&] { return mfft_ew_mul(this, arr(c / 3), arr(3 + c % 3), arr(6), (size_t)nr, prec); }));
+      MFFT_TRY(fwd(arr(6), u.dst(c, nc, es)));
+    }
+    return 0;
+  }
   if (both) {
     MFFT_TRY(stage("nl_dot", 7.0 * (double)nr * rs, [&] { return mfft_ew_dot(this, arr(0), arr(6), arr(6), (size_t)nr, prec); }));
     MFFT_TRY(stage("nl_cross", 9.0 * (double)nr * rs, [&] { return mfft_ew_cross(this, arr(0), arr(3), arr(9), (size_t)nr, prec); }));
@@ -89,7 +103,7 @@ static int nlz_rows(mfft_plan_s* p, char* Y, size_t yelems, int64_t L2, int64_t 
     z.b[f] = Yf(3 + f);
     if (q.nin > 6) z.c[f] = Yf(6 + f);
   }
-  for (int f = 0; f < q.nout; ++f) z.out[f] = Yf(f);      // (four results: the scalar row over b_0)
+  for (int f = 0; f < q.nout; ++f) z.out[f] = Yf(f);      // (four results: the scalar row over b_0; nine: 6..8 in three more fields)
   z.product = product;
   z.n = (int)L2; z.prec = p->prec; z.in_stride = Za; z.out_stride = Za; z.nrows = nrows; z.valid = (int)p->Nf;
   z.valid_in = valid_in;
@@ -214,9 +228,10 @@ int mfft_plan_s::nonlinear_fused(const NlFields& u, int dealias, Op product, boo
   // gain nothing from it and pay for their short launches: profiles/r06_dns_batch.txt), so: batches of 16 GiB -- ONE batch up to
   // 512^3 with the 3/2-rule (14.9 GB), four at 768^3, eight at 1024^3 (14.7 GB of batch buffers beside 78.5 GB of x-pass
   // buffers).  MFFT_NLZ_BATCH_MB overrides.
-  const size_t plane6 = (size_t)(nin * L1 * Za) * es;      // (the bytes of a plane of every input field: six, or nine)
+  const int nf = std::max(nin, nout);                     // fields of the buffers: the outer product has more results than inputs
+  const size_t plane6 = (size_t)(nf * L1 * Za) * es;      // (the bytes of a plane of every field: six, or nine)
   const int64_t mb = std::min(std::max<int64_t>(nlz_batch_planes(plane6, L0), 1), L0);
-  MFFT_TRY(ensure(nlx, (size_t)nin * xelems * es));
+  MFFT_TRY(ensure(nlx, (size_t)nf * xelems * es));
   MFFT_TRY(ensure(nly, (size_t)mb * plane6));
   const size_t yelems = (size_t)(mb * L1 * Za);
   // field f of the x-pass buffers from element `off` of it on, of the batch buffers; where the batch of planes from i0 on starts
@@ -319,10 +334,11 @@ int mfft_plan_s::nonlinear_fused_ranks(const NlFields& u, int dealias, Op produc
   const int64_t S = Np1 * Nf + (pad ? 0 : xplane_pad(true));      // x-row pitch of the forward exchange's layout (sched())
   const int64_t C = N0 * Np1 * Nf;                                 // one component of the caller's arrays
   const size_t xelems = (size_t)(L0 * S);                          // one field in any of the exchanged layouts
-  const size_t plane6 = (size_t)(nin * L1 * Za) * es;      // (the bytes of a plane of every input field: six, or nine)
+  const int nf = std::max(nin, nout);                     // fields of the buffers: the outer product has more results than inputs
+  const size_t plane6 = (size_t)(nf * L1 * Za) * es;      // (the bytes of a plane of every field: six, or nine)
   const int64_t mb = nlz_batch_planes(plane6, Lp0);
-  MFFT_TRY(ensure(nlw[0], (size_t)nin * xelems * es));
-  MFFT_TRY(ensure(nlw[1], (size_t)nin * xelems * es));
+  MFFT_TRY(ensure(nlw[0], (size_t)nf * xelems * es));
+  MFFT_TRY(ensure(nlw[1], (size_t)nf * xelems * es));
   MFFT_TRY(ensure(nly, (size_t)mb * plane6));
   const size_t yelems = (size_t)(mb * L1 * Za);
   // field f of the two exchange buffers from element `off` of it on, of the batch buffers; where the batch of planes from i0 on
@@ -410,7 +426,7 @@ int mfft_plan_s::nonlinear_fused_ranks(const NlFields& u, int dealias, Op produc
 // stats does not touch it.
 int mfft_plan_s::nonlinear(const NlFields& u, int dealias, Op product, bool stats) {
   const NlProduct& q = nl_product(product);
-  if ((stats && !q.absmax) || (q.nin > 6 && !u.c) || (q.nout > 3 && !u.outs))
+  if ((stats && !q.absmax) || (q.nin > 6 && !u.c) || (q.nout > u.nres && !u.outs))
     return set_error(MFFT_ERR_INVALID, "nonlinear_%s: %d fields in, %d components out, %s", q.name, q.nin, q.nout, q.absmax ? "statistics" : "no statistics");
   if (dealias == MFFT_DEALIAS_2_3) MFFT_TRY(require_mask());
   if (stats) {

@@ -120,6 +120,19 @@ void register_nlc(const char* name) {
   reg.push_back(make_entry<K, NlcParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::CrossDot, Build::Default, R, name));
 }
 
+// Op::Outer: all nine products a_i b_j in one pass over the rows (fft_nlz.h body_outer, NloParams; kernels_nlo*.hip): six rows in,
+// nine out.  Rows, twiddle placement, exchange, wave-synchronous build and the two-waves-per-SIMD cap are the cross kernels', as
+// register_nlc's are: the body parks 7 E reals next to its first forward transform where body_cross_dot parks 6 E, and inlines
+// eight transforms (profiles/nonlinear_outer_regs.tsv).  No other cap was measured.
+template <class S, typename T>
+void register_nlo(const char* name) {
+  auto& reg = kernel_registry();
+  constexpr int R = nlz_rows<S, T>();
+  constexpr int W = MFFT_NLZ_OCC > 1 ? 16 + MFFT_NLZ_OCC : 0;
+  typedef NlzProd<NlzFft<S, T, R, nlz_twlds<S, T>(), nlz_split<S, T>(), nlz_wave<S, T>()>, NlzProduct::Outer> K;
+  reg.push_back(make_entry<K, NloParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::Outer, Build::Default, R, name));
+}
+
 // Op::Moments: the stage that ends in a reduction (fft_nlz.h body_moments, NlsParams; kernels_nls*.hip).  Rows, twiddle placement,
 // exchange, wave-synchronous build and the two-waves-per-SIMD cap are the cross kernels': the body inlines ONE transform where
 // the cross body inlines five and parks no row, but holds 36 doubles of accumulators for the whole launch: no scratch in single

@@ -38,6 +38,12 @@ __global__ __launch_bounds__(EW_BLOCK) void dot_kernel(const T* a, const T* b, T
     out[i] = a[i] * b[i] + a[n + i] * b[n + i] + a[2 * n + i] * b[2 * n + i];
 }
 
+// out = a b   (real space: one product a_i b_j of the composed outer product; out may be a or b)
+template <typename T>
+__global__ __launch_bounds__(EW_BLOCK) void mul_kernel(const T* a, const T* b, T* out, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) out[i] = a[i] * b[i];
+}
+
 // out_f = i K_f s   (spectral space: the gradient of a scalar)
 template <typename T>
 __global__ __launch_bounds__(EW_BLOCK) void grad_kernel(const cx<T>* __restrict__ S, cx<T>* __restrict__ out,
@@ -129,6 +135,48 @@ __global__ __launch_bounds__(EW_BLOCK) void rhs_kernel(cx<T>* __restrict__ dU, c
     dU[i] = mk<T>(d0.x - P.x * K0 - v * u0.x, d0.y - P.y * K0 - v * u0.y);
     dU[n + i] = mk<T>(d1.x - P.x * K1 - v * u1.x, d1.y - P.y * K1 - v * u1.y);
     dU[2 * n + i] = mk<T>(d2.x - P.x * K2 - v * u2.x, d2.y - P.y * K2 - v * u2.y);
+  }
+}
+
+// The right-hand side of incompressible MHD in Elsasser variables z+- = u +- b in ONE sweep: Tn holds the nine transformed products
+// T[3 i + j] = fftn(z+_i z-_j) (mfft_nonlinear_outer with a = z+, b = z-); per bin
+//     N+_i = -i sum_j K_j T[3 i + j]       the divergence over the SECOND index: -(z- . grad) z+
+//     N-_i = -i sum_j K_j T[3 j + i]       ... over the FIRST: -(z+ . grad) z-
+//     N   <- N - K (K . N) / |K|^2         both projected (the total pressure); the K = 0 bin is 0
+//     dZ+-_i = N+-_i - |K|^2 (np Z+-_i + nm Z-+_i),   np = (nu + eta) / 2, nm = (nu - eta) / 2
+template <typename T>
+__global__ __launch_bounds__(EW_BLOCK) void elsasser_rhs_kernel(const cx<T>* __restrict__ Tn, const cx<T>* __restrict__ Zp,
+                                                               const cx<T>* __restrict__ Zm, cx<T>* __restrict__ dZp,
+                                                               cx<T>* __restrict__ dZm, const T* __restrict__ kx,
+                                                               const T* __restrict__ ky, const T* __restrict__ kz, int64_t s1,
+                                                               int64_t s2, size_t n, T np, T nm) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const int64_t k = (int64_t)(i % s2), j = (int64_t)((i / s2) % s1), l = (int64_t)(i / (s2 * s1));
+    const T K[3] = {kx[l], ky[j], kz[k]};
+    const T k2 = K[0] * K[0] + K[1] * K[1] + K[2] * K[2];
+    const T inv = k2 == (T)0 ? (T)0 : (T)1 / k2;
+    cx<T> t[9], zp[3], zm[3], Np[3], Nm[3];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) t[c] = Tn[c * n + i];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { zp[c] = Zp[c * n + i]; zm[c] = Zm[c * n + i]; }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {                  // -i (x + i y) = (y, -x)
+      const cx<T> sp = mk<T>(K[0] * t[3 * c].x + K[1] * t[3 * c + 1].x + K[2] * t[3 * c + 2].x,
+                             K[0] * t[3 * c].y + K[1] * t[3 * c + 1].y + K[2] * t[3 * c + 2].y);
+      const cx<T> sm = mk<T>(K[0] * t[c].x + K[1] * t[3 + c].x + K[2] * t[6 + c].x, K[0] * t[c].y + K[1] * t[3 + c].y + K[2] * t[6 + c].y);
+      Np[c] = mk<T>(sp.y, -sp.x);
+      Nm[c] = mk<T>(sm.y, -sm.x);
+    }
+    const cx<T> Pp = mk<T>((Np[0].x * K[0] + Np[1].x * K[1] + Np[2].x * K[2]) * inv, (Np[0].y * K[0] + Np[1].y * K[1] + Np[2].y * K[2]) * inv);
+    const cx<T> Pm = mk<T>((Nm[0].x * K[0] + Nm[1].x * K[1] + Nm[2].x * K[2]) * inv, (Nm[0].y * K[0] + Nm[1].y * K[1] + Nm[2].y * K[2]) * inv);
+    const T keep = k2 == (T)0 ? (T)0 : (T)1;       // the mean mode has no nonlinear term
+    const T vp = np * k2, vm = nm * k2;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      dZp[c * n + i] = mk<T>(keep * (Np[c].x - Pp.x * K[c]) - vp * zp[c].x - vm * zm[c].x, keep * (Np[c].y - Pp.y * K[c]) - vp * zp[c].y - vm * zm[c].y);
+      dZm[c * n + i] = mk<T>(keep * (Nm[c].x - Pm.x * K[c]) - vp * zm[c].x - vm * zp[c].x, keep * (Nm[c].y - Pm.y * K[c]) - vp * zm[c].y - vm * zp[c].y);
+    }
   }
 }
 
@@ -314,6 +362,39 @@ int mfft_ew_dot(mfft_plan_t plan, const void* a, const void* b, void* out, size_
     hipLaunchKernelGGL(dot_kernel<double>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, st, (const double*)a, (const double*)b, (double*)out, n);
   else
     hipLaunchKernelGGL(dot_kernel<float>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, st, (const float*)a, (const float*)b, (float*)out, n);
+  MFFT_HIP(hipGetLastError());
+  return 0;
+}
+
+int mfft_ew_mul(mfft_plan_t plan, const void* a, const void* b, void* out, size_t n, int precision) {
+  hipStream_t st = plan_stream(plan);
+  if (!a || !b || !out) return set_error(MFFT_ERR_INVALID, "null argument");
+  if (precision == MFFT_DOUBLE)
+    hipLaunchKernelGGL(mul_kernel<double>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, st, (const double*)a, (const double*)b, (double*)out, n);
+  else
+    hipLaunchKernelGGL(mul_kernel<float>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, st, (const float*)a, (const float*)b, (float*)out, n);
+  MFFT_HIP(hipGetLastError());
+  return 0;
+}
+
+// dZp, dZm = the right-hand sides of the Elsasser equations from T_hat = the nine products of mfft_nonlinear_outer(Zp, Zm): see the
+// kernel.  T_hat (9, shape), the others (3, shape); dZp and dZm may not be an input.  Pitched spectra: shape[2] is the pitch.
+int mfft_ew_elsasser_rhs(mfft_plan_t plan, const void* T_hat, const void* Zp_hat, const void* Zm_hat, void* dZp, void* dZm, const void* kx,
+                         const void* ky, const void* kz, const int64_t shape[3], double nu, double eta, int precision) {
+  hipStream_t st = plan_stream(plan);
+  if (!T_hat || !Zp_hat || !Zm_hat || !dZp || !dZm || !kx || !ky || !kz || !shape) return set_error(MFFT_ERR_INVALID, "null argument");
+  if (dZp == dZm || dZp == Zp_hat || dZp == Zm_hat || dZm == Zp_hat || dZm == Zm_hat || dZp == T_hat || dZm == T_hat)
+    return set_error(MFFT_ERR_INVALID, "elsasser_rhs: the results must be arrays of their own");
+  const size_t n = (size_t)(shape[0] * shape[1] * shape[2]);
+  const double np = 0.5 * (nu + eta), nm = 0.5 * (nu - eta);
+  if (precision == MFFT_DOUBLE)
+    hipLaunchKernelGGL(elsasser_rhs_kernel<double>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, st, (const cx<double>*)T_hat, (const cx<double>*)Zp_hat,
+                       (const cx<double>*)Zm_hat, (cx<double>*)dZp, (cx<double>*)dZm, (const double*)kx, (const double*)ky, (const double*)kz,
+                       shape[1], shape[2], n, np, nm);
+  else
+    hipLaunchKernelGGL(elsasser_rhs_kernel<float>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, st, (const cx<float>*)T_hat, (const cx<float>*)Zp_hat,
+                       (const cx<float>*)Zm_hat, (cx<float>*)dZp, (cx<float>*)dZm, (const float*)kx, (const float*)ky, (const float*)kz,
+                       shape[1], shape[2], n, (float)np, (float)nm);
   MFFT_HIP(hipGetLastError());
   return 0;
 }

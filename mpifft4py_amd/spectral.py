@@ -68,13 +68,14 @@ def ns_rhs(FFT, K, dU, U_hat, nu):
 
 def _nonlinear(FFT, name, fields, dealias, head=None, tail=()):
     """One nonlinear operation of the plan, mfft_<name>: `fields` are its (DeviceArray, is_vector) pairs in the order of the
-    call's arguments, each of shape FFT.complex_shape() -- (3,) + that for a vector field -- and of the plan's pitch.
+    call's arguments, each of shape FFT.complex_shape() -- (3,) + that for a vector field, (n,) + that where `is_vector` is a
+    component count n (the nine of the outer product) -- and of the plan's pitch.
     `head`: the arguments before the dealias code where they are not just the fields' pointers; `tail`: those after it."""
     from ._base import _DEALIAS
     assert dealias in ('3/2-rule', '2/3-rule', 'None', None)
     cs = tuple(int(s) for s in FFT.complex_shape())
     for x, is_vector in fields:
-        shape = (3,) + cs if is_vector else cs
+        shape = (3 if is_vector is True else int(is_vector),) + cs if is_vector else cs
         assert x.shape == shape and x.dtype == np.dtype(FFT.complex), (x.shape, x.dtype, shape)
         FFT._check_pitch(x, FFT.complex_pitch)
     code = _DEALIAS[dealias]
@@ -103,6 +104,15 @@ def dot(FFT, a, b, out):
     n = a.size // 3
     assert b.size == 3 * n and out.size == n, (a.shape, b.shape, out.shape)
     _lib.call("mfft_ew_dot", FFT._plan, a.ptr, b.ptr, out.ptr, n, _prec(FFT))
+    return out
+
+
+def mul(FFT, a, b, out):
+    """out = a * b for real fields of the real shape (out may be a or b): one product a_i b_j of a composed outer product
+    (mfft_ew_mul)."""
+    assert a.pitch is None and b.pitch is None and out.pitch is None
+    assert a.size == b.size == out.size and a.dtype == b.dtype == out.dtype == np.dtype(FFT.float), (a.shape, b.shape, out.shape)
+    _lib.call("mfft_ew_mul", FFT._plan, a.ptr, b.ptr, out.ptr, a.size, _prec(FFT))
     return out
 
 
@@ -154,6 +164,39 @@ def cross_dot_transform(FFT, a_hat, b_hat, c_hat, out_hat, s_hat, dealias=None):
     There is no `absmax` here: take the maxima of a CFL step from one `cross_transform(.., absmax=True)`."""
     _nonlinear(FFT, "nonlinear_cross_dot", [(a_hat, True), (b_hat, True), (c_hat, True), (out_hat, True), (s_hat, False)], dealias)
     return out_hat, s_hat
+
+
+def outer_transform(FFT, a_hat, b_hat, out_hat, dealias=None):
+    """out_hat[3 * i + j] = fftn(ifftn(a_hat[i]) * ifftn(b_hat[j])), all nine products of two vector fields as ONE operation of
+    the plan (mfft_nonlinear_outer): the Elsasser products z+_i z-_j of incompressible MHD, a convective term in conservative
+    form, a stress u_i u_j -- what a caller composes from six `FFT.ifftn(.., dealias)`, nine products of numpy arrays and nine
+    `FFT.fftn(.., dealias)`, or today from three `cross_transform` calls (eighteen inverse and nine forward transforms instead
+    of six and nine).  a_hat and b_hat are DeviceArrays of shape (3,) + FFT.complex_shape(), out_hat = FFT.empty_complex(9) has
+    shape (9,) + FFT.complex_shape(): component 3 * i + j belongs to a_hat[i] and b_hat[j].  a_hat may be b_hat (the symmetric
+    tensor, all nine components computed).  out_hat may NOT overlap a_hat or b_hat: the call raises before anything runs; the
+    inputs are preserved.  On slab plans with radix kernels on every axis the z stages are one fused kernel and no real-space
+    work array exists (`FFT.plan_info("nonlinear_outer_fused_3_2")`); elsewhere the plan composes it on seven work arrays of
+    its own."""
+    _nonlinear(FFT, "nonlinear_outer", [(a_hat, True), (b_hat, True), (out_hat, 9)], dealias)
+    return out_hat
+
+
+def elsasser_rhs(FFT, K, T_hat, Zp_hat, Zm_hat, dZp, dZm, nu, eta):
+    """The right-hand sides of incompressible MHD in Elsasser variables z+- = u +- b in one sweep (mfft_ew_elsasser_rhs).
+    T_hat = outer_transform(FFT, Zp_hat, Zm_hat, ..), shape (9,) + FFT.complex_shape(); the others (3,) + that.  Per bin
+        N+[i] = -1j * sum_j K[j] * T_hat[3 * i + j],    N-[i] = -1j * sum_j K[j] * T_hat[3 * j + i],
+    both projected, N - K (K . N) / |K|^2 with the K = 0 bin set to 0, and
+        dZp[i] = N+[i] - |K|^2 ((nu + eta) / 2 * Zp_hat[i] + (nu - eta) / 2 * Zm_hat[i]),   dZm likewise with Zp_hat, Zm_hat swapped.
+    dZp and dZm are arrays of their own; pitched spectra are swept as they lie in memory, like `ns_rhs`.  Returns (dZp, dZm)."""
+    cs = tuple(int(x) for x in FFT.complex_shape())
+    assert T_hat.shape == (9,) + cs, (T_hat.shape, cs)
+    for x in (Zp_hat, Zm_hat, dZp, dZm):
+        assert x.shape == (3,) + cs and x.pitch == T_hat.pitch, (x.shape, x.pitch, cs, T_hat.pitch)
+    for x in (T_hat, Zp_hat, Zm_hat, dZp, dZm):
+        assert x.dtype == np.dtype(FFT.complex), (x.dtype, FFT.complex)
+    _lib.call("mfft_ew_elsasser_rhs", FFT._plan, T_hat.ptr, Zp_hat.ptr, Zm_hat.ptr, dZp.ptr, dZm.ptr, K.dev[0].ptr, K.dev[1].ptr,
+              K.dev[2].ptr, K.cshape, float(nu), float(eta), _prec(FFT))
+    return dZp, dZm
 
 
 def _max_over_ranks(FFT, v):

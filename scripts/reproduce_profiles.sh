@@ -111,6 +111,10 @@ run() {
     nonlinear_cross_dot_ab.txt) python scripts/nonlinear_cross_dot_ab.py --procs 3 --out out/nonlinear_cross_dot_ab.txt
       # its last section: the example's loop, one operation per stage against two calls
       for n in 256 512; do for dl in 3/2-rule 2/3-rule; do python examples/boussinesq_device.py --N $n --steps 5 --stages --dealias $dl; python examples/boussinesq_device.py --N $n --steps 5 --stages --dealias $dl --two-calls; done; done ;;
+    nonlinear_outer_regs.tsv) make -C mpifft4py_amd/csrc -j8 >/dev/null; python scripts/nonlinear_outer_regs.py ;;
+    nonlinear_outer_ab.txt) python scripts/nonlinear_outer_ab.py --procs 3 --out out/nonlinear_outer_ab.txt
+      # the example's loop, one operation per stage against the 6 + 9 transforms issued by the example
+      for n in 256 512; do for dl in 3/2-rule 2/3-rule; do python examples/mhd_device.py --N $n --steps 5 --dealias $dl; python examples/mhd_device.py --N $n --steps 5 --dealias $dl --composed; done; done ;;
     real_moments_regs.tsv) make -C mpifft4py_amd/csrc -j8 >/dev/null; python scripts/real_moments_regs.py ;;
     real_moments_ab.txt) python scripts/real_moments_ab.py --procs 3 --out out/real_moments_ab.txt ;;
     real_histogram_regs.tsv) make -C mpifft4py_amd/csrc -j8 >/dev/null; python scripts/real_histogram_regs.py ;;
