@@ -30,7 +30,7 @@ def _zero(a):
 
 def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double", nu=0.000625, dt=0.01, steps=10,
           report=None, fused=True, timing=False, complex_pitch="default", edge=None, spectrum=False, cfl=None, dt_max=None,
-          stats=False, pdf=False, dissipation=False):
+          stats=False, pdf=False, dissipation=False, structure=False):
     """fused=True (round 6): the nonlinear term is ONE plan operation (spectral.cross_transform: no real-space work
     arrays, the z stages one kernel) and a Runge-Kutta stage's projection, viscous term, both updates and the next
     curl are ONE sweep (spectral.ns_rk_stage).  fused=False: the composition of rounds 3 - 5 (nine transforms, cross,
@@ -50,7 +50,12 @@ def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double
     and of the enstrophy density omega^2 -- quadratic forms of six and of three fields that exist as spectra only
     (spectral.strain_hat, spectral.real_quadratic): report["dissipation"] lists (<eps>, <omega^2>, <eps^2> / <eps>^2,
     <omega^4> / <omega^2>^2) and rank 0 prints them with nu <omega^2> / <eps>, which is 1 for a periodic solenoidal field; with pdf
-    also the two histograms of the final state, report["dissipation_pdf"]."""
+    also the two histograms of the final state, report["dissipation_pdf"].
+    structure=True (fused loop): before every step and of the final state, the structure functions of the velocity along z at the
+    default separations (the powers of two below M / 2, then M / 2) -- a two-point statistic of fields that exist as spectra only
+    (spectral.real_increments: the z kernel reads the real row back shifted, no real-space array): report["structure"] lists the
+    spectral.Increments and rank 0 prints S_2 of u_0 (transverse) and of u_2 (longitudinal: the increment runs along z) and the
+    skewness and flatness of the longitudinal increment."""
     if complex_pitch == "default":       # the fused loop on ONE rank keeps its spectra pitched (rows a whole number of cache lines
         # apart: every pass runs on them); several ranks and the composition of rounds 3 - 5 keep compact rows
         complex_pitch = "auto" if (fused and comm.Get_size() == 1) else None
@@ -64,6 +69,8 @@ def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double
         raise ValueError("pdf needs the fused loop")
     if dissipation and not fused:
         raise ValueError("dissipation needs the fused loop")
+    if structure and not fused:
+        raise ValueError("structure needs the fused loop")
     if decomposition == 'slab':
         FFT = Slab_R2C(N, L, comm, precision, complex_pitch=complex_pitch)
     else:
@@ -122,10 +129,22 @@ def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double
                 print("%s: <eps> = %.15e  <omega^2> = %.15e  nu <omega^2> / <eps> = %.15f  flatness of eps = %.9f  of omega^2 = %.9f"
                       % (label, eps, w2, nu * w2 / eps, fe, fw))
 
+        def structure_report(label):                 # (collective: every rank calls it; one plan operation)
+            inc = spectral.real_increments(FFT, U_hat, None, dealias)
+            if report is not None:
+                report.setdefault("structure", []).append(inc)
+            if comm.Get_rank() == 0:
+                fmt = lambda v: "[" + " ".join("%.12e" % float(x) for x in v) + "]"
+                S2 = inc.S(2)
+                print("structure %s: s = [%s]  S2(u_0) = %s  S2(u_2) = %s  skewness(du_2) = %s  flatness(du_2) = %s"
+                      % (label, " ".join(str(int(x)) for x in inc.seps), fmt(S2[0]), fmt(S2[2]), fmt(inc.skewness()[2]), fmt(inc.flatness()[2])))
+
         dis_work = []
         for step_ in range(steps):
             if dissipation:
                 dissipation_report("step %d" % step_)
+            if structure:
+                structure_report("step %d" % step_)
             for rk in range(4):
                 spectral.cross_transform(FFT, U_hat, dU, dU, dealias, absmax=(cfl is not None and rk == 0))      # dU = fftn(U x curl U)
                 if cfl is not None and rk == 0:      # max |u_f|, max |omega_f| of the state the step starts from (one stream synchronisation)
@@ -167,6 +186,8 @@ def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double
                 report["pdf"] = (h, mean, sigma)
         if dissipation:
             dissipation_report("final", bins=32 if pdf else 0)
+        if structure:
+            structure_report("final")
         for i in range(3):
             FFT.ifftn(U_hat.component(i), U.component(i))
         return FFT.comm.reduce(spectral.sumsq(FFT, U) / float(N[0]) / float(N[1]) / float(N[2]) / 2)
@@ -243,6 +264,9 @@ def main():
     ap.add_argument("--dissipation", action="store_true", help="print before every step and of the final state <eps>, <omega^2>, nu <omega^2> / <eps> "
                     "(1 for a periodic solenoidal field) and the flatness <eps^2> / <eps>^2, <omega^4> / <omega^2>^2, from the spectra "
                     "(spectral.real_quadratic: no real-space array); with --pdf also the two histograms of the final state")
+    ap.add_argument("--structure", action="store_true", help="print before every step and of the final state the structure functions along z "
+                    "at the separations 1, 2, 4, .. M / 2: S_2 of u_0 and u_2 and the skewness and flatness of the longitudinal increment "
+                    "of u_2, from the spectra (spectral.real_increments: no real-space array)")
     args = ap.parse_args()
     dealias = None if args.dealias == "None" else args.dealias
     from mpifft4py_amd import LocalGroup, SelfComm
@@ -251,11 +275,11 @@ def main():
         ks = LocalGroup(args.ranks).run(lambda c: solve(c, args.M, dealias, steps=args.steps, precision=args.precision,
                                                         report=rep if c.Get_rank() == 0 else None, fused=not args.composed,
                                                         timing=args.stages, complex_pitch=None if args.compact else "default",
-                                                        edge=args.N or None, spectrum=args.spectrum, cfl=args.cfl, dt_max=args.dt_max, stats=args.stats, pdf=args.pdf, dissipation=args.dissipation))
+                                                        edge=args.N or None, spectrum=args.spectrum, cfl=args.cfl, dt_max=args.dt_max, stats=args.stats, pdf=args.pdf, dissipation=args.dissipation, structure=args.structure))
     else:
         ks = [solve(SelfComm(), args.M, dealias, steps=args.steps, precision=args.precision, report=rep,
                     fused=not args.composed, timing=args.stages, complex_pitch=None if args.compact else "default",
-                    edge=args.N or None, spectrum=args.spectrum, cfl=args.cfl, dt_max=args.dt_max, stats=args.stats, pdf=args.pdf, dissipation=args.dissipation)]
+                    edge=args.N or None, spectrum=args.spectrum, cfl=args.cfl, dt_max=args.dt_max, stats=args.stats, pdf=args.pdf, dissipation=args.dissipation, structure=args.structure)]
     print("N = %d^3, %d RK4 steps, %.3f ms per step (%s, device-resident; plan work buffers %.2f GB)"
           % (args.N or 2 ** args.M, args.steps, rep.get("ms_per_step", float("nan")),
              "composed: 36 transforms + element-wise kernels" if args.composed else

@@ -321,6 +321,27 @@ MFFT_API int mfft_nlz_quad_rows(const void* a, const void* b, int nfields, int64
                                 int64_t valid_in, int precision, const double* weights, double center, double lo, double hi, int nbins,
                                 double* out6, int64_t* counts);
 MFFT_API int64_t mfft_nlz_quad_groups(int64_t nrows, int64_t n, int precision);
+/* Structure functions along z: the rule that the fused kernel, the sweep, the emulator and the tests share.  For a real z row of
+ * length M (N2 for dealias None and the 2/3-rule, 3 N2 / 2 for the 3/2-rule) and a separation s, 1 <= s <= M - 1, in grid points of
+ * that row, periodic:
+ *     r(z) = (double)v(z) * norm          the transform's value in the plan's precision, taken to double, then normalised (one
+ *                                         rounded product; a real array that is given as such: r = (double)x)
+ *     d    = r((z + s) mod M) - r(z)
+ *     d2 = d * d;   S2 += d2;   S3 += d2 * d;   S4 += d2 * d2
+ * Powers and sums in double in both precisions, over all rows and all M positions; S1 is identically zero on a periodic row and
+ * is not computed.  Per field and separation the result is three doubles, [S2, S3, S4].  One launch takes up to MFFT_INCR_MAXSEP
+ * separations; duplicates are allowed. */
+#define MFFT_INCR_MAXSEP 8
+/* The z stage that ends in structure functions (csrc/fft_nlz.h body_incr), synchronous: the increment sums of the real rows
+ * irfft(row, n) without the real rows.  Fields, rows, valid and valid_in as mfft_nlz_moments_rows; out[(f * nsep + i) * 3 + {0, 1,
+ * 2}] = S2, S3, S4 of field f at seps[i], fields in the order a_0.., then b_0...  No atomics: bitwise reproducible run to run.  A
+ * NaN or Inf bin of a field makes all of THAT field's sums NaN; the partner on the same transform stays exact.
+ * MFFT_ERR_INVALID for nsep outside 1 .. MFFT_INCR_MAXSEP and any seps[i] < 1 or >= n; MFFT_ERR_UNSUPPORTED for lengths without a
+ * kernel; reported before anything is enqueued, the outputs untouched.  The z stage of mfft_real_increments on its own, for tests.
+ * mfft_nlz_incr_groups: the workgroups of that launch (it strides over the rows; 0: no kernel of that length). */
+MFFT_API int mfft_nlz_incr_rows(const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
+                                int64_t valid_in, int precision, const int64_t* seps, int nsep, double* out);
+MFFT_API int64_t mfft_nlz_incr_groups(int64_t nrows, int64_t n, int precision);
 /* slab pack / unpack (slab.py:403; cython/maths.pyx:21-31 transpose_Uc) */
 MFFT_API int mfft_slab_pack(const void* uc_hatT, void* u_mpi, int P, int64_t np0, int64_t np1, int64_t nf, int precision);
 MFFT_API int mfft_slab_unpack(const void* u_mpi, void* uc_hatT, int P, int64_t np0, int64_t np1, int64_t nf, int precision);
@@ -460,6 +481,26 @@ MFFT_API int mfft_ew_quadratic(mfft_plan_t plan, const void* x, int ncomp, size_
  * inputs are preserved.  Synchronises the plan's stream. */
 MFFT_API int mfft_real_quadratic(mfft_plan_t plan, const void* a_hat, const void* b_hat, int ncomp, int dealias, const double* weights,
                                  double center, double lo, double hi, int nbins, double* out6, int64_t* counts, int64_t* count);
+
+/* out_host[(c * nsep + i) * 3 + {0, 1, 2}] = S2, S3, S4 of the increments along the rows of a real device array of ncomp x nrows
+ * rows of n elements, row_pitch elements apart (>= n; component c starts c * nrows * row_pitch elements in), ncomp = 1, 2, 3 or 6,
+ * in the plan's precision, by the rule above with norm = 1.  One sweep: every element is read once per separation and once for
+ * itself, out of the caches where the row is short; partials by plain stores, one fold in fixed order, no atomics.  Errors as
+ * mfft_nlz_incr_rows (any n >= 2 is supported).  The plan must not be null; synchronises the plan's stream. */
+MFFT_API int mfft_ew_increments(mfft_plan_t plan, const void* x, int ncomp, int64_t nrows, int64_t n, int64_t row_pitch, int precision,
+                                const int64_t* seps, int nsep, double* out_host);
+
+/* Structure functions of fields that exist as spectra only: for the ncomp (1 or 3) components of a_hat and, where b_hat is not
+ * NULL, of b_hat -- 1, 2, 3 or 6 fields, in that order -- out[(f * nsep + i) * 3 + {0, 1, 2}] = the sums S2, S3, S4 of the
+ * increments of x = ifftn(field f, dealias) along z at the separation seps[i], by the rule above, over THIS RANK's part of the
+ * real-space grid (as mfft_real_moments; z is local to a rank on slabs and pencils alike: no halo), *count = the points per field
+ * (S_p / count is the structure function).  Routes (mfft_plan_get_info "nonlinear_increments_fused_3_2" / "_none" / "_2_3"):
+ * fused, the z kernel keeps the real row in its exchange buffer and reads it back shifted (csrc/fft_nlz.h body_incr), no
+ * real-space array exists; every other plan transforms one field at a time into ONE real work array and sweeps it
+ * (mfft_ew_increments).  Bitwise reproducible run to run on one plan and device.  Errors as mfft_nlz_incr_rows with n = M,
+ * reported before anything is enqueued.  The inputs are preserved.  Synchronises the plan's stream. */
+MFFT_API int mfft_real_increments(mfft_plan_t plan, const void* a_hat, const void* b_hat, int ncomp, int dealias, const int64_t* seps,
+                                  int nsep, double* out, int64_t* count);
 
 /* The nonlinear term of a pseudo-spectral step as ONE operation:
  *     out_hat = fftn(ifftn(a_hat) x ifftn(b_hat))        (cross product in real space, component by component)

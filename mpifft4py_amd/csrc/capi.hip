@@ -388,6 +388,61 @@ int64_t mfft_nlz_moments_groups(int64_t nrows, int64_t n, int precision) {
   return ngroups;
 }
 
+// The stage that ends in structure functions (fft_nlz.h body_incr), synchronous.  Fields and rows as mfft_nlz_moments_rows;
+// out[(f * nsep + i) * 3 + {0, 1, 2}] = S2, S3, S4 of the increments of irfft(row, n) at seps[i] over all rows, fields in the order
+// a_0.., then b_0...  Everything is checked before the first launch; the output is written on success only.
+int mfft_nlz_incr_rows(const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid, int64_t valid_in,
+                       int precision, const int64_t* seps, int nsep, double* out) {
+  if (!a || !out || !seps || nrows < 1 || n < 2 || n >= 65536 || pitch < valid || valid < 1 || valid > n / 2 + 1 || valid_in < 0 || valid_in > valid)
+    return set_error(MFFT_ERR_INVALID, "bad argument");
+  if (precision != MFFT_DOUBLE && precision != MFFT_SINGLE) return set_error(MFFT_ERR_INVALID, "unknown precision %d", precision);
+  if ((nfields != 1 && nfields != 2 && nfields != 3 && nfields != 6) || ((nfields % 2 == 0) != (b != nullptr)))
+    return set_error(MFFT_ERR_INVALID, "nfields must be 1 or 3 (a alone) or 2 or 6 (a and b), not %d", nfields);
+  MFFT_TRY(incr_check(seps, nsep, n));
+  const size_t es = elem_bytes(precision, true);
+  const int ncomp = b ? nfields / 2 : nfields;
+  NliArgs z;
+  int slot_of[6] = {0, 0, 0, 0, 0, 0};
+  for (int f = 0; f < nfields; ++f) {
+    const int slot = b ? (f < ncomp ? 2 * f : 2 * (f - ncomp) + 1) : f;
+    const char* base = static_cast<const char*>(f < ncomp ? a : b) + (size_t)((f % ncomp) * nrows * pitch) * es;
+    (slot % 2 ? z.b : z.a)[slot / 2] = base;
+    slot_of[f] = slot;
+  }
+  z.npairs = (nfields + 1) / 2;
+  z.n = (int)n; z.prec = precision; z.in_stride = pitch; z.nrows = nrows; z.valid = (int)valid; z.valid_in = (int)valid_in;
+  z.norm = 1.0 / (double)n;
+  for (int i = 0; i < nsep; ++i) z.sep[i] = (int)seps[i];
+  z.nsep = nsep;
+  int ngroups = 0;
+  int64_t waves = 0;
+  MFFT_TRY(nli_launch_shape(n, precision, nrows, &ngroups, &waves));
+  z.ngroups = ngroups;
+  char* buf = nullptr;
+  MFFT_HIP(hipMalloc(reinterpret_cast<void**>(&buf), (size_t)(waves + 1) * INCR_SLOTS * sizeof(double)));
+  double* acc = reinterpret_cast<double*>(buf);
+  z.part = acc + INCR_SLOTS;
+  int rc = hipMemsetAsync(acc, 0, INCR_SLOTS * sizeof(double), nullptr) == hipSuccess ? 0 : set_error(MFFT_ERR_HIP, "hipMemsetAsync failed");
+  if (!rc) rc = launch_nli(z, nullptr);
+  if (!rc) rc = incr_fold(static_cast<const double*>(z.part), (size_t)waves, INCR_SLOTS, acc, nullptr);
+  double host[INCR_SLOTS];
+  if (!rc && hipMemcpy(host, acc, sizeof host, hipMemcpyDeviceToHost) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemcpy failed");
+  if (hipStreamSynchronize(nullptr) != hipSuccess && !rc) rc = set_error(MFFT_ERR_HIP, "hipStreamSynchronize failed");
+  (void)hipFree(buf);
+  if (!rc)
+    for (int f = 0; f < nfields; ++f)
+      for (int i = 0; i < nsep; ++i)
+        for (int k = 0; k < 3; ++k) out[(f * nsep + i) * 3 + k] = host[(slot_of[f] * MFFT_INCR_MAXSEP + i) * 3 + k];
+  return rc;
+}
+// workgroups of that launch (0: no kernel of that length)
+int64_t mfft_nlz_incr_groups(int64_t nrows, int64_t n, int precision) {
+  int ngroups = 0;
+  int64_t waves = 0;
+  if (nli_launch_shape(n, precision, nrows, &ngroups, &waves) != 0) return 0;
+  return ngroups;
+}
+
 // The stage that ends in a histogram (fft_nlz.h body_hist), synchronous.  Fields and rows as mfft_nlz_moments_rows;
 // out[f * (nbins + 3) + slot] = counts of irfft(row, n) over all rows, fields in the order a_0.., then b_0...
 int mfft_nlz_hist_rows(const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid, int64_t valid_in,

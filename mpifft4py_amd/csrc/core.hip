@@ -816,6 +816,63 @@ int launch_nlq(const NlqArgs& a, hipStream_t s) {
   return by_prec(a.prec, [&](auto t) { return launch_nlq_t<decltype(t)>(e, a, tw, s); });
 }
 
+// The stage that ends in structure functions (fft_nlz.h body_incr, Op::Increments): the grid of the moments stage by the same
+// query; waves = groups of NLI_SLOTS doubles written to NliArgs::part.  Sums of doubles: no count to keep below 2^32.
+static_assert(NLI_MAXSEP == MFFT_INCR_MAXSEP && NLI_FIELD == INCR_FIELD && NLI_SLOTS == INCR_SLOTS, "one number of separations per launch");
+int nli_launch_shape(int64_t n, int prec, int64_t nrows, int* ngroups, int64_t* waves) {
+  const KernelEntry* e = find_nlz(n, prec, Op::Increments);
+  if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused z-stage kernel with increments of length %lld", (long long)n);
+  if (nrows < 1) return set_error(MFFT_ERR_INVALID, "no rows");
+  void* tw = nullptr;
+  MFFT_TRY(prepare_kernel(e, &tw));                // (the LDS attribute is set before the occupancy is asked for)
+  int cap = 0;
+  MFFT_TRY(nls_resident(e, &cap));
+  const int64_t units = (nrows + 2 * e->tile - 1) / (2 * e->tile);
+  *ngroups = (int)std::min<int64_t>(units, cap);
+  *waves = (int64_t)*ngroups * ((e->threads + 63) / 64);
+  return 0;
+}
+template <typename T>
+static int launch_nli_t(const KernelEntry* e, const NliArgs& a, void* tw, hipStream_t s) {
+  NliParams<T> P;
+  for (int f = 0; f < 3; ++f) {
+    P.a[f] = static_cast<const cx<T>*>(f < a.npairs ? a.a[f] : nullptr);
+    P.b[f] = static_cast<const cx<T>*>(f < a.npairs ? a.b[f] : nullptr);
+    P.out[f] = nullptr;
+  }
+  P.tw = static_cast<const cx<T>*>(tw);
+  P.rt3 = nullptr;
+  P.in_stride = a.in_stride;
+  P.out_stride = 0;
+  P.nrows = a.nrows;
+  P.valid = a.valid > 0 && a.valid < a.n / 2 + 1 ? a.valid : a.n / 2 + 1;
+  P.valid_in = a.valid_in > 0 && a.valid_in < P.valid ? a.valid_in : P.valid;
+  P.scale = (T)1;
+  P.part = static_cast<double*>(a.part);
+  P.norm = a.norm;
+  for (int i = 0; i < NLI_MAXSEP; ++i) P.sep[i] = i < a.nsep ? a.sep[i] : 1;
+  P.nsep = a.nsep;
+  P.npairs = a.npairs;
+  P.ngroups = a.ngroups;
+  e->launch(&P, a.ngroups, s);
+  MFFT_HIP(hipGetLastError());
+  return 0;
+}
+int launch_nli(const NliArgs& a, hipStream_t s) {
+  const KernelEntry* e = find_nlz(a.n, a.prec, Op::Increments);
+  if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused z-stage kernel with increments of length %d", a.n);
+  const int64_t units = (a.nrows + 2 * e->tile - 1) / (2 * e->tile);
+  if (a.npairs < 1 || a.npairs > NLS_PAIRS || !a.part || a.nrows < 1 || a.ngroups < 1 || a.ngroups > units || a.nsep < 1 || a.nsep > NLI_MAXSEP)
+    return set_error(MFFT_ERR_INVALID, "bad argument");
+  for (int i = 0; i < a.nsep; ++i)                 // (the kernel reads the row's exchange buffer at (position + sep) mod n)
+    if (a.sep[i] < 1 || a.sep[i] >= a.n) return set_error(MFFT_ERR_INVALID, "separation %d outside 1 .. %d", a.sep[i], a.n - 1);
+  for (int p = 0; p < a.npairs; ++p)
+    if (!a.a[p]) return set_error(MFFT_ERR_INVALID, "null argument");
+  void* tw = nullptr;
+  MFFT_TRY(prepare_kernel(e, &tw));
+  return by_prec(a.prec, [&](auto t) { return launch_nli_t<decltype(t)>(e, a, tw, s); });
+}
+
 // ---------------------------------------------------------------------------
 // data-movement kernels
 // ---------------------------------------------------------------------------

@@ -152,6 +152,7 @@ constexpr NlProduct NL_PRODUCTS[] = {
     {Op::Moments, "moments", 6, 0, false, false},      // (up to six fields: the call says how many, NlFields::nfields)
     {Op::Histogram, "histogram", 6, 0, false, false},
     {Op::Quadratic, "quadratic", 6, 0, false, false},
+    {Op::Increments, "increments", 6, 0, false, false},
 };
 inline const NlProduct& nl_product(Op op) {
   for (const NlProduct& q : NL_PRODUCTS)
@@ -245,6 +246,31 @@ size_t quad_hpart_bytes(int ngroups, int nbins);
 int quad_rows(const NlqArgs& z, void* part, double* macc, int64_t* hacc, hipStream_t s);
 // finite weights, 0 <= nbins <= NLH_MAXBINS, and with nbins > 0 a valid range (hist_range); *inv = 1 where nbins == 0
 int quad_check(const double* weights, int nfields, double lo, double hi, int nbins, double* inv);
+// The z stage that ends in structure functions (fft_nlz.h body_incr): pairs as in NlsArgs; per field and separation the sums
+// S2, S3, S4 of d = r(z + sep) - r(z) over all rows and positions, r = norm * (the un-normalised inverse transform), rows periodic.
+struct NliArgs {
+  const void* a[3] = {nullptr, nullptr, nullptr};
+  const void* b[3] = {nullptr, nullptr, nullptr};
+  int npairs = 0;
+  int n = 0;             // REAL length of a z row
+  int prec = MFFT_DOUBLE;
+  int64_t in_stride = 0, nrows = 0;   // complex elements
+  int valid = 0;         // bins per row present in memory (0 = all n/2+1)
+  int valid_in = 0;      // bins per row that are read, where fewer (pruned 2/3-rule); 0 = valid
+  double norm = 1.0;
+  int sep[MFFT_INCR_MAXSEP] = {0};    // 1 <= sep[i] < n, i < nsep
+  int nsep = 0;          // 1 .. MFFT_INCR_MAXSEP
+  int ngroups = 0;       // workgroups of the launch, from nli_launch_shape() of (n, prec, nrows)
+  void* part = nullptr;  // `waves` of nli_launch_shape() groups of INCR_SLOTS doubles, [wave][pair][a, b][separation][sum]
+};
+int nli_launch_shape(int64_t n, int prec, int64_t nrows, int* ngroups, int64_t* waves);
+int launch_nli(const NliArgs& a, hipStream_t s);
+// Sums of increment powers (incr.hip).  acc: device doubles, [slot][MFFT_INCR_MAXSEP][S2, S3, S4], six slots (fft_nlz.h NLI_SLOTS).
+// incr_fold: acc[v] += the groups' part[g * nvals + v] added in a fixed order, nvals = whole slots
+constexpr int INCR_FIELD = MFFT_INCR_MAXSEP * 3, INCR_SLOTS = 6 * INCR_FIELD;
+int incr_fold(const double* part, size_t groups, int nvals, double* acc, hipStream_t s);
+// MFFT_ERR_INVALID for nsep outside 1 .. MFFT_INCR_MAXSEP or a separation outside 1 .. m - 1
+int incr_check(const int64_t* seps, int nsep, int64_t m);
 // max |x| reductions (absmax.hip): acc[s] = max(acc[s], scale * max_g part[g * period + s]), NaNs kept; `scratch` holds
 // absmax_fold_scratch_bytes(), `part` is in precision `prec`, acc in double
 size_t absmax_fold_scratch_bytes();

@@ -149,6 +149,10 @@ struct mfft_plan_s {
   Buf nlq{false, false};
   double nlq_w[6] = {0, 0, 0, 0, 0, 0}, nlq_center = 0.0, nlq_lo = 0.0, nlq_inv = 1.0;
   int nlq_bins = 0;
+  // mfft_real_increments / mfft_ew_increments (incr.hip): the sums in slot order, [slot][MFFT_INCR_MAXSEP][S2, S3, S4]; the partials
+  // go to nlm.  The call's separations.
+  Buf nliacc{false, false};
+  int nli_sep[MFFT_INCR_MAXSEP] = {0}, nli_nsep = 0;
   bool nlm_valid = false;       // a statistics call has run: nlmacc[0..5] hold max |ifftn(a_f)|, max |ifftn(b_f)| of this rank
   uint8_t* mask = nullptr;
   size_t mask_count = 0;
@@ -566,6 +570,14 @@ struct mfft_plan_s {
   int quad_end(double out6[6], int64_t* counts);
   int quad_sweep(const void* x, bool as_double, int ncomp, size_t stride, size_t n, const double* w, bool square);
   int quad_accum(const void* r, double* q, size_t n, double w, bool first);
+  // Structure functions along z of up to six fields given as spectra (plan_nonlinear.hip; the z stage fft_nlz.h body_incr on the
+  // fused routes, one inverse transform and one sweep per field on the composed one), and the sweep itself (incr.hip).
+  // out[(f * nsep + i) * 3 + {0, 1, 2}] = S2, S3, S4
+  int real_increments(const mfft::NlFields& u, int dealias, const int64_t* seps, int nsep, double* out, int64_t* count);
+  int incr_composed(const mfft::NlFields& u, int dealias);
+  int incr_sweep(const void* x, int ncomp, int64_t nrows, int64_t n, int64_t pitch, double* acc);
+  int incr_begin(const int64_t* seps, int nsep);
+  int incr_end(double* host);
 };
 
 namespace mfft {

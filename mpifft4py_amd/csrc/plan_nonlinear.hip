@@ -185,6 +185,29 @@ static int nlq_rows(mfft_plan_s* p, const NlFields& u, char* Y, size_t yelems, i
   return quad_rows(z, p->nlm.p, static_cast<double*>(p->nlsacc.p), static_cast<int64_t*>(p->nlhacc.p), p->stream);
 }
 
+// the z stage that ends in structure functions, on a batch: rows of the call's fields in Y in, the waves' partial sums into nlm,
+// folded into the plan's accumulator (incr_begin) after the launch: the sums accumulate over the batches.
+static int nli_rows(mfft_plan_s* p, const NlFields& u, char* Y, size_t yelems, int64_t L2, int64_t Za, int64_t nrows, int valid_in) {
+  NliArgs z;
+  int ngroups = 0;
+  int64_t waves = 0;
+  MFFT_TRY(nli_launch_shape(L2, p->prec, nrows, &ngroups, &waves));
+  MFFT_TRY(p->ensure(p->nlm, (size_t)waves * INCR_SLOTS * sizeof(double)));
+  for (int f = 0; f < u.nfields; ++f) {
+    const int slot = nls_slot(u, f);
+    (slot % 2 ? z.b : z.a)[slot / 2] = Y + (size_t)f * yelems * p->es;
+  }
+  z.npairs = (u.nfields + 1) / 2;
+  z.n = (int)L2; z.prec = p->prec; z.in_stride = Za; z.nrows = nrows; z.valid = (int)p->Nf; z.valid_in = valid_in;
+  z.norm = 1.0 / (double)L2;
+  for (int i = 0; i < MFFT_INCR_MAXSEP; ++i) z.sep[i] = p->nli_sep[i];
+  z.nsep = p->nli_nsep;
+  z.ngroups = ngroups;
+  z.part = p->nlm.p;
+  MFFT_TRY(launch_nli(z, p->stream));
+  return incr_fold(static_cast<const double*>(z.part), (size_t)waves, INCR_SLOTS, static_cast<double*>(p->nliacc.p), p->stream);
+}
+
 // Fused route: one rank, slab, real data, radix kernels on every axis.
 bool mfft_plan_s::nonlinear_fusable(int dealias, Op product, bool stats) const {
   static const bool off = env_on("MFFT_NO_NLZ"), ranks_off = env_on("MFFT_NO_NLZ_RANKS");      // read once per process
@@ -294,6 +317,7 @@ int mfft_plan_s::nonlinear_fused(const NlFields& u, int dealias, Op product, boo
       if (product == Op::Moments) return nls_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0);
       if (product == Op::Histogram) return nlh_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0);
       if (product == Op::Quadratic) return nlq_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0);
+      if (product == Op::Increments) return nli_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0);
       return nlz_rows(this, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0, product, stats);
     }));
     if (nout) MFFT_TRY(stage("nl_y_fwd", nout * (Xb + Yb) * frac, [&] {
@@ -400,6 +424,7 @@ int mfft_plan_s::nonlinear_fused_ranks(const NlFields& u, int dealias, Op produc
       if (product == Op::Moments) return nls_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0);
       if (product == Op::Histogram) return nlh_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0);
       if (product == Op::Quadratic) return nlq_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0);
+      if (product == Op::Increments) return nli_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0);
       return nlz_rows(this, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0, product, stats);
     }));
     if (nout) MFFT_TRY(stage("nl_y_fwd", 0, [&] {      // truncate + fold in y, straight into the packed (P, Lp0, S) send layout
@@ -563,5 +588,42 @@ int mfft_plan_s::real_quadratic(const NlFields& u, int dealias, const double* we
                : quad_composed(u, dealias, nlq_w));
   MFFT_TRY(quad_end(out6, counts));
   *count = local_real_count(pad);
+  return 0;
+}
+
+// Structure functions along z of the real-space fields of up to six spectra: per field and separation the sums S2, S3, S4 of
+// d = x(z + s) - x(z), x = ifftn(field, dealias), rows periodic, over this rank's part of the grid a product would be formed on --
+// z is whole on every rank of a slab and of a pencil plan, so no halo is needed.  The routes are real_moments': fused, the inverse
+// passes of the products and the z stage that ends in these sums (fft_nlz.h body_incr; no real array); composed, ONE real work
+// array field by field -- inverse transform, sweep (incr.hip), next field.  Everything is checked before anything is enqueued.
+// Synchronises the plan's stream; the inputs are preserved.
+int mfft_plan_s::incr_composed(const NlFields& u, int dealias) {
+  const bool pad = dealias == MFFT_DEALIAS_3_2;
+  const int64_t nr = local_real_count(pad), nc = local_complex_alloc(), M = pad ? M2 : N2;
+  MFFT_TRY(ensure(nlr, (size_t)nr * rs));
+  double* acc = static_cast<double*>(nliacc.p);
+  for (int f = 0; f < u.nfields; ++f) {
+    const int slot = nls_slot(u, f);
+    MFFT_TRY(exec(false, u.src(f, nc, es), nlr.p, dealias));
+    MFFT_TRY(stage("nl_increments", (double)nr * rs, [&] { return incr_sweep(nlr.p, 1, nr / M, M, M, acc + slot * INCR_FIELD); }));
+  }
+  return 0;
+}
+int mfft_plan_s::real_increments(const NlFields& u, int dealias, const int64_t* seps, int nsep, double* out, int64_t* count) {
+  const bool pad = dealias == MFFT_DEALIAS_3_2;
+  const int64_t nr = local_real_count(pad), M = pad ? M2 : N2;
+  if (nr <= 0 || !r2c || M < 2 || nr % M != 0) return set_error(MFFT_ERR_UNSUPPORTED, "real_increments needs a 3-D real-to-complex plan");
+  MFFT_TRY(incr_check(seps, nsep, M));
+  if (dealias == MFFT_DEALIAS_2_3) MFFT_TRY(require_mask());
+  MFFT_TRY(incr_begin(seps, nsep));
+  MFFT_TRY(nonlinear_fusable(dealias, Op::Increments, false)
+               ? (P == 1 ? nonlinear_fused(u, dealias, Op::Increments, false) : nonlinear_fused_ranks(u, dealias, Op::Increments, false))
+               : incr_composed(u, dealias));
+  double host[INCR_SLOTS];
+  MFFT_TRY(incr_end(host));
+  for (int f = 0; f < u.nfields; ++f)
+    for (int i = 0; i < nsep; ++i)
+      for (int k = 0; k < 3; ++k) out[(f * nsep + i) * 3 + k] = host[(nls_slot(u, f) * MFFT_INCR_MAXSEP + i) * 3 + k];
+  *count = nr;
   return 0;
 }

@@ -179,6 +179,19 @@ void register_nlq(const char* name) {
   reg.push_back(make_entry<K, NlqParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::Quadratic, Build::Default, R, name));
 }
 
+// Op::Increments: the stage that ends in structure functions along z (fft_nlz.h body_incr, NliParams; kernels_nli*.hip).  Rows,
+// twiddle placement, exchange, wave-synchronous build and the two-waves-per-SIMD cap are those of register_nls: the body inlines ONE
+// transform and holds ONE pair's accumulators across it, 2 x NLI_MAXSEP x 3 = 48 doubles where body_moments holds 36, and takes no
+// LDS of its own (profiles/real_increments_regs.tsv).  No other cap was measured.
+template <class S, typename T>
+void register_nli(const char* name) {
+  auto& reg = kernel_registry();
+  constexpr int R = nlz_rows<S, T>();
+  constexpr int W = MFFT_NLZ_OCC > 1 ? 16 + MFFT_NLZ_OCC : 0;
+  typedef NlzIncr<NlzFft<S, T, R, nlz_twlds<S, T>(), nlz_split<S, T>(), nlz_wave<S, T>()>> K;
+  reg.push_back(make_entry<K, NliParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::Increments, Build::Default, R, name));
+}
+
 // ... and its pruned 3/2-rule flavour (Nlz3Fft: Build::Nlz3, entry.n = M = 3 L): three thread groups of SL::TPT threads per row
 template <class SL, typename T> constexpr int nlz3_rows() { return 256 / (3 * SL::TPT) > 0 ? 256 / (3 * SL::TPT) : 1; }
 template <class SL, typename T>

@@ -602,6 +602,133 @@ def quadratic(FFT, x, weights=None, center=0.0, bins=0, range=None, reduce=False
     return _quad_result(FFT, out6, counts, x.size // ncomp, center, int(bins), lo, hi, reduce)
 
 
+INCR_MAXSEP = 8         # separations of one call (MFFT_INCR_MAXSEP: what one launch's accumulators hold); longer lists go in chunks
+
+
+def incr_rule(r, seps):
+    """The rule of the increments, in numpy float64 (include/mpifft4py_amd.h): r of shape (..., M) holds periodic rows along its
+    last axis (normalised values, already double); returns sums[i] = [S2, S3, S4] of d = r[(z + seps[i]) mod M] - r[z] over all
+    rows and positions, shape (len(seps), 3)."""
+    r = np.asarray(r, dtype=np.float64)
+    out = np.zeros((len(seps), 3), dtype=np.float64)
+    for i, s in enumerate(seps):
+        d = np.roll(r, -int(s), axis=-1) - r
+        d2 = d * d
+        out[i] = (d2.sum(), (d2 * d).sum(), (d2 * d2).sum())
+    return out
+
+
+def default_seps(M):
+    """The separations a call takes where none are given: the powers of two below M / 2, then M / 2."""
+    M = int(M)
+    seps, s = [], 1
+    while s < M // 2:
+        seps.append(s)
+        s *= 2
+    if M // 2 >= 1 and (not seps or seps[-1] != M // 2):
+        seps.append(M // 2)
+    return seps
+
+
+class Increments(object):
+    """Raw two-point statistics along z of `nfields` real fields over `count` points per field: `seps` (grid points of the z row
+    of `M` points) and `sums` of shape (nfields, nsep, 3) with sums[f, i] = [S2, S3, S4], S_p = sum (x(z + s) - x(z))^p.  The
+    derived numbers are formed on the host in np.longdouble.  On a velocity field 2 is the LONGITUDINAL structure function (the
+    increment runs along z), fields 0 and 1 the transverse ones."""
+
+    def __init__(self, count, seps, sums, M):
+        self.count = int(count)
+        self.seps = np.asarray(seps, dtype=np.int64).reshape(-1)
+        self.sums = np.asarray(sums, dtype=np.float64).reshape(-1, self.seps.size, 3)
+        self.M = int(M)
+
+    def S(self, p):
+        """The structure function of order p = 2, 3 or 4: <(x(z + s) - x(z))^p>, shape (nfields, nsep)."""
+        if p not in (2, 3, 4):
+            raise ValueError("orders 2, 3 and 4 are computed, not %r" % (p,))
+        return self.sums[:, :, p - 2].astype(np.longdouble) / np.longdouble(self.count)
+
+    def skewness(self):
+        with np.errstate(divide="ignore", invalid="ignore"):      # (a field without increments has none: nan)
+            return self.S(3) / self.S(2) ** np.longdouble(1.5)
+
+    def flatness(self):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return self.S(4) / (self.S(2) * self.S(2))
+
+    def r(self, FFT):
+        """The separations as lengths: s * L_z / M."""
+        return self.seps.astype(np.float64) * float(FFT.L[2]) / self.M
+
+
+def _incr_chunks(seps, M):
+    seps = default_seps(M) if seps is None else [int(s) for s in np.asarray(seps).reshape(-1)]
+    if not seps:
+        raise ValueError("no separations")
+    return seps, [seps[i:i + INCR_MAXSEP] for i in range(0, len(seps), INCR_MAXSEP)]
+
+
+def _incr_result(FFT, sums, count, seps, M, reduce):
+    if reduce:      # sums and count: comm.allreduce adds in rank order, the same bits on every rank
+        tot = np.asarray(FFT.comm.allreduce(np.concatenate([sums.ravel(), [float(count)]])))
+        sums, count = tot[:-1].reshape(sums.shape), int(round(float(tot[-1])))
+    return Increments(count, seps, sums, M)
+
+
+def real_increments(FFT, a_hat, b_hat=None, dealias=None, seps=None, reduce=True):
+    """Structure functions along z of fields that exist as SPECTRA only (mfft_real_increments): for every separation s in
+    `seps` (grid points of the z row of M points: M = N[2], or 3 N[2] / 2 under the 3/2-rule; 1 <= s <= M - 1, periodic) the
+    sums of the second, third and fourth powers of ifftn(field, dealias)(z + s) - ifftn(field, dealias)(z) -- the first
+    two-point statistic, what the 4/5 law, the increment skewness and flatness and the intermittency exponents are read from --
+    without a real array: on slab plans with radix kernels on every axis the z kernel keeps the real row in its exchange buffer
+    and reads it back shifted (`FFT.plan_info("nonlinear_increments_fused_3_2")`); elsewhere the plan transforms one field at a
+    time into ONE work array and sweeps it.  z is whole on every rank, so no halo is exchanged.  Fields as `real_moments`: 1, 2,
+    3 or 6, a's first.  `seps=None`: the powers of two below M / 2, then M / 2.  One call of the library takes INCR_MAXSEP
+    separations; a longer list is issued in chunks, and EACH CHUNK REPEATS THE TRANSFORMS.  Returns an `Increments`; with
+    `reduce` the raw sums and the count are added over FFT.comm.  A NaN or Inf anywhere in a field gives NaN sums for that
+    field; the values are bitwise reproducible.  Synchronises the plan's stream; the inputs are preserved."""
+    cs = tuple(int(s) for s in FFT.complex_shape())
+    assert a_hat.shape in (cs, (3,) + cs), (a_hat.shape, cs)
+    vec = len(a_hat.shape) == 4
+    fields = [(a_hat, vec)] + ([(b_hat, vec)] if b_hat is not None else [])
+    ncomp = 3 if vec else 1
+    nfields = ncomp * len(fields)
+    M = int(FFT.N[2]) * 3 // 2 if dealias == '3/2-rule' else int(FFT.N[2])
+    seps, chunks = _incr_chunks(seps, M)
+    count = ctypes.c_int64(0)
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
+    parts = []
+    for ch in chunks:
+        sv = np.ascontiguousarray(ch, dtype=np.int64)
+        out = np.zeros(nfields * len(ch) * 3, dtype=np.float64)
+        _nonlinear(FFT, "real_increments", fields, dealias, head=(a_hat.ptr, b_hat.ptr if b_hat is not None else None, ncomp),
+                   tail=(sv.ctypes.data_as(ip), len(ch), out.ctypes.data_as(dp), ctypes.byref(count)))
+        parts.append(out.reshape(nfields, len(ch), 3))
+    return _incr_result(FFT, np.concatenate(parts, axis=1), count.value, seps, M, reduce)
+
+
+def increments(FFT, u, seps=None, reduce=False):
+    """The same sums of a real DeviceArray along its LAST axis (mfft_ew_increments, the companion of `moments`): an array of
+    four axes is taken as (components, ..) with 1, 2, 3 or 6 components, any other as one field; the rows of the last axis are
+    periodic, M = u.shape[-1], and a pitched array is swept as it lies.  `seps` and the chunks as `real_increments` (each chunk
+    is one more sweep).  Returns an `Increments`; with `reduce` over FFT.comm."""
+    assert u.dtype == np.dtype(FFT.float), (u.dtype, FFT.float)
+    ncomp = int(u.shape[0]) if len(u.shape) == 4 else 1
+    M = int(u.shape[-1])
+    nrows = u.size // (ncomp * M)
+    seps, chunks = _incr_chunks(seps, M)
+    FFT.comm.use_device()
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
+    parts = []
+    for ch in chunks:
+        sv = np.ascontiguousarray(ch, dtype=np.int64)
+        out = np.zeros(ncomp * len(ch) * 3, dtype=np.float64)
+        _lib.call("mfft_ew_increments", FFT._plan, u.ptr, ncomp, nrows, M, M if u.pitch is None else int(u.pitch), _prec(FFT),
+                  sv.ctypes.data_as(ip), len(ch), out.ctypes.data_as(dp))
+        parts.append(out.reshape(ncomp, len(ch), 3))
+    return _incr_result(FFT, np.concatenate(parts, axis=1), nrows * M, seps, M, reduce)
+
+
 def strain_hat(FFT, K, U_hat, diag, off):
     """The strain-rate tensor S_ij = (du_i/dx_j + du_j/dx_i) / 2 of a vector field in spectral space (mfft_ew_strain_hat), U_hat
     read once: diag[f] = i K[f] U_hat[f] (S_00, S_11, S_22) and off = (S_01, S_02, S_12), S_ij = i (K[i] U_hat[j] + K[j] U_hat[i]) / 2.
