@@ -41,12 +41,15 @@ def _copy(FFT, dst, src):
 
 
 def solve(comm, N, U0_hat, theta0_hat, nu, kappa, dt, steps, dealias, one_op=True, g=0.0, precision="double", report=None,
-          timing=False, FFT=None):
+          timing=False, FFT=None, joint=False):
     """Advance (U_hat, theta_hat) by `steps` RK4 steps and return them (DeviceArrays of (3,) + FFT.complex_shape() and
     FFT.complex_shape()); U0_hat and theta0_hat (DeviceArrays of the plan) are not modified.
     one_op=True: both nonlinear terms are ONE spectral.cross_dot_transform per stage.  one_op=False (--two-calls):
     spectral.dot_transform and spectral.cross_transform, the same arithmetic with ifftn(U_hat) done twice -- the parity and A/B
-    partner.  g: buoyancy, N_hat[2] += g theta_hat before the velocity's stage (0: the scalar is passive)."""
+    partner.  g: buoyancy, N_hat[2] += g theta_hat before the velocity's stage (0: the scalar is passive).
+    joint=True: after every step report["joint"] gains the `spectral.JointHistogram` of (u_z, theta) in 64 x 64 bins over the
+    fields' extremes, from ONE spectral.real_joint_histogram call on the two spectra (fused, the z kernel ends in the grid: no
+    real-space array); the timing then includes it."""
     if FFT is None:
         FFT = make_plan(comm, N, precision)
     K = spectral.Wavenumbers(FFT)
@@ -101,6 +104,8 @@ def solve(comm, N, U0_hat, theta0_hat, nu, kappa, dt, steps, dealias, one_op=Tru
         for rk in range(4):
             stage(rk)
         _copy(FFT, th, th1)
+        if joint and report is not None:                 # (collective: a moments call for the ranges, then the joint histogram)
+            report.setdefault("joint", []).append(spectral.real_joint_histogram(FFT, U_hat.component(2), th, dealias, bins=64))
     FFT.sync()
     wall = time.perf_counter() - t0
     if report is not None:
@@ -132,9 +137,26 @@ def random_scalar_hat(FFT, seed=0):
     return th
 
 
+def joint_summary(h):
+    """(correlation coefficient of (a, b) from the bin centres, <a | b> at five b bins, the counted total) of pair 0 of a
+    JointHistogram: what the heat flux <u_z theta> looks like as a PDF.  The coefficient is 0 where a field has no variance."""
+    w = h.counts[0].astype(np.float64)
+    ca, cb = h.centers(0, 0), h.centers(0, 1)
+    tot = w.sum()
+    ma, mb = (w.sum(1) * ca).sum() / tot, (w.sum(0) * cb).sum() / tot
+    va, vb = (w.sum(1) * (ca - ma) ** 2).sum() / tot, (w.sum(0) * (cb - mb) ** 2).sum() / tot
+    cov = (w * np.outer(ca - ma, cb - mb)).sum() / tot
+    corr = cov / np.sqrt(va * vb) if va > 0 and vb > 0 else 0.0
+    five = np.linspace(0, h.nbins[1] - 1, 7)[1:-1].astype(int)
+    return float(corr), h.conditional_mean(0, of=0)[five], int(h.raw[0].sum())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--N", type=int, default=32, help="mesh edge")
+    ap.add_argument("--M", type=int, default=0, help="mesh edge 2^M (overrides --N)")
+    ap.add_argument("--joint", action="store_true", help="print per step the correlation coefficient of (u_z, theta), <u_z | theta> at five "
+                    "theta bins and the counted total, from ONE spectral.real_joint_histogram call on the spectra (no real-space array)")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--dt", type=float, default=0.0, help="time step; default: inside the explicit scheme's stability bounds for this mesh")
     ap.add_argument("--nu", type=float, default=0.000625)
@@ -145,6 +167,8 @@ def main():
     ap.add_argument("--two-calls", action="store_true", help="cross_transform + dot_transform per stage instead of one cross_dot_transform")
     ap.add_argument("--stages", action="store_true", help="print ms per step by plan stage (HIP events)")
     args = ap.parse_args()
+    if args.M:
+        args.N = 2 ** args.M
     dealias = None if args.dealias == "None" else args.dealias
     # RK4 is explicit: kappa |k|^2 dt and |u| |k| dt must stay inside its stability region (|u| <= 1 for Taylor-Green)
     dt = args.dt or 1.0 / (max(args.kappa, args.nu) * 3 * (args.N / 2) ** 2 + 1.5 * args.N)
@@ -154,7 +178,7 @@ def main():
     U0, th0 = taylor_green_hat(FFT), random_scalar_hat(FFT)
     rep = {}
     U, th = solve(comm, args.N, U0, th0, args.nu, args.kappa, dt, args.steps, dealias, one_op=not args.two_calls, g=args.g,
-                  precision=args.precision, report=rep, timing=args.stages, FFT=FFT)
+                  precision=args.precision, report=rep, timing=args.stages, FFT=FFT, joint=args.joint)
     print("N = %d^3, %d RK4 steps of dt = %.3g, %.3f ms per step (%s; plan work buffers %.2f GB)"
           % (args.N, args.steps, dt, rep["ms_per_step"],
              "two calls per stage: cross_transform + dot_transform" if args.two_calls else
@@ -162,6 +186,9 @@ def main():
              rep["work_bytes"] / 1e9))
     for name, (ms, calls) in sorted(rep.get("stages", {}).items()):
         print("  %-10s %8.3f ms per step  (%d launches)" % (name, ms, calls))
+    for step, h in enumerate(rep.get("joint", [])):
+        corr, cond, total = joint_summary(h)
+        print("joint step %d: corr(u_z, theta) = %+.9e  <u_z | theta> = [%s]  total = %d" % (step + 1, corr, ", ".join("%+.6e" % c for c in cond), total))
     Kw = spectral.Wavenumbers(FFT)
     print("kinetic energy: %.15e -> %.15e" % (spectral.energy_spectrum(FFT, Kw, U0).sum(), spectral.energy_spectrum(FFT, Kw, U).sum()))
     print("mean of theta: %.15e -> %.15e" % (th0.get()[0, 0, 0].real, th.get()[0, 0, 0].real))

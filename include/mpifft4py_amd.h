@@ -300,6 +300,28 @@ MFFT_API int64_t mfft_nlz_moments_groups(int64_t nrows, int64_t n, int precision
 MFFT_API int mfft_nlz_hist_rows(const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
                                 int64_t valid_in, int precision, const double* lo, const double* hi, int nbins, int64_t* out);
 MFFT_API int64_t mfft_nlz_hist_groups(int64_t nrows, int64_t n, int precision);
+/* Joint histograms: the cell rule that the host, the sweep, the fused kernel and the tests share.  For a pair of real values
+ * (x_a, x_b) of the same grid point, normalised as in the histograms; each field has its own lo < hi (both finite) and its own bin
+ * count, 1 <= nba, nbb <= MFFT_JOINT_MAXBINS; inv_a = nba / (hi_a - lo_a) and inv_b = nbb / (hi_b - lo_b) are formed once on the
+ * host, in double:
+ *     sa   = slot(x_a, lo_a, inv_a, nba)      the slot rule above, unchanged: 0 below, 1 .. nba, nba + 1 above, nba + 2 not finite
+ *     sb   = slot(x_b, lo_b, inv_b, nbb)
+ *     cell = sa * (nbb + 3) + sb
+ * A pair's result is (nba + 3) * (nbb + 3) int64 counts; they always sum to the number of points.  A non-finite bin of a spectrum
+ * marks ITS field's slot only: the bad field goes to nba + 2 (or nbb + 2), the partner keeps its exact slot.  64 bins per field
+ * is what a workgroup can hold next to its exchange buffers: (64 + 3)^2 x 4 = 17956 bytes of LDS.  A finer PDF is had by a second
+ * call on a narrower range. */
+#define MFFT_JOINT_MAXBINS 64
+/* The z stage that ends in a joint histogram (csrc/fft_nlz.h body_joint), synchronous: a and b are (ncomp, nrows, pitch) complex
+ * rows, ncomp 1 or 3; pair p is (a_p, b_p), both ride ONE inverse transform.  Rows, valid and valid_in as mfft_nlz_hist_rows; lo
+ * and hi have 2 ncomp entries in the order a_0.., then b_0..; out[p * cells + cell], cells = (nba + 3)(nbb + 3).  Integers: bitwise
+ * reproducible, whatever the launch looks like.  MFFT_ERR_UNSUPPORTED for lengths without a kernel; MFFT_ERR_INVALID for a bin count
+ * outside 1 .. MFFT_JOINT_MAXBINS, hi <= lo, ranges that are not finite, a NULL b and valid > n / 2 + 1: reported before anything
+ * is enqueued, out untouched.  The z stage of mfft_real_joint_histogram on its own, for tests.
+ * mfft_nlz_joint_groups: the workgroups of that launch (it strides over the rows; 0: no kernel of that length). */
+MFFT_API int mfft_nlz_joint_rows(const void* a, const void* b, int ncomp, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
+                                 int64_t valid_in, int precision, const double* lo, const double* hi, int nba, int nbb, int64_t* out);
+MFFT_API int64_t mfft_nlz_joint_groups(int64_t nrows, int64_t n, int precision);
 /* Quadratic forms: the evaluation rule that the fused kernel, the sweeps, the emulator and the tests share.  For n = 1, 2, 3 or 6
  * real fields r_f at a point and weights w_f (finite doubles of either sign):
  *     r_f = (double)v * norm                          the transform's value in the plan's precision, taken to double, then
@@ -460,6 +482,26 @@ MFFT_API int mfft_ew_histogram(mfft_plan_t plan, const void* x, int ncomp, size_
  * a fused slab plan.  The inputs are preserved.  Synchronises the plan's stream. */
 MFFT_API int mfft_real_histogram(mfft_plan_t plan, const void* a_hat, const void* b_hat, int ncomp, int dealias, const double* lo,
                                  const double* hi, int nbins, int64_t* out, int64_t* count);
+
+/* out_host[c * cells + cell]: the joint histogram of the pairs (x[c, i], y[c, i]) of two real device arrays (ncomp, n) of equal
+ * length, ncomp = 1 or 3, in the plan's precision, by the cell rule above; lo and hi have 2 ncomp entries, x_0.., then y_0...  The
+ * companion of mfft_ew_histogram: one sweep, 16 bytes per lane of each array, counts in ONE LDS grid per workgroup, plain
+ * stores, one fold in fixed order into int64; no global atomics.  The plan must not be null; synchronises the plan's stream. */
+MFFT_API int mfft_ew_joint_histogram(mfft_plan_t plan, const void* x, const void* y, int ncomp, size_t n, int precision, const double* lo,
+                                     const double* hi, int nba, int nbb, int64_t* out_host);
+
+/* Joint PDFs of fields that exist as spectra only: for the ncomp (1 or 3) components of a_hat and b_hat, pair p = (a_p, b_p),
+ * out[p * cells + cell] = the counts of the points (ifftn(a_p, dealias), ifftn(b_p, dealias)) by the cell rule above, over THIS
+ * RANK's part of the real-space grid (as mfft_real_histogram), *count = the points counted (every pair's cells sum to it).  lo, hi:
+ * 2 ncomp entries, a_0.., then b_0...  b_hat must not be NULL; a_hat == b_hat is allowed; the inputs are read only.  Routes
+ * (mfft_plan_get_info "nonlinear_joint_fused_3_2" / "_none" / "_2_3"): fused, the z kernel ends in a joint histogram (csrc/fft_nlz.h
+ * body_joint; the pair rides one transform, so one thread holds both values) and no real-space array exists; every other plan
+ * transforms a_p and b_p into TWO real work arrays -- the least a pair can do with -- and sweeps them (mfft_ew_joint_histogram).
+ * Integers: bitwise reproducible run to run, and the same for every number of ranks of a fused slab plan.  Errors
+ * (MFFT_ERR_INVALID: bins outside 1 .. MFFT_JOINT_MAXBINS, hi <= lo, ranges not finite, NULL b_hat) are reported before anything
+ * is enqueued and leave out and count untouched.  Synchronises the plan's stream. */
+MFFT_API int mfft_real_joint_histogram(mfft_plan_t plan, const void* a_hat, const void* b_hat, int ncomp, int dealias, const double* lo,
+                                       const double* hi, int nba, int nbb, int64_t* out, int64_t* count);
 
 /* Statistics of q = sum_c weights[c] x[c, :]^2 of a real device array (ncomp, n), ncomp = 1, 2, 3 or 6, in the plan's precision,
  * by the evaluation rule above: out6 = [min, max, S1 .. S4] about `center`, counts[nbins + 3] over [lo, hi) (NULL allowed where

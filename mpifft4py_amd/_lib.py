@@ -100,6 +100,9 @@ _SIGNATURES = {
     "mfft_nlz_hist_rows": ([c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, POINTER(c_double),
                             POINTER(c_double), c_int, POINTER(c_int64)], c_int),
     "mfft_nlz_hist_groups": ([c_int64, c_int64, c_int], c_int64),
+    "mfft_nlz_joint_rows": ([c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, POINTER(c_double),
+                             POINTER(c_double), c_int, c_int, POINTER(c_int64)], c_int),
+    "mfft_nlz_joint_groups": ([c_int64, c_int64, c_int], c_int64),
     "mfft_nlz_quad_rows": ([c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, POINTER(c_double), c_double,
                             c_double, c_double, c_int, POINTER(c_double), POINTER(c_int64)], c_int),
     "mfft_nlz_quad_groups": ([c_int64, c_int64, c_int], c_int64),
@@ -136,6 +139,10 @@ _SIGNATURES = {
     "mfft_ew_moments": ([c_void_p, c_void_p, c_int, c_size_t, c_int, POINTER(c_double), POINTER(c_double)], c_int),
     "mfft_real_moments": ([c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_double), POINTER(c_double), POINTER(c_int64)], c_int),
     "mfft_ew_histogram": ([c_void_p, c_void_p, c_int, c_size_t, c_int, POINTER(c_double), POINTER(c_double), c_int, POINTER(c_int64)], c_int),
+    "mfft_ew_joint_histogram": ([c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_int, POINTER(c_double), POINTER(c_double), c_int, c_int,
+                                 POINTER(c_int64)], c_int),
+    "mfft_real_joint_histogram": ([c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_double), POINTER(c_double), c_int, c_int,
+                                   POINTER(c_int64), POINTER(c_int64)], c_int),
     "mfft_real_histogram": ([c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_double), POINTER(c_double), c_int, POINTER(c_int64),
                              POINTER(c_int64)], c_int),
     "mfft_ew_quadratic": ([c_void_p, c_void_p, c_int, c_size_t, c_int, POINTER(c_double), c_double, c_double, c_double, c_int,
@@ -158,7 +165,7 @@ _SIGNATURES = {
 # functions whose int result is a count, not a status
 _COUNT_RESULT = {"mfft_version", "mfft_length_supported", "mfft_length_route", "mfft_length_route_precision", "mfft_plan_timing_get",
                  "mfft_nlz_moments_groups", "mfft_nlz_hist_groups", "mfft_nlz_quad_groups",
-                 "mfft_nlz_incr_groups"}
+                 "mfft_nlz_incr_groups", "mfft_nlz_joint_groups"}
 
 _lib = None
 

@@ -497,6 +497,54 @@ int64_t mfft_nlz_hist_groups(int64_t nrows, int64_t n, int precision) {
   return ngroups;
 }
 
+// The stage that ends in a joint histogram (fft_nlz.h body_joint), synchronous.  a, b: (ncomp, nrows, pitch), pair p = (a_p, b_p);
+// out[p * cells + sa * (nbb + 3) + sb] = counts of the points of (irfft(a_p row, n), irfft(b_p row, n)) over all rows.
+int mfft_nlz_joint_rows(const void* a, const void* b, int ncomp, int64_t nrows, int64_t n, int64_t pitch, int64_t valid, int64_t valid_in,
+                        int precision, const double* lo, const double* hi, int nba, int nbb, int64_t* out) {
+  if (!a || !b || !out || !lo || !hi || nrows < 1 || n < 2 || n >= 65536 || pitch < valid || valid < 1 || valid > n / 2 + 1 || valid_in < 0 || valid_in > valid)
+    return set_error(MFFT_ERR_INVALID, "bad argument");
+  if (precision != MFFT_DOUBLE && precision != MFFT_SINGLE) return set_error(MFFT_ERR_INVALID, "unknown precision %d", precision);
+  if (ncomp != 1 && ncomp != 3) return set_error(MFFT_ERR_INVALID, "ncomp must be 1 or 3, not %d", ncomp);
+  const size_t es = elem_bytes(precision, true);
+  NljArgs z;
+  for (int p = 0; p < ncomp; ++p) {
+    z.a[p] = static_cast<const char*>(a) + (size_t)(p * nrows * pitch) * es;
+    z.b[p] = static_cast<const char*>(b) + (size_t)(p * nrows * pitch) * es;
+    MFFT_TRY(joint_range(lo[p], hi[p], nba, &z.inv[2 * p]));
+    MFFT_TRY(joint_range(lo[ncomp + p], hi[ncomp + p], nbb, &z.inv[2 * p + 1]));
+    z.lo[2 * p] = lo[p];
+    z.lo[2 * p + 1] = lo[ncomp + p];
+  }
+  z.npairs = ncomp;
+  z.nba = nba; z.nbb = nbb;
+  z.n = (int)n; z.prec = precision; z.in_stride = pitch; z.nrows = nrows; z.valid = (int)valid; z.valid_in = (int)valid_in;
+  z.norm = 1.0 / (double)n;
+  int ngroups = 0;
+  int64_t max_rows = 0;
+  MFFT_TRY(nlj_launch_shape(n, precision, nrows, &ngroups, &max_rows));
+  const size_t acc_bytes = (size_t)ncomp * joint_cells(nba, nbb) * sizeof(int64_t);
+  char* buf = nullptr;
+  MFFT_HIP(hipMalloc(reinterpret_cast<void**>(&buf), acc_bytes + joint_part_bytes(ngroups, ncomp, nba, nbb)));
+  int64_t* acc = reinterpret_cast<int64_t*>(buf);
+  z.part = buf + acc_bytes;
+  int rc = 0;
+  if (hipMemsetAsync(acc, 0, acc_bytes, nullptr) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemsetAsync failed");
+  if (!rc) rc = joint_rows(z, acc, nullptr);
+  std::vector<int64_t> host((size_t)ncomp * joint_cells(nba, nbb));
+  if (!rc && hipMemcpy(host.data(), acc, acc_bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemcpy failed");
+  if (hipStreamSynchronize(nullptr) != hipSuccess && !rc) rc = set_error(MFFT_ERR_HIP, "hipStreamSynchronize failed");
+  (void)hipFree(buf);
+  if (!rc) memcpy(out, host.data(), acc_bytes);
+  return rc;
+}
+// workgroups of that launch (0: no kernel of that length)
+int64_t mfft_nlz_joint_groups(int64_t nrows, int64_t n, int precision) {
+  int ngroups = 0;
+  int64_t max_rows = 0;
+  if (nlj_launch_shape(n, precision, nrows, &ngroups, &max_rows) != 0) return 0;
+  return ngroups;
+}
+
 // The stage that ends in the statistics of a quadratic form (fft_nlz.h body_quad), synchronous.  Fields and rows as
 // mfft_nlz_moments_rows; q = sum_f weights[f] irfft(row of field f, n)^2, fields in the order a_0.., then b_0..; out6 = [min, max,
 // S1 .. S4] of q about center over all rows, counts[nbins + 3] its histogram over [lo, hi) (null allowed where nbins == 0).

@@ -741,6 +741,74 @@ int launch_nlh(const NlhArgs& a, hipStream_t s) {
   return by_prec(a.prec, [&](auto t) { return launch_nlh_t<decltype(t)>(e, a, tw, s); });
 }
 
+// The stage that ends in a joint histogram (fft_nlz.h body_joint, Op::JointHistogram): the grid of the histogram stage by the same
+// query, and its limit -- a workgroup counts passes x 2 rows-per-workgroup x n points into unsigned cells, one cell could take
+// them all; max_rows is what ONE launch may take (joint.hip joint_rows splits a longer run of rows; nothing wraps silently).
+int nlj_launch_shape(int64_t n, int prec, int64_t nrows, int* ngroups, int64_t* max_rows) {
+  const KernelEntry* e = find_nlz(n, prec, Op::JointHistogram);
+  if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused z-stage kernel with a joint histogram of length %lld", (long long)n);
+  if (nrows < 1) return set_error(MFFT_ERR_INVALID, "no rows");
+  void* tw = nullptr;
+  MFFT_TRY(prepare_kernel(e, &tw));                // (the LDS attribute is set before the occupancy is asked for)
+  int cap = 0;
+  MFFT_TRY(nls_resident(e, &cap));
+  const int64_t per_pass = 2 * (int64_t)e->tile * n;                   // points of one workgroup's pass
+  const int64_t passes = ((int64_t)1 << 32) / per_pass - 1;
+  if (passes < 1) return set_error(MFFT_ERR_INTERNAL, "%s: one pass of a workgroup counts 2^32 points", e->name);
+  *max_rows = passes * cap * 2 * e->tile;
+  const int64_t rows = std::min(nrows, *max_rows);
+  const int64_t units = (rows + 2 * e->tile - 1) / (2 * e->tile);
+  *ngroups = (int)std::min<int64_t>(units, cap);
+  return 0;
+}
+template <typename T>
+static int launch_nlj_t(const KernelEntry* e, const NljArgs& a, void* tw, hipStream_t s) {
+  NljParams<T> P;
+  for (int f = 0; f < 3; ++f) {
+    P.a[f] = static_cast<const cx<T>*>(f < a.npairs ? a.a[f] : nullptr);
+    P.b[f] = static_cast<const cx<T>*>(f < a.npairs ? a.b[f] : nullptr);
+    P.out[f] = nullptr;
+  }
+  P.tw = static_cast<const cx<T>*>(tw);
+  P.rt3 = nullptr;
+  P.in_stride = a.in_stride;
+  P.out_stride = 0;
+  P.nrows = a.nrows;
+  P.valid = a.valid > 0 && a.valid < a.n / 2 + 1 ? a.valid : a.n / 2 + 1;
+  P.valid_in = a.valid_in > 0 && a.valid_in < P.valid ? a.valid_in : P.valid;
+  P.scale = (T)1;
+  P.part = static_cast<unsigned*>(a.part);
+  for (int i = 0; i < 2 * NLS_PAIRS; ++i) { P.lo[i] = a.lo[i]; P.inv[i] = a.inv[i]; }
+  P.norm = a.norm;
+  P.nba = a.nba;
+  P.nbb = a.nbb;
+  P.npairs = a.npairs;
+  P.ngroups = a.ngroups;
+  e->launch(&P, a.ngroups, s);
+  MFFT_HIP(hipGetLastError());
+  return 0;
+}
+int launch_nlj(const NljArgs& a, hipStream_t s) {
+  const KernelEntry* e = find_nlz(a.n, a.prec, Op::JointHistogram);
+  if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused z-stage kernel with a joint histogram of length %d", a.n);
+  const int64_t units = (a.nrows + 2 * e->tile - 1) / (2 * e->tile);
+  if (a.npairs < 1 || a.npairs > NLS_PAIRS || !a.part || a.nrows < 1 || a.ngroups < 1 || a.ngroups > units || a.nba < 1 || a.nba > NLJ_MAXBINS ||
+      a.nbb < 1 || a.nbb > NLJ_MAXBINS)
+    return set_error(MFFT_ERR_INVALID, "bad argument");
+  // what one workgroup counts stays below 2^32: passes x 2 x rows per workgroup x n
+  const int64_t passes = (units + a.ngroups - 1) / a.ngroups;
+  if (passes * 2 * e->tile * (int64_t)a.n >= ((int64_t)1 << 32))
+    return set_error(MFFT_ERR_INVALID, "%lld rows in one joint-histogram launch of %d workgroups: a count could wrap", (long long)a.nrows, a.ngroups);
+  for (int p = 0; p < a.npairs; ++p) {
+    if (!a.a[p] || !a.b[p]) return set_error(MFFT_ERR_INVALID, "null argument: a joint histogram counts pairs of fields");
+    for (int i = 2 * p; i < 2 * p + 2; ++i)
+      if (!(a.inv[i] > 0.0) || !std::isfinite(a.inv[i]) || !std::isfinite(a.lo[i])) return set_error(MFFT_ERR_INVALID, "bad histogram range");
+  }
+  void* tw = nullptr;
+  MFFT_TRY(prepare_kernel(e, &tw));
+  return by_prec(a.prec, [&](auto t) { return launch_nlj_t<decltype(t)>(e, a, tw, s); });
+}
+
 // The stage that ends in the statistics of a quadratic form (fft_nlz.h body_quad, Op::Quadratic): the grid of the moments stage by
 // the same query, the waves of nls_launch_shape (groups of NLS_STATS doubles in mpart) and the limit of nlh_launch_shape -- a
 // workgroup counts passes x 2 rows-per-workgroup x n values of q at the most, max_rows keeps that below 2^32.

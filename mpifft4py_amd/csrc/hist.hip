@@ -99,9 +99,15 @@ int hist_range(double lo, double hi, int nbins, double* inv) {
 
 int hist_fold(const unsigned* part, size_t groups, int nfields, int nbins, int64_t* acc, hipStream_t s) {
   if (nfields < 1 || nfields > 6 || nbins < 1 || nbins > NLH_MAXBINS) return set_error(MFFT_ERR_INTERNAL, "hist_fold: %d fields, %d bins", nfields, nbins);
+  return hist_fold_slots(part, groups, nfields, nbins + 3, acc, s);
+}
+
+// the same fold for rows of any length (the joint histograms' grids, joint.hip): acc[f][s] += sum over the groups g, in fixed
+// order, of part[(g * nfields + f) * nslots + s]
+int hist_fold_slots(const unsigned* part, size_t groups, int nfields, int nslots, int64_t* acc, hipStream_t s) {
+  if (nfields < 1 || nfields > 65535 || nslots < 1) return set_error(MFFT_ERR_INTERNAL, "hist_fold_slots: %d fields, %d slots", nfields, nslots);
   if (groups == 0) return 0;
-  const int nb3 = nbins + 3;
-  hipLaunchKernelGGL(hist_fold_kernel, dim3((nb3 + HF_SLOTS - 1) / HF_SLOTS, nfields), dim3(HF_BLOCK), 0, s, part, groups, nfields, nb3, acc);
+  hipLaunchKernelGGL(hist_fold_kernel, dim3((nslots + HF_SLOTS - 1) / HF_SLOTS, nfields), dim3(HF_BLOCK), 0, s, part, groups, nfields, nslots, acc);
   MFFT_HIP(hipGetLastError());
   return 0;
 }

@@ -1,0 +1,7 @@
+// gfx950 instantiations: fused nonlinear z stage that ends in a joint histogram (fft_nlz.h NlzJoint), double precision
+#include "registry_nlz.h"
+#include "plans.h"
+namespace {
+#define MFFT_REG_NLJ(N, ...) mfft::register_nlj<mfft::Spec<N, __VA_ARGS__>, double>("nlj n" #N "(" #__VA_ARGS__ ")double");
+mfft::PlanRegistrar registrar([] { MFFT_NLZPLANS_P2(MFFT_REG_NLJ) MFFT_NLZPLANS_3(MFFT_REG_NLJ) });
+}

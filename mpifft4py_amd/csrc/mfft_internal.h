@@ -153,6 +153,7 @@ constexpr NlProduct NL_PRODUCTS[] = {
     {Op::Histogram, "histogram", 6, 0, false, false},
     {Op::Quadratic, "quadratic", 6, 0, false, false},
     {Op::Increments, "increments", 6, 0, false, false},
+    {Op::JointHistogram, "joint", 6, 0, false, false},       // (one or three PAIRS of fields: a_p with b_p)
 };
 inline const NlProduct& nl_product(Op op) {
   for (const NlProduct& q : NL_PRODUCTS)
@@ -212,9 +213,39 @@ int hist_rows(const NlhArgs& z, int64_t* acc, hipStream_t s);
 // Histograms (hist.hip).  acc: device int64, (nfields, nbins + 3).  hist_fold: acc[f][s] += sum over the groups g, in fixed
 // order, of part[(g * nfields + f) * (nbins + 3) + s]; nfields <= 6.
 int hist_fold(const unsigned* part, size_t groups, int nfields, int nbins, int64_t* acc, hipStream_t s);
+// ... for rows of any length nslots (the grids of the joint histograms): part[(g * nfields + f) * nslots + s]
+int hist_fold_slots(const unsigned* part, size_t groups, int nfields, int nslots, int64_t* acc, hipStream_t s);
 // inv = nbins / (hi - lo) of a valid range; MFFT_ERR_INVALID for nbins outside 1 .. NLH_MAXBINS, hi <= lo, a range that is not finite
 int hist_range(double lo, double hi, int nbins, double* inv);
 int hist_max_bins();
+// The z stage that ends in a joint histogram (fft_nlz.h body_joint): pair p is the rows a[p] + i b[p], BOTH present; per pair
+// (nba + 3)(nbb + 3) counts, cell = slot of a_p * (nbb + 3) + slot of b_p (fft_nlz.h joint_cell).
+struct NljArgs {
+  const void* a[3] = {nullptr, nullptr, nullptr};
+  const void* b[3] = {nullptr, nullptr, nullptr};
+  int npairs = 0;
+  int n = 0;             // REAL length of a z row
+  int prec = MFFT_DOUBLE;
+  int64_t in_stride = 0, nrows = 0;   // complex elements
+  int valid = 0;         // bins per row present in memory (0 = all n/2+1)
+  int valid_in = 0;      // bins per row that are read, where fewer (pruned 2/3-rule); 0 = valid
+  double norm = 1.0;
+  double lo[6] = {0, 0, 0, 0, 0, 0}, inv[6] = {1, 1, 1, 1, 1, 1};   // [pair][a, b]: lower edge, nb / (hi - lo)
+  int nba = 0, nbb = 0;  // 1 .. MFFT_JOINT_MAXBINS
+  int ngroups = 0;       // workgroups of the launch, from nlj_launch_shape() of (n, prec, nrows)
+  void* part = nullptr;  // (ngroups, npairs, cells) unsigned counts: hist_fold_slots adds them up
+};
+// workgroups of the launch over nrows rows, and the rows ONE launch may take so that no workgroup counts 2^32 points
+int nlj_launch_shape(int64_t n, int prec, int64_t nrows, int* ngroups, int64_t* max_rows);
+int launch_nlj(const NljArgs& a, hipStream_t s);
+// all rows of z (ngroups not set; part holds joint_part_bytes() of the shape's ngroups): launches of at most max_rows rows, each
+// folded into acc (pairs joint_cells() apart) -- counts accumulate over launches and calls (joint.hip)
+inline int joint_cells(int nba, int nbb) { return (nba + 3) * (nbb + 3); }
+size_t joint_part_bytes(int ngroups, int npairs, int nba, int nbb);
+int joint_rows(const NljArgs& z, int64_t* acc, hipStream_t s);
+// inv_a, inv_b of a valid pair of ranges; MFFT_ERR_INVALID for a bin count outside 1 .. MFFT_JOINT_MAXBINS, hi <= lo, a range
+// that is not finite
+int joint_range(double lo, double hi, int nb, double* inv);
 // The z stage that ends in the statistics of a quadratic form (fft_nlz.h body_quad): pairs as in NlsArgs; q = sum over the slots
 // of w[slot] r^2, r = norm * (the un-normalised inverse transform); [min, max, S1 .. S4] of q about `center` and, nbins > 0, the
 // nbins + 3 counts of q over [lo, lo + nbins / inv).

@@ -9,7 +9,7 @@ using namespace mfft;
 #endif
 
 mfft_plan_s::~mfft_plan_s() {
-  for (Buf* b : {&work[0], &work[1], &work[2], &work3, &nlw[0], &nlw[1], &nlx, &nly, &nlr, &pcomp, &shl, &nlm, &nlmacc, &nlsacc, &nlhacc, &nlq, &nliacc})
+  for (Buf* b : {&work[0], &work[1], &work[2], &work3, &nlw[0], &nlw[1], &nlx, &nly, &nlr, &pcomp, &shl, &nlm, &nlmacc, &nlsacc, &nlhacc, &nlq, &nliacc, &nljacc, &nlr2})
     if (b->p) (void)(b->arena ? wfree(b->p) : dev_free(b->p));
   if (mask) (void)hipFree(mask);
   if (band_tiles) (void)hipFree(band_tiles);
@@ -443,6 +443,21 @@ int mfft_real_increments(mfft_plan_t p, const void* a_hat, const void* b_hat, in
   u.ncomp = ncomp;
   u.nfields = b_hat ? 2 * ncomp : ncomp;
   return p->real_increments(u, dealias, seps, nsep, out, count);
+}
+
+// counts of the pairs (ifftn(a_f), ifftn(b_f)) in a grid of nba x nbb equal bins per pair: see include/mpifft4py_amd.h
+int mfft_real_joint_histogram(mfft_plan_t p, const void* a_hat, const void* b_hat, int ncomp, int dealias, const double* lo, const double* hi,
+                              int nba, int nbb, int64_t* out, int64_t* count) {
+  if (!out || !count || !lo || !hi) return set_error(MFFT_ERR_INVALID, "null argument");
+  if (!b_hat) return set_error(MFFT_ERR_INVALID, "a joint histogram counts pairs of fields: b_hat must not be NULL");
+  MFFT_TRY(check_ready(p, a_hat, a_hat));
+  if (ncomp != 1 && ncomp != 3) return set_error(MFFT_ERR_INVALID, "ncomp must be 1 or 3, not %d", ncomp);
+  if (dealias != MFFT_DEALIAS_NONE && dealias != MFFT_DEALIAS_2_3 && dealias != MFFT_DEALIAS_3_2)
+    return set_error(MFFT_ERR_INVALID, "unknown dealias mode %d", dealias);
+  NlFields u{a_hat, b_hat, nullptr, nullptr, nullptr};
+  u.ncomp = ncomp;
+  u.nfields = 2 * ncomp;
+  return p->real_joint_histogram(u, dealias, lo, hi, nba, nbb, out, count);
 }
 
 int mfft_plan_sync(mfft_plan_t p) {

@@ -141,6 +141,13 @@ struct mfft_plan_s {
   // mfft_real_histogram / mfft_ew_histogram (hist.hip): 6 x (NLH_MAXBINS + 3) int64 counts in slot order, rows nbins + 3 apart,
   // cleared on the stream when a call starts; the workgroups' partial histograms go to nlm.  The call's ranges, in slot order.
   Buf nlhacc{false, false};
+  // mfft_real_joint_histogram / mfft_ew_joint_histogram (joint.hip): 3 x (MFFT_JOINT_MAXBINS + 3)^2 int64 counts, pairs cells apart,
+  // cleared on the stream when a call starts; the workgroups' partial grids go to nlm.  The call's ranges in slot order, and its
+  // bin counts.  nlr2: the SECOND real work array of the composed route (a_p in nlr, b_p here: two is the minimum for a pair).
+  Buf nljacc{false, false};
+  Buf nlr2{false, false};
+  double nlj_lo[6] = {0, 0, 0, 0, 0, 0}, nlj_inv[6] = {1, 1, 1, 1, 1, 1};
+  int nlj_nba = 0, nlj_nbb = 0;
   double nlh_lo[6] = {0, 0, 0, 0, 0, 0}, nlh_inv[6] = {1, 1, 1, 1, 1, 1};
   int nlh_bins = 0;
   // mfft_real_quadratic / mfft_ew_quadratic (quad.hip): the statistics of q in slot 0 of nlsacc, its counts in the first nbins + 3
@@ -560,6 +567,14 @@ struct mfft_plan_s {
   int hist_sweep(const void* x, int ncomp, size_t n, const double* lo, const double* inv, int nbins, int64_t* acc);
   int hist_begin(const double lo_slots[6], const double inv_slots[6], int nbins);
   int hist_end(int64_t* host, int nslots);
+  // Joint histograms of one or three pairs of fields given as spectra (plan_nonlinear.hip; the z stage fft_nlz.h body_joint on the
+  // fused routes; composed, two inverse transforms and one sweep per pair), and the sweep itself (joint.hip).
+  // out: (npairs, nba + 3, nbb + 3).  lo, hi: 2 ncomp entries, a_0.., then b_0..
+  int real_joint_histogram(const mfft::NlFields& u, int dealias, const double* lo, const double* hi, int nba, int nbb, int64_t* out, int64_t* count);
+  int joint_composed(const mfft::NlFields& u, int dealias);
+  int joint_sweep(const void* x, const void* y, size_t n, const double lo[2], const double inv[2], int nba, int nbb, int64_t* acc);
+  int joint_begin(const double lo_slots[6], const double inv_slots[6], int nba, int nbb);
+  int joint_end(int64_t* host, int npairs);
   // Statistics of q = sum_f w_f ifftn(field f)^2 over up to six fields given as spectra (plan_nonlinear.hip; the z stage fft_nlz.h
   // body_quad on the fused routes; composed: one inverse transform per field into ONE real work array, its term added into nlq,
   // one sweep of nlq), and the sweeps themselves (quad.hip).  out6: [min, max, S1 .. S4]; counts: nbins + 3, may be null if nbins == 0

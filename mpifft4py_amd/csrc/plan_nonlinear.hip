@@ -163,6 +163,27 @@ static int nlh_rows(mfft_plan_s* p, const NlFields& u, char* Y, size_t yelems, i
   return hist_rows(z, static_cast<int64_t*>(p->nlhacc.p), p->stream);
 }
 
+// the z stage that ends in a joint histogram, on a batch: rows of the call's pairs in Y in, the workgroups' partial grids into nlm,
+// folded into the plan's int64 accumulator (joint_begin) after each launch: the counts accumulate over the batches.
+static int nlj_rows(mfft_plan_s* p, const NlFields& u, char* Y, size_t yelems, int64_t L2, int64_t Za, int64_t nrows, int valid_in) {
+  NljArgs z;
+  int ngroups = 0;
+  int64_t max_rows = 0;
+  MFFT_TRY(nlj_launch_shape(L2, p->prec, nrows, &ngroups, &max_rows));
+  z.npairs = u.nfields / 2;
+  z.nba = p->nlj_nba; z.nbb = p->nlj_nbb;
+  MFFT_TRY(p->ensure(p->nlm, joint_part_bytes(ngroups, z.npairs, z.nba, z.nbb)));
+  for (int f = 0; f < u.nfields; ++f) {
+    const int slot = nls_slot(u, f);
+    (slot % 2 ? z.b : z.a)[slot / 2] = Y + (size_t)f * yelems * p->es;
+  }
+  for (int i = 0; i < 6; ++i) { z.lo[i] = p->nlj_lo[i]; z.inv[i] = p->nlj_inv[i]; }
+  z.n = (int)L2; z.prec = p->prec; z.in_stride = Za; z.nrows = nrows; z.valid = (int)p->Nf; z.valid_in = valid_in;
+  z.norm = 1.0 / (double)L2;
+  z.part = p->nlm.p;
+  return joint_rows(z, static_cast<int64_t*>(p->nljacc.p), p->stream);
+}
+
 // the z stage that ends in the statistics of a quadratic form, on a batch: rows of the call's fields in Y in, the waves' partial
 // statistics and the workgroups' partial histograms into nlm, folded into the plan's accumulators (quad_begin) after each launch:
 // both accumulate over the batches.
@@ -318,6 +339,7 @@ int mfft_plan_s::nonlinear_fused(const NlFields& u, int dealias, Op product, boo
       if (product == Op::Histogram) return nlh_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0);
       if (product == Op::Quadratic) return nlq_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0);
       if (product == Op::Increments) return nli_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0);
+      if (product == Op::JointHistogram) return nlj_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0);
       return nlz_rows(this, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0, product, stats);
     }));
     if (nout) MFFT_TRY(stage("nl_y_fwd", nout * (Xb + Yb) * frac, [&] {
@@ -425,6 +447,7 @@ int mfft_plan_s::nonlinear_fused_ranks(const NlFields& u, int dealias, Op produc
       if (product == Op::Histogram) return nlh_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0);
       if (product == Op::Quadratic) return nlq_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0);
       if (product == Op::Increments) return nli_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0);
+      if (product == Op::JointHistogram) return nlj_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0);
       return nlz_rows(this, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0, product, stats);
     }));
     if (nout) MFFT_TRY(stage("nl_y_fwd", 0, [&] {      // truncate + fold in y, straight into the packed (P, Lp0, S) send layout
@@ -625,5 +648,46 @@ int mfft_plan_s::real_increments(const NlFields& u, int dealias, const int64_t* 
     for (int i = 0; i < nsep; ++i)
       for (int k = 0; k < 3; ++k) out[(f * nsep + i) * 3 + k] = host[(nls_slot(u, f) * MFFT_INCR_MAXSEP + i) * 3 + k];
   *count = nr;
+  return 0;
+}
+
+// Joint histograms of the real-space fields of one or three PAIRS of spectra: per pair (nba + 3)(nbb + 3) counts of the points
+// (x_a, x_b) = (ifftn(a_p), ifftn(b_p))(dealias), cell = slot of x_a * (nbb + 3) + slot of x_b (fft_nlz.h joint_cell), over this
+// rank's part of the grid a product would be formed on.  The routes are real_histogram's: fused, the inverse passes of the
+// products and the z stage that ends in a joint histogram (no real array); composed, a_p into nlr and b_p into nlr2 -- two real
+// work arrays, the least a pair can do with --, one sweep (joint.hip), next pair.  Synchronises the plan's stream.
+int mfft_plan_s::joint_composed(const NlFields& u, int dealias) {
+  const bool pad = dealias == MFFT_DEALIAS_3_2;
+  const int64_t nr = local_real_count(pad), nc = local_complex_alloc();
+  if (nr <= 0 || !r2c) return set_error(MFFT_ERR_UNSUPPORTED, "real_joint_histogram needs a 3-D real-to-complex plan");
+  MFFT_TRY(ensure(nlr, (size_t)nr * rs));
+  MFFT_TRY(ensure(nlr2, (size_t)nr * rs));
+  int64_t* acc = static_cast<int64_t*>(nljacc.p);
+  const int cells = joint_cells(nlj_nba, nlj_nbb);
+  for (int p = 0; p < u.ncomp; ++p) {
+    MFFT_TRY(exec(false, u.src(p, nc, es), nlr.p, dealias));
+    MFFT_TRY(exec(false, u.src(u.ncomp + p, nc, es), nlr2.p, dealias));
+    MFFT_TRY(stage("nl_joint", 2.0 * (double)nr * rs, [&] {
+      return joint_sweep(nlr.p, nlr2.p, (size_t)nr, nlj_lo + 2 * p, nlj_inv + 2 * p, nlj_nba, nlj_nbb, acc + (size_t)p * cells);
+    }));
+  }
+  return 0;
+}
+int mfft_plan_s::real_joint_histogram(const NlFields& u, int dealias, const double* lo, const double* hi, int nba, int nbb, int64_t* out,
+                                      int64_t* count) {
+  double l6[6] = {0, 0, 0, 0, 0, 0}, i6[6] = {1, 1, 1, 1, 1, 1};
+  for (int f = 0; f < u.nfields; ++f) {            // (everything is checked before anything is enqueued)
+    const int slot = nls_slot(u, f);
+    MFFT_TRY(joint_range(lo[f], hi[f], slot % 2 ? nbb : nba, &i6[slot]));
+    l6[slot] = lo[f];
+  }
+  if (dealias == MFFT_DEALIAS_2_3) MFFT_TRY(require_mask());
+  MFFT_TRY(joint_begin(l6, i6, nba, nbb));
+  const bool pad = dealias == MFFT_DEALIAS_3_2;
+  MFFT_TRY(nonlinear_fusable(dealias, Op::JointHistogram, false)
+               ? (P == 1 ? nonlinear_fused(u, dealias, Op::JointHistogram, false) : nonlinear_fused_ranks(u, dealias, Op::JointHistogram, false))
+               : joint_composed(u, dealias));
+  MFFT_TRY(joint_end(out, u.ncomp));
+  *count = local_real_count(pad);
   return 0;
 }

@@ -192,6 +192,40 @@ void register_nli(const char* name) {
   reg.push_back(make_entry<K, NliParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::Increments, Build::Default, R, name));
 }
 
+// Op::JointHistogram: the stage that ends in a joint histogram (fft_nlz.h body_joint, NljParams; kernels_nlj*.hip).  Rows, twiddle
+// placement and the two-waves-per-SIMD cap are those of register_nlh: the body inlines ONE transform, computes the two slots that
+// body_hist computes and issues one LDS add where it issues two.  What differs is the LDS: the grid takes NLJ_MAXCELLS x 4 = 17956
+// bytes behind the exchange buffers where the histograms take 4120, so the exchange has a rule of its own (nlj_split): whole complex
+// values where twiddles + exchange + grid stay within the 81920 bytes that keep two workgroups on a CU, real and imaginary halves
+// in turn beyond.  Every kernel whose twin has TWO resident workgroups by LDS keeps them, but for 3072 points in double precision,
+// whose twin is split already (eight kernels in all hold one fewer than the twin, six of them three -> two).  The
+// rule changes double precision 768, 1296, 1536, 2048, 2304, 4096 and single precision 4096; of these 768 was a wave build and
+// becomes a barrier build (nlz_wave needs the whole exchange).  DESIGN.md 7 has the table and what was measured.  MFFT_NLJ_TWIN=1 builds the alternative (`make nlj_variant`): the twin's exchange and wave build,
+// one resident workgroup fewer where the grid does not fit (scripts/real_joint_ab.py).  Measured on the device, z stage alone
+// (profiles/real_joint_ab.txt): the rule wins by 1.4 - 1.7 x for the double-precision kernels of 768 .. 2304 points and by 1.4 x for
+// 4096 in single precision, which it gives a second workgroup.  The ONE exception: 4096 points in double precision, 512 threads
+// and 180 VGPRs, keeps one workgroup by REGISTERS whichever exchange it has; halving the exchange buys nothing there and
+// the twin's whole exchange is 1.3 x faster: it keeps the twin's.
+#ifndef MFFT_NLJ_TWIN
+#define MFFT_NLJ_TWIN 0
+#endif
+template <class S, typename T> constexpr bool nlj_split() {
+  if (MFFT_NLJ_TWIN || (sizeof(T) == 8 && S::N == 4096)) return nlz_split<S, T>();
+  constexpr long long tw = nlz_twlds<S, T>() ? (long long)S::TW * (int)sizeof(cx<T>) : 0;
+  return tw + (long long)padded_len<S::N, S::R(0)>() * nlz_rows<S, T>() * (int)sizeof(cx<T>) + (long long)NLJ_MAXCELLS * 4 > 81920;
+}
+template <class S, typename T> constexpr bool nlj_wave() {
+  return MFFT_NLZ_WAVE && S::TPT <= 64 && 64 % S::TPT == 0 && !nlj_split<S, T>();
+}
+template <class S, typename T>
+void register_nlj(const char* name) {
+  auto& reg = kernel_registry();
+  constexpr int R = nlz_rows<S, T>();
+  constexpr int W = MFFT_NLZ_OCC > 1 ? 16 + MFFT_NLZ_OCC : 0;
+  typedef NlzJoint<NlzFft<S, T, R, nlz_twlds<S, T>(), nlj_split<S, T>(), nlj_wave<S, T>()>> K;
+  reg.push_back(make_entry<K, NljParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::JointHistogram, Build::Default, R, name));
+}
+
 // ... and its pruned 3/2-rule flavour (Nlz3Fft: Build::Nlz3, entry.n = M = 3 L): three thread groups of SL::TPT threads per row
 template <class SL, typename T> constexpr int nlz3_rows() { return 256 / (3 * SL::TPT) > 0 ? 256 / (3 * SL::TPT) : 1; }
 template <class SL, typename T>

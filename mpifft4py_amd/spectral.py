@@ -428,6 +428,17 @@ def _hist_check(lo, hi, bins):
         raise ValueError("every range needs finite lo < hi, not %r .. %r" % (lo, hi))
 
 
+def _range_of_moments(m, what):
+    """Every field's [min, max] as a histogram range: hi widened by (max - min) * 2^-20 so that the maximum falls inside; a
+    constant field gets a range of width 1 about its value."""
+    if not (np.all(np.isfinite(m.min)) and np.all(np.isfinite(m.max))):
+        raise ValueError("a %s is not finite (min %r, max %r): give `range`" % (what, m.min, m.max))
+    lo, hi = m.min.copy(), np.maximum(m.max + (m.max - m.min) * 2.0 ** -20, np.nextafter(m.max, np.inf))
+    const = ~(m.min < m.max)
+    lo[const], hi[const] = m.min[const] - 0.5, m.min[const] + 0.5
+    return lo, hi
+
+
 def real_histogram(FFT, a_hat, b_hat=None, dealias=None, bins=256, range=None, reduce=True):
     """Histograms of fields that exist as SPECTRA only (mfft_real_histogram): the counts of ifftn(a_hat[f], dealias) -- and of
     ifftn(b_hat[f], dealias) where b_hat is given -- in `bins` equal bins per field, without a real array: on slab plans with
@@ -446,11 +457,7 @@ def real_histogram(FFT, a_hat, b_hat=None, dealias=None, bins=256, range=None, r
     nfields = ncomp * len(fields)
     if range is None:
         m = real_moments(FFT, a_hat, b_hat, dealias, reduce=True)
-        if not (np.all(np.isfinite(m.min)) and np.all(np.isfinite(m.max))):
-            raise ValueError("a field is not finite (min %r, max %r): give `range`" % (m.min, m.max))
-        lo, hi = m.min.copy(), np.maximum(m.max + (m.max - m.min) * 2.0 ** -20, np.nextafter(m.max, np.inf))
-        const = ~(m.min < m.max)
-        lo[const], hi[const] = m.min[const] - 0.5, m.min[const] + 0.5
+        lo, hi = _range_of_moments(m, "field")
     else:
         lo, hi = _hist_ranges(range, nfields)
     _hist_check(lo, hi, bins)
@@ -475,11 +482,7 @@ def histogram(FFT, x, bins=256, range=None, reduce=False):
     ncomp = int(x.shape[0]) if len(x.shape) == 4 else 1
     if range is None:
         m = moments(FFT, x, reduce=reduce)
-        if not (np.all(np.isfinite(m.min)) and np.all(np.isfinite(m.max))):
-            raise ValueError("a component is not finite (min %r, max %r): give `range`" % (m.min, m.max))
-        lo, hi = m.min.copy(), np.maximum(m.max + (m.max - m.min) * 2.0 ** -20, np.nextafter(m.max, np.inf))
-        const = ~(m.min < m.max)
-        lo[const], hi[const] = m.min[const] - 0.5, m.min[const] + 0.5
+        lo, hi = _range_of_moments(m, "component")
     else:
         lo, hi = _hist_ranges(range, ncomp)
     _hist_check(lo, hi, bins)
@@ -492,6 +495,157 @@ def histogram(FFT, x, bins=256, range=None, reduce=False):
     if reduce:
         out, n = _add_over_ranks(FFT, out), int(_add_over_ranks(FFT, [n])[0])
     return Histogram(n, out, lo, hi)
+
+
+JOINT_MAXBINS = 64      # bins per field of one joint call (MFFT_JOINT_MAXBINS: (64 + 3)^2 cells are what a workgroup's LDS holds)
+
+
+def joint_cells(xa, xb, lo, hi, bins):
+    """The cell rule of the joint histograms, in numpy float64 (include/mpifft4py_amd.h): cell = sa * (nbb + 3) + sb with
+    sa = hist_slots(xa, lo[0], hi[0], nba), sb = hist_slots(xb, lo[1], hi[1], nbb); `bins` is an int or (nba, nbb)."""
+    nba, nbb = _joint_bins(bins)
+    return hist_slots(xa, lo[0], hi[0], nba) * (nbb + 3) + hist_slots(xb, lo[1], hi[1], nbb)
+
+
+def _joint_bins(bins):
+    nba, nbb = (int(bins), int(bins)) if np.ndim(bins) == 0 else (int(bins[0]), int(bins[1]))
+    return nba, nbb
+
+
+def _joint_check(lo, hi, nba, nbb):
+    if not (1 <= nba <= JOINT_MAXBINS and 1 <= nbb <= JOINT_MAXBINS):
+        raise ValueError("bins must be 1 .. %d per field, not %r: a finer PDF is a second call on a narrower range" % (JOINT_MAXBINS, (nba, nbb)))
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo < hi)):
+        raise ValueError("every range needs finite lo < hi, not %r .. %r" % (lo, hi))
+
+
+class JointHistogram(object):
+    """Counts of `npairs` pairs of real fields (a_p, b_p) over `count` points in nba x nbb equal bins of [lo[p, 0], hi[p, 0]) x
+    [lo[p, 1], hi[p, 1]): `raw` of shape (npairs, nba + 3, nbb + 3), int64, rows and columns in slot order (0 below, 1 .. nb the
+    bins, nb + 1 at or above hi, nb + 2 not a number); `counts` = raw[:, 1:-2, 1:-2] of shape (npairs, nba, nbb).  For every
+    pair raw[p].sum() == count."""
+
+    def __init__(self, count, raw, lo, hi, bins):
+        nba, nbb = _joint_bins(bins)
+        self.count = int(count)
+        self.raw = np.asarray(raw, dtype=np.int64).reshape(-1, nba + 3, nbb + 3).copy()
+        self.counts = self.raw[:, 1:-2, 1:-2].copy()
+        self.lo = np.asarray(lo, dtype=np.float64).reshape(self.raw.shape[0], 2).copy()      # [pair][a, b]
+        self.hi = np.asarray(hi, dtype=np.float64).reshape(self.raw.shape[0], 2).copy()
+
+    @property
+    def npairs(self):
+        return int(self.raw.shape[0])
+
+    @property
+    def nbins(self):
+        return (int(self.counts.shape[1]), int(self.counts.shape[2]))
+
+    def outside(self, p=0):
+        """The points of pair p with either value below, above or not a number: count - counts[p].sum()."""
+        return int(self.raw[p].sum() - self.counts[p].sum())
+
+    def edges(self, p=0, axis=0):
+        """The nb + 1 edges of the bins of pair p's field a (axis 0) or b (axis 1)."""
+        nb = self.nbins[axis]
+        return self.lo[p, axis] + (self.hi[p, axis] - self.lo[p, axis]) * (np.arange(nb + 1, dtype=np.float64) / nb)
+
+    def centers(self, p=0, axis=0):
+        e = self.edges(p, axis)
+        return 0.5 * (e[:-1] + e[1:])
+
+    def pdf(self, p=0):
+        """The density over the rectangle, normalised by ALL `count` points: times the cell area it sums to 1 - outside(p) / count."""
+        area = (self.hi[p, 0] - self.lo[p, 0]) / self.nbins[0] * (self.hi[p, 1] - self.lo[p, 1]) / self.nbins[1]
+        return self.counts[p] / (float(self.count) * area)
+
+    def marginal(self, axis=0):
+        """The `Histogram` of the a fields (axis 0) or the b fields (axis 1): the row or column sums, border slots included, so
+        that below, above and nonfinite are those of the one-dimensional histogram of the same range and bins."""
+        return Histogram(self.count, self.raw.sum(axis=2 - axis), self.lo[:, axis], self.hi[:, axis])
+
+    def conditional_mean(self, p=0, of=1):
+        """<b | a in bin i> (of=1; of=0: <a | b in bin j>) from the bin centres of the averaged field, over the points inside the
+        rectangle; NaN where a row is empty.  Exact only to half a bin width of the averaged field."""
+        c = self.counts[p] if of == 1 else self.counts[p].T
+        n = c.sum(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(n > 0, (c * self.centers(p, of)[None, :]).sum(axis=1) / np.where(n > 0, n, 1), np.nan)
+
+
+def _joint_ranges(rng, ncomp):
+    """(lo, hi) in the order of the C interface, a_0.., then b_0..: `rng` is ((lo_a, hi_a), (lo_b, hi_b)) for all pairs, or
+    of shape (npairs, 2, 2), [pair][a, b][lo, hi]."""
+    r = np.asarray(rng, dtype=np.float64)
+    if r.shape == (2, 2):
+        r = np.tile(r, (ncomp, 1, 1))
+    assert r.shape == (ncomp, 2, 2), (r.shape, ncomp)
+    return np.ascontiguousarray(r[:, :, 0].T.ravel()), np.ascontiguousarray(r[:, :, 1].T.ravel())
+
+
+def _joint_result(FFT, n, out, lo, hi, ncomp, nba, nbb, reduce):
+    if reduce:
+        out, n = _add_over_ranks(FFT, out), int(_add_over_ranks(FFT, [n])[0])
+    return JointHistogram(n, out, lo.reshape(2, ncomp).T, hi.reshape(2, ncomp).T, (nba, nbb))
+
+
+def real_joint_histogram(FFT, a_hat, b_hat, dealias=None, bins=64, range=None, reduce=True):
+    """Joint histograms of fields that exist as SPECTRA only (mfft_real_joint_histogram): the counts of the points
+    (ifftn(a_hat[p], dealias), ifftn(b_hat[p], dealias)) in a grid of `bins` = nba x nbb equal bins per pair (an int: the same for
+    both), p over the 1 or 3 components -- the joint PDF of two fields at the same grid point, which no pair of marginal
+    histograms gives.  On slab plans with radix kernels on every axis the z stage ends in the grid
+    (`FFT.plan_info("nonlinear_joint_fused_3_2")`): a pair rides ONE inverse transform, one thread holds both values, no real
+    array exists.  Elsewhere the plan transforms a_p and b_p into TWO real work arrays -- the least a pair can do with -- and
+    sweeps them.  At most JOINT_MAXBINS = 64 bins per field ((64 + 3)^2 cells are what a workgroup's LDS holds next to its
+    exchange buffers): a finer PDF is a second call on a narrower `range`.  `range` is ((lo_a, hi_a), (lo_b, hi_b)) for all
+    pairs or of shape (npairs, 2, 2); None: ONE `real_moments` call runs first and every field gets its own [min, max] over
+    FFT.comm, widened as in `real_histogram`, so every point falls inside.  b_hat may be a_hat.  Returns a `JointHistogram`;
+    with `reduce` the int64 counts are added over FFT.comm.  Counts are integers: the same bits run to run and for every number
+    of ranks of a fused slab plan.  Synchronises the plan's stream; the inputs are preserved."""
+    if b_hat is None:
+        raise ValueError("a joint histogram counts pairs of fields: b_hat must be given")
+    cs = tuple(int(s) for s in FFT.complex_shape())
+    assert a_hat.shape in (cs, (3,) + cs) and b_hat.shape == a_hat.shape, (a_hat.shape, b_hat.shape, cs)
+    vec = len(a_hat.shape) == 4
+    ncomp = 3 if vec else 1
+    nba, nbb = _joint_bins(bins)
+    if range is None:
+        lo, hi = _range_of_moments(real_moments(FFT, a_hat, b_hat, dealias, reduce=True), "field")      # (a_0.., then b_0..)
+    else:
+        lo, hi = _joint_ranges(range, ncomp)
+    _joint_check(lo, hi, nba, nbb)
+    out = np.zeros((ncomp, nba + 3, nbb + 3), dtype=np.int64)
+    count = ctypes.c_int64(0)
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
+    _nonlinear(FFT, "real_joint_histogram", [(a_hat, vec), (b_hat, vec)], dealias, head=(a_hat.ptr, b_hat.ptr, ncomp),
+               tail=(lo.ctypes.data_as(dp), hi.ctypes.data_as(dp), nba, nbb, out.ctypes.data_as(ip), ctypes.byref(count)))
+    return _joint_result(FFT, count.value, out, lo, hi, ncomp, nba, nbb, reduce)
+
+
+def joint_histogram(FFT, x, y, bins=64, range=None, reduce=False):
+    """The joint histogram of two real DeviceArrays of the same shape (mfft_ew_joint_histogram, the companion of `histogram`):
+    arrays of the real shape are one pair, a leading extent of 1 or 3 is taken as components, pair p = (x[p], y[p]).  `bins`
+    and `range` as in `real_joint_histogram`; None: the components' [min, max] from `moments` (over FFT.comm with `reduce`).
+    Returns a `JointHistogram`; with `reduce` over FFT.comm."""
+    if x.pitch is not None or y.pitch is not None:
+        raise ValueError("a histogram of a pitched array would count the elements between its rows")
+    assert x.dtype == np.dtype(FFT.float) and y.dtype == x.dtype and x.shape == y.shape, (x.dtype, y.dtype, x.shape, y.shape)
+    ncomp = int(x.shape[0]) if len(x.shape) == 4 else 1
+    assert ncomp in (1, 3), ncomp
+    nba, nbb = _joint_bins(bins)
+    if range is None:
+        lx, hx = _range_of_moments(moments(FFT, x, reduce=reduce), "component")
+        ly, hy = _range_of_moments(moments(FFT, y, reduce=reduce), "component")
+        lo, hi = np.concatenate([lx, ly]), np.concatenate([hx, hy])
+    else:
+        lo, hi = _joint_ranges(range, ncomp)
+    _joint_check(lo, hi, nba, nbb)
+    FFT.comm.use_device()
+    out = np.zeros((ncomp, nba + 3, nbb + 3), dtype=np.int64)
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
+    _lib.call("mfft_ew_joint_histogram", FFT._plan, x.ptr, y.ptr, ncomp, x.size // ncomp, _prec(FFT), lo.ctypes.data_as(dp),
+              hi.ctypes.data_as(dp), nba, nbb, out.ctypes.data_as(ip))
+    return _joint_result(FFT, x.size // ncomp, out, lo, hi, ncomp, nba, nbb, reduce)
 
 
 def quad_rule(r, weights):

@@ -127,6 +127,9 @@ run() {
     real_quadratic_ab.txt) python scripts/real_quadratic_ab.py --procs 3 --out out/real_quadratic_ab.txt ;;
     real_increments_regs.tsv) make -C mpifft4py_amd/csrc -j8 >/dev/null; python scripts/real_increments_regs.py ;;
     real_increments_ab.txt) python scripts/real_increments_ab.py --procs 3 --out out/real_increments_ab.txt ;;
+    real_joint_regs.tsv) make -C mpifft4py_amd/csrc -j8 >/dev/null; python scripts/real_joint_regs.py ;;
+    real_joint_ab.txt) make -C mpifft4py_amd/csrc -j8 nlj_variant >/dev/null      # the joint kernels with their twins' exchange, for section (3)
+      python scripts/real_joint_ab.py --procs 3 --out out/real_joint_ab.txt ;;
     shell_spectrum_ab.txt) python scripts/shell_spectrum_ab.py --procs 3 --out out/shell_spectrum_ab.txt
       # its last section: the kernels' trace statistics, and in a run of their own the LDS counters
       rocprofv3 --kernel-trace --stats --output-format csv -d out/shell_trace -- python scripts/shell_spectrum_ab.py --worker --cases 512:double,1024:double,1024:single
