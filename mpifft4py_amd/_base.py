@@ -327,7 +327,8 @@ class DistFFTBase(object):
     def plan_info(self, key):
         """What the plan decided (mfft_plan_get_info): "pruned_route", "comm_cus", "kz_slices", "row_batches", "zfuse",
         "plane_pad", "split_last", "split_last_yblock", "split_last_row_pitch",
-        "split_last_block_pitch", "split_last_yfirst", "work_bytes", "complex_pitch", "complex_pitch_native", "nonlinear_bytes" and, for the fused route of the
+        "split_last_block_pitch", "split_last_yfirst", "split_last_xnear", "split_last_xnear_row_pitch", "split_last_xnear_block_pitch",
+        "split_last_xnear_work_bytes", "split_last_pairblock", "split_last_pairxfast", "work_bytes", "complex_pitch", "complex_pitch_native", "nonlinear_bytes" and, for the fused route of the
         nonlinear term, "nonlinear[_dot|_cross_dot|_outer][_absmax]_fused_3_2" / "_none" / "_2_3": unnamed the cross product, "_dot",
         "_cross_dot" and "_outer" the other three (spectral.py), "_absmax" the call that records the maxima (none for "_cross_dot"
         and "_outer")."""

@@ -442,6 +442,8 @@ static int launch_pair_t(const KernelEntry* e, const RealArgs& a, int64_t real_s
   P.p_rplane = a.pair_rplane;
   P.p_cplane = a.pair_cplane;
   P.p_ymap = make_rowmap(a.pair_rblock, real_stride, a.pair_yblock, a.pair_n1);
+  P.p_tile = a.pair_tile;
+  P.p_tile_xfast = a.pair_tile_xfast ? 1 : 0;
   return launch_rows(e, P, P.nrows, e->tile / 2, s);
 }
 
@@ -505,6 +507,7 @@ static int launch_real(int fam, const RealArgs& a, hipStream_t s) {
     const bool blocked = a.pair_yblock > 0 && a.pair_yblock < a.pair_n1;      // (its fastdiv: rows and block below 2^16)
     if (!e || a.zs.nchunk || a.valid > 0 || real_stride % 2 != 0 || a.pair_rplane % 2 != 0 ||
         a.nrows != (int64_t)a.pair_n0 * a.pair_n1 || a.nrows >= (int64_t)1 << 31 ||
+        a.pair_tile < 0 || a.pair_tile > 32768 || (int64_t)a.pair_tile * a.pair_n1 >= (int64_t)1 << 31 ||
         (blocked && (a.pair_n1 >= 65536 || a.pair_n1 % a.pair_yblock != 0 || a.pair_rblock % 2 != 0)))
       return set_error(MFFT_ERR_UNSUPPORTED, "no pair-row real kernel of length %d for this layout", a.n);
     void *tw = nullptr, *rtw = nullptr;

@@ -228,9 +228,10 @@ static void test_real() {
 // complex (n0, n1, N/2 + 1) array goes in (not the transform of a real field: the planes kz = 0 and N/2 are not Hermitian); the
 // inverse x and y transforms of what comes out, read as reals, must be numpy's irfftn of it (inverse c2c over x and y, then the
 // c2r that ignores the imaginary parts of bins 0 and N/2).  Rows and planes of both sides are pitched.  yb > 0: the real side is
-// blocked in y (RealPairParams::p_ymap): blocks of yb rows per x, pitched x rows inside a block, pitched blocks.
+// blocked in y (RealPairParams::p_ymap): blocks of yb rows per x, pitched x rows inside a block, pitched blocks.  tile > 0: the
+// workgroups take the slots in tiles of tile x tile (pair_slot), xfast: kx fastest inside a tile.
 template <class S, typename T, int ROWS, bool TWLDS>
-static void test_pair(int n0, int n1, int yb = 0) {
+static void test_pair(int n0, int n1, int yb = 0, int tile = 0, bool xfast = false) {
   const int M = S::N, N = 2 * M, Nf = M + 1;
   Uniform U(11 + N + 7 * n0 + n1);
   const int wrow = M + 1, wplane = (yb ? yb : n1) * wrow + 3, crow = Nf + 2, cplane = n1 * crow + 5;      // complex elements
@@ -280,7 +281,7 @@ static void test_pair(int n0, int n1, int yb = 0) {
         }
     typedef R2CFft<S, T, ROWS, TWLDS, false, false, false, false, true> K;
     RealPairParams<T> P{{W.data(), fu.data(), tw.data(), rtw.data(), 2 * wrow, crow, slots, Nf, (T)1}};
-    P.pn0 = n0; P.pn1 = n1; P.p_rplane = 2 * wplane; P.p_cplane = cplane; P.p_ymap = ymap;
+    P.pn0 = n0; P.pn1 = n1; P.p_rplane = 2 * wplane; P.p_cplane = cplane; P.p_ymap = ymap; P.p_tile = tile; P.p_tile_xfast = xfast;
     emu_launch(grid, K::THREADS, K::LDS_BYTES, [&](int b, int t, char* lds) { K::body(P, b, t, lds); });
     RelL2 err;
     bool gaps = true;        // nothing outside the rows is written
@@ -289,7 +290,7 @@ static void test_pair(int n0, int n1, int yb = 0) {
       if (y < n1 && k < Nf) err.add(fu[i], ref[((size_t)x * n1 + y) * Nf + k]);
       else if (fu[i].x != (T)7 || fu[i].y != (T)7) gaps = false;
     }
-    snprintf(name, sizeof name, "r2c pair r%d %dx%d b%d%s", ROWS, n0, n1, yb, TWLDS ? " twlds" : "");
+    snprintf(name, sizeof name, "r2c pair r%d %dx%d b%d g%d%s%s", ROWS, n0, n1, yb, tile, xfast ? "x" : "", TWLDS ? " twlds" : "");
     report(name, N, pname<T>(), gaps ? err.value() : 1.0, tol_of<T>());
   }
   {
@@ -319,7 +320,7 @@ static void test_pair(int n0, int n1, int yb = 0) {
     }
     typedef C2RFft<S, T, ROWS, TWLDS, false, false, false, false, false, true> K;
     RealPairParams<T> P{{fu.data(), W.data(), tw.data(), rtw.data(), crow, 2 * wrow, slots, Nf, (T)(1.0 / N)}};
-    P.pn0 = n0; P.pn1 = n1; P.p_rplane = 2 * wplane; P.p_cplane = cplane; P.p_ymap = ymap;
+    P.pn0 = n0; P.pn1 = n1; P.p_rplane = 2 * wplane; P.p_cplane = cplane; P.p_ymap = ymap; P.p_tile = tile; P.p_tile_xfast = xfast;
     emu_launch(grid, K::THREADS, K::LDS_BYTES, [&](int b, int t, char* lds) { K::body(P, b, t, lds); });
     bool gaps = true;
     std::vector<cx<long double>> w((size_t)n0 * n1 * M);
@@ -334,7 +335,7 @@ static void test_pair(int n0, int n1, int yb = 0) {
       const cx<long double> got = {w[i].x / ((long double)n0 * n1), w[i].y / ((long double)n0 * n1)}, want = {ref[2 * i], ref[2 * i + 1]};
       err.add(got, want);
     }
-    snprintf(name, sizeof name, "c2r pair r%d %dx%d b%d%s", ROWS, n0, n1, yb, TWLDS ? " twlds" : "");
+    snprintf(name, sizeof name, "c2r pair r%d %dx%d b%d g%d%s%s", ROWS, n0, n1, yb, tile, xfast ? "x" : "", TWLDS ? " twlds" : "");
     report(name, N, pname<T>(), gaps ? err.value() : 1.0, 4 * tol_of<T>());
   }
 }

@@ -234,12 +234,36 @@ struct RealPairParams : RealParams<T> {
   int pn0, pn1;
   i64 p_rplane, p_cplane;
   RowMap p_ymap;
+  int p_tile = 0;              // pair_slot's G: 0 = the slots in row order
+  int p_tile_xfast = 0;        // ... and its xfast
 };
+
+// Launch index q -> slot (kx, ky) of the (nx = n0 / 2 + 1) x n1 slot grid.  G = 0: row order, (q / n1, q % n1).  G > 0: tiles of
+// G x G slots, the tile rows in kx order, the tiles of a tile row in ky order, and inside a tile ky fastest -- or, xfast, kx
+// fastest; the tiles of the last tile row and the last tile of every tile row are as small as the grid leaves them, so the map is
+// a bijection for any nx, n1, G (G * n1 < 2^31: the launcher's business).  Consecutive workgroups then walk G adjacent rows of G
+// planes on the complex side, and on a real side that is transposed (y blocks of one row, plan_slab.hip W_T) G adjacent rows of G
+// blocks, instead of one row per block: a few pages per tile on both sides.  A workgroup's own slots are neighbours in the fastest
+// direction: their rows are adjacent on the complex side with ky fastest, on a transposed real side with kx fastest.
+MFFT_HD void pair_slot(unsigned q, unsigned nx, unsigned n1, unsigned G, bool xfast, unsigned* kx, unsigned* ky) {
+  if (G == 0) {
+    *kx = q / n1;
+    *ky = q - *kx * n1;
+    return;
+  }
+  const unsigned band = G * n1, tx = q / band, r = q - tx * band;
+  const unsigned hx = nx - tx * G < G ? nx - tx * G : G;          // rows of this tile row
+  const unsigned ty = r / (hx * G), r2 = r - ty * (hx * G);
+  const unsigned wy = n1 - ty * G < G ? n1 - ty * G : G;          // columns of this tile
+  const unsigned d = xfast ? hx : wy, hi = r2 / d, lo = r2 - hi * d;
+  *kx = tx * G + (xfast ? lo : hi);
+  *ky = ty * G + (xfast ? hi : lo);
+}
 
 // PAIR kernels (R2CFft / C2RFft): the real side holds, row by row, the x and y transforms of the real field read as complex
 // pairs w[m] = u[2m] + i u[2m+1] -- a COMPLEX field, so the half-spectrum row (kx, ky) needs the mirrored bins of its
 // Hermitian partner row ((n0 - kx) % n0, (n1 - ky) % n1) where the plain kernels take their own.  Slot q lists the row
-// (kx, ky) = (q / n1, q % n1) of the planes kx <= n0 / 2 as side 0 and its partner as side 1.  In a plane that is its own
+// (kx, ky) = pair_slot(q) of the planes kx <= n0 / 2 as side 0 and its partner as side 1.  In a plane that is its own
 // partner (kx = 0, 2 kx = n0) the rows ky > n1 / 2 have been listed as partners already: such a slot does nothing, and a row
 // that is its own partner is stored by side 0 alone.  Every row belongs to exactly one live (slot, side).
 struct PairRow {
@@ -251,7 +275,8 @@ MFFT_D PairRow pair_row(const RealPairParams<T>& P, i64 q, int side, i64 cplx_pi
   const bool inrange = q < P.nrows;
   if (!inrange) q = P.nrows - 1;         // loads stay unconditional (see RowFft)
   const unsigned n0 = (unsigned)P.pn0, n1 = (unsigned)P.pn1;
-  const unsigned kx = (unsigned)q / n1, ky = (unsigned)q - kx * n1;
+  unsigned kx, ky;
+  pair_slot((unsigned)q, n0 / 2 + 1, n1, (unsigned)P.p_tile, P.p_tile_xfast != 0, &kx, &ky);
   const unsigned px = kx ? n0 - kx : 0u, py = ky ? n1 - ky : 0u;
   bool live = inrange && !(px == kx && ky > py);
   if (side && px == kx && py == ky) live = false;

@@ -111,6 +111,9 @@ struct RealArgs {
   // x row INSIDE a block (fft_kernels.h RealPairParams::p_ymap); 0 or pair_n1: one block, the plain layout
   int pair_yblock = 0;
   int64_t pair_rblock = 0;
+  // order in which the workgroups take the pair slots (fft_kernels.h pair_slot): tiles of pair_tile x pair_tile slots; 0: row order
+  int pair_tile = 0;
+  bool pair_tile_xfast = false;      // kx fastest inside a tile (ky: the default)
 };
 int launch_r2c(const RealArgs& a, hipStream_t s);
 int launch_c2r(const RealArgs& a, hipStream_t s);

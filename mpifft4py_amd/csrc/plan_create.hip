@@ -504,6 +504,14 @@ int mfft_plan_get_info(mfft_plan_t p, const char* key, int64_t* value) {
   else if (k == "split_last_row_pitch") *value = p->split_last_route() ? p->split_last_layout().SR : 0;
   else if (k == "split_last_block_pitch") *value = p->split_last_route() ? p->split_last_layout().SB : 0;
   else if (k == "split_last_yfirst") *value = p->split_last_route() ? p->split_last_layout().yfirst : 0;
+  // route "x near" (plan_slab.hip): the directions that take it (0 none, 1 both, 2 forward, 3 inverse), the pitches of its transposed
+  // array W_T, the tile of the z passes' slot order on it, and the bytes of W_T as allocated
+  else if (k == "split_last_xnear") *value = p->split_last_xnear_mode();
+  else if (k == "split_last_xnear_row_pitch") *value = p->split_last_xnear_mode() ? p->split_last_layout_t().SR : 0;
+  else if (k == "split_last_xnear_block_pitch") *value = p->split_last_xnear_mode() ? p->split_last_layout_t().SB : 0;
+  else if (k == "split_last_pairblock") *value = p->split_last_route() ? p->split_last_pair_tile(p->split_last_xnear_mode() != 0) : 0;
+  else if (k == "split_last_pairxfast") *value = !p->split_last_route() ? 0 : (p->split_last_pair_xfast(p->split_last_xnear_mode() != 0, false) ? 1 : 0) + (p->split_last_pair_xfast(p->split_last_xnear_mode() != 0, true) ? 2 : 0);
+  else if (k == "split_last_xnear_work_bytes") *value = p->split_last_xnear_mode() ? (int64_t)p->work[1].bytes : 0;
   else if (k == "work_bytes") *value = (int64_t)p->work[0].bytes;
   else if (k == "plane_pad") *value = (p->P == 1 && p->d.decomp == MFFT_SLAB) ? p->p1_plane_pad() : 0;   // elements added to the intermediate's plane pitch
   else return set_error(MFFT_ERR_INVALID, "mfft_plan_get_info: unknown key '%s'", key);

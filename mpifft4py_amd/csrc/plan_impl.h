@@ -421,9 +421,22 @@ struct mfft_plan_s {
   SplitLastLayout split_last_layout() const;
   bool split_last_eligible() const;
   bool split_last_route();
+  // Route "x near" (plan_slab.hip): a second work array W_T, the transposed layout (B = 1: element (x, y, m) at y * SB + x * SR + m),
+  // so that the x pass reads or writes rows 8 KiB apart.  Forward: y u -> W, x W -> W_T out of place, z W_T -> fu; inverse: z fu -> W_T,
+  // x in place on W_T, y W_T -> u.
+  int split_last_xnear = -1;    // MFFT_SPLIT_LAST_XNEAR, read when the plan is created: 0 off, 1 both directions, 2 forward only,
+                                // 3 inverse only; unset: by rule
+  int split_last_xnear_fit = -1;       // both arrays fit: decided with split_last_fit
+  int64_t split_last_xnear_pad_bytes = -1;   // MFFT_SPLIT_LAST_XNEAR_PAD: bytes added to N0 * SR for W_T's SB (whole cache lines); unset: by rule
+  int split_last_pairblock = -1;       // MFFT_SPLIT_LAST_PAIRBLOCK: G of fft_kernels.h pair_slot for the z passes of the route; unset: by rule
+  int split_last_pairxfast = -1;       // MFFT_SPLIT_LAST_PAIRXFAST: kx fastest inside a tile in the forward (1), the inverse (2) or both (3) z passes; unset: by rule
+  SplitLastLayout split_last_layout_t() const;
+  int split_last_xnear_mode();         // what runs: 0 ... 3 as above
+  int split_last_pair_tile(bool xnear) const;
+  bool split_last_pair_xfast(bool xnear, bool inv) const;
   int split_last_x(const SplitLastLayout& l, const void* user_in, void* user_out, void* W, bool inv);
   int split_last_y(const SplitLastLayout& l, const void* user_in, void* user_out, void* W, bool inv);
-  int split_last_z(const SplitLastLayout& l, const void* in, void* out, bool inv);
+  int split_last_z(const SplitLastLayout& l, const void* in, void* out, bool inv, bool xnear = false);
   int slab_forward_split_last(const void* u, void* fu);
   int slab_backward_split_last(const void* fu, void* u);
   int slab_forward(const void* u, void* fu);

@@ -302,6 +302,10 @@ int mfft::decomp_init(mfft_plan_s* p, const mfft_plan_desc* desc, int nranks, in
   p->split_last_yblock = (int)env_int("MFFT_SPLIT_LAST_YBLOCK", p->split_last_yblock);
   p->split_last_yfirst = (int)env_int("MFFT_SPLIT_LAST_YFIRST", p->split_last_yfirst);
   p->split_last_pad_bytes = env_int("MFFT_SPLIT_LAST_PAD", p->split_last_pad_bytes);
+  p->split_last_xnear = (int)env_int("MFFT_SPLIT_LAST_XNEAR", p->split_last_xnear);
+  p->split_last_xnear_pad_bytes = env_int("MFFT_SPLIT_LAST_XNEAR_PAD", p->split_last_xnear_pad_bytes);
+  p->split_last_pairblock = (int)env_int("MFFT_SPLIT_LAST_PAIRBLOCK", p->split_last_pairblock);
+  p->split_last_pairxfast = (int)env_int("MFFT_SPLIT_LAST_PAIRXFAST", p->split_last_pairxfast);
   if (getenv("MFFT_PAD_ALIGN")) p->pad_align = env_on("MFFT_PAD_ALIGN") ? 1 : 0;
   p->pad_align_inv = (int)env_int("MFFT_PAD_ALIGN_INV", p->pad_align_inv);
   const int P = p->P;

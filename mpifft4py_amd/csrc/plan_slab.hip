@@ -64,14 +64,68 @@ mfft_plan_s::SplitLastLayout mfft_plan_s::split_last_layout() const {
   l.SB = N0 * l.SR + (l.nblk > 1 ? slow_pitch_pad(N0 * l.SR) : 0);
   return l;
 }
+// Route "x near": the transposed array W_T next to W.  With ONE work array a transpose is paid on one side or the other
+// (profiles/split_last_blocked_ab.txt section 3); with two, the x pass is the transposing pass, out of place, and a strided pass that
+// READS far rows and writes near ones is the cheap kind (bwd_y on B = 1: 2.92 - 3.12 ms against fwd_y's 3.40 - 3.46).  Forward: y
+// u -> W as ever, x W -> W_T (one outer batch per y: rows a plane of W apart in, SR apart out), z W_T -> fu.  Inverse: the existing
+// order "B = 1, y first" on W_T alone -- z fu -> W_T, x in place on near rows, y W_T -> u.  The z passes take their slots in tiles
+// (fft_kernels.h pair_slot; the forward one with kx fastest: measured) so that the rows they move are near on both sides.  Same kernels, same order of sums: the results are the
+// bits of the route without it.  MFFT_SPLIT_LAST_XNEAR chooses the directions (plan_impl.h); the forward direction needs the plain W
+// with y first.  By rule (profiles/split_last_xnear_ab.txt) only on the mesh the split-last route is on for by itself.
+#ifndef MFFT_SPLIT_LAST_XNEAR_DEFAULT
+#define MFFT_SPLIT_LAST_XNEAR_DEFAULT 1
+#endif
+#ifndef MFFT_SPLIT_LAST_PAIRBLOCK_DEFAULT
+#define MFFT_SPLIT_LAST_PAIRBLOCK_DEFAULT 16
+#endif
+#ifndef MFFT_SPLIT_LAST_PAIRXFAST_DEFAULT
+#define MFFT_SPLIT_LAST_PAIRXFAST_DEFAULT 1
+#endif
+static int xnear_wanted(const mfft_plan_s* p) {
+  if (p->N1 >= 65536) return 0;          // (the pair kernels' blocked real side: core.hip launch_real)
+  if (p->split_last_xnear >= 0) return std::min(p->split_last_xnear, 3);
+  return p->prec == MFFT_DOUBLE && p->N0 == 1024 && p->N1 == 1024 && p->N2 == 1024 ? MFFT_SPLIT_LAST_XNEAR_DEFAULT : 0;
+}
+mfft_plan_s::SplitLastLayout mfft_plan_s::split_last_layout_t() const {
+  const int64_t M = N2 / 2;
+  SplitLastLayout l;
+  l.B = 1;
+  l.nblk = N1;
+  l.yfirst = 1;
+  l.SR = M + slow_pitch_pad(M);
+  int64_t pad_b = slow_pitch_pad(N0 * l.SR);
+  if (split_last_xnear_pad_bytes >= 0 && split_last_xnear_pad_bytes % 128 == 0) pad_b = split_last_xnear_pad_bytes / (int64_t)es;
+  l.SB = N0 * l.SR + pad_b;
+  return l;
+}
+int mfft_plan_s::split_last_xnear_mode() {
+  if (!split_last_route() || split_last_xnear_fit != 1) return 0;
+  const int want = xnear_wanted(this);
+  const SplitLastLayout l = split_last_layout();
+  const bool fwd = (want == 1 || want == 2) && l.B == N1 && l.yfirst_fwd(), bwd = want == 1 || want == 3;
+  return fwd && bwd ? 1 : fwd ? 2 : bwd ? 3 : 0;
+}
+// G of pair_slot for a z pass of the route: what MFFT_SPLIT_LAST_PAIRBLOCK says; by rule tiles for the route "x near" alone
+int mfft_plan_s::split_last_pair_tile(bool xnear) const {
+  const int64_t g = split_last_pairblock >= 0 ? std::min(split_last_pairblock, 32768) : xnear ? MFFT_SPLIT_LAST_PAIRBLOCK_DEFAULT : 0;
+  return g * N1 < ((int64_t)1 << 31) ? (int)g : 0;
+}
+// ... and whether kx runs fastest inside a tile (bit 0: forward, bit 1: inverse)
+bool mfft_plan_s::split_last_pair_xfast(bool xnear, bool inv) const {
+  const int mask = split_last_pairxfast >= 0 ? split_last_pairxfast : xnear ? MFFT_SPLIT_LAST_PAIRXFAST_DEFAULT : 0;
+  return (mask >> (inv ? 1 : 0)) & 1;
+}
 bool mfft_plan_s::split_last_route() {
   if (!split_last_eligible()) return false;
   if (split_last_fit < 0) {      // the forward transform needs a work buffer now: as fwd_out_of_place decides
+    // (both arrays of the route "x near" inside the same quarter of the free memory, or the plan goes without W_T)
     const size_t need = (size_t)split_last_layout().elems() * es;
+    const size_t need_t = xnear_wanted(this) ? (size_t)split_last_layout_t().elems() * es : 0;
+    const size_t miss = work[0].bytes >= need ? 0 : need, miss_t = work[1].bytes >= need_t ? 0 : need_t;
     size_t fr = 0, tot = 0;
-    if (work[0].bytes >= need) split_last_fit = 1;
-    else if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); split_last_fit = 0; }
-    else split_last_fit = need <= fr / 4 ? 1 : 0;
+    if (miss + miss_t > 0 && hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); fr = 0; }
+    split_last_fit = miss <= fr / 4 ? 1 : 0;
+    split_last_xnear_fit = need_t > 0 && split_last_fit == 1 && miss + miss_t <= fr / 4 ? 1 : 0;
   }
   return split_last_fit == 1;
 }
@@ -94,17 +148,29 @@ int mfft_plan_s::split_last_y(const SplitLastLayout& l, const void* user_in, voi
   return col(in, out, N1, inv, N0, M, user_in ? N1 * M : l.SR, user_in ? plain(M) : wrows, user_out ? N1 * M : l.SR,
              user_out ? plain(M) : wrows);
 }
-int mfft_plan_s::split_last_z(const SplitLastLayout& l, const void* in, void* out, bool inv) {
+int mfft_plan_s::split_last_z(const SplitLastLayout& l, const void* in, void* out, bool inv, bool xnear) {
   RealArgs a = inv ? real_args(in, out, N0 * N1, N2, Nf, N2, 1.0 / (double)N2) : real_args(in, out, N0 * N1, N2, N2, Nf, 1.0);
   a.pair_n0 = (int)N0; a.pair_n1 = (int)N1; a.pair_rplane = 2 * l.SR; a.pair_cplane = N1 * Nf;
   a.pair_yblock = (int)l.B; a.pair_rblock = 2 * l.SB;
+  a.pair_tile = split_last_pair_tile(xnear);
+  a.pair_tile_xfast = split_last_pair_xfast(xnear, inv);
   return inv ? mfft::launch_c2r(a, stream) : mfft::launch_r2c(a, stream);
 }
 int mfft_plan_s::slab_forward_split_last(const void* u, void* fu) {
   const SplitLastLayout l = split_last_layout();
   const double Wb = (double)(N0 * N1 * (N2 / 2)) * es;
+  const int xnear = split_last_xnear_mode();
   MFFT_TRY(ensure(work[0], (size_t)l.elems() * es));
   void* W = work[0].p;
+  if (xnear == 1 || xnear == 2) {
+    const SplitLastLayout t = split_last_layout_t();
+    const int64_t M = N2 / 2;
+    MFFT_TRY(ensure(work[1], (size_t)t.elems() * es));
+    void* WT = work[1].p;
+    MFFT_TRY(stage("fwd_y", 2 * Wb, [&] { return split_last_y(l, u, nullptr, W, false); }));
+    MFFT_TRY(stage("fwd_x", 2 * Wb, [&] { return col(W, WT, N0, false, N1, M, M, plain(l.SR), t.SB, plain(t.SR)); }));
+    return stage("fwd_z", Wb + (double)(N0 * N1 * Nf) * es, [&] { return split_last_z(t, WT, fu, false, true); });
+  }
   if (l.yfirst_fwd()) {
     MFFT_TRY(stage("fwd_y", 2 * Wb, [&] { return split_last_y(l, u, nullptr, W, false); }));
     MFFT_TRY(stage("fwd_x", 2 * Wb, [&] { return split_last_x(l, nullptr, nullptr, W, false); }));
@@ -117,6 +183,15 @@ int mfft_plan_s::slab_forward_split_last(const void* u, void* fu) {
 int mfft_plan_s::slab_backward_split_last(const void* fu, void* u) {
   const SplitLastLayout l = split_last_layout();
   const double Wb = (double)(N0 * N1 * (N2 / 2)) * es;
+  const int xnear = split_last_xnear_mode();
+  if (xnear == 1 || xnear == 3) {
+    const SplitLastLayout t = split_last_layout_t();
+    MFFT_TRY(ensure(work[1], (size_t)t.elems() * es));
+    void* WT = work[1].p;
+    MFFT_TRY(stage("bwd_z", Wb + (double)(N0 * N1 * Nf) * es, [&] { return split_last_z(t, fu, WT, true, true); }));
+    MFFT_TRY(stage("bwd_x", 2 * Wb, [&] { return split_last_x(t, nullptr, nullptr, WT, true); }));
+    return stage("bwd_y", 2 * Wb, [&] { return split_last_y(t, nullptr, u, WT, true); });
+  }
   MFFT_TRY(ensure(work[0], (size_t)l.elems() * es));
   void* W = work[0].p;
   MFFT_TRY(stage("bwd_z", Wb + (double)(N0 * N1 * Nf) * es, [&] { return split_last_z(l, fu, W, true); }));
