@@ -335,272 +335,155 @@ int mfft_nlz_rows_absmax(const void* a, const void* b, void* out, int64_t nrows,
   return rc;
 }
 
-// The stage that ends in a reduction (fft_nlz.h body_moments), synchronous.  nfields = 1: a is (nrows, pitch); 2: a and b are;
-// 3: a is (3, nrows, pitch); 6: a and b are.  `valid` bins per row exist, the first valid_in of them are read (0: all of them).
-// out[f * 6 + {0: min, 1: max, 2..5: S1..S4}] of irfft(row, n) over all rows, fields in the order a_0.., then b_0..;
-// S_p = sum (x - center[f])^p (center null: zeros).
+// The stages that end in a reduction (fft_nlz.h body_moments, body_hist, body_joint, body_quad, body_incr), synchronous; what their
+// five entry points share.  nfields = 1: a is (nrows, pitch); 2: a and b are; 3: a is (3, nrows, pitch); 6: a and b are.  `valid`
+// bins per row exist, the first valid_in of them are read (0: all of them).  Fields in the order a_0.., then b_0..; field f rides in
+// slot nls_slot(u, f), the plan's rule.  Everything is checked before the first launch; the outputs are written on success only.
+static int nlr_stage_args(Op kind, const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
+                          int64_t valid_in, int precision, NlFields* u, NlrArgs* z) {
+  if (!a || nrows < 1 || n < 2 || n >= 65536 || pitch < valid || valid < 1 || valid > n / 2 + 1 || valid_in < 0 || valid_in > valid)
+    return set_error(MFFT_ERR_INVALID, "bad argument");
+  if (precision != MFFT_DOUBLE && precision != MFFT_SINGLE) return set_error(MFFT_ERR_INVALID, "unknown precision %d", precision);
+  if ((nfields != 1 && nfields != 2 && nfields != 3 && nfields != 6) || ((nfields % 2 == 0) != (b != nullptr)))
+    return set_error(MFFT_ERR_INVALID, "nfields must be 1 or 3 (a alone) or 2 or 6 (a and b), not %d", nfields);
+  *u = NlFields{a, b, nullptr, nullptr, nullptr};
+  u->nfields = nfields;
+  u->ncomp = b ? nfields / 2 : nfields;
+  z->kind = kind;
+  for (int f = 0; f < nfields; ++f) {
+    const int slot = nls_slot(*u, f);
+    (slot % 2 ? z->b : z->a)[slot / 2] = u->src(f, nrows * pitch, elem_bytes(precision, true));
+  }
+  z->npairs = (nfields + 1) / 2;
+  z->n = (int)n; z->prec = precision; z->in_stride = pitch; z->nrows = nrows; z->valid = (int)valid; z->valid_in = (int)valid_in;
+  z->norm = 1.0 / (double)n;
+  return 0;
+}
+// One device buffer [acc | acc2 | part]: the accumulators cleared (statistics: the identity of moments_clear; sums and counts:
+// zeros), all rows run and folded (nlr_rows), the accumulators copied to host and host2.
+static int nlr_stage_run(NlrArgs& z, size_t acc_bytes, void* host, size_t acc2_bytes, void* host2) {
+  NlrShape shape;
+  MFFT_TRY(nlr_launch_shape(z.kind, z.n, z.prec, z.nrows, &shape));
+  const size_t off2 = (acc_bytes + 127) / 128 * 128, offp = off2 + (acc2_bytes + 127) / 128 * 128;
+  char* buf = nullptr;
+  MFFT_HIP(hipMalloc(reinterpret_cast<void**>(&buf), offp + nlr_part_bytes(z, shape)));
+  z.part = buf + offp;
+  const bool stats = z.kind == Op::Moments || z.kind == Op::Quadratic;
+  int rc = stats ? moments_clear(reinterpret_cast<double*>(buf), (int)(acc_bytes / sizeof(double)), nullptr) : 0;
+  if (!rc && !stats && hipMemsetAsync(buf, 0, acc_bytes, nullptr) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemsetAsync failed");
+  if (!rc && acc2_bytes && hipMemsetAsync(buf + off2, 0, acc2_bytes, nullptr) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemsetAsync failed");
+  if (!rc) rc = nlr_rows(z, buf, buf + off2, nullptr);
+  if (!rc && hipMemcpy(host, buf, acc_bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemcpy failed");
+  if (!rc && acc2_bytes && hipMemcpy(host2, buf + off2, acc2_bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemcpy failed");
+  if (hipStreamSynchronize(nullptr) != hipSuccess && !rc) rc = set_error(MFFT_ERR_HIP, "hipStreamSynchronize failed");
+  (void)hipFree(buf);
+  return rc;
+}
+// workgroups of the first launch over those rows: a caller that wants more rows than one pass of the grid asks here (0: no kernel
+// of that length)
+static int64_t nlr_stage_groups(Op kind, int64_t nrows, int64_t n, int precision) {
+  NlrShape shape;
+  return nlr_launch_shape(kind, n, precision, nrows, &shape) == 0 ? shape.ngroups : 0;
+}
+
+// out[f * 6 + {0: min, 1: max, 2..5: S1..S4}] of irfft(row, n) over all rows; S_p = sum (x - center[f])^p (center null: zeros).
 int mfft_nlz_moments_rows(const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
                           int64_t valid_in, int precision, const double* center, double* out) {
-  if (!a || !out || nrows < 1 || n < 2 || n >= 65536 || pitch < valid || valid < 1 || valid > n / 2 + 1 || valid_in < 0 || valid_in > valid)
-    return set_error(MFFT_ERR_INVALID, "bad argument");
-  if (precision != MFFT_DOUBLE && precision != MFFT_SINGLE) return set_error(MFFT_ERR_INVALID, "unknown precision %d", precision);
-  if ((nfields != 1 && nfields != 2 && nfields != 3 && nfields != 6) || ((nfields % 2 == 0) != (b != nullptr)))
-    return set_error(MFFT_ERR_INVALID, "nfields must be 1 or 3 (a alone) or 2 or 6 (a and b), not %d", nfields);
-  const size_t es = elem_bytes(precision, true);
-  const int ncomp = b ? nfields / 2 : nfields;
-  NlsArgs z;
-  int slot_of[6] = {0, 0, 0, 0, 0, 0};
-  for (int f = 0; f < nfields; ++f) {
-    const int slot = b ? (f < ncomp ? 2 * f : 2 * (f - ncomp) + 1) : f;
-    const char* base = static_cast<const char*>(f < ncomp ? a : b) + (size_t)((f % ncomp) * nrows * pitch) * es;
-    (slot % 2 ? z.b : z.a)[slot / 2] = base;
-    z.center[slot] = center ? center[f] : 0.0;
-    slot_of[f] = slot;
-  }
-  z.npairs = (nfields + 1) / 2;
-  z.n = (int)n; z.prec = precision; z.in_stride = pitch; z.nrows = nrows; z.valid = (int)valid; z.valid_in = (int)valid_in;
-  z.norm = 1.0 / (double)n;
-  int ngroups = 0;
-  int64_t waves = 0;
-  MFFT_TRY(nls_launch_shape(n, precision, nrows, &ngroups, &waves));
-  z.ngroups = ngroups;
-  char* buf = nullptr;
-  MFFT_HIP(hipMalloc(reinterpret_cast<void**>(&buf), (size_t)(waves + 1) * NLS_SLOTS * sizeof(double)));
-  double* acc = reinterpret_cast<double*>(buf);
-  z.part = acc + NLS_SLOTS;
-  int rc = moments_clear(acc, NLS_SLOTS, nullptr);
-  if (!rc) rc = launch_nls(z, nullptr);
-  if (!rc) rc = moments_fold(static_cast<const double*>(z.part), (size_t)waves, NLS_SLOTS, acc, nullptr);
+  if (!out) return set_error(MFFT_ERR_INVALID, "bad argument");
+  NlFields u;
+  NlrArgs z;
+  MFFT_TRY(nlr_stage_args(Op::Moments, a, b, nfields, nrows, n, pitch, valid, valid_in, precision, &u, &z));
+  for (int f = 0; center && f < nfields; ++f) z.call.center[nls_slot(u, f)] = center[f];
   double host[NLS_SLOTS];
-  if (!rc && hipMemcpy(host, acc, sizeof host, hipMemcpyDeviceToHost) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemcpy failed");
-  if (hipStreamSynchronize(nullptr) != hipSuccess && !rc) rc = set_error(MFFT_ERR_HIP, "hipStreamSynchronize failed");
-  (void)hipFree(buf);
-  if (!rc)
-    for (int f = 0; f < nfields; ++f)
-      for (int k = 0; k < NLS_STATS; ++k) out[f * NLS_STATS + k] = host[slot_of[f] * NLS_STATS + k];
-  return rc;
+  MFFT_TRY(nlr_stage_run(z, sizeof host, host, 0, nullptr));
+  for (int f = 0; f < nfields; ++f)
+    for (int k = 0; k < NLS_STATS; ++k) out[f * NLS_STATS + k] = host[nls_slot(u, f) * NLS_STATS + k];
+  return 0;
 }
-// workgroups of that launch: a caller that wants more rows than one pass of the grid asks here (0: no kernel of that length)
-int64_t mfft_nlz_moments_groups(int64_t nrows, int64_t n, int precision) {
-  int ngroups = 0;
-  int64_t waves = 0;
-  if (nls_launch_shape(n, precision, nrows, &ngroups, &waves) != 0) return 0;
-  return ngroups;
-}
+int64_t mfft_nlz_moments_groups(int64_t nrows, int64_t n, int precision) { return nlr_stage_groups(Op::Moments, nrows, n, precision); }
 
-// The stage that ends in structure functions (fft_nlz.h body_incr), synchronous.  Fields and rows as mfft_nlz_moments_rows;
-// out[(f * nsep + i) * 3 + {0, 1, 2}] = S2, S3, S4 of the increments of irfft(row, n) at seps[i] over all rows, fields in the order
-// a_0.., then b_0...  Everything is checked before the first launch; the output is written on success only.
+// out[(f * nsep + i) * 3 + {0, 1, 2}] = S2, S3, S4 of the increments of irfft(row, n) at seps[i] over all rows
 int mfft_nlz_incr_rows(const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid, int64_t valid_in,
                        int precision, const int64_t* seps, int nsep, double* out) {
-  if (!a || !out || !seps || nrows < 1 || n < 2 || n >= 65536 || pitch < valid || valid < 1 || valid > n / 2 + 1 || valid_in < 0 || valid_in > valid)
-    return set_error(MFFT_ERR_INVALID, "bad argument");
-  if (precision != MFFT_DOUBLE && precision != MFFT_SINGLE) return set_error(MFFT_ERR_INVALID, "unknown precision %d", precision);
-  if ((nfields != 1 && nfields != 2 && nfields != 3 && nfields != 6) || ((nfields % 2 == 0) != (b != nullptr)))
-    return set_error(MFFT_ERR_INVALID, "nfields must be 1 or 3 (a alone) or 2 or 6 (a and b), not %d", nfields);
+  if (!out || !seps) return set_error(MFFT_ERR_INVALID, "bad argument");
+  NlFields u;
+  NlrArgs z;
+  MFFT_TRY(nlr_stage_args(Op::Increments, a, b, nfields, nrows, n, pitch, valid, valid_in, precision, &u, &z));
   MFFT_TRY(incr_check(seps, nsep, n));
-  const size_t es = elem_bytes(precision, true);
-  const int ncomp = b ? nfields / 2 : nfields;
-  NliArgs z;
-  int slot_of[6] = {0, 0, 0, 0, 0, 0};
-  for (int f = 0; f < nfields; ++f) {
-    const int slot = b ? (f < ncomp ? 2 * f : 2 * (f - ncomp) + 1) : f;
-    const char* base = static_cast<const char*>(f < ncomp ? a : b) + (size_t)((f % ncomp) * nrows * pitch) * es;
-    (slot % 2 ? z.b : z.a)[slot / 2] = base;
-    slot_of[f] = slot;
-  }
-  z.npairs = (nfields + 1) / 2;
-  z.n = (int)n; z.prec = precision; z.in_stride = pitch; z.nrows = nrows; z.valid = (int)valid; z.valid_in = (int)valid_in;
-  z.norm = 1.0 / (double)n;
-  for (int i = 0; i < nsep; ++i) z.sep[i] = (int)seps[i];
-  z.nsep = nsep;
-  int ngroups = 0;
-  int64_t waves = 0;
-  MFFT_TRY(nli_launch_shape(n, precision, nrows, &ngroups, &waves));
-  z.ngroups = ngroups;
-  char* buf = nullptr;
-  MFFT_HIP(hipMalloc(reinterpret_cast<void**>(&buf), (size_t)(waves + 1) * INCR_SLOTS * sizeof(double)));
-  double* acc = reinterpret_cast<double*>(buf);
-  z.part = acc + INCR_SLOTS;
-  int rc = hipMemsetAsync(acc, 0, INCR_SLOTS * sizeof(double), nullptr) == hipSuccess ? 0 : set_error(MFFT_ERR_HIP, "hipMemsetAsync failed");
-  if (!rc) rc = launch_nli(z, nullptr);
-  if (!rc) rc = incr_fold(static_cast<const double*>(z.part), (size_t)waves, INCR_SLOTS, acc, nullptr);
+  for (int i = 0; i < nsep; ++i) z.call.sep[i] = (int)seps[i];
+  z.call.nsep = nsep;
   double host[INCR_SLOTS];
-  if (!rc && hipMemcpy(host, acc, sizeof host, hipMemcpyDeviceToHost) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemcpy failed");
-  if (hipStreamSynchronize(nullptr) != hipSuccess && !rc) rc = set_error(MFFT_ERR_HIP, "hipStreamSynchronize failed");
-  (void)hipFree(buf);
-  if (!rc)
-    for (int f = 0; f < nfields; ++f)
-      for (int i = 0; i < nsep; ++i)
-        for (int k = 0; k < 3; ++k) out[(f * nsep + i) * 3 + k] = host[(slot_of[f] * MFFT_INCR_MAXSEP + i) * 3 + k];
-  return rc;
+  MFFT_TRY(nlr_stage_run(z, sizeof host, host, 0, nullptr));
+  for (int f = 0; f < nfields; ++f)
+    for (int i = 0; i < nsep; ++i)
+      for (int k = 0; k < 3; ++k) out[(f * nsep + i) * 3 + k] = host[(nls_slot(u, f) * MFFT_INCR_MAXSEP + i) * 3 + k];
+  return 0;
 }
-// workgroups of that launch (0: no kernel of that length)
-int64_t mfft_nlz_incr_groups(int64_t nrows, int64_t n, int precision) {
-  int ngroups = 0;
-  int64_t waves = 0;
-  if (nli_launch_shape(n, precision, nrows, &ngroups, &waves) != 0) return 0;
-  return ngroups;
-}
+int64_t mfft_nlz_incr_groups(int64_t nrows, int64_t n, int precision) { return nlr_stage_groups(Op::Increments, nrows, n, precision); }
 
-// The stage that ends in a histogram (fft_nlz.h body_hist), synchronous.  Fields and rows as mfft_nlz_moments_rows;
-// out[f * (nbins + 3) + slot] = counts of irfft(row, n) over all rows, fields in the order a_0.., then b_0...
+// out[f * (nbins + 3) + slot] = counts of irfft(row, n) over all rows
 int mfft_nlz_hist_rows(const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid, int64_t valid_in,
                        int precision, const double* lo, const double* hi, int nbins, int64_t* out) {
-  if (!a || !out || !lo || !hi || nrows < 1 || n < 2 || n >= 65536 || pitch < valid || valid < 1 || valid > n / 2 + 1 || valid_in < 0 || valid_in > valid)
-    return set_error(MFFT_ERR_INVALID, "bad argument");
-  if (precision != MFFT_DOUBLE && precision != MFFT_SINGLE) return set_error(MFFT_ERR_INVALID, "unknown precision %d", precision);
-  if ((nfields != 1 && nfields != 2 && nfields != 3 && nfields != 6) || ((nfields % 2 == 0) != (b != nullptr)))
-    return set_error(MFFT_ERR_INVALID, "nfields must be 1 or 3 (a alone) or 2 or 6 (a and b), not %d", nfields);
-  const size_t es = elem_bytes(precision, true);
-  const int ncomp = b ? nfields / 2 : nfields;
-  NlhArgs z;
-  int slot_of[6] = {0, 0, 0, 0, 0, 0};
+  if (!out || !lo || !hi) return set_error(MFFT_ERR_INVALID, "bad argument");
+  NlFields u;
+  NlrArgs z;
+  MFFT_TRY(nlr_stage_args(Op::Histogram, a, b, nfields, nrows, n, pitch, valid, valid_in, precision, &u, &z));
   for (int f = 0; f < nfields; ++f) {
-    const int slot = b ? (f < ncomp ? 2 * f : 2 * (f - ncomp) + 1) : f;
-    const char* base = static_cast<const char*>(f < ncomp ? a : b) + (size_t)((f % ncomp) * nrows * pitch) * es;
-    (slot % 2 ? z.b : z.a)[slot / 2] = base;
-    MFFT_TRY(hist_range(lo[f], hi[f], nbins, &z.inv[slot]));
-    z.lo[slot] = lo[f];
-    slot_of[f] = slot;
+    const int slot = nls_slot(u, f);
+    MFFT_TRY(hist_range(lo[f], hi[f], nbins, &z.call.inv[slot]));
+    z.call.lo[slot] = lo[f];
   }
-  z.npairs = (nfields + 1) / 2;
-  z.nbins = nbins;
-  z.n = (int)n; z.prec = precision; z.in_stride = pitch; z.nrows = nrows; z.valid = (int)valid; z.valid_in = (int)valid_in;
-  z.norm = 1.0 / (double)n;
-  int ngroups = 0;
-  int64_t max_rows = 0;
-  MFFT_TRY(nlh_launch_shape(n, precision, nrows, &ngroups, &max_rows));
-  const int nb3 = nbins + 3, nslots = 2 * z.npairs;
-  const size_t acc_bytes = (size_t)nslots * nb3 * sizeof(int64_t);
-  char* buf = nullptr;
-  MFFT_HIP(hipMalloc(reinterpret_cast<void**>(&buf), acc_bytes + hist_part_bytes(ngroups, nslots, nbins)));
-  int64_t* acc = reinterpret_cast<int64_t*>(buf);
-  z.part = buf + acc_bytes;
-  int rc = 0;
-  if (hipMemsetAsync(acc, 0, acc_bytes, nullptr) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemsetAsync failed");
-  if (!rc) rc = hist_rows(z, acc, nullptr);
-  std::vector<int64_t> host((size_t)nslots * nb3);
-  if (!rc && hipMemcpy(host.data(), acc, acc_bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemcpy failed");
-  if (hipStreamSynchronize(nullptr) != hipSuccess && !rc) rc = set_error(MFFT_ERR_HIP, "hipStreamSynchronize failed");
-  (void)hipFree(buf);
-  if (!rc)
-    for (int f = 0; f < nfields; ++f)
-      for (int k = 0; k < nb3; ++k) out[(size_t)f * nb3 + k] = host[(size_t)slot_of[f] * nb3 + k];
-  return rc;
+  z.call.nbins = nbins;
+  const int nb3 = nbins + 3;
+  std::vector<int64_t> host((size_t)2 * z.npairs * nb3);
+  MFFT_TRY(nlr_stage_run(z, host.size() * sizeof(int64_t), host.data(), 0, nullptr));
+  for (int f = 0; f < nfields; ++f)
+    for (int k = 0; k < nb3; ++k) out[(size_t)f * nb3 + k] = host[(size_t)nls_slot(u, f) * nb3 + k];
+  return 0;
 }
-// workgroups of that launch (0: no kernel of that length)
-int64_t mfft_nlz_hist_groups(int64_t nrows, int64_t n, int precision) {
-  int ngroups = 0;
-  int64_t max_rows = 0;
-  if (nlh_launch_shape(n, precision, nrows, &ngroups, &max_rows) != 0) return 0;
-  return ngroups;
-}
+int64_t mfft_nlz_hist_groups(int64_t nrows, int64_t n, int precision) { return nlr_stage_groups(Op::Histogram, nrows, n, precision); }
 
-// The stage that ends in a joint histogram (fft_nlz.h body_joint), synchronous.  a, b: (ncomp, nrows, pitch), pair p = (a_p, b_p);
+// a, b: (ncomp, nrows, pitch), ncomp 1 or 3, pair p = (a_p, b_p); lo, hi: a_0.., then b_0..
 // out[p * cells + sa * (nbb + 3) + sb] = counts of the points of (irfft(a_p row, n), irfft(b_p row, n)) over all rows.
 int mfft_nlz_joint_rows(const void* a, const void* b, int ncomp, int64_t nrows, int64_t n, int64_t pitch, int64_t valid, int64_t valid_in,
                         int precision, const double* lo, const double* hi, int nba, int nbb, int64_t* out) {
-  if (!a || !b || !out || !lo || !hi || nrows < 1 || n < 2 || n >= 65536 || pitch < valid || valid < 1 || valid > n / 2 + 1 || valid_in < 0 || valid_in > valid)
-    return set_error(MFFT_ERR_INVALID, "bad argument");
-  if (precision != MFFT_DOUBLE && precision != MFFT_SINGLE) return set_error(MFFT_ERR_INVALID, "unknown precision %d", precision);
+  if (!b || !out || !lo || !hi) return set_error(MFFT_ERR_INVALID, "bad argument");
   if (ncomp != 1 && ncomp != 3) return set_error(MFFT_ERR_INVALID, "ncomp must be 1 or 3, not %d", ncomp);
-  const size_t es = elem_bytes(precision, true);
-  NljArgs z;
-  for (int p = 0; p < ncomp; ++p) {
-    z.a[p] = static_cast<const char*>(a) + (size_t)(p * nrows * pitch) * es;
-    z.b[p] = static_cast<const char*>(b) + (size_t)(p * nrows * pitch) * es;
-    MFFT_TRY(joint_range(lo[p], hi[p], nba, &z.inv[2 * p]));
-    MFFT_TRY(joint_range(lo[ncomp + p], hi[ncomp + p], nbb, &z.inv[2 * p + 1]));
-    z.lo[2 * p] = lo[p];
-    z.lo[2 * p + 1] = lo[ncomp + p];
+  NlFields u;
+  NlrArgs z;
+  MFFT_TRY(nlr_stage_args(Op::JointHistogram, a, b, 2 * ncomp, nrows, n, pitch, valid, valid_in, precision, &u, &z));
+  for (int f = 0; f < 2 * ncomp; ++f) {
+    const int slot = nls_slot(u, f);
+    MFFT_TRY(joint_range(lo[f], hi[f], slot % 2 ? nbb : nba, &z.call.inv[slot]));
+    z.call.lo[slot] = lo[f];
   }
-  z.npairs = ncomp;
-  z.nba = nba; z.nbb = nbb;
-  z.n = (int)n; z.prec = precision; z.in_stride = pitch; z.nrows = nrows; z.valid = (int)valid; z.valid_in = (int)valid_in;
-  z.norm = 1.0 / (double)n;
-  int ngroups = 0;
-  int64_t max_rows = 0;
-  MFFT_TRY(nlj_launch_shape(n, precision, nrows, &ngroups, &max_rows));
-  const size_t acc_bytes = (size_t)ncomp * joint_cells(nba, nbb) * sizeof(int64_t);
-  char* buf = nullptr;
-  MFFT_HIP(hipMalloc(reinterpret_cast<void**>(&buf), acc_bytes + joint_part_bytes(ngroups, ncomp, nba, nbb)));
-  int64_t* acc = reinterpret_cast<int64_t*>(buf);
-  z.part = buf + acc_bytes;
-  int rc = 0;
-  if (hipMemsetAsync(acc, 0, acc_bytes, nullptr) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemsetAsync failed");
-  if (!rc) rc = joint_rows(z, acc, nullptr);
-  std::vector<int64_t> host((size_t)ncomp * joint_cells(nba, nbb));
-  if (!rc && hipMemcpy(host.data(), acc, acc_bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemcpy failed");
-  if (hipStreamSynchronize(nullptr) != hipSuccess && !rc) rc = set_error(MFFT_ERR_HIP, "hipStreamSynchronize failed");
-  (void)hipFree(buf);
-  if (!rc) memcpy(out, host.data(), acc_bytes);
-  return rc;
+  z.call.nba = nba; z.call.nbb = nbb;
+  std::vector<int64_t> host((size_t)ncomp * joint_cells(nba, nbb));      // (the pairs lie in slot order already)
+  MFFT_TRY(nlr_stage_run(z, host.size() * sizeof(int64_t), host.data(), 0, nullptr));
+  memcpy(out, host.data(), host.size() * sizeof(int64_t));
+  return 0;
 }
-// workgroups of that launch (0: no kernel of that length)
-int64_t mfft_nlz_joint_groups(int64_t nrows, int64_t n, int precision) {
-  int ngroups = 0;
-  int64_t max_rows = 0;
-  if (nlj_launch_shape(n, precision, nrows, &ngroups, &max_rows) != 0) return 0;
-  return ngroups;
-}
+int64_t mfft_nlz_joint_groups(int64_t nrows, int64_t n, int precision) { return nlr_stage_groups(Op::JointHistogram, nrows, n, precision); }
 
-// The stage that ends in the statistics of a quadratic form (fft_nlz.h body_quad), synchronous.  Fields and rows as
-// mfft_nlz_moments_rows; q = sum_f weights[f] irfft(row of field f, n)^2, fields in the order a_0.., then b_0..; out6 = [min, max,
-// S1 .. S4] of q about center over all rows, counts[nbins + 3] its histogram over [lo, hi) (null allowed where nbins == 0).
+// q = sum_f weights[f] irfft(row of field f, n)^2; out6 = [min, max, S1 .. S4] of q about center over all rows, counts[nbins + 3] its
+// histogram over [lo, hi) (null allowed where nbins == 0).
 int mfft_nlz_quad_rows(const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid, int64_t valid_in,
                        int precision, const double* weights, double center, double lo, double hi, int nbins, double* out6, int64_t* counts) {
-  if (!a || !out6 || !weights || (nbins > 0 && !counts) || nrows < 1 || n < 2 || n >= 65536 || pitch < valid || valid < 1 || valid > n / 2 + 1 ||
-      valid_in < 0 || valid_in > valid || !std::isfinite(center))
-    return set_error(MFFT_ERR_INVALID, "bad argument");
-  if (precision != MFFT_DOUBLE && precision != MFFT_SINGLE) return set_error(MFFT_ERR_INVALID, "unknown precision %d", precision);
-  if ((nfields != 1 && nfields != 2 && nfields != 3 && nfields != 6) || ((nfields % 2 == 0) != (b != nullptr)))
-    return set_error(MFFT_ERR_INVALID, "nfields must be 1 or 3 (a alone) or 2 or 6 (a and b), not %d", nfields);
-  const size_t es = elem_bytes(precision, true);
-  const int ncomp = b ? nfields / 2 : nfields;
-  NlqArgs z;
-  MFFT_TRY(quad_check(weights, nfields, lo, hi, nbins, &z.inv));
-  for (int f = 0; f < nfields; ++f) {
-    const int slot = b ? (f < ncomp ? 2 * f : 2 * (f - ncomp) + 1) : f;
-    const char* base = static_cast<const char*>(f < ncomp ? a : b) + (size_t)((f % ncomp) * nrows * pitch) * es;
-    (slot % 2 ? z.b : z.a)[slot / 2] = base;
-    z.w[slot] = weights[f];
-  }
-  z.npairs = (nfields + 1) / 2;
-  z.nbins = nbins; z.lo = lo; z.center = center;
-  z.n = (int)n; z.prec = precision; z.in_stride = pitch; z.nrows = nrows; z.valid = (int)valid; z.valid_in = (int)valid_in;
-  z.norm = 1.0 / (double)n;
-  int ngroups = 0;
-  int64_t waves = 0, max_rows = 0;
-  MFFT_TRY(nlq_launch_shape(n, precision, nrows, &ngroups, &waves, &max_rows));
-  const int nb3 = nbins + 3;
-  const size_t macc_bytes = 128, hacc_bytes = ((size_t)nb3 * sizeof(int64_t) + 127) / 128 * 128;
-  char* buf = nullptr;
-  MFFT_HIP(hipMalloc(reinterpret_cast<void**>(&buf), macc_bytes + hacc_bytes + quad_mpart_bytes(waves) + quad_hpart_bytes(ngroups, nbins)));
-  double* macc = reinterpret_cast<double*>(buf);
-  int64_t* hacc = reinterpret_cast<int64_t*>(buf + macc_bytes);
-  int rc = moments_clear(macc, NLS_STATS, nullptr);
-  if (!rc && hipMemsetAsync(hacc, 0, hacc_bytes, nullptr) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemsetAsync failed");
-  if (!rc) rc = quad_rows(z, buf + macc_bytes + hacc_bytes, macc, hacc, nullptr);
+  if (!out6 || !weights || (nbins > 0 && !counts) || !std::isfinite(center)) return set_error(MFFT_ERR_INVALID, "bad argument");
+  NlFields u;
+  NlrArgs z;
+  MFFT_TRY(nlr_stage_args(Op::Quadratic, a, b, nfields, nrows, n, pitch, valid, valid_in, precision, &u, &z));
+  MFFT_TRY(quad_check(weights, nfields, lo, hi, nbins, &z.call.inv[0]));
+  for (int f = 0; f < nfields; ++f) z.call.w[nls_slot(u, f)] = weights[f];
+  z.call.nbins = nbins; z.call.lo[0] = lo; z.call.center[0] = center;
   double m6[NLS_STATS];
-  std::vector<int64_t> host((size_t)nb3);
-  if (!rc && hipMemcpy(m6, macc, sizeof m6, hipMemcpyDeviceToHost) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemcpy failed");
-  if (!rc && hipMemcpy(host.data(), hacc, (size_t)nb3 * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) rc = set_error(MFFT_ERR_HIP, "hipMemcpy failed");
-  if (hipStreamSynchronize(nullptr) != hipSuccess && !rc) rc = set_error(MFFT_ERR_HIP, "hipStreamSynchronize failed");
-  (void)hipFree(buf);
-  if (!rc) {
-    for (int k = 0; k < NLS_STATS; ++k) out6[k] = m6[k];
-    for (int k = 0; nbins > 0 && k < nb3; ++k) counts[k] = host[k];
-  }
-  return rc;
+  std::vector<int64_t> host((size_t)nbins + 3);
+  MFFT_TRY(nlr_stage_run(z, sizeof m6, m6, host.size() * sizeof(int64_t), host.data()));
+  for (int k = 0; k < NLS_STATS; ++k) out6[k] = m6[k];
+  for (int k = 0; nbins > 0 && k < nbins + 3; ++k) counts[k] = host[k];
+  return 0;
 }
-// workgroups of that launch (0: no kernel of that length)
-int64_t mfft_nlz_quad_groups(int64_t nrows, int64_t n, int precision) {
-  int ngroups = 0;
-  int64_t waves = 0, max_rows = 0;
-  if (nlq_launch_shape(n, precision, nrows, &ngroups, &waves, &max_rows) != 0) return 0;
-  return ngroups;
-}
+int64_t mfft_nlz_quad_groups(int64_t nrows, int64_t n, int precision) { return nlr_stage_groups(Op::Quadratic, nrows, n, precision); }
 
 // U_mpi[p, i, j, k] = Uc_hatT[i, p*Np1 + j, k]   (slab.py:403)
 int mfft_slab_pack(const void* uc_hatT, void* u_mpi, int P, int64_t np0, int64_t np1, int64_t nf, int precision) {

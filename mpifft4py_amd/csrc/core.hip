@@ -605,9 +605,10 @@ int launch_nlz(const NlzArgs& a, hipStream_t s) {
   });
 }
 
-// The stage that ends in a reduction (fft_nlz.h body_moments, Op::Moments).  Its grid does not follow the rows: the workgroups
-// that are resident at once, CUs x min(what the runtime says fits, NLS_WG_PER_CU), asked once per device and kernel, and never
-// more than there are pairs of rows to start on.
+// The stages that end in a reduction (fft_nlz.h body_moments, body_hist, body_joint, body_quad, body_incr: the table entries with
+// nout == 0; NlrArgs of mfft_internal.h).  Their grid does not follow the rows: the workgroups that are resident at once, CUs x
+// min(what the runtime says fits, NLS_WG_PER_CU), asked once per device and kernel, and never more than there are pairs of rows to
+// start on.
 constexpr int NLS_WG_PER_CU = 4;
 static int nls_resident(const KernelEntry* e, int* cap) {
   struct Key { int dev; const void* fn; int cap; };
@@ -626,23 +627,31 @@ static int nls_resident(const KernelEntry* e, int* cap) {
   known.push_back(Key{dev, e->func, *cap});
   return 0;
 }
-// workgroups and waves (= groups of NLS_SLOTS doubles written to NlsArgs::part) of the launch over nrows rows
-int nls_launch_shape(int64_t n, int prec, int64_t nrows, int* ngroups, int64_t* waves) {
-  const KernelEntry* e = find_nlz(n, prec, Op::Moments);
-  if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused z-stage kernel with moments of length %lld", (long long)n);
+static_assert(NLI_MAXSEP == MFFT_INCR_MAXSEP && NLI_FIELD == INCR_FIELD && NLI_SLOTS == INCR_SLOTS, "one number of separations per launch");
+static int find_nlr(Op kind, int64_t n, int prec, const KernelEntry** e) {
+  const NlProduct& q = nl_product(kind);
+  *e = q.op == kind && q.nout == 0 ? find_nlz(n, prec, kind) : nullptr;
+  if (!*e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused z-stage kernel with %s of length %lld", q.name, (long long)n);
+  return 0;
+}
+// The arithmetic is nlr_shape.h's; only the resident workgroups come from the runtime.
+int nlr_launch_shape(Op kind, int64_t n, int prec, int64_t nrows, NlrShape* shape) {
+  const KernelEntry* e = nullptr;
+  MFFT_TRY(find_nlr(kind, n, prec, &e));
   if (nrows < 1) return set_error(MFFT_ERR_INVALID, "no rows");
   void* tw = nullptr;
   MFFT_TRY(prepare_kernel(e, &tw));                // (the LDS attribute is set before the occupancy is asked for)
   int cap = 0;
   MFFT_TRY(nls_resident(e, &cap));
-  const int64_t units = (nrows + 2 * e->tile - 1) / (2 * e->tile);
-  *ngroups = (int)std::min<int64_t>(units, cap);
-  *waves = (int64_t)*ngroups * ((e->threads + 63) / 64);
+  if (!nlr_shape(e->tile, e->threads, n, cap, nrows, nl_product(kind).counts, shape))
+    return set_error(MFFT_ERR_INTERNAL, "%s: one pass of a workgroup counts 2^32 values", e->name);
   return 0;
 }
-template <typename T>
-static int launch_nls_t(const KernelEntry* e, const NlsArgs& a, int ngroups, void* tw, hipStream_t s) {
-  NlsParams<T> P;
+// what the parameters of every reduction kernel share: the head (NlzParams<T>; out, scale and rt3 are not used) and the three
+// members each Nl?Params ends in
+template <typename T, template <typename> class PT>
+static PT<T> nlr_params(const NlrArgs& a, void* tw) {
+  PT<T> P;
   for (int f = 0; f < 3; ++f) {
     P.a[f] = static_cast<const cx<T>*>(f < a.npairs ? a.a[f] : nullptr);
     P.b[f] = static_cast<const cx<T>*>(f < a.npairs ? a.b[f] : nullptr);
@@ -656,292 +665,137 @@ static int launch_nls_t(const KernelEntry* e, const NlsArgs& a, int ngroups, voi
   P.valid = a.valid > 0 && a.valid < a.n / 2 + 1 ? a.valid : a.n / 2 + 1;
   P.valid_in = a.valid_in > 0 && a.valid_in < P.valid ? a.valid_in : P.valid;
   P.scale = (T)1;
-  P.part = static_cast<double*>(a.part);
-  for (int i = 0; i < 2 * NLS_PAIRS; ++i) P.center[i] = a.center[i];
   P.norm = a.norm;
   P.npairs = a.npairs;
-  P.ngroups = ngroups;
-  e->launch(&P, ngroups, s);
-  MFFT_HIP(hipGetLastError());
-  return 0;
+  P.ngroups = a.ngroups;
+  return P;
 }
-int launch_nls(const NlsArgs& a, hipStream_t s) {
-  const KernelEntry* e = find_nlz(a.n, a.prec, Op::Moments);
-  if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused z-stage kernel with moments of length %d", a.n);
+template <typename T>
+static int launch_nlr_t(const KernelEntry* e, const NlrArgs& a, void* tw, hipStream_t s) {
+  const NlrCall& c = a.call;
+  auto run = [&](const auto& P) {
+    e->launch(&P, a.ngroups, s);
+    MFFT_HIP(hipGetLastError());
+    return 0;
+  };
+  if (a.kind == Op::Moments) {
+    auto P = nlr_params<T, NlsParams>(a, tw);
+    P.part = static_cast<double*>(a.part);
+    for (int i = 0; i < 2 * NLS_PAIRS; ++i) P.center[i] = c.center[i];
+    return run(P);
+  }
+  if (a.kind == Op::Histogram) {
+    auto P = nlr_params<T, NlhParams>(a, tw);
+    P.part = static_cast<unsigned*>(a.part);
+    for (int i = 0; i < 2 * NLS_PAIRS; ++i) { P.lo[i] = c.lo[i]; P.inv[i] = c.inv[i]; }
+    P.nbins = c.nbins;
+    return run(P);
+  }
+  if (a.kind == Op::JointHistogram) {
+    auto P = nlr_params<T, NljParams>(a, tw);
+    P.part = static_cast<unsigned*>(a.part);
+    for (int i = 0; i < 2 * NLS_PAIRS; ++i) { P.lo[i] = c.lo[i]; P.inv[i] = c.inv[i]; }
+    P.nba = c.nba;
+    P.nbb = c.nbb;
+    return run(P);
+  }
+  if (a.kind == Op::Quadratic) {
+    auto P = nlr_params<T, NlqParams>(a, tw);
+    P.mpart = static_cast<double*>(a.part);
+    P.hpart = static_cast<unsigned*>(a.part2);
+    for (int i = 0; i < 2 * NLS_PAIRS; ++i) {        // (a slot without a field has weight 0)
+      const bool used = i / 2 < a.npairs && (i % 2 == 0 || a.b[i / 2]);
+      P.w[i] = used ? c.w[i] : 0.0;
+    }
+    P.center = c.center[0];
+    P.lo = c.lo[0];
+    P.inv = c.inv[0];
+    P.nbins = c.nbins;
+    return run(P);
+  }
+  auto P = nlr_params<T, NliParams>(a, tw);          // Op::Increments
+  P.part = static_cast<double*>(a.part);
+  for (int i = 0; i < NLI_MAXSEP; ++i) P.sep[i] = i < c.nsep ? c.sep[i] : 1;
+  P.nsep = c.nsep;
+  return run(P);
+}
+// Everything is checked before the launch: the common arguments, then the kind's own, then that no count can wrap.
+int launch_nlr(const NlrArgs& a, hipStream_t s) {
+  const KernelEntry* e = nullptr;
+  MFFT_TRY(find_nlr(a.kind, a.n, a.prec, &e));
+  const NlrCall& c = a.call;
   const int64_t units = (a.nrows + 2 * e->tile - 1) / (2 * e->tile);
   if (a.npairs < 1 || a.npairs > NLS_PAIRS || !a.part || a.nrows < 1 || a.ngroups < 1 || a.ngroups > units)
     return set_error(MFFT_ERR_INVALID, "bad argument");
   for (int p = 0; p < a.npairs; ++p)
     if (!a.a[p]) return set_error(MFFT_ERR_INVALID, "null argument");
-  void* tw = nullptr;
-  MFFT_TRY(prepare_kernel(e, &tw));
-  return by_prec(a.prec, [&](auto t) { return launch_nls_t<decltype(t)>(e, a, a.ngroups, tw, s); });
-}
-
-// The stage that ends in a histogram (fft_nlz.h body_hist, Op::Histogram): the grid of the moments stage, by the same query.  A
-// workgroup counts into unsigned slots, passes x 2 rows-per-workgroup x n values per field at the most: max_rows is what ONE launch
-// may take so that this stays below 2^32 (hist.hip hist_rows splits a longer run of rows; nothing wraps silently).
-int nlh_launch_shape(int64_t n, int prec, int64_t nrows, int* ngroups, int64_t* max_rows) {
-  const KernelEntry* e = find_nlz(n, prec, Op::Histogram);
-  if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused z-stage kernel with a histogram of length %lld", (long long)n);
-  if (nrows < 1) return set_error(MFFT_ERR_INVALID, "no rows");
-  void* tw = nullptr;
-  MFFT_TRY(prepare_kernel(e, &tw));                // (the LDS attribute is set before the occupancy is asked for)
-  int cap = 0;
-  MFFT_TRY(nls_resident(e, &cap));
-  const int64_t per_pass = 2 * (int64_t)e->tile * n;                   // values per field of one workgroup's pass
-  const int64_t passes = ((int64_t)1 << 32) / per_pass - 1;
-  if (passes < 1) return set_error(MFFT_ERR_INTERNAL, "%s: one pass of a workgroup counts 2^32 values", e->name);
-  *max_rows = passes * cap * 2 * e->tile;
-  const int64_t rows = std::min(nrows, *max_rows);
-  const int64_t units = (rows + 2 * e->tile - 1) / (2 * e->tile);
-  *ngroups = (int)std::min<int64_t>(units, cap);
-  return 0;
-}
-template <typename T>
-static int launch_nlh_t(const KernelEntry* e, const NlhArgs& a, void* tw, hipStream_t s) {
-  NlhParams<T> P;
-  for (int f = 0; f < 3; ++f) {
-    P.a[f] = static_cast<const cx<T>*>(f < a.npairs ? a.a[f] : nullptr);
-    P.b[f] = static_cast<const cx<T>*>(f < a.npairs ? a.b[f] : nullptr);
-    P.out[f] = nullptr;
+  auto range_ok = [&](int i) { return c.inv[i] > 0.0 && std::isfinite(c.inv[i]) && std::isfinite(c.lo[i]); };
+  if (a.kind == Op::Histogram || a.kind == Op::JointHistogram) {
+    const bool joint = a.kind == Op::JointHistogram;
+    if (joint ? c.nba < 1 || c.nba > NLJ_MAXBINS || c.nbb < 1 || c.nbb > NLJ_MAXBINS : c.nbins < 1 || c.nbins > NLH_MAXBINS)
+      return set_error(MFFT_ERR_INVALID, "bad argument");
+    for (int p = 0; p < a.npairs; ++p) {
+      if (joint && !a.b[p]) return set_error(MFFT_ERR_INVALID, "null argument: a joint histogram counts pairs of fields");
+      if (!range_ok(2 * p) || !range_ok(2 * p + 1)) return set_error(MFFT_ERR_INVALID, "bad histogram range");
+    }
+  } else if (a.kind == Op::Quadratic) {
+    if (!a.part2 || c.nbins < 0 || c.nbins > NLH_MAXBINS) return set_error(MFFT_ERR_INVALID, "bad argument");
+    for (int i = 0; i < 2 * a.npairs; ++i)
+      if (!std::isfinite(c.w[i])) return set_error(MFFT_ERR_INVALID, "a weight is not finite");
+    if (c.nbins > 0 && !range_ok(0)) return set_error(MFFT_ERR_INVALID, "bad histogram range");
+  } else if (a.kind == Op::Increments) {
+    if (c.nsep < 1 || c.nsep > NLI_MAXSEP) return set_error(MFFT_ERR_INVALID, "bad argument");
+    for (int i = 0; i < c.nsep; ++i)               // (the kernel reads the row's exchange buffer at (position + sep) mod n)
+      if (c.sep[i] < 1 || c.sep[i] >= a.n) return set_error(MFFT_ERR_INVALID, "separation %d outside 1 .. %d", c.sep[i], a.n - 1);
   }
-  P.tw = static_cast<const cx<T>*>(tw);
-  P.rt3 = nullptr;
-  P.in_stride = a.in_stride;
-  P.out_stride = 0;
-  P.nrows = a.nrows;
-  P.valid = a.valid > 0 && a.valid < a.n / 2 + 1 ? a.valid : a.n / 2 + 1;
-  P.valid_in = a.valid_in > 0 && a.valid_in < P.valid ? a.valid_in : P.valid;
-  P.scale = (T)1;
-  P.part = static_cast<unsigned*>(a.part);
-  for (int i = 0; i < 2 * NLS_PAIRS; ++i) { P.lo[i] = a.lo[i]; P.inv[i] = a.inv[i]; }
-  P.norm = a.norm;
-  P.nbins = a.nbins;
-  P.npairs = a.npairs;
-  P.ngroups = a.ngroups;
-  e->launch(&P, a.ngroups, s);
-  MFFT_HIP(hipGetLastError());
-  return 0;
-}
-int launch_nlh(const NlhArgs& a, hipStream_t s) {
-  const KernelEntry* e = find_nlz(a.n, a.prec, Op::Histogram);
-  if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused z-stage kernel with a histogram of length %d", a.n);
-  const int64_t units = (a.nrows + 2 * e->tile - 1) / (2 * e->tile);
-  if (a.npairs < 1 || a.npairs > NLS_PAIRS || !a.part || a.nrows < 1 || a.ngroups < 1 || a.ngroups > units || a.nbins < 1 || a.nbins > NLH_MAXBINS)
-    return set_error(MFFT_ERR_INVALID, "bad argument");
   // what one workgroup counts per field stays below 2^32: passes x 2 x rows per workgroup x n
-  const int64_t passes = (units + a.ngroups - 1) / a.ngroups;
-  if (passes * 2 * e->tile * (int64_t)a.n >= ((int64_t)1 << 32))
-    return set_error(MFFT_ERR_INVALID, "%lld rows in one histogram launch of %d workgroups: a count could wrap", (long long)a.nrows, a.ngroups);
-  for (int p = 0; p < a.npairs; ++p) {
-    if (!a.a[p]) return set_error(MFFT_ERR_INVALID, "null argument");
-    for (int i = 2 * p; i < 2 * p + 2; ++i)
-      if (!(a.inv[i] > 0.0) || !std::isfinite(a.inv[i]) || !std::isfinite(a.lo[i])) return set_error(MFFT_ERR_INVALID, "bad histogram range");
-  }
+  if (nl_product(a.kind).counts && nlr_counted(e->tile, a.n, a.nrows, a.ngroups) >= ((int64_t)1 << 32))
+    return set_error(MFFT_ERR_INVALID, "%lld rows in one %s launch of %d workgroups: a count could wrap", (long long)a.nrows,
+                     nl_product(a.kind).name, a.ngroups);
   void* tw = nullptr;
   MFFT_TRY(prepare_kernel(e, &tw));
-  return by_prec(a.prec, [&](auto t) { return launch_nlh_t<decltype(t)>(e, a, tw, s); });
+  return by_prec(a.prec, [&](auto t) { return launch_nlr_t<decltype(t)>(e, a, tw, s); });
 }
 
-// The stage that ends in a joint histogram (fft_nlz.h body_joint, Op::JointHistogram): the grid of the histogram stage by the same
-// query, and its limit -- a workgroup counts passes x 2 rows-per-workgroup x n points into unsigned cells, one cell could take
-// them all; max_rows is what ONE launch may take (joint.hip joint_rows splits a longer run of rows; nothing wraps silently).
-int nlj_launch_shape(int64_t n, int prec, int64_t nrows, int* ngroups, int64_t* max_rows) {
-  const KernelEntry* e = find_nlz(n, prec, Op::JointHistogram);
-  if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused z-stage kernel with a joint histogram of length %lld", (long long)n);
-  if (nrows < 1) return set_error(MFFT_ERR_INVALID, "no rows");
-  void* tw = nullptr;
-  MFFT_TRY(prepare_kernel(e, &tw));                // (the LDS attribute is set before the occupancy is asked for)
-  int cap = 0;
-  MFFT_TRY(nls_resident(e, &cap));
-  const int64_t per_pass = 2 * (int64_t)e->tile * n;                   // points of one workgroup's pass
-  const int64_t passes = ((int64_t)1 << 32) / per_pass - 1;
-  if (passes < 1) return set_error(MFFT_ERR_INTERNAL, "%s: one pass of a workgroup counts 2^32 points", e->name);
-  *max_rows = passes * cap * 2 * e->tile;
-  const int64_t rows = std::min(nrows, *max_rows);
-  const int64_t units = (rows + 2 * e->tile - 1) / (2 * e->tile);
-  *ngroups = (int)std::min<int64_t>(units, cap);
-  return 0;
+size_t nlr_part_bytes(const NlrArgs& z, const NlrShape& shape) {
+  if (z.kind == Op::Histogram) return hist_part_bytes(shape.ngroups, 2 * z.npairs, z.call.nbins);
+  if (z.kind == Op::JointHistogram) return joint_part_bytes(shape.ngroups, z.npairs, z.call.nba, z.call.nbb);
+  if (z.kind == Op::Quadratic) return quad_mpart_bytes(shape.waves) + quad_hpart_bytes(shape.ngroups, z.call.nbins);
+  return (size_t)shape.waves * (z.kind == Op::Increments ? INCR_SLOTS : NLS_SLOTS) * sizeof(double);
 }
-template <typename T>
-static int launch_nlj_t(const KernelEntry* e, const NljArgs& a, void* tw, hipStream_t s) {
-  NljParams<T> P;
-  for (int f = 0; f < 3; ++f) {
-    P.a[f] = static_cast<const cx<T>*>(f < a.npairs ? a.a[f] : nullptr);
-    P.b[f] = static_cast<const cx<T>*>(f < a.npairs ? a.b[f] : nullptr);
-    P.out[f] = nullptr;
+// The ONE loop over the rows of a batch.  The kinds that sum doubles have no limit on the rows of a launch: one launch, one fold.
+int nlr_rows(const NlrArgs& z0, void* acc, void* acc2, hipStream_t s) {
+  const size_t es = elem_bytes(z0.prec, true);
+  NlrShape all, shape;
+  MFFT_TRY(nlr_launch_shape(z0.kind, z0.n, z0.prec, z0.nrows, &all));      // (the shape `part` was sized by: the largest of the launches)
+  for (int64_t r0 = 0; r0 < z0.nrows;) {
+    MFFT_TRY(nlr_launch_shape(z0.kind, z0.n, z0.prec, z0.nrows - r0, &shape));
+    NlrArgs z = z0;
+    z.nrows = std::min(z0.nrows - r0, shape.max_rows);
+    z.ngroups = shape.ngroups;
+    if (z.kind == Op::Quadratic) z.part2 = static_cast<char*>(z0.part) + quad_mpart_bytes(all.waves);
+    for (int p = 0; p < z.npairs; ++p) {
+      if (z.a[p]) z.a[p] = static_cast<const char*>(z0.a[p]) + (size_t)(r0 * z0.in_stride) * es;
+      if (z.b[p]) z.b[p] = static_cast<const char*>(z0.b[p]) + (size_t)(r0 * z0.in_stride) * es;
+    }
+    MFFT_TRY(launch_nlr(z, s));
+    const size_t groups = (size_t)shape.ngroups, waves = (size_t)shape.waves;
+    const NlrCall& c = z.call;
+    if (z.kind == Op::Moments) {
+      MFFT_TRY(moments_fold(static_cast<const double*>(z.part), waves, NLS_SLOTS, static_cast<double*>(acc), s));
+    } else if (z.kind == Op::Histogram) {
+      MFFT_TRY(hist_fold(static_cast<const unsigned*>(z.part), groups, 2 * z.npairs, c.nbins, static_cast<int64_t*>(acc), s));
+    } else if (z.kind == Op::JointHistogram) {
+      MFFT_TRY(hist_fold_slots(static_cast<const unsigned*>(z.part), groups, z.npairs, joint_cells(c.nba, c.nbb), static_cast<int64_t*>(acc), s));
+    } else if (z.kind == Op::Quadratic) {
+      MFFT_TRY(moments_fold(static_cast<const double*>(z.part), waves, NLS_STATS, static_cast<double*>(acc), s));
+      if (c.nbins > 0) MFFT_TRY(hist_fold(static_cast<const unsigned*>(z.part2), groups, 1, c.nbins, static_cast<int64_t*>(acc2), s));
+    } else {
+      MFFT_TRY(incr_fold(static_cast<const double*>(z.part), waves, INCR_SLOTS, static_cast<double*>(acc), s));
+    }
+    r0 += z.nrows;
   }
-  P.tw = static_cast<const cx<T>*>(tw);
-  P.rt3 = nullptr;
-  P.in_stride = a.in_stride;
-  P.out_stride = 0;
-  P.nrows = a.nrows;
-  P.valid = a.valid > 0 && a.valid < a.n / 2 + 1 ? a.valid : a.n / 2 + 1;
-  P.valid_in = a.valid_in > 0 && a.valid_in < P.valid ? a.valid_in : P.valid;
-  P.scale = (T)1;
-  P.part = static_cast<unsigned*>(a.part);
-  for (int i = 0; i < 2 * NLS_PAIRS; ++i) { P.lo[i] = a.lo[i]; P.inv[i] = a.inv[i]; }
-  P.norm = a.norm;
-  P.nba = a.nba;
-  P.nbb = a.nbb;
-  P.npairs = a.npairs;
-  P.ngroups = a.ngroups;
-  e->launch(&P, a.ngroups, s);
-  MFFT_HIP(hipGetLastError());
   return 0;
-}
-int launch_nlj(const NljArgs& a, hipStream_t s) {
-  const KernelEntry* e = find_nlz(a.n, a.prec, Op::JointHistogram);
-  if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused z-stage kernel with a joint histogram of length %d", a.n);
-  const int64_t units = (a.nrows + 2 * e->tile - 1) / (2 * e->tile);
-  if (a.npairs < 1 || a.npairs > NLS_PAIRS || !a.part || a.nrows < 1 || a.ngroups < 1 || a.ngroups > units || a.nba < 1 || a.nba > NLJ_MAXBINS ||
-      a.nbb < 1 || a.nbb > NLJ_MAXBINS)
-    return set_error(MFFT_ERR_INVALID, "bad argument");
-  // what one workgroup counts stays below 2^32: passes x 2 x rows per workgroup x n
-  const int64_t passes = (units + a.ngroups - 1) / a.ngroups;
-  if (passes * 2 * e->tile * (int64_t)a.n >= ((int64_t)1 << 32))
-    return set_error(MFFT_ERR_INVALID, "%lld rows in one joint-histogram launch of %d workgroups: a count could wrap", (long long)a.nrows, a.ngroups);
-  for (int p = 0; p < a.npairs; ++p) {
-    if (!a.a[p] || !a.b[p]) return set_error(MFFT_ERR_INVALID, "null argument: a joint histogram counts pairs of fields");
-    for (int i = 2 * p; i < 2 * p + 2; ++i)
-      if (!(a.inv[i] > 0.0) || !std::isfinite(a.inv[i]) || !std::isfinite(a.lo[i])) return set_error(MFFT_ERR_INVALID, "bad histogram range");
-  }
-  void* tw = nullptr;
-  MFFT_TRY(prepare_kernel(e, &tw));
-  return by_prec(a.prec, [&](auto t) { return launch_nlj_t<decltype(t)>(e, a, tw, s); });
-}
-
-// The stage that ends in the statistics of a quadratic form (fft_nlz.h body_quad, Op::Quadratic): the grid of the moments stage by
-// the same query, the waves of nls_launch_shape (groups of NLS_STATS doubles in mpart) and the limit of nlh_launch_shape -- a
-// workgroup counts passes x 2 rows-per-workgroup x n values of q at the most, max_rows keeps that below 2^32.
-int nlq_launch_shape(int64_t n, int prec, int64_t nrows, int* ngroups, int64_t* waves, int64_t* max_rows) {
-  const KernelEntry* e = find_nlz(n, prec, Op::Quadratic);
-  if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused z-stage kernel with a quadratic form of length %lld", (long long)n);
-  if (nrows < 1) return set_error(MFFT_ERR_INVALID, "no rows");
-  void* tw = nullptr;
-  MFFT_TRY(prepare_kernel(e, &tw));                // (the LDS attribute is set before the occupancy is asked for)
-  int cap = 0;
-  MFFT_TRY(nls_resident(e, &cap));
-  const int64_t per_pass = 2 * (int64_t)e->tile * n;                   // values of one workgroup's pass
-  const int64_t passes = ((int64_t)1 << 32) / per_pass - 1;
-  if (passes < 1) return set_error(MFFT_ERR_INTERNAL, "%s: one pass of a workgroup counts 2^32 values", e->name);
-  *max_rows = passes * cap * 2 * e->tile;
-  const int64_t rows = std::min(nrows, *max_rows);
-  const int64_t units = (rows + 2 * e->tile - 1) / (2 * e->tile);
-  *ngroups = (int)std::min<int64_t>(units, cap);
-  *waves = (int64_t)*ngroups * ((e->threads + 63) / 64);
-  return 0;
-}
-template <typename T>
-static int launch_nlq_t(const KernelEntry* e, const NlqArgs& a, void* tw, hipStream_t s) {
-  NlqParams<T> P;
-  for (int f = 0; f < 3; ++f) {
-    P.a[f] = static_cast<const cx<T>*>(f < a.npairs ? a.a[f] : nullptr);
-    P.b[f] = static_cast<const cx<T>*>(f < a.npairs ? a.b[f] : nullptr);
-    P.out[f] = nullptr;
-  }
-  P.tw = static_cast<const cx<T>*>(tw);
-  P.rt3 = nullptr;
-  P.in_stride = a.in_stride;
-  P.out_stride = 0;
-  P.nrows = a.nrows;
-  P.valid = a.valid > 0 && a.valid < a.n / 2 + 1 ? a.valid : a.n / 2 + 1;
-  P.valid_in = a.valid_in > 0 && a.valid_in < P.valid ? a.valid_in : P.valid;
-  P.scale = (T)1;
-  P.mpart = static_cast<double*>(a.mpart);
-  P.hpart = static_cast<unsigned*>(a.hpart);
-  for (int i = 0; i < 2 * NLS_PAIRS; ++i) {        // (a slot without a field has weight 0)
-    const bool used = i / 2 < a.npairs && (i % 2 == 0 || a.b[i / 2]);
-    P.w[i] = used ? a.w[i] : 0.0;
-  }
-  P.center = a.center;
-  P.norm = a.norm;
-  P.lo = a.lo;
-  P.inv = a.inv;
-  P.nbins = a.nbins;
-  P.npairs = a.npairs;
-  P.ngroups = a.ngroups;
-  e->launch(&P, a.ngroups, s);
-  MFFT_HIP(hipGetLastError());
-  return 0;
-}
-int launch_nlq(const NlqArgs& a, hipStream_t s) {
-  const KernelEntry* e = find_nlz(a.n, a.prec, Op::Quadratic);
-  if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused z-stage kernel with a quadratic form of length %d", a.n);
-  const int64_t units = (a.nrows + 2 * e->tile - 1) / (2 * e->tile);
-  if (a.npairs < 1 || a.npairs > NLS_PAIRS || !a.mpart || !a.hpart || a.nrows < 1 || a.ngroups < 1 || a.ngroups > units || a.nbins < 0 ||
-      a.nbins > NLH_MAXBINS)
-    return set_error(MFFT_ERR_INVALID, "bad argument");
-  // what one workgroup counts stays below 2^32: passes x 2 x rows per workgroup x n
-  const int64_t passes = (units + a.ngroups - 1) / a.ngroups;
-  if (passes * 2 * e->tile * (int64_t)a.n >= ((int64_t)1 << 32))
-    return set_error(MFFT_ERR_INVALID, "%lld rows in one launch of %d workgroups: a count could wrap", (long long)a.nrows, a.ngroups);
-  for (int p = 0; p < a.npairs; ++p)
-    if (!a.a[p]) return set_error(MFFT_ERR_INVALID, "null argument");
-  for (int i = 0; i < 2 * a.npairs; ++i)
-    if (!std::isfinite(a.w[i])) return set_error(MFFT_ERR_INVALID, "a weight is not finite");
-  if (a.nbins > 0 && (!(a.inv > 0.0) || !std::isfinite(a.inv) || !std::isfinite(a.lo))) return set_error(MFFT_ERR_INVALID, "bad histogram range");
-  void* tw = nullptr;
-  MFFT_TRY(prepare_kernel(e, &tw));
-  return by_prec(a.prec, [&](auto t) { return launch_nlq_t<decltype(t)>(e, a, tw, s); });
-}
-
-// The stage that ends in structure functions (fft_nlz.h body_incr, Op::Increments): the grid of the moments stage by the same
-// query; waves = groups of NLI_SLOTS doubles written to NliArgs::part.  Sums of doubles: no count to keep below 2^32.
-static_assert(NLI_MAXSEP == MFFT_INCR_MAXSEP && NLI_FIELD == INCR_FIELD && NLI_SLOTS == INCR_SLOTS, "one number of separations per launch");
-int nli_launch_shape(int64_t n, int prec, int64_t nrows, int* ngroups, int64_t* waves) {
-  const KernelEntry* e = find_nlz(n, prec, Op::Increments);
-  if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused z-stage kernel with increments of length %lld", (long long)n);
-  if (nrows < 1) return set_error(MFFT_ERR_INVALID, "no rows");
-  void* tw = nullptr;
-  MFFT_TRY(prepare_kernel(e, &tw));                // (the LDS attribute is set before the occupancy is asked for)
-  int cap = 0;
-  MFFT_TRY(nls_resident(e, &cap));
-  const int64_t units = (nrows + 2 * e->tile - 1) / (2 * e->tile);
-  *ngroups = (int)std::min<int64_t>(units, cap);
-  *waves = (int64_t)*ngroups * ((e->threads + 63) / 64);
-  return 0;
-}
-template <typename T>
-static int launch_nli_t(const KernelEntry* e, const NliArgs& a, void* tw, hipStream_t s) {
-  NliParams<T> P;
-  for (int f = 0; f < 3; ++f) {
-    P.a[f] = static_cast<const cx<T>*>(f < a.npairs ? a.a[f] : nullptr);
-    P.b[f] = static_cast<const cx<T>*>(f < a.npairs ? a.b[f] : nullptr);
-    P.out[f] = nullptr;
-  }
-  P.tw = static_cast<const cx<T>*>(tw);
-  P.rt3 = nullptr;
-  P.in_stride = a.in_stride;
-  P.out_stride = 0;
-  P.nrows = a.nrows;
-  P.valid = a.valid > 0 && a.valid < a.n / 2 + 1 ? a.valid : a.n / 2 + 1;
-  P.valid_in = a.valid_in > 0 && a.valid_in < P.valid ? a.valid_in : P.valid;
-  P.scale = (T)1;
-  P.part = static_cast<double*>(a.part);
-  P.norm = a.norm;
-  for (int i = 0; i < NLI_MAXSEP; ++i) P.sep[i] = i < a.nsep ? a.sep[i] : 1;
-  P.nsep = a.nsep;
-  P.npairs = a.npairs;
-  P.ngroups = a.ngroups;
-  e->launch(&P, a.ngroups, s);
-  MFFT_HIP(hipGetLastError());
-  return 0;
-}
-int launch_nli(const NliArgs& a, hipStream_t s) {
-  const KernelEntry* e = find_nlz(a.n, a.prec, Op::Increments);
-  if (!e) return set_error(MFFT_ERR_UNSUPPORTED, "no fused z-stage kernel with increments of length %d", a.n);
-  const int64_t units = (a.nrows + 2 * e->tile - 1) / (2 * e->tile);
-  if (a.npairs < 1 || a.npairs > NLS_PAIRS || !a.part || a.nrows < 1 || a.ngroups < 1 || a.ngroups > units || a.nsep < 1 || a.nsep > NLI_MAXSEP)
-    return set_error(MFFT_ERR_INVALID, "bad argument");
-  for (int i = 0; i < a.nsep; ++i)                 // (the kernel reads the row's exchange buffer at (position + sep) mod n)
-    if (a.sep[i] < 1 || a.sep[i] >= a.n) return set_error(MFFT_ERR_INVALID, "separation %d outside 1 .. %d", a.sep[i], a.n - 1);
-  for (int p = 0; p < a.npairs; ++p)
-    if (!a.a[p]) return set_error(MFFT_ERR_INVALID, "null argument");
-  void* tw = nullptr;
-  MFFT_TRY(prepare_kernel(e, &tw));
-  return by_prec(a.prec, [&](auto t) { return launch_nli_t<decltype(t)>(e, a, tw, s); });
 }
 
 // ---------------------------------------------------------------------------

@@ -114,26 +114,6 @@ int hist_fold_slots(const unsigned* part, size_t groups, int nfields, int nslots
 
 size_t hist_part_bytes(int ngroups, int nslots, int nbins) { return (size_t)ngroups * (size_t)nslots * (size_t)(nbins + 3) * sizeof(unsigned); }
 
-int hist_rows(const NlhArgs& z0, int64_t* acc, hipStream_t s) {
-  const size_t es = z0.prec == MFFT_DOUBLE ? 16 : 8;
-  for (int64_t r0 = 0; r0 < z0.nrows;) {
-    int ngroups = 0;
-    int64_t max_rows = 0;
-    MFFT_TRY(nlh_launch_shape(z0.n, z0.prec, z0.nrows - r0, &ngroups, &max_rows));
-    NlhArgs z = z0;
-    z.nrows = std::min(z0.nrows - r0, max_rows);
-    z.ngroups = ngroups;
-    for (int p = 0; p < z.npairs; ++p) {
-      if (z.a[p]) z.a[p] = static_cast<const char*>(z0.a[p]) + (size_t)(r0 * z0.in_stride) * es;
-      if (z.b[p]) z.b[p] = static_cast<const char*>(z0.b[p]) + (size_t)(r0 * z0.in_stride) * es;
-    }
-    MFFT_TRY(launch_nlh(z, s));
-    MFFT_TRY(hist_fold(static_cast<const unsigned*>(z.part), (size_t)ngroups, 2 * z.npairs, z.nbins, acc, s));
-    r0 += z.nrows;
-  }
-  return 0;
-}
-
 }  // namespace mfft
 
 // acc[c][s] += counts of x[c, :], c < ncomp <= 6, on the plan's stream (acc: device int64 of the plan, rows nbins + 3 apart)
@@ -159,12 +139,12 @@ int mfft_plan_s::hist_sweep(const void* x, int ncomp, size_t n, const double* lo
 int mfft_plan_s::hist_begin(const double lo_slots[6], const double inv_slots[6], int nbins) {
   MFFT_TRY(ensure(nlhacc, (size_t)6 * NB3_MAX * sizeof(int64_t)));
   MFFT_HIP(hipMemsetAsync(nlhacc.p, 0, (size_t)6 * NB3_MAX * sizeof(int64_t), stream));
-  for (int i = 0; i < 6; ++i) { nlh_lo[i] = lo_slots[i]; nlh_inv[i] = inv_slots[i]; }
-  nlh_bins = nbins;
+  for (int i = 0; i < 6; ++i) { nlcall.lo[i] = lo_slots[i]; nlcall.inv[i] = inv_slots[i]; }
+  nlcall.nbins = nbins;
   return 0;
 }
 int mfft_plan_s::hist_end(int64_t* host, int nslots) {
-  MFFT_HIP(hipMemcpyAsync(host, nlhacc.p, (size_t)nslots * (nlh_bins + 3) * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+  MFFT_HIP(hipMemcpyAsync(host, nlhacc.p, (size_t)nslots * (nlcall.nbins + 3) * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
   MFFT_HIP(hipStreamSynchronize(stream));
   return 0;
 }

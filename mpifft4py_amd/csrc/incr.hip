@@ -100,8 +100,8 @@ int mfft_plan_s::incr_sweep(const void* x, int ncomp, int64_t nrows, int64_t n, 
   MFFT_TRY(ensure(nlm, waves * (size_t)ncomp * NLI_FIELD * sizeof(double)));
   double* part = static_cast<double*>(nlm.p);
   SepList L;
-  for (int i = 0; i < NLI_MAXSEP; ++i) L.sep[i] = i < nli_nsep ? nli_sep[i] : 1;
-  L.nsep = nli_nsep;
+  for (int i = 0; i < NLI_MAXSEP; ++i) L.sep[i] = i < nlcall.nsep ? nlcall.sep[i] : 1;
+  L.nsep = nlcall.nsep;
   if (prec == MFFT_DOUBLE)
     hipLaunchKernelGGL(incr_kernel<double>, dim3(grid, ncomp), dim3(IS_BLOCK), 0, stream, static_cast<const double*>(x), nrows, (int)n, pitch, ncomp, L, part);
   else
@@ -115,8 +115,8 @@ int mfft_plan_s::incr_sweep(const void* x, int ncomp, int64_t nrows, int64_t n, 
 int mfft_plan_s::incr_begin(const int64_t* seps, int nsep) {
   MFFT_TRY(ensure(nliacc, NLI_SLOTS * sizeof(double)));
   MFFT_HIP(hipMemsetAsync(nliacc.p, 0, NLI_SLOTS * sizeof(double), stream));
-  for (int i = 0; i < NLI_MAXSEP; ++i) nli_sep[i] = i < nsep ? (int)seps[i] : 1;
-  nli_nsep = nsep;
+  for (int i = 0; i < NLI_MAXSEP; ++i) nlcall.sep[i] = i < nsep ? (int)seps[i] : 1;
+  nlcall.nsep = nsep;
   return 0;
 }
 int mfft_plan_s::incr_end(double* host) {

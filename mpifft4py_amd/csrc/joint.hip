@@ -1,8 +1,8 @@
 // joint.hip -- joint histograms on the device: per PAIR of real fields (nba + 3)(nbb + 3) int64 counts,
 //     cell = sa * (nbb + 3) + sb,   sa = hist_slot(x_a, lo_a, inv_a, nba),   sb = hist_slot(x_b, lo_b, inv_b, nbb)
-// (fft_nlz.h hist_slot and joint_cell: the one rule of host, sweep, fused kernel and tests).  The launches of the fused z stage
-// that ends in a joint histogram (fft_nlz.h body_joint) with their fold, and the streaming sweep mfft_ew_joint_histogram over two
-// real arrays of equal length (the composed route of mfft_real_joint_histogram, and the caller's own arrays), the companion of
+// (fft_nlz.h hist_slot and joint_cell: the one rule of host, sweep, fused kernel and tests).  The plan's accumulator of the fused z
+// stage that ends in a joint histogram (fft_nlz.h body_joint; launches and fold: core.hip nlr_rows), and the streaming sweep
+// mfft_ew_joint_histogram over two real arrays of equal length (the composed route of mfft_real_joint_histogram, and the caller's own arrays), the companion of
 // mfft_ew_histogram.  No global atomics anywhere: a workgroup counts in ONE LDS grid (unsigned), stores it with plain stores, the
 // fold of hist.hip adds the workgroups' rows in a FIXED order into int64.  Counts are integers: the same bits run to run, device
 // to device and for every number of ranks.
@@ -86,26 +86,6 @@ size_t joint_part_bytes(int ngroups, int npairs, int nba, int nbb) {
   return (size_t)ngroups * (size_t)npairs * (size_t)joint_cells(nba, nbb) * sizeof(unsigned);
 }
 
-int joint_rows(const NljArgs& z0, int64_t* acc, hipStream_t s) {
-  const size_t es = z0.prec == MFFT_DOUBLE ? 16 : 8;
-  for (int64_t r0 = 0; r0 < z0.nrows;) {
-    int ngroups = 0;
-    int64_t max_rows = 0;
-    MFFT_TRY(nlj_launch_shape(z0.n, z0.prec, z0.nrows - r0, &ngroups, &max_rows));
-    NljArgs z = z0;
-    z.nrows = std::min(z0.nrows - r0, max_rows);
-    z.ngroups = ngroups;
-    for (int p = 0; p < z.npairs; ++p) {
-      if (z.a[p]) z.a[p] = static_cast<const char*>(z0.a[p]) + (size_t)(r0 * z0.in_stride) * es;
-      if (z.b[p]) z.b[p] = static_cast<const char*>(z0.b[p]) + (size_t)(r0 * z0.in_stride) * es;
-    }
-    MFFT_TRY(launch_nlj(z, s));
-    MFFT_TRY(hist_fold_slots(static_cast<const unsigned*>(z.part), (size_t)ngroups, z.npairs, joint_cells(z.nba, z.nbb), acc, s));
-    r0 += z.nrows;
-  }
-  return 0;
-}
-
 }  // namespace mfft
 
 // acc[cell] += counts of the pairs (x[i], y[i]), i < n, on the plan's stream (acc: device int64 of the plan, one pair's cells)
@@ -138,13 +118,13 @@ int mfft_plan_s::joint_begin(const double lo_slots[6], const double inv_slots[6]
   if (nba < 1 || nba > NLJ_MAXBINS || nbb < 1 || nbb > NLJ_MAXBINS) return set_error(MFFT_ERR_INVALID, "bins outside 1 .. %d", NLJ_MAXBINS);
   MFFT_TRY(ensure(nljacc, (size_t)3 * NLJ_MAXCELLS * sizeof(int64_t)));
   MFFT_HIP(hipMemsetAsync(nljacc.p, 0, (size_t)3 * NLJ_MAXCELLS * sizeof(int64_t), stream));
-  for (int i = 0; i < 6; ++i) { nlj_lo[i] = lo_slots[i]; nlj_inv[i] = inv_slots[i]; }
-  nlj_nba = nba;
-  nlj_nbb = nbb;
+  for (int i = 0; i < 6; ++i) { nlcall.lo[i] = lo_slots[i]; nlcall.inv[i] = inv_slots[i]; }
+  nlcall.nba = nba;
+  nlcall.nbb = nbb;
   return 0;
 }
 int mfft_plan_s::joint_end(int64_t* host, int npairs) {
-  MFFT_HIP(hipMemcpyAsync(host, nljacc.p, (size_t)npairs * joint_cells(nlj_nba, nlj_nbb) * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+  MFFT_HIP(hipMemcpyAsync(host, nljacc.p, (size_t)npairs * joint_cells(nlcall.nba, nlcall.nbb) * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
   MFFT_HIP(hipStreamSynchronize(stream));
   return 0;
 }

@@ -6,6 +6,7 @@
 #include <vector>
 #include "../../include/mpifft4py_amd.h"
 #include "registry.h"
+#include "nlr_shape.h"
 
 namespace mfft {
 
@@ -146,29 +147,69 @@ struct NlProduct {
   int nin, nout;         // fields in (a, b, then c), rows / components out (out, then the scalar one)
   bool absmax;           // a Build::AbsMax kernel family exists (the call with real-space maxima)
   bool nlz3;             // Build::Nlz3, the pruned 3/2-rule kernel, may stand in
+  bool counts = false;   // a reduction whose workgroups count into unsigned slots: one launch stays below 2^32 values (nlr_shape.h)
 };
 constexpr NlProduct NL_PRODUCTS[] = {
     {Op::Plain, "cross", 6, 3, true, true},
     {Op::Dot, "dot", 6, 1, true, false},
     {Op::CrossDot, "cross_dot", 9, 4, false, false},
     {Op::Outer, "outer", 6, 9, false, false},
-    {Op::Moments, "moments", 6, 0, false, false},      // (up to six fields: the call says how many, NlFields::nfields)
-    {Op::Histogram, "histogram", 6, 0, false, false},
-    {Op::Quadratic, "quadratic", 6, 0, false, false},
+    // nout == 0: the reductions (NlrArgs below).  Up to six fields: the call says how many, NlFields::nfields
+    {Op::Moments, "moments", 6, 0, false, false},
+    {Op::Histogram, "histogram", 6, 0, false, false, true},
+    {Op::Quadratic, "quadratic", 6, 0, false, false, true},
     {Op::Increments, "increments", 6, 0, false, false},
-    {Op::JointHistogram, "joint", 6, 0, false, false},       // (one or three PAIRS of fields: a_p with b_p)
+    {Op::JointHistogram, "joint", 6, 0, false, false, true},       // (one or three PAIRS of fields: a_p with b_p)
 };
 inline const NlProduct& nl_product(Op op) {
   for (const NlProduct& q : NL_PRODUCTS)
     if (q.op == op) return q;
   return NL_PRODUCTS[0];
 }
+// The caller's arrays of one nonlinear operation (plan_nonlinear.hip): vector fields a, b and -- where the product has one -- c
+// in, the result out (three components, the ONE of the dot product, or the NINE of the outer product) and, of the product with
+// both, the scalar result outs.
+// An operation whose number of fields belongs to the call (the reductions): nfields of them, ncomp components of a, then of b.
+struct NlFields {
+  const void *a, *b, *c;
+  void *out, *outs;
+  int ncomp = 3;               // components per field
+  int nfields = 0;             // 0: what the table of products says (NlProduct::nin)
+  int nres = 3;                // components `out` holds (nine: the outer product); results beyond them are outs
+  int nin(const NlProduct& q) const { return nfields > 0 ? nfields : q.nin; }
+  // component f of the inputs (a, b, then c) / of the results (out, then outs), C elements of es bytes per component
+  const void* src(int f, int64_t C, size_t es) const {
+    return static_cast<const char*>(f < ncomp ? a : f < 2 * ncomp ? b : c) + (size_t)((f % ncomp) * C) * es;
+  }
+  void* dst(int f, int64_t C, size_t es) const { return f < nres ? static_cast<char*>(out) + (size_t)(f * C) * es : outs; }
+};
+// Where field f of a reduction (ncomp components of a, then of b) rides: slot 2 p is the first half of pair p, 2 p + 1 the
+// second.  With two fields a_f and b_f share a transform, as in the products; with one the components pair up among themselves.
+// THE slot rule: the plan's routes, the stage-level entry points and the un-slotting of every result call this.
+inline int nls_slot(const NlFields& u, int f) {
+  const int ncomp = u.ncomp;
+  return u.b ? (f < ncomp ? 2 * f : 2 * (f - ncomp) + 1) : f;
+}
 bool nlz_supported(int64_t n, int prec, Op product = Op::Plain, bool absmax = false);
 int64_t nlz_absmax_waves(int64_t n, int prec, Op product, int64_t nrows);
 int launch_nlz(const NlzArgs& a, hipStream_t s);
-// The z stage that ends in a reduction (fft_nlz.h body_moments): pair p is the rows a[p] + i b[p] (b[p] may be null), p < npairs
-// <= 3; [min, max, S1 .. S4] of the 2 npairs real fields, x = norm * (the un-normalised inverse transform), S_p about center[].
-struct NlsArgs {
+// The z stages that end in a REDUCTION instead of a product (the table entries with nout == 0; fft_nlz.h body_moments, body_hist,
+// body_joint, body_quad, body_incr), described ONCE: the launch, its shape, the loop over the rows and the routes of the plan read
+// NlrArgs.  Pair p is the rows a[p] + i b[p] on one complex transform, p < npairs <= 3; b[p] may be null (an odd field count) except
+// in a joint histogram.  x = norm * (the un-normalised inverse transform).  Slots are [pair][a, b].
+// What a call of one kind adds to that -- the plan parks it between a call's begin and its batches (mfft_plan_s::nlcall):
+struct NlrCall {
+  double center[6] = {0, 0, 0, 0, 0, 0};   // Moments: S_p about center[slot]; Quadratic: about center[0]
+  double lo[6] = {0, 0, 0, 0, 0, 0}, inv[6] = {1, 1, 1, 1, 1, 1};   // Histogram, JointHistogram: lower edge and bins / (hi - lo) per
+                                                                    // slot; Quadratic: lo[0], inv[0] of q
+  double w[6] = {0, 0, 0, 0, 0, 0};        // Quadratic: q = sum over the slots of w[slot] x^2
+  int nbins = 0;                           // Histogram: 1 .. NLH_MAXBINS; Quadratic: 0 .. NLH_MAXBINS, 0: no histogram
+  int nba = 0, nbb = 0;                    // JointHistogram: 1 .. MFFT_JOINT_MAXBINS bins of the a fields / of the b fields
+  int sep[MFFT_INCR_MAXSEP] = {0};         // Increments: 1 <= sep[i] < n, i < nsep
+  int nsep = 0;                            // 1 .. MFFT_INCR_MAXSEP
+};
+struct NlrArgs {
+  Op kind = Op::Moments;
   const void* a[3] = {nullptr, nullptr, nullptr};
   const void* b[3] = {nullptr, nullptr, nullptr};
   int npairs = 0;
@@ -178,128 +219,47 @@ struct NlsArgs {
   int valid = 0;         // bins per row present in memory (0 = all n/2+1)
   int valid_in = 0;      // bins per row that are read, where fewer (pruned 2/3-rule); 0 = valid
   double norm = 1.0;
-  double center[6] = {0, 0, 0, 0, 0, 0};   // [pair][a, b]
-  int ngroups = 0;       // workgroups of the launch, from nls_launch_shape() of (n, prec, nrows): the caller asks once and sizes `part` by it
-  void* part = nullptr;  // `waves` of nls_launch_shape() groups of 36 doubles, [wave][pair][a, b][statistic]: moments_fold adds them up
+  int ngroups = 0;       // workgroups of the launch, from nlr_launch_shape(): nlr_rows sets it
+  void* part = nullptr;  // the launch's partial results, nlr_part_bytes() of the shape of all rows: per wave NLS_SLOTS (Moments),
+                         // INCR_SLOTS (Increments), NLS_STATS (Quadratic) doubles; per workgroup the unsigned counts (npairs, 2, nbins
+                         // + 3) (Histogram), (npairs, cells) (JointHistogram)
+  void* part2 = nullptr; // Quadratic: per workgroup nbins + 3 unsigned counts of q, behind the doubles; nlr_rows sets it
+  NlrCall call;
 };
-int nls_launch_shape(int64_t n, int prec, int64_t nrows, int* ngroups, int64_t* waves);
-int launch_nls(const NlsArgs& a, hipStream_t s);
+// {workgroups, waves, rows one launch may take} of the launch over nrows rows (nlr_shape.h; the resident workgroups from the runtime)
+int nlr_launch_shape(Op kind, int64_t n, int prec, int64_t nrows, NlrShape* shape);
+int launch_nlr(const NlrArgs& a, hipStream_t s);
+// bytes of `part` for a launch of that shape
+size_t nlr_part_bytes(const NlrArgs& z, const NlrShape& shape);
+// All rows of z (ngroups, part2 not set): launches of at most max_rows rows, each folded into acc with the kind's fold below --
+// statistics and counts accumulate over launches, batches and calls.  acc2: the int64 counts of a Quadratic call.
+int nlr_rows(const NlrArgs& z, void* acc, void* acc2, hipStream_t s);
 // Statistics [min, max, S1 .. S4] per slot (moments.hip).  acc: device doubles, nvals = 6 * slots of them.  moments_clear: the
 // identity (+Inf, -Inf, zeros); moments_fold: acc[v] = merge(acc[v], the groups' part[g * nvals + v] in a fixed order), NaNs kept.
 int moments_clear(double* acc, int nvals, hipStream_t s);
 int moments_fold(const double* part, size_t groups, int nvals, double* acc, hipStream_t s);
-// The z stage that ends in a histogram (fft_nlz.h body_hist): pairs as in NlsArgs; per field nbins + 3 counts of x = norm * (the
-// un-normalised inverse transform) -- below lo, the nbins bins of [lo, hi), at or above hi, not finite (fft_nlz.h hist_slot).
-struct NlhArgs {
-  const void* a[3] = {nullptr, nullptr, nullptr};
-  const void* b[3] = {nullptr, nullptr, nullptr};
-  int npairs = 0;
-  int n = 0;             // REAL length of a z row
-  int prec = MFFT_DOUBLE;
-  int64_t in_stride = 0, nrows = 0;   // complex elements
-  int valid = 0;         // bins per row present in memory (0 = all n/2+1)
-  int valid_in = 0;      // bins per row that are read, where fewer (pruned 2/3-rule); 0 = valid
-  double norm = 1.0;
-  double lo[6] = {0, 0, 0, 0, 0, 0}, inv[6] = {1, 1, 1, 1, 1, 1};   // [pair][a, b]: lower edge, nbins / (hi - lo)
-  int nbins = 0;
-  int ngroups = 0;       // workgroups of the launch, from nlh_launch_shape() of (n, prec, nrows)
-  void* part = nullptr;  // (ngroups, npairs, 2, nbins + 3) unsigned counts: hist_fold adds them up
-};
-// workgroups of the launch over nrows rows, and the rows ONE launch may take so that no workgroup counts 2^32 values (the caller
-// splits a longer run of rows into launches of at most that many)
-int nlh_launch_shape(int64_t n, int prec, int64_t nrows, int* ngroups, int64_t* max_rows);
-int launch_nlh(const NlhArgs& a, hipStream_t s);
-// all rows of z (ngroups not set; part holds hist_part_bytes() of the shape's ngroups): launches of at most max_rows rows, each
-// folded into acc (slot order, rows nbins + 3 apart) -- counts accumulate over launches and calls
+// Histograms (hist.hip): per field nbins + 3 counts -- below lo, the nbins bins of [lo, hi), at or above hi, not finite (fft_nlz.h
+// hist_slot).  acc: device int64, (nfields, nbins + 3).  hist_fold: acc[f][s] += sum over the groups g, in fixed order, of
+// part[(g * nfields + f) * (nbins + 3) + s]; nfields <= 6.
 size_t hist_part_bytes(int ngroups, int nslots, int nbins);
-int hist_rows(const NlhArgs& z, int64_t* acc, hipStream_t s);
-// Histograms (hist.hip).  acc: device int64, (nfields, nbins + 3).  hist_fold: acc[f][s] += sum over the groups g, in fixed
-// order, of part[(g * nfields + f) * (nbins + 3) + s]; nfields <= 6.
 int hist_fold(const unsigned* part, size_t groups, int nfields, int nbins, int64_t* acc, hipStream_t s);
 // ... for rows of any length nslots (the grids of the joint histograms): part[(g * nfields + f) * nslots + s]
 int hist_fold_slots(const unsigned* part, size_t groups, int nfields, int nslots, int64_t* acc, hipStream_t s);
 // inv = nbins / (hi - lo) of a valid range; MFFT_ERR_INVALID for nbins outside 1 .. NLH_MAXBINS, hi <= lo, a range that is not finite
 int hist_range(double lo, double hi, int nbins, double* inv);
 int hist_max_bins();
-// The z stage that ends in a joint histogram (fft_nlz.h body_joint): pair p is the rows a[p] + i b[p], BOTH present; per pair
-// (nba + 3)(nbb + 3) counts, cell = slot of a_p * (nbb + 3) + slot of b_p (fft_nlz.h joint_cell).
-struct NljArgs {
-  const void* a[3] = {nullptr, nullptr, nullptr};
-  const void* b[3] = {nullptr, nullptr, nullptr};
-  int npairs = 0;
-  int n = 0;             // REAL length of a z row
-  int prec = MFFT_DOUBLE;
-  int64_t in_stride = 0, nrows = 0;   // complex elements
-  int valid = 0;         // bins per row present in memory (0 = all n/2+1)
-  int valid_in = 0;      // bins per row that are read, where fewer (pruned 2/3-rule); 0 = valid
-  double norm = 1.0;
-  double lo[6] = {0, 0, 0, 0, 0, 0}, inv[6] = {1, 1, 1, 1, 1, 1};   // [pair][a, b]: lower edge, nb / (hi - lo)
-  int nba = 0, nbb = 0;  // 1 .. MFFT_JOINT_MAXBINS
-  int ngroups = 0;       // workgroups of the launch, from nlj_launch_shape() of (n, prec, nrows)
-  void* part = nullptr;  // (ngroups, npairs, cells) unsigned counts: hist_fold_slots adds them up
-};
-// workgroups of the launch over nrows rows, and the rows ONE launch may take so that no workgroup counts 2^32 points
-int nlj_launch_shape(int64_t n, int prec, int64_t nrows, int* ngroups, int64_t* max_rows);
-int launch_nlj(const NljArgs& a, hipStream_t s);
-// all rows of z (ngroups not set; part holds joint_part_bytes() of the shape's ngroups): launches of at most max_rows rows, each
-// folded into acc (pairs joint_cells() apart) -- counts accumulate over launches and calls (joint.hip)
+// Joint histograms (joint.hip): per pair (nba + 3)(nbb + 3) counts, cell = slot of a_p * (nbb + 3) + slot of b_p (fft_nlz.h joint_cell)
 inline int joint_cells(int nba, int nbb) { return (nba + 3) * (nbb + 3); }
 size_t joint_part_bytes(int ngroups, int npairs, int nba, int nbb);
-int joint_rows(const NljArgs& z, int64_t* acc, hipStream_t s);
-// inv_a, inv_b of a valid pair of ranges; MFFT_ERR_INVALID for a bin count outside 1 .. MFFT_JOINT_MAXBINS, hi <= lo, a range
-// that is not finite
+// inv of a valid range; MFFT_ERR_INVALID for a bin count outside 1 .. MFFT_JOINT_MAXBINS, hi <= lo, a range that is not finite
 int joint_range(double lo, double hi, int nb, double* inv);
-// The z stage that ends in the statistics of a quadratic form (fft_nlz.h body_quad): pairs as in NlsArgs; q = sum over the slots
-// of w[slot] r^2, r = norm * (the un-normalised inverse transform); [min, max, S1 .. S4] of q about `center` and, nbins > 0, the
-// nbins + 3 counts of q over [lo, lo + nbins / inv).
-struct NlqArgs {
-  const void* a[3] = {nullptr, nullptr, nullptr};
-  const void* b[3] = {nullptr, nullptr, nullptr};
-  int npairs = 0;
-  int n = 0;             // REAL length of a z row
-  int prec = MFFT_DOUBLE;
-  int64_t in_stride = 0, nrows = 0;   // complex elements
-  int valid = 0;         // bins per row present in memory (0 = all n/2+1)
-  int valid_in = 0;      // bins per row that are read, where fewer (pruned 2/3-rule); 0 = valid
-  double norm = 1.0;
-  double w[6] = {0, 0, 0, 0, 0, 0};   // [pair][a, b]
-  double center = 0.0, lo = 0.0, inv = 1.0;
-  int nbins = 0;         // 0: no histogram
-  int ngroups = 0;       // workgroups of the launch, from nlq_launch_shape() of (n, prec, nrows)
-  void* mpart = nullptr; // `waves` of nlq_launch_shape() groups of 6 doubles: moments_fold adds them up
-  void* hpart = nullptr; // (ngroups, nbins + 3) unsigned counts: hist_fold adds them up
-};
-// workgroups and waves of the launch over nrows rows, and the rows ONE launch may take so that no workgroup counts 2^32 values
-int nlq_launch_shape(int64_t n, int prec, int64_t nrows, int* ngroups, int64_t* waves, int64_t* max_rows);
-int launch_nlq(const NlqArgs& a, hipStream_t s);
-// bytes of mpart and of hpart for a launch of that shape, mpart first (hpart starts quad_mpart_bytes() behind it)
+// Quadratic forms (quad.hip): bytes of the doubles and of the counts in `part`, the doubles first
 size_t quad_mpart_bytes(int64_t waves);
 size_t quad_hpart_bytes(int ngroups, int nbins);
-// all rows of z (ngroups, mpart, hpart not set; `part` holds quad_mpart_bytes() + quad_hpart_bytes() of the shape of all rows):
-// launches of at most max_rows rows, each folded into macc (6 doubles) and, nbins > 0, hacc (nbins + 3 int64)
-int quad_rows(const NlqArgs& z, void* part, double* macc, int64_t* hacc, hipStream_t s);
 // finite weights, 0 <= nbins <= NLH_MAXBINS, and with nbins > 0 a valid range (hist_range); *inv = 1 where nbins == 0
 int quad_check(const double* weights, int nfields, double lo, double hi, int nbins, double* inv);
-// The z stage that ends in structure functions (fft_nlz.h body_incr): pairs as in NlsArgs; per field and separation the sums
-// S2, S3, S4 of d = r(z + sep) - r(z) over all rows and positions, r = norm * (the un-normalised inverse transform), rows periodic.
-struct NliArgs {
-  const void* a[3] = {nullptr, nullptr, nullptr};
-  const void* b[3] = {nullptr, nullptr, nullptr};
-  int npairs = 0;
-  int n = 0;             // REAL length of a z row
-  int prec = MFFT_DOUBLE;
-  int64_t in_stride = 0, nrows = 0;   // complex elements
-  int valid = 0;         // bins per row present in memory (0 = all n/2+1)
-  int valid_in = 0;      // bins per row that are read, where fewer (pruned 2/3-rule); 0 = valid
-  double norm = 1.0;
-  int sep[MFFT_INCR_MAXSEP] = {0};    // 1 <= sep[i] < n, i < nsep
-  int nsep = 0;          // 1 .. MFFT_INCR_MAXSEP
-  int ngroups = 0;       // workgroups of the launch, from nli_launch_shape() of (n, prec, nrows)
-  void* part = nullptr;  // `waves` of nli_launch_shape() groups of INCR_SLOTS doubles, [wave][pair][a, b][separation][sum]
-};
-int nli_launch_shape(int64_t n, int prec, int64_t nrows, int* ngroups, int64_t* waves);
-int launch_nli(const NliArgs& a, hipStream_t s);
-// Sums of increment powers (incr.hip).  acc: device doubles, [slot][MFFT_INCR_MAXSEP][S2, S3, S4], six slots (fft_nlz.h NLI_SLOTS).
+// Sums of increment powers (incr.hip): per field and separation S2, S3, S4 of d = x(z + sep) - x(z), rows periodic.  acc: device
+// doubles, [slot][MFFT_INCR_MAXSEP][S2, S3, S4], six slots (fft_nlz.h NLI_SLOTS).
 // incr_fold: acc[v] += the groups' part[g * nvals + v] added in a fixed order, nvals = whole slots
 constexpr int INCR_FIELD = MFFT_INCR_MAXSEP * 3, INCR_SLOTS = 6 * INCR_FIELD;
 int incr_fold(const double* part, size_t groups, int nvals, double* acc, hipStream_t s);

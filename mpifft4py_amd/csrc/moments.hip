@@ -119,8 +119,8 @@ int mfft_plan_s::moments_begin(const double center_slots[6]) {
   MFFT_TRY(ensure(nlsacc, (NLS_SLOTS + 2 * NLS_PAIRS) * sizeof(double)));
   double* acc = static_cast<double*>(nlsacc.p);
   MFFT_TRY(moments_clear(acc, NLS_SLOTS, stream));
-  for (int i = 0; i < 2 * NLS_PAIRS; ++i) nls_center[i] = center_slots[i];      // (a member: the copy below is asynchronous)
-  MFFT_HIP(hipMemcpyAsync(acc + NLS_SLOTS, nls_center, sizeof nls_center, hipMemcpyHostToDevice, stream));
+  for (int i = 0; i < 2 * NLS_PAIRS; ++i) nlcall.center[i] = center_slots[i];      // (a member: the copy below is asynchronous)
+  MFFT_HIP(hipMemcpyAsync(acc + NLS_SLOTS, nlcall.center, sizeof nlcall.center, hipMemcpyHostToDevice, stream));
   return 0;
 }
 int mfft_plan_s::moments_end(double host[36]) {

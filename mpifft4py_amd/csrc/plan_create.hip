@@ -386,17 +386,24 @@ int mfft_plan_nonlinear_absmax(mfft_plan_t p, double out6[6]) {
   return p->nonlinear_absmax(out6);
 }
 
-// [min, max, S1 .. S4] of ifftn(field, dealias) for the ncomp components of a and, where given, of b: see include/mpifft4py_amd.h
-int mfft_real_moments(mfft_plan_t p, const void* a_hat, const void* b_hat, int ncomp, int dealias, const double* center, double* out,
-                      int64_t* count) {
-  if (!out || !count) return set_error(MFFT_ERR_INVALID, "null argument");
+// The five reductions: the plan on its device, a (and b, where given) of ncomp components, a known dealias mode -> the call's fields
+static int reduce_fields(mfft_plan_t p, const void* a_hat, const void* b_hat, int ncomp, int dealias, NlFields* u) {
   MFFT_TRY(check_ready(p, a_hat, a_hat));
   if (ncomp != 1 && ncomp != 3) return set_error(MFFT_ERR_INVALID, "ncomp must be 1 or 3, not %d", ncomp);
   if (dealias != MFFT_DEALIAS_NONE && dealias != MFFT_DEALIAS_2_3 && dealias != MFFT_DEALIAS_3_2)
     return set_error(MFFT_ERR_INVALID, "unknown dealias mode %d", dealias);
-  NlFields u{a_hat, b_hat, nullptr, nullptr, nullptr};
-  u.ncomp = ncomp;
-  u.nfields = b_hat ? 2 * ncomp : ncomp;
+  *u = NlFields{a_hat, b_hat, nullptr, nullptr, nullptr};
+  u->ncomp = ncomp;
+  u->nfields = b_hat ? 2 * ncomp : ncomp;
+  return 0;
+}
+
+// [min, max, S1 .. S4] of ifftn(field, dealias) for the ncomp components of a and, where given, of b: see include/mpifft4py_amd.h
+int mfft_real_moments(mfft_plan_t p, const void* a_hat, const void* b_hat, int ncomp, int dealias, const double* center, double* out,
+                      int64_t* count) {
+  if (!out || !count) return set_error(MFFT_ERR_INVALID, "null argument");
+  NlFields u;
+  MFFT_TRY(reduce_fields(p, a_hat, b_hat, ncomp, dealias, &u));
   return p->real_moments(u, dealias, center, out, count);
 }
 
@@ -405,13 +412,8 @@ int mfft_real_moments(mfft_plan_t p, const void* a_hat, const void* b_hat, int n
 int mfft_real_histogram(mfft_plan_t p, const void* a_hat, const void* b_hat, int ncomp, int dealias, const double* lo, const double* hi,
                         int nbins, int64_t* out, int64_t* count) {
   if (!out || !count || !lo || !hi) return set_error(MFFT_ERR_INVALID, "null argument");
-  MFFT_TRY(check_ready(p, a_hat, a_hat));
-  if (ncomp != 1 && ncomp != 3) return set_error(MFFT_ERR_INVALID, "ncomp must be 1 or 3, not %d", ncomp);
-  if (dealias != MFFT_DEALIAS_NONE && dealias != MFFT_DEALIAS_2_3 && dealias != MFFT_DEALIAS_3_2)
-    return set_error(MFFT_ERR_INVALID, "unknown dealias mode %d", dealias);
-  NlFields u{a_hat, b_hat, nullptr, nullptr, nullptr};
-  u.ncomp = ncomp;
-  u.nfields = b_hat ? 2 * ncomp : ncomp;
+  NlFields u;
+  MFFT_TRY(reduce_fields(p, a_hat, b_hat, ncomp, dealias, &u));
   return p->real_histogram(u, dealias, lo, hi, nbins, out, count);
 }
 
@@ -420,13 +422,8 @@ int mfft_real_histogram(mfft_plan_t p, const void* a_hat, const void* b_hat, int
 int mfft_real_quadratic(mfft_plan_t p, const void* a_hat, const void* b_hat, int ncomp, int dealias, const double* weights, double center,
                         double lo, double hi, int nbins, double* out6, int64_t* counts, int64_t* count) {
   if (!out6 || !count || !weights || (nbins > 0 && !counts)) return set_error(MFFT_ERR_INVALID, "null argument");
-  MFFT_TRY(check_ready(p, a_hat, a_hat));
-  if (ncomp != 1 && ncomp != 3) return set_error(MFFT_ERR_INVALID, "ncomp must be 1 or 3, not %d", ncomp);
-  if (dealias != MFFT_DEALIAS_NONE && dealias != MFFT_DEALIAS_2_3 && dealias != MFFT_DEALIAS_3_2)
-    return set_error(MFFT_ERR_INVALID, "unknown dealias mode %d", dealias);
-  NlFields u{a_hat, b_hat, nullptr, nullptr, nullptr};
-  u.ncomp = ncomp;
-  u.nfields = b_hat ? 2 * ncomp : ncomp;
+  NlFields u;
+  MFFT_TRY(reduce_fields(p, a_hat, b_hat, ncomp, dealias, &u));
   return p->real_quadratic(u, dealias, weights, center, lo, hi, nbins, out6, counts, count);
 }
 
@@ -435,13 +432,8 @@ int mfft_real_quadratic(mfft_plan_t p, const void* a_hat, const void* b_hat, int
 int mfft_real_increments(mfft_plan_t p, const void* a_hat, const void* b_hat, int ncomp, int dealias, const int64_t* seps, int nsep,
                          double* out, int64_t* count) {
   if (!out || !count || !seps) return set_error(MFFT_ERR_INVALID, "null argument");
-  MFFT_TRY(check_ready(p, a_hat, a_hat));
-  if (ncomp != 1 && ncomp != 3) return set_error(MFFT_ERR_INVALID, "ncomp must be 1 or 3, not %d", ncomp);
-  if (dealias != MFFT_DEALIAS_NONE && dealias != MFFT_DEALIAS_2_3 && dealias != MFFT_DEALIAS_3_2)
-    return set_error(MFFT_ERR_INVALID, "unknown dealias mode %d", dealias);
-  NlFields u{a_hat, b_hat, nullptr, nullptr, nullptr};
-  u.ncomp = ncomp;
-  u.nfields = b_hat ? 2 * ncomp : ncomp;
+  NlFields u;
+  MFFT_TRY(reduce_fields(p, a_hat, b_hat, ncomp, dealias, &u));
   return p->real_increments(u, dealias, seps, nsep, out, count);
 }
 
@@ -450,13 +442,8 @@ int mfft_real_joint_histogram(mfft_plan_t p, const void* a_hat, const void* b_ha
                               int nba, int nbb, int64_t* out, int64_t* count) {
   if (!out || !count || !lo || !hi) return set_error(MFFT_ERR_INVALID, "null argument");
   if (!b_hat) return set_error(MFFT_ERR_INVALID, "a joint histogram counts pairs of fields: b_hat must not be NULL");
-  MFFT_TRY(check_ready(p, a_hat, a_hat));
-  if (ncomp != 1 && ncomp != 3) return set_error(MFFT_ERR_INVALID, "ncomp must be 1 or 3, not %d", ncomp);
-  if (dealias != MFFT_DEALIAS_NONE && dealias != MFFT_DEALIAS_2_3 && dealias != MFFT_DEALIAS_3_2)
-    return set_error(MFFT_ERR_INVALID, "unknown dealias mode %d", dealias);
-  NlFields u{a_hat, b_hat, nullptr, nullptr, nullptr};
-  u.ncomp = ncomp;
-  u.nfields = 2 * ncomp;
+  NlFields u;
+  MFFT_TRY(reduce_fields(p, a_hat, b_hat, ncomp, dealias, &u));
   return p->real_joint_histogram(u, dealias, lo, hi, nba, nbb, out, count);
 }
 

@@ -74,24 +74,6 @@ struct Buf {                   // a device buffer of the plan that only grows (m
   size_t bytes = 0;
 };
 
-// The caller's arrays of one nonlinear operation (plan_nonlinear.hip): vector fields a, b and -- where the product has one -- c
-// in, the result out (three components, the ONE of the dot product, or the NINE of the outer product) and, of the product with
-// both, the scalar result outs.
-// An operation whose number of fields belongs to the call (Op::Moments): nfields of them, ncomp components of a, then of b.
-struct NlFields {
-  const void *a, *b, *c;
-  void *out, *outs;
-  int ncomp = 3;               // components per field
-  int nfields = 0;             // 0: what the table of products says (NlProduct::nin)
-  int nres = 3;                // components `out` holds (nine: the outer product); results beyond them are outs
-  int nin(const NlProduct& q) const { return nfields > 0 ? nfields : q.nin; }
-  // component f of the inputs (a, b, then c) / of the results (out, then outs), C elements of es bytes per component
-  const void* src(int f, int64_t C, size_t es) const {
-    return static_cast<const char*>(f < ncomp ? a : f < 2 * ncomp ? b : c) + (size_t)((f % ncomp) * C) * es;
-  }
-  void* dst(int f, int64_t C, size_t es) const { return f < nres ? static_cast<char*>(out) + (size_t)(f * C) * es : outs; }
-};
-
 // host-only part of plan construction: decomposition bookkeeping (no HIP call; plan_sched.hip)
 int decomp_init(mfft_plan_s* p, const mfft_plan_desc* desc, int nranks, int rank);
 
@@ -137,29 +119,23 @@ struct mfft_plan_s {
   Buf nlx{false, true}, nly{false, true}, nlr{false, true}, pcomp{false, true}, shl{false, false}, nlm{false, false}, nlmacc{false, false};
   // mfft_real_moments / mfft_ew_moments (moments.hip): 36 statistics in slot order, then the six centres; the partials go to nlm
   Buf nlsacc{false, false};
-  double nls_center[6] = {0, 0, 0, 0, 0, 0};
   // mfft_real_histogram / mfft_ew_histogram (hist.hip): 6 x (NLH_MAXBINS + 3) int64 counts in slot order, rows nbins + 3 apart,
-  // cleared on the stream when a call starts; the workgroups' partial histograms go to nlm.  The call's ranges, in slot order.
+  // cleared on the stream when a call starts; the workgroups' partial histograms go to nlm.
   Buf nlhacc{false, false};
   // mfft_real_joint_histogram / mfft_ew_joint_histogram (joint.hip): 3 x (MFFT_JOINT_MAXBINS + 3)^2 int64 counts, pairs cells apart,
-  // cleared on the stream when a call starts; the workgroups' partial grids go to nlm.  The call's ranges in slot order, and its
-  // bin counts.  nlr2: the SECOND real work array of the composed route (a_p in nlr, b_p here: two is the minimum for a pair).
+  // cleared on the stream when a call starts; the workgroups' partial grids go to nlm.
+  // nlr2: the SECOND real work array of the composed route (a_p in nlr, b_p here: two is the minimum for a pair).
   Buf nljacc{false, false};
   Buf nlr2{false, false};
-  double nlj_lo[6] = {0, 0, 0, 0, 0, 0}, nlj_inv[6] = {1, 1, 1, 1, 1, 1};
-  int nlj_nba = 0, nlj_nbb = 0;
-  double nlh_lo[6] = {0, 0, 0, 0, 0, 0}, nlh_inv[6] = {1, 1, 1, 1, 1, 1};
-  int nlh_bins = 0;
   // mfft_real_quadratic / mfft_ew_quadratic (quad.hip): the statistics of q in slot 0 of nlsacc, its counts in the first nbins + 3
-  // of nlhacc, the partials in nlm; nlq is the ONE array of doubles the composed route adds the fields' terms into.  The call's
-  // weights (slot order), centre and range.
+  // of nlhacc, the partials in nlm; nlq is the ONE array of doubles the composed route adds the fields' terms into.
   Buf nlq{false, false};
-  double nlq_w[6] = {0, 0, 0, 0, 0, 0}, nlq_center = 0.0, nlq_lo = 0.0, nlq_inv = 1.0;
-  int nlq_bins = 0;
   // mfft_real_increments / mfft_ew_increments (incr.hip): the sums in slot order, [slot][MFFT_INCR_MAXSEP][S2, S3, S4]; the partials
-  // go to nlm.  The call's separations.
+  // go to nlm.
   Buf nliacc{false, false};
-  int nli_sep[MFFT_INCR_MAXSEP] = {0}, nli_nsep = 0;
+  // The parameters of the reduction call that is running, in slot order (centres, ranges, weights, separations: whichever its kind
+  // has), parked by its *_begin for the batches of the fused routes and the sweeps of the composed one.
+  mfft::NlrCall nlcall;
   bool nlm_valid = false;       // a statistics call has run: nlmacc[0..5] hold max |ifftn(a_f)|, max |ifftn(b_f)| of this rank
   uint8_t* mask = nullptr;
   size_t mask_count = 0;
@@ -566,43 +542,40 @@ struct mfft_plan_s {
   int nonlinear_composed(const mfft::NlFields& u, int dealias, mfft::Op product, bool stats);
   int nonlinear_absmax(double out6[6]);                                   // this rank's maxima of the last statistics call
   int absmax_sweep(const void* x, int ncomp, size_t n, double* acc);      // absmax.hip
-  // One-point statistics of up to six fields given as spectra (plan_nonlinear.hip; the z stage fft_nlz.h body_moments on the
-  // fused routes, one inverse transform and one sweep per field on the composed one), and the sweep itself (moments.hip)
+  // The reductions (mfft::NL_PRODUCTS with nout == 0): statistics of ifftn(field, dealias) of up to six fields given as spectra, over
+  // this rank's part of the grid a product would be formed on.  ONE route (plan_nonlinear.hip): real_reduce is a call from its
+  // begin to its end -- the fused routes above with the z stage that ends in the kind's reduction, or reduce_composed, inverse
+  // transforms into a real work array and the kind's sweep; reduce_batch is that z stage on a batch of the fused routes.
+  template <class Begin, class End>
+  int real_reduce(const mfft::NlFields& u, int dealias, mfft::Op kind, int64_t* count, Begin begin, End end);
+  int reduce_composed(const mfft::NlFields& u, int dealias, mfft::Op kind);
+  int reduce_batch(mfft::Op kind, const mfft::NlFields& u, char* Y, size_t yelems, int64_t L2, int64_t Za, int64_t nrows, int valid_in);
+  // What a kind supplies: its entry, begin / end around its accumulator, and its sweep (moments.hip, hist.hip, joint.hip, quad.hip,
+  // incr.hip).  [min, max, S1 .. S4] per field:
   int real_moments(const mfft::NlFields& u, int dealias, const double* center, double* out, int64_t* count);
-  int moments_composed(const mfft::NlFields& u, int dealias);
   int moments_sweep(const void* x, int ncomp, size_t n, const double* center, double* acc);
   int moments_begin(const double center_slots[6]);
   int moments_end(double host[36]);
-  // Histograms of up to six fields given as spectra (plan_nonlinear.hip; the z stage fft_nlz.h body_hist on the fused routes, one
-  // inverse transform and one sweep per field on the composed one), and the sweep itself (hist.hip).  out: (nfields, nbins + 3)
+  // histograms, out: (nfields, nbins + 3)
   int real_histogram(const mfft::NlFields& u, int dealias, const double* lo, const double* hi, int nbins, int64_t* out, int64_t* count);
-  int hist_composed(const mfft::NlFields& u, int dealias);
   int hist_sweep(const void* x, int ncomp, size_t n, const double* lo, const double* inv, int nbins, int64_t* acc);
   int hist_begin(const double lo_slots[6], const double inv_slots[6], int nbins);
   int hist_end(int64_t* host, int nslots);
-  // Joint histograms of one or three pairs of fields given as spectra (plan_nonlinear.hip; the z stage fft_nlz.h body_joint on the
-  // fused routes; composed, two inverse transforms and one sweep per pair), and the sweep itself (joint.hip).
-  // out: (npairs, nba + 3, nbb + 3).  lo, hi: 2 ncomp entries, a_0.., then b_0..
+  // joint histograms of one or three pairs, out: (npairs, nba + 3, nbb + 3).  lo, hi: 2 ncomp entries, a_0.., then b_0..
   int real_joint_histogram(const mfft::NlFields& u, int dealias, const double* lo, const double* hi, int nba, int nbb, int64_t* out, int64_t* count);
-  int joint_composed(const mfft::NlFields& u, int dealias);
   int joint_sweep(const void* x, const void* y, size_t n, const double lo[2], const double inv[2], int nba, int nbb, int64_t* acc);
   int joint_begin(const double lo_slots[6], const double inv_slots[6], int nba, int nbb);
   int joint_end(int64_t* host, int npairs);
-  // Statistics of q = sum_f w_f ifftn(field f)^2 over up to six fields given as spectra (plan_nonlinear.hip; the z stage fft_nlz.h
-  // body_quad on the fused routes; composed: one inverse transform per field into ONE real work array, its term added into nlq,
-  // one sweep of nlq), and the sweeps themselves (quad.hip).  out6: [min, max, S1 .. S4]; counts: nbins + 3, may be null if nbins == 0
+  // q = sum_f w_f ifftn(field f)^2 (composed: each field's term added into nlq, one sweep of nlq).  out6: [min, max, S1 .. S4];
+  // counts: nbins + 3, may be null if nbins == 0
   int real_quadratic(const mfft::NlFields& u, int dealias, const double* weights, double center, double lo, double hi, int nbins, double* out6,
                      int64_t* counts, int64_t* count);
-  int quad_composed(const mfft::NlFields& u, int dealias, const double w_slots[6]);
   int quad_begin(double center, double lo, double inv, int nbins);
   int quad_end(double out6[6], int64_t* counts);
   int quad_sweep(const void* x, bool as_double, int ncomp, size_t stride, size_t n, const double* w, bool square);
   int quad_accum(const void* r, double* q, size_t n, double w, bool first);
-  // Structure functions along z of up to six fields given as spectra (plan_nonlinear.hip; the z stage fft_nlz.h body_incr on the
-  // fused routes, one inverse transform and one sweep per field on the composed one), and the sweep itself (incr.hip).
-  // out[(f * nsep + i) * 3 + {0, 1, 2}] = S2, S3, S4
+  // structure functions along z, out[(f * nsep + i) * 3 + {0, 1, 2}] = S2, S3, S4
   int real_increments(const mfft::NlFields& u, int dealias, const int64_t* seps, int nsep, double* out, int64_t* count);
-  int incr_composed(const mfft::NlFields& u, int dealias);
   int incr_sweep(const void* x, int ncomp, int64_t nrows, int64_t n, int64_t pitch, double* acc);
   int incr_begin(const int64_t* seps, int nsep);
   int incr_end(double* host);

@@ -20,8 +20,13 @@ extern "C" int mfft_ew_mul(mfft_plan_t plan, const void* a, const void* b, void*
 // The outer product, all nine a_i b_j (the Elsasser products of MHD, a stress u_i u_j): six fields in, NINE results -- the first
 // product with nout > nin, so the fused routes size their buffers and batches by max(nin, nout) fields: the z kernel writes results
 // 0..5 in place on the six inputs and 6..8 into three more fields of the batch, nine forward passes follow.
-// The routes read nin and nout from the table of products (mfft_internal.h NlProduct) and the caller's arrays through NlFields
-// (plan_impl.h); only the composed route, which chooses the element-wise products, names a product.
+// The routes read nin and nout from the table of products (mfft_internal.h NlProduct) and the caller's arrays through NlFields;
+// only the composed route, which chooses the element-wise products, names a product.
+// The REDUCTIONS are the table's entries with nout == 0 (moments, histograms, quadratic forms, increments, joint histograms): the
+// fused routes run their inverse passes and end the z stage in reduce_batch -- nothing forward is launched -- and a call is
+// real_reduce: mask, begin, fused or reduce_composed, end.  What a new kind supplies: its row of NL_PRODUCTS and its kernels'
+// registration; its members of NlrCall with their copy and checks in launch_nlr, its partials' size and its fold (core.hip); its
+// sweep over a real array for reduce_composed; *_begin / *_end around its accumulator; its real_* entry.
 
 int64_t mfft_plan_s::local_real_count(bool padded) const {
   if (d.line2d) return 0;
@@ -115,118 +120,27 @@ static int nlz_rows(mfft_plan_s* p, char* Y, size_t yelems, int64_t L2, int64_t 
   return 0;
 }
 
-// Where field f of a moments call (ncomp components of a, then of b) rides: slot 2 p is the first half of pair p, 2 p + 1 the
-// second.  With two fields a_f and b_f share a transform, as in the products; with one the components pair up among themselves.
-static int nls_slot(const NlFields& u, int f) { return u.b ? (f < u.ncomp ? 2 * f : 2 * (f - u.ncomp) + 1) : f; }
-
-// the z stage that ends in a reduction, on a batch: rows of the call's fields in Y (yelems apart, pitch Za) in, the partial
-// statistics of the launch's waves into nlm, folded into the plan's accumulator (moments_begin) after the launch: the statistics
-// accumulate over the batches.  The inverse z transform is un-normalised: norm = 1 / L2.
-static int nls_rows(mfft_plan_s* p, const NlFields& u, char* Y, size_t yelems, int64_t L2, int64_t Za, int64_t nrows, int valid_in) {
-  NlsArgs z;
-  int ngroups = 0;
-  int64_t waves = 0;
-  MFFT_TRY(nls_launch_shape(L2, p->prec, nrows, &ngroups, &waves));
-  MFFT_TRY(p->ensure(p->nlm, (size_t)waves * NLS_SLOTS * sizeof(double)));
+// The z stage that ends in a reduction, on a batch: rows of the call's fields in Y (yelems apart, pitch Za) in, bound to their
+// slots; the call's parameters from nlcall; the partial results of each launch into nlm, folded into the kind's accumulator (its
+// *_begin cleared it) after the launch, so that the statistics accumulate over the batches (core.hip nlr_rows).  The inverse z
+// transform is un-normalised: norm = 1 / L2.
+int mfft_plan_s::reduce_batch(Op kind, const NlFields& u, char* Y, size_t yelems, int64_t L2, int64_t Za, int64_t nrows, int valid_in) {
+  NlrArgs z;
+  z.kind = kind;
+  z.call = nlcall;
   for (int f = 0; f < u.nfields; ++f) {
     const int slot = nls_slot(u, f);
-    (slot % 2 ? z.b : z.a)[slot / 2] = Y + (size_t)f * yelems * p->es;
-    z.center[slot] = p->nls_center[slot];
+    (slot % 2 ? z.b : z.a)[slot / 2] = Y + (size_t)f * yelems * es;
   }
   z.npairs = (u.nfields + 1) / 2;
-  z.n = (int)L2; z.prec = p->prec; z.in_stride = Za; z.nrows = nrows; z.valid = (int)p->Nf; z.valid_in = valid_in;
+  z.n = (int)L2; z.prec = prec; z.in_stride = Za; z.nrows = nrows; z.valid = (int)Nf; z.valid_in = valid_in;
   z.norm = 1.0 / (double)L2;
-  z.ngroups = ngroups;
-  z.part = p->nlm.p;
-  MFFT_TRY(launch_nls(z, p->stream));
-  return moments_fold(static_cast<const double*>(z.part), (size_t)waves, NLS_SLOTS, static_cast<double*>(p->nlsacc.p), p->stream);
-}
-
-// the z stage that ends in a histogram, on a batch: rows of the call's fields in Y in, the workgroups' partial histograms into nlm,
-// folded into the plan's int64 accumulator (hist_begin) after each launch: the counts accumulate over the batches.
-static int nlh_rows(mfft_plan_s* p, const NlFields& u, char* Y, size_t yelems, int64_t L2, int64_t Za, int64_t nrows, int valid_in) {
-  NlhArgs z;
-  int ngroups = 0;
-  int64_t max_rows = 0;
-  MFFT_TRY(nlh_launch_shape(L2, p->prec, nrows, &ngroups, &max_rows));
-  z.npairs = (u.nfields + 1) / 2;
-  z.nbins = p->nlh_bins;
-  MFFT_TRY(p->ensure(p->nlm, hist_part_bytes(ngroups, 2 * z.npairs, z.nbins)));
-  for (int f = 0; f < u.nfields; ++f) {
-    const int slot = nls_slot(u, f);
-    (slot % 2 ? z.b : z.a)[slot / 2] = Y + (size_t)f * yelems * p->es;
-  }
-  for (int i = 0; i < 6; ++i) { z.lo[i] = p->nlh_lo[i]; z.inv[i] = p->nlh_inv[i]; }
-  z.n = (int)L2; z.prec = p->prec; z.in_stride = Za; z.nrows = nrows; z.valid = (int)p->Nf; z.valid_in = valid_in;
-  z.norm = 1.0 / (double)L2;
-  z.part = p->nlm.p;
-  return hist_rows(z, static_cast<int64_t*>(p->nlhacc.p), p->stream);
-}
-
-// the z stage that ends in a joint histogram, on a batch: rows of the call's pairs in Y in, the workgroups' partial grids into nlm,
-// folded into the plan's int64 accumulator (joint_begin) after each launch: the counts accumulate over the batches.
-static int nlj_rows(mfft_plan_s* p, const NlFields& u, char* Y, size_t yelems, int64_t L2, int64_t Za, int64_t nrows, int valid_in) {
-  NljArgs z;
-  int ngroups = 0;
-  int64_t max_rows = 0;
-  MFFT_TRY(nlj_launch_shape(L2, p->prec, nrows, &ngroups, &max_rows));
-  z.npairs = u.nfields / 2;
-  z.nba = p->nlj_nba; z.nbb = p->nlj_nbb;
-  MFFT_TRY(p->ensure(p->nlm, joint_part_bytes(ngroups, z.npairs, z.nba, z.nbb)));
-  for (int f = 0; f < u.nfields; ++f) {
-    const int slot = nls_slot(u, f);
-    (slot % 2 ? z.b : z.a)[slot / 2] = Y + (size_t)f * yelems * p->es;
-  }
-  for (int i = 0; i < 6; ++i) { z.lo[i] = p->nlj_lo[i]; z.inv[i] = p->nlj_inv[i]; }
-  z.n = (int)L2; z.prec = p->prec; z.in_stride = Za; z.nrows = nrows; z.valid = (int)p->Nf; z.valid_in = valid_in;
-  z.norm = 1.0 / (double)L2;
-  z.part = p->nlm.p;
-  return joint_rows(z, static_cast<int64_t*>(p->nljacc.p), p->stream);
-}
-
-// the z stage that ends in the statistics of a quadratic form, on a batch: rows of the call's fields in Y in, the waves' partial
-// statistics and the workgroups' partial histograms into nlm, folded into the plan's accumulators (quad_begin) after each launch:
-// both accumulate over the batches.
-static int nlq_rows(mfft_plan_s* p, const NlFields& u, char* Y, size_t yelems, int64_t L2, int64_t Za, int64_t nrows, int valid_in) {
-  NlqArgs z;
-  int ngroups = 0;
-  int64_t waves = 0, max_rows = 0;
-  MFFT_TRY(nlq_launch_shape(L2, p->prec, nrows, &ngroups, &waves, &max_rows));
-  z.npairs = (u.nfields + 1) / 2;
-  z.nbins = p->nlq_bins;
-  MFFT_TRY(p->ensure(p->nlm, quad_mpart_bytes(waves) + quad_hpart_bytes(ngroups, z.nbins)));
-  for (int f = 0; f < u.nfields; ++f) {
-    const int slot = nls_slot(u, f);
-    (slot % 2 ? z.b : z.a)[slot / 2] = Y + (size_t)f * yelems * p->es;
-  }
-  for (int i = 0; i < 6; ++i) z.w[i] = p->nlq_w[i];
-  z.center = p->nlq_center; z.lo = p->nlq_lo; z.inv = p->nlq_inv;
-  z.n = (int)L2; z.prec = p->prec; z.in_stride = Za; z.nrows = nrows; z.valid = (int)p->Nf; z.valid_in = valid_in;
-  z.norm = 1.0 / (double)L2;
-  return quad_rows(z, p->nlm.p, static_cast<double*>(p->nlsacc.p), static_cast<int64_t*>(p->nlhacc.p), p->stream);
-}
-
-// the z stage that ends in structure functions, on a batch: rows of the call's fields in Y in, the waves' partial sums into nlm,
-// folded into the plan's accumulator (incr_begin) after the launch: the sums accumulate over the batches.
-static int nli_rows(mfft_plan_s* p, const NlFields& u, char* Y, size_t yelems, int64_t L2, int64_t Za, int64_t nrows, int valid_in) {
-  NliArgs z;
-  int ngroups = 0;
-  int64_t waves = 0;
-  MFFT_TRY(nli_launch_shape(L2, p->prec, nrows, &ngroups, &waves));
-  MFFT_TRY(p->ensure(p->nlm, (size_t)waves * INCR_SLOTS * sizeof(double)));
-  for (int f = 0; f < u.nfields; ++f) {
-    const int slot = nls_slot(u, f);
-    (slot % 2 ? z.b : z.a)[slot / 2] = Y + (size_t)f * yelems * p->es;
-  }
-  z.npairs = (u.nfields + 1) / 2;
-  z.n = (int)L2; z.prec = p->prec; z.in_stride = Za; z.nrows = nrows; z.valid = (int)p->Nf; z.valid_in = valid_in;
-  z.norm = 1.0 / (double)L2;
-  for (int i = 0; i < MFFT_INCR_MAXSEP; ++i) z.sep[i] = p->nli_sep[i];
-  z.nsep = p->nli_nsep;
-  z.ngroups = ngroups;
-  z.part = p->nlm.p;
-  MFFT_TRY(launch_nli(z, p->stream));
-  return incr_fold(static_cast<const double*>(z.part), (size_t)waves, INCR_SLOTS, static_cast<double*>(p->nliacc.p), p->stream);
+  NlrShape shape;
+  MFFT_TRY(nlr_launch_shape(kind, L2, prec, nrows, &shape));
+  MFFT_TRY(ensure(nlm, nlr_part_bytes(z, shape)));
+  z.part = nlm.p;
+  Buf& acc = kind == Op::Histogram ? nlhacc : kind == Op::JointHistogram ? nljacc : kind == Op::Increments ? nliacc : nlsacc;
+  return nlr_rows(z, acc.p, nlhacc.p, stream);      // (the counts of a quadratic form: the second accumulator)
 }
 
 // Fused route: one rank, slab, real data, radix kernels on every axis.
@@ -335,11 +249,7 @@ int mfft_plan_s::nonlinear_fused(const NlFields& u, int dealias, Op product, boo
       return 0;
     }));
     MFFT_TRY(stage("nl_z", (nin * keep2 + nout) * Yb * frac, [&] {
-      if (product == Op::Moments) return nls_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0);
-      if (product == Op::Histogram) return nlh_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0);
-      if (product == Op::Quadratic) return nlq_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0);
-      if (product == Op::Increments) return nli_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0);
-      if (product == Op::JointHistogram) return nlj_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0);
+      if (nout == 0) return reduce_batch(product, u, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0);
       return nlz_rows(this, Yf(0), yelems, L2, Za, m * L1, pruned ? ba2 : 0, product, stats);
     }));
     if (nout) MFFT_TRY(stage("nl_y_fwd", nout * (Xb + Yb) * frac, [&] {
@@ -443,11 +353,7 @@ int mfft_plan_s::nonlinear_fused_ranks(const NlFields& u, int dealias, Op produc
       return 0;
     }));
     MFFT_TRY(stage("nl_z", 0, [&] {
-      if (product == Op::Moments) return nls_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0);
-      if (product == Op::Histogram) return nlh_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0);
-      if (product == Op::Quadratic) return nlq_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0);
-      if (product == Op::Increments) return nli_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0);
-      if (product == Op::JointHistogram) return nlj_rows(this, u, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0);
+      if (nout == 0) return reduce_batch(product, u, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0);
       return nlz_rows(this, Yf(0), yelems, L2, Za, m * L1, pruned ? (int)a2 : 0, product, stats);
     }));
     if (nout) MFFT_TRY(stage("nl_y_fwd", 0, [&] {      // truncate + fold in y, straight into the packed (P, Lp0, S) send layout
@@ -495,199 +401,144 @@ int mfft_plan_s::nonlinear_absmax(double out6[6]) {
   return 0;
 }
 
-// One-point statistics of the real-space fields of up to six spectra: [min, max, S1 .. S4] per field, S_p = sum (x - center)^p over
-// this rank's part of the grid a product would be formed on (the padded one under the 3/2-rule, the masked field under the
-// 2/3-rule), x = ifftn(field, dealias).  Fused routes: the inverse passes of the products and the z stage that ends in a reduction,
-// no real array.  Composed route (pencils, lengths without a kernel, MFFT_NO_NLZ): the statistics are per field, so ONE real work
-// array serves them in turn -- inverse transform, sweep (moments.hip), next field.  Synchronises the plan's stream.
-int mfft_plan_s::moments_composed(const NlFields& u, int dealias) {
-  const bool pad = dealias == MFFT_DEALIAS_3_2;
-  const int64_t nr = local_real_count(pad), nc = local_complex_alloc();
-  if (nr <= 0 || !r2c) return set_error(MFFT_ERR_UNSUPPORTED, "real_moments needs a 3-D real-to-complex plan");
-  MFFT_TRY(ensure(nlr, (size_t)nr * rs));
-  double* acc = static_cast<double*>(nlsacc.p);
-  for (int f = 0; f < u.nfields; ++f) {
-    const int slot = nls_slot(u, f);
-    MFFT_TRY(exec(false, u.src(f, nc, es), nlr.p, dealias));
-    MFFT_TRY(stage("nl_moments", (double)nr * rs, [&] { return moments_sweep(nlr.p, 1, (size_t)nr, acc + NLS_SLOTS + slot, acc + slot * NLS_STATS); }));
-  }
+// The reductions: statistics of x = ifftn(field, dealias) of up to six spectra over this rank's part of the grid a product would be
+// formed on (the padded one under the 3/2-rule, the masked field under the 2/3-rule).  A call is: its own arguments checked, the
+// mask, begin (the kind's accumulator cleared on the stream, the call's parameters parked in nlcall), the route, end (the
+// accumulator read back: this synchronises the plan's stream), the result taken out of slot order.  Everything is checked before
+// anything is enqueued; the inputs are preserved.  The route is the products': fused, their inverse passes and the z stage that ends
+// in the kind's reduction (reduce_batch above; no real array); composed (pencils, lengths without a kernel, MFFT_NO_NLZ), below.
+template <class Begin, class End>
+int mfft_plan_s::real_reduce(const NlFields& u, int dealias, Op kind, int64_t* count, Begin begin, End end) {
+  if (dealias == MFFT_DEALIAS_2_3) MFFT_TRY(require_mask());
+  MFFT_TRY(begin());
+  MFFT_TRY(nonlinear_fusable(dealias, kind, false)
+               ? (P == 1 ? nonlinear_fused(u, dealias, kind, false) : nonlinear_fused_ranks(u, dealias, kind, false))
+               : reduce_composed(u, dealias, kind));
+  MFFT_TRY(end());
+  *count = local_real_count(dealias == MFFT_DEALIAS_3_2);
   return 0;
 }
-int mfft_plan_s::real_moments(const NlFields& u, int dealias, const double* center, double* out, int64_t* count) {
-  if (dealias == MFFT_DEALIAS_2_3) MFFT_TRY(require_mask());
-  double c6[6] = {0, 0, 0, 0, 0, 0};
-  for (int f = 0; center && f < u.nfields; ++f) c6[nls_slot(u, f)] = center[f];
-  MFFT_TRY(moments_begin(c6));
+// Composed route: the statistics are per field, so ONE real work array serves the fields in turn -- inverse transform into nlr, the
+// kind's sweep, next field.  Two kinds keep a loop of their own: the quadratic form adds each field's term into the plan's ONE array
+// of doubles, in slot order (the order the fused kernel adds in), and sweeps that once; the joint histogram needs a pair at a
+// time, a_p in nlr and b_p in nlr2 (two real work arrays, the least a pair can do with).
+int mfft_plan_s::reduce_composed(const NlFields& u, int dealias, Op kind) {
   const bool pad = dealias == MFFT_DEALIAS_3_2;
-  MFFT_TRY(nonlinear_fusable(dealias, Op::Moments, false)
-               ? (P == 1 ? nonlinear_fused(u, dealias, Op::Moments, false) : nonlinear_fused_ranks(u, dealias, Op::Moments, false))
-               : moments_composed(u, dealias));
-  double host[NLS_SLOTS];
-  MFFT_TRY(moments_end(host));
-  for (int f = 0; f < u.nfields; ++f)
-    for (int k = 0; k < NLS_STATS; ++k) out[f * NLS_STATS + k] = host[nls_slot(u, f) * NLS_STATS + k];
-  *count = local_real_count(pad);
+  const int64_t nr = local_real_count(pad), nc = local_complex_alloc(), M = pad ? M2 : N2;
+  if (nr <= 0 || !r2c) return set_error(MFFT_ERR_UNSUPPORTED, "real_%s needs a 3-D real-to-complex plan", nl_product(kind).name);
+  MFFT_TRY(ensure(nlr, (size_t)nr * rs));
+  const NlrCall& c = nlcall;
+  auto back = [&](int f, Buf& to) { return exec(false, u.src(f, nc, es), to.p, dealias); };
+  if (kind == Op::JointHistogram) {
+    MFFT_TRY(ensure(nlr2, (size_t)nr * rs));
+    int64_t* acc = static_cast<int64_t*>(nljacc.p);
+    for (int p = 0; p < u.ncomp; ++p) {
+      MFFT_TRY(back(p, nlr));
+      MFFT_TRY(back(u.ncomp + p, nlr2));
+      MFFT_TRY(stage("nl_joint", 2.0 * (double)nr * rs, [&] {
+        return joint_sweep(nlr.p, nlr2.p, (size_t)nr, c.lo + 2 * p, c.inv + 2 * p, c.nba, c.nbb, acc + (size_t)p * joint_cells(c.nba, c.nbb));
+      }));
+    }
+    return 0;
+  }
+  if (kind == Op::Quadratic) {
+    MFFT_TRY(ensure(nlq, (size_t)nr * sizeof(double)));
+    double* q = static_cast<double*>(nlq.p);
+    bool first = true;
+    for (int slot = 0; slot < 6; ++slot)
+      for (int f = 0; f < u.nfields; ++f) {
+        if (nls_slot(u, f) != slot) continue;
+        MFFT_TRY(back(f, nlr));
+        MFFT_TRY(stage("nl_quadratic_add", (double)nr * (rs + 16), [&] { return quad_accum(nlr.p, q, (size_t)nr, c.w[slot], first); }));
+        first = false;
+      }
+    const double one[1] = {1.0};
+    return stage("nl_quadratic", (double)nr * 8, [&] { return quad_sweep(q, true, 1, (size_t)nr, (size_t)nr, one, false); });
+  }
+  for (int f = 0; f < u.nfields; ++f) {
+    const int slot = nls_slot(u, f);
+    MFFT_TRY(back(f, nlr));
+    if (kind == Op::Moments) {
+      double* acc = static_cast<double*>(nlsacc.p);
+      MFFT_TRY(stage("nl_moments", (double)nr * rs, [&] { return moments_sweep(nlr.p, 1, (size_t)nr, acc + NLS_SLOTS + slot, acc + slot * NLS_STATS); }));
+    } else if (kind == Op::Histogram) {
+      int64_t* acc = static_cast<int64_t*>(nlhacc.p);
+      MFFT_TRY(stage("nl_histogram", (double)nr * rs, [&] {
+        return hist_sweep(nlr.p, 1, (size_t)nr, c.lo + slot, c.inv + slot, c.nbins, acc + (size_t)slot * (c.nbins + 3));
+      }));
+    } else {      // Op::Increments: z is whole on every rank of a slab and of a pencil plan, so no halo is needed
+      double* acc = static_cast<double*>(nliacc.p);
+      MFFT_TRY(stage("nl_increments", (double)nr * rs, [&] { return incr_sweep(nlr.p, 1, nr / M, M, M, acc + slot * INCR_FIELD); }));
+    }
+  }
   return 0;
 }
 
-// Histograms of the real-space fields of up to six spectra: per field nbins + 3 counts (below lo, the nbins equal bins of [lo, hi),
-// at or above hi, not finite: fft_nlz.h hist_slot) of x = ifftn(field, dealias) over this rank's part of the grid a product would
-// be formed on.  The routes are real_moments': fused, the inverse passes of the products and the z stage that ends in a histogram
-// (no real array); composed, ONE real work array field by field -- inverse transform, sweep (hist.hip), next field.  Counts are
-// integers: the same bits on every route that computes the same values.  Synchronises the plan's stream.
-int mfft_plan_s::hist_composed(const NlFields& u, int dealias) {
-  const bool pad = dealias == MFFT_DEALIAS_3_2;
-  const int64_t nr = local_real_count(pad), nc = local_complex_alloc();
-  if (nr <= 0 || !r2c) return set_error(MFFT_ERR_UNSUPPORTED, "real_histogram needs a 3-D real-to-complex plan");
-  MFFT_TRY(ensure(nlr, (size_t)nr * rs));
-  int64_t* acc = static_cast<int64_t*>(nlhacc.p);
-  for (int f = 0; f < u.nfields; ++f) {
-    const int slot = nls_slot(u, f);
-    MFFT_TRY(exec(false, u.src(f, nc, es), nlr.p, dealias));
-    MFFT_TRY(stage("nl_histogram", (double)nr * rs, [&] {
-      return hist_sweep(nlr.p, 1, (size_t)nr, nlh_lo + slot, nlh_inv + slot, nlh_bins, acc + (size_t)slot * (nlh_bins + 3));
-    }));
-  }
+// [min, max, S1 .. S4] per field, S_p = sum (x - center)^p
+int mfft_plan_s::real_moments(const NlFields& u, int dealias, const double* center, double* out, int64_t* count) {
+  double c6[6] = {0, 0, 0, 0, 0, 0}, host[NLS_SLOTS];
+  for (int f = 0; center && f < u.nfields; ++f) c6[nls_slot(u, f)] = center[f];
+  MFFT_TRY(real_reduce(u, dealias, Op::Moments, count, [&] { return moments_begin(c6); }, [&] { return moments_end(host); }));
+  for (int f = 0; f < u.nfields; ++f)
+    for (int k = 0; k < NLS_STATS; ++k) out[f * NLS_STATS + k] = host[nls_slot(u, f) * NLS_STATS + k];
   return 0;
 }
+
+// per field nbins + 3 counts: below lo, the nbins equal bins of [lo, hi), at or above hi, not finite (fft_nlz.h hist_slot).  Counts are
+// integers: the same bits on every route that computes the same values.
 int mfft_plan_s::real_histogram(const NlFields& u, int dealias, const double* lo, const double* hi, int nbins, int64_t* out, int64_t* count) {
-  if (dealias == MFFT_DEALIAS_2_3) MFFT_TRY(require_mask());
   double l6[6] = {0, 0, 0, 0, 0, 0}, i6[6] = {1, 1, 1, 1, 1, 1};
   for (int f = 0; f < u.nfields; ++f) {
     const int slot = nls_slot(u, f);
     MFFT_TRY(hist_range(lo[f], hi[f], nbins, &i6[slot]));
     l6[slot] = lo[f];
   }
-  MFFT_TRY(hist_begin(l6, i6, nbins));
-  const bool pad = dealias == MFFT_DEALIAS_3_2;
-  MFFT_TRY(nonlinear_fusable(dealias, Op::Histogram, false)
-               ? (P == 1 ? nonlinear_fused(u, dealias, Op::Histogram, false) : nonlinear_fused_ranks(u, dealias, Op::Histogram, false))
-               : hist_composed(u, dealias));
   const int nb3 = nbins + 3, nslots = 2 * ((u.nfields + 1) / 2);
   std::vector<int64_t> host((size_t)nslots * nb3);
-  MFFT_TRY(hist_end(host.data(), nslots));
+  MFFT_TRY(real_reduce(u, dealias, Op::Histogram, count, [&] { return hist_begin(l6, i6, nbins); }, [&] { return hist_end(host.data(), nslots); }));
   for (int f = 0; f < u.nfields; ++f)
     memcpy(out + (size_t)f * nb3, host.data() + (size_t)nls_slot(u, f) * nb3, (size_t)nb3 * sizeof(int64_t));
-  *count = local_real_count(pad);
   return 0;
 }
 
-// Statistics of a quadratic form of the real-space fields of up to six spectra: q(x) = sum_f w_f r_f(x)^2, r_f = ifftn(field f,
-// dealias), by the one rule of include/mpifft4py_amd.h, over this rank's part of the grid a product would be formed on:
-// [min, max, S1 .. S4] of q about `center` and, nbins > 0, its nbins + 3 counts over [lo, hi).  The routes are real_moments': fused,
-// the inverse passes of the products and the z stage that ends in these statistics (fft_nlz.h body_quad; no real array);
-// composed, ONE real work array field by field in slot order -- inverse transform, its term added into the plan's ONE array of
-// doubles (quad.hip) -- and one sweep of that array.  Synchronises the plan's stream; the inputs are preserved.
-int mfft_plan_s::quad_composed(const NlFields& u, int dealias, const double w_slots[6]) {
-  const bool pad = dealias == MFFT_DEALIAS_3_2;
-  const int64_t nr = local_real_count(pad), nc = local_complex_alloc();
-  if (nr <= 0 || !r2c) return set_error(MFFT_ERR_UNSUPPORTED, "real_quadratic needs a 3-D real-to-complex plan");
-  MFFT_TRY(ensure(nlr, (size_t)nr * rs));
-  MFFT_TRY(ensure(nlq, (size_t)nr * sizeof(double)));
-  double* q = static_cast<double*>(nlq.p);
-  bool first = true;
-  for (int slot = 0; slot < 6; ++slot)             // (slot order: the order the fused kernel adds in)
-    for (int f = 0; f < u.nfields; ++f) {
-      if (nls_slot(u, f) != slot) continue;
-      MFFT_TRY(exec(false, u.src(f, nc, es), nlr.p, dealias));
-      MFFT_TRY(stage("nl_quadratic_add", (double)nr * (rs + 16), [&] { return quad_accum(nlr.p, q, (size_t)nr, w_slots[slot], first); }));
-      first = false;
-    }
-  const double one[1] = {1.0};
-  return stage("nl_quadratic", (double)nr * 8, [&] { return quad_sweep(q, true, 1, (size_t)nr, (size_t)nr, one, false); });
-}
+// q(x) = sum_f w_f r_f(x)^2, r_f = ifftn(field f, dealias), by the one rule of include/mpifft4py_amd.h: [min, max, S1 .. S4] of q about
+// `center` and, nbins > 0, its nbins + 3 counts over [lo, hi) (fft_nlz.h body_quad)
 int mfft_plan_s::real_quadratic(const NlFields& u, int dealias, const double* weights, double center, double lo, double hi, int nbins, double* out6,
                                 int64_t* counts, int64_t* count) {
-  if (dealias == MFFT_DEALIAS_2_3) MFFT_TRY(require_mask());
   if (!std::isfinite(center)) return set_error(MFFT_ERR_INVALID, "the centre is not finite");
   double inv = 1.0;
   MFFT_TRY(quad_check(weights, u.nfields, lo, hi, nbins, &inv));
-  for (int i = 0; i < 6; ++i) nlq_w[i] = 0.0;
-  for (int f = 0; f < u.nfields; ++f) nlq_w[nls_slot(u, f)] = weights[f];
-  MFFT_TRY(quad_begin(center, lo, inv, nbins));
-  const bool pad = dealias == MFFT_DEALIAS_3_2;
-  MFFT_TRY(nonlinear_fusable(dealias, Op::Quadratic, false)
-               ? (P == 1 ? nonlinear_fused(u, dealias, Op::Quadratic, false) : nonlinear_fused_ranks(u, dealias, Op::Quadratic, false))
-               : quad_composed(u, dealias, nlq_w));
-  MFFT_TRY(quad_end(out6, counts));
-  *count = local_real_count(pad);
-  return 0;
+  auto begin = [&] {
+    for (int i = 0; i < 6; ++i) nlcall.w[i] = 0.0;
+    for (int f = 0; f < u.nfields; ++f) nlcall.w[nls_slot(u, f)] = weights[f];
+    return quad_begin(center, lo, inv, nbins);
+  };
+  return real_reduce(u, dealias, Op::Quadratic, count, begin, [&] { return quad_end(out6, counts); });
 }
 
-// Structure functions along z of the real-space fields of up to six spectra: per field and separation the sums S2, S3, S4 of
-// d = x(z + s) - x(z), x = ifftn(field, dealias), rows periodic, over this rank's part of the grid a product would be formed on --
-// z is whole on every rank of a slab and of a pencil plan, so no halo is needed.  The routes are real_moments': fused, the inverse
-// passes of the products and the z stage that ends in these sums (fft_nlz.h body_incr; no real array); composed, ONE real work
-// array field by field -- inverse transform, sweep (incr.hip), next field.  Everything is checked before anything is enqueued.
-// Synchronises the plan's stream; the inputs are preserved.
-int mfft_plan_s::incr_composed(const NlFields& u, int dealias) {
-  const bool pad = dealias == MFFT_DEALIAS_3_2;
-  const int64_t nr = local_real_count(pad), nc = local_complex_alloc(), M = pad ? M2 : N2;
-  MFFT_TRY(ensure(nlr, (size_t)nr * rs));
-  double* acc = static_cast<double*>(nliacc.p);
-  for (int f = 0; f < u.nfields; ++f) {
-    const int slot = nls_slot(u, f);
-    MFFT_TRY(exec(false, u.src(f, nc, es), nlr.p, dealias));
-    MFFT_TRY(stage("nl_increments", (double)nr * rs, [&] { return incr_sweep(nlr.p, 1, nr / M, M, M, acc + slot * INCR_FIELD); }));
-  }
-  return 0;
-}
+// per field and separation the sums S2, S3, S4 of d = x(z + s) - x(z), rows periodic (fft_nlz.h body_incr)
 int mfft_plan_s::real_increments(const NlFields& u, int dealias, const int64_t* seps, int nsep, double* out, int64_t* count) {
   const bool pad = dealias == MFFT_DEALIAS_3_2;
   const int64_t nr = local_real_count(pad), M = pad ? M2 : N2;
   if (nr <= 0 || !r2c || M < 2 || nr % M != 0) return set_error(MFFT_ERR_UNSUPPORTED, "real_increments needs a 3-D real-to-complex plan");
   MFFT_TRY(incr_check(seps, nsep, M));
-  if (dealias == MFFT_DEALIAS_2_3) MFFT_TRY(require_mask());
-  MFFT_TRY(incr_begin(seps, nsep));
-  MFFT_TRY(nonlinear_fusable(dealias, Op::Increments, false)
-               ? (P == 1 ? nonlinear_fused(u, dealias, Op::Increments, false) : nonlinear_fused_ranks(u, dealias, Op::Increments, false))
-               : incr_composed(u, dealias));
   double host[INCR_SLOTS];
-  MFFT_TRY(incr_end(host));
+  MFFT_TRY(real_reduce(u, dealias, Op::Increments, count, [&] { return incr_begin(seps, nsep); }, [&] { return incr_end(host); }));
   for (int f = 0; f < u.nfields; ++f)
     for (int i = 0; i < nsep; ++i)
       for (int k = 0; k < 3; ++k) out[(f * nsep + i) * 3 + k] = host[(nls_slot(u, f) * MFFT_INCR_MAXSEP + i) * 3 + k];
-  *count = nr;
   return 0;
 }
 
-// Joint histograms of the real-space fields of one or three PAIRS of spectra: per pair (nba + 3)(nbb + 3) counts of the points
-// (x_a, x_b) = (ifftn(a_p), ifftn(b_p))(dealias), cell = slot of x_a * (nbb + 3) + slot of x_b (fft_nlz.h joint_cell), over this
-// rank's part of the grid a product would be formed on.  The routes are real_histogram's: fused, the inverse passes of the
-// products and the z stage that ends in a joint histogram (no real array); composed, a_p into nlr and b_p into nlr2 -- two real
-// work arrays, the least a pair can do with --, one sweep (joint.hip), next pair.  Synchronises the plan's stream.
-int mfft_plan_s::joint_composed(const NlFields& u, int dealias) {
-  const bool pad = dealias == MFFT_DEALIAS_3_2;
-  const int64_t nr = local_real_count(pad), nc = local_complex_alloc();
-  if (nr <= 0 || !r2c) return set_error(MFFT_ERR_UNSUPPORTED, "real_joint_histogram needs a 3-D real-to-complex plan");
-  MFFT_TRY(ensure(nlr, (size_t)nr * rs));
-  MFFT_TRY(ensure(nlr2, (size_t)nr * rs));
-  int64_t* acc = static_cast<int64_t*>(nljacc.p);
-  const int cells = joint_cells(nlj_nba, nlj_nbb);
-  for (int p = 0; p < u.ncomp; ++p) {
-    MFFT_TRY(exec(false, u.src(p, nc, es), nlr.p, dealias));
-    MFFT_TRY(exec(false, u.src(u.ncomp + p, nc, es), nlr2.p, dealias));
-    MFFT_TRY(stage("nl_joint", 2.0 * (double)nr * rs, [&] {
-      return joint_sweep(nlr.p, nlr2.p, (size_t)nr, nlj_lo + 2 * p, nlj_inv + 2 * p, nlj_nba, nlj_nbb, acc + (size_t)p * cells);
-    }));
-  }
-  return 0;
-}
+// per PAIR (x_a, x_b) = (ifftn(a_p), ifftn(b_p)) the (nba + 3)(nbb + 3) counts, cell = slot of x_a * (nbb + 3) + slot of x_b (fft_nlz.h
+// joint_cell); the pairs lie in slot order already
 int mfft_plan_s::real_joint_histogram(const NlFields& u, int dealias, const double* lo, const double* hi, int nba, int nbb, int64_t* out,
                                       int64_t* count) {
   double l6[6] = {0, 0, 0, 0, 0, 0}, i6[6] = {1, 1, 1, 1, 1, 1};
-  for (int f = 0; f < u.nfields; ++f) {            // (everything is checked before anything is enqueued)
+  for (int f = 0; f < u.nfields; ++f) {
     const int slot = nls_slot(u, f);
     MFFT_TRY(joint_range(lo[f], hi[f], slot % 2 ? nbb : nba, &i6[slot]));
     l6[slot] = lo[f];
   }
-  if (dealias == MFFT_DEALIAS_2_3) MFFT_TRY(require_mask());
-  MFFT_TRY(joint_begin(l6, i6, nba, nbb));
-  const bool pad = dealias == MFFT_DEALIAS_3_2;
-  MFFT_TRY(nonlinear_fusable(dealias, Op::JointHistogram, false)
-               ? (P == 1 ? nonlinear_fused(u, dealias, Op::JointHistogram, false) : nonlinear_fused_ranks(u, dealias, Op::JointHistogram, false))
-               : joint_composed(u, dealias));
-  MFFT_TRY(joint_end(out, u.ncomp));
-  *count = local_real_count(pad);
-  return 0;
+  return real_reduce(u, dealias, Op::JointHistogram, count, [&] { return joint_begin(l6, i6, nba, nbb); }, [&] { return joint_end(out, u.ncomp); });
 }

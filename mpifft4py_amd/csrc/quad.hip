@@ -1,6 +1,6 @@
 // quad.hip -- statistics of a quadratic form q = sum_f w_f r_f^2 of up to six real fields: [min, max, S1 .. S4] of q about a
-// centre and, with nbins > 0, its nbins + 3 counts (fft_nlz.h hist_slot).  The launches and folds around the fused z stage that
-// ends in them (fft_nlz.h body_quad), the streaming sweep mfft_ew_quadratic over real fields -- q is formed on the fly, there is
+// centre and, with nbins > 0, its nbins + 3 counts (fft_nlz.h hist_slot).  The plan's accumulators of the fused z stage that
+// ends in them (fft_nlz.h body_quad; launches and folds: core.hip nlr_rows), the streaming sweep mfft_ew_quadratic over real fields -- q is formed on the fly, there is
 // no q array --, and the two small kernels of the composed route of mfft_real_quadratic: add one field's (w r) r into the plan's
 // array of doubles, sweep that array once.  ONE evaluation rule (include/mpifft4py_amd.h; fft_nlz.h quad_term): q = 0, then per
 // field in slot order q = q + (w r) r, every product and sum rounded on its own, in double.
@@ -102,54 +102,25 @@ int quad_check(const double* weights, int nfields, double lo, double hi, int nbi
   return 0;
 }
 
-int quad_rows(const NlqArgs& z0, void* part, double* macc, int64_t* hacc, hipStream_t s) {
-  const size_t es = z0.prec == MFFT_DOUBLE ? 16 : 8;
-  int g0 = 0;
-  int64_t w0 = 0, m0 = 0;
-  MFFT_TRY(nlq_launch_shape(z0.n, z0.prec, z0.nrows, &g0, &w0, &m0));      // (the shape `part` was sized by: the largest of the launches)
-  for (int64_t r0 = 0; r0 < z0.nrows;) {
-    int ngroups = 0;
-    int64_t waves = 0, max_rows = 0;
-    MFFT_TRY(nlq_launch_shape(z0.n, z0.prec, z0.nrows - r0, &ngroups, &waves, &max_rows));
-    NlqArgs z = z0;
-    z.nrows = std::min(z0.nrows - r0, max_rows);
-    z.ngroups = ngroups;
-    z.mpart = part;
-    z.hpart = static_cast<char*>(part) + quad_mpart_bytes(w0);
-    for (int p = 0; p < z.npairs; ++p) {
-      if (z.a[p]) z.a[p] = static_cast<const char*>(z0.a[p]) + (size_t)(r0 * z0.in_stride) * es;
-      if (z.b[p]) z.b[p] = static_cast<const char*>(z0.b[p]) + (size_t)(r0 * z0.in_stride) * es;
-    }
-    MFFT_TRY(launch_nlq(z, s));
-    MFFT_TRY(moments_fold(static_cast<const double*>(z.mpart), (size_t)waves, NLS_STATS, macc, s));
-    if (z.nbins > 0) MFFT_TRY(hist_fold(static_cast<const unsigned*>(z.hpart), (size_t)ngroups, 1, z.nbins, hacc, s));
-    r0 += z.nrows;
-  }
-  return 0;
-}
-
 }  // namespace mfft
 
 // the plan's accumulators of a quadratic call: slot 0 of nlsacc (six doubles, the centre behind the statistics) and, nbins > 0, the
-// first nbins + 3 counts of nlhacc, both cleared on the stream
+// first nbins + 3 counts of nlhacc, both cleared on the stream; centre and range of q are slot 0 of the call's parameters
 int mfft_plan_s::quad_begin(double center, double lo, double inv, int nbins) {
-  const double c6[6] = {center, 0, 0, 0, 0, 0};
+  const double c6[6] = {center, 0, 0, 0, 0, 0}, l6[6] = {lo, 0, 0, 0, 0, 0}, i6[6] = {inv, 1, 1, 1, 1, 1};
   MFFT_TRY(moments_begin(c6));
-  nlq_center = center; nlq_lo = lo; nlq_inv = inv; nlq_bins = nbins;
-  if (nbins > 0) {
-    const double l6[6] = {lo, 0, 0, 0, 0, 0}, i6[6] = {inv, 1, 1, 1, 1, 1};
-    MFFT_TRY(hist_begin(l6, i6, nbins));
-  }
+  if (nbins > 0) MFFT_TRY(hist_begin(l6, i6, nbins));
+  nlcall.lo[0] = lo; nlcall.inv[0] = inv; nlcall.nbins = nbins;
   return 0;
 }
 int mfft_plan_s::quad_end(double out6[6], int64_t* counts) {
   double nlq_host[NLS_STATS];
   MFFT_HIP(hipMemcpyAsync(nlq_host, nlsacc.p, NLS_STATS * sizeof(double), hipMemcpyDeviceToHost, stream));
-  std::vector<int64_t> h((size_t)nlq_bins + 3);
-  if (nlq_bins > 0) MFFT_HIP(hipMemcpyAsync(h.data(), nlhacc.p, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+  std::vector<int64_t> h((size_t)nlcall.nbins + 3);
+  if (nlcall.nbins > 0) MFFT_HIP(hipMemcpyAsync(h.data(), nlhacc.p, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
   MFFT_HIP(hipStreamSynchronize(stream));
   for (int k = 0; k < NLS_STATS; ++k) out6[k] = nlq_host[k];      // (the outputs are written only once nothing can fail any more)
-  if (nlq_bins > 0) memcpy(counts, h.data(), h.size() * sizeof(int64_t));
+  if (nlcall.nbins > 0) memcpy(counts, h.data(), h.size() * sizeof(int64_t));
   return 0;
 }
 
@@ -158,7 +129,7 @@ int mfft_plan_s::quad_end(double out6[6], int64_t* counts) {
 int mfft_plan_s::quad_sweep(const void* x, bool as_double, int ncomp, size_t stride, size_t n, const double* w, bool square) {
   QuadSweep a;
   for (int c = 0; c < 6; ++c) a.w[c] = c < ncomp ? w[c] : 0.0;
-  a.center = nlq_center; a.lo = nlq_lo; a.inv = nlq_inv; a.nbins = nlq_bins; a.ncomp = ncomp;
+  a.center = nlcall.center[0]; a.lo = nlcall.lo[0]; a.inv = nlcall.inv[0]; a.nbins = nlcall.nbins; a.ncomp = ncomp;
   double* macc = static_cast<double*>(nlsacc.p);
   int64_t* hacc = static_cast<int64_t*>(nlhacc.p);
   for (size_t o = 0; o < n; o += QS_CHUNK) {

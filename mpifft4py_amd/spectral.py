@@ -295,6 +295,18 @@ def _centers(center, nfields):
     return np.ascontiguousarray(c)
 
 
+def _real_fields(FFT, a_hat, b_hat):
+    """The opening of the `real_*` statistics: a_hat of FFT.complex_shape() or (3,) + that, b_hat None or of the same shape.
+    Returns the fields as `_nonlinear` takes them, the components per field, the number of fields (a's first) and the head of
+    the library call's arguments."""
+    cs = tuple(int(s) for s in FFT.complex_shape())
+    assert a_hat.shape in (cs, (3,) + cs), (a_hat.shape, cs)
+    vec = len(a_hat.shape) == 4
+    fields = [(a_hat, vec)] + ([(b_hat, vec)] if b_hat is not None else [])
+    ncomp = 3 if vec else 1
+    return fields, ncomp, ncomp * len(fields), (a_hat.ptr, b_hat.ptr if b_hat is not None else None, ncomp)
+
+
 def real_moments(FFT, a_hat, b_hat=None, dealias=None, center=None, reduce=True):
     """One-point statistics of fields that exist as SPECTRA only (mfft_real_moments): minimum, maximum and the sums of the
     first four powers of ifftn(a_hat[f], dealias) -- and of ifftn(b_hat[f], dealias) where b_hat is given -- without a real
@@ -308,17 +320,12 @@ def real_moments(FFT, a_hat, b_hat=None, dealias=None, center=None, reduce=True)
     them -- a scalar of mean 3 and deviation 1e-3 keeps nothing of its flatness about 0 -- and that is what `center` is
     for: pass the mean (a_hat[0, 0, 0] / N^3 on the rank that holds it).  A NaN or Inf anywhere in a field gives NaN sums for
     that field; the values are bitwise reproducible.  Synchronises the plan's stream; the inputs are preserved."""
-    cs = tuple(int(s) for s in FFT.complex_shape())
-    assert a_hat.shape in (cs, (3,) + cs), (a_hat.shape, cs)
-    vec = len(a_hat.shape) == 4
-    fields = [(a_hat, vec)] + ([(b_hat, vec)] if b_hat is not None else [])
-    ncomp = 3 if vec else 1
-    nfields = ncomp * len(fields)
+    fields, ncomp, nfields, head = _real_fields(FFT, a_hat, b_hat)
     c = _centers(center, nfields)
     out = np.zeros(nfields * 6, dtype=np.float64)
     count = ctypes.c_int64(0)
     dp = ctypes.POINTER(ctypes.c_double)
-    _nonlinear(FFT, "real_moments", fields, dealias, head=(a_hat.ptr, b_hat.ptr if b_hat is not None else None, ncomp),
+    _nonlinear(FFT, "real_moments", fields, dealias, head=head,
                tail=(c.ctypes.data_as(dp), out.ctypes.data_as(dp), ctypes.byref(count)))
     return _moments_result(FFT, out, count.value, c, reduce)
 
@@ -449,12 +456,7 @@ def real_histogram(FFT, a_hat, b_hat=None, dealias=None, bins=256, range=None, r
     of width 1 about its value).  Returns a `Histogram`; with `reduce` the int64 counts are added over FFT.comm (every rank
     calls it, every rank gets the same arrays).  Counts are integers: the result is the same bits run to run, on every device
     and for every number of ranks that computes the same values.  Synchronises the plan's stream; the inputs are preserved."""
-    cs = tuple(int(s) for s in FFT.complex_shape())
-    assert a_hat.shape in (cs, (3,) + cs), (a_hat.shape, cs)
-    vec = len(a_hat.shape) == 4
-    fields = [(a_hat, vec)] + ([(b_hat, vec)] if b_hat is not None else [])
-    ncomp = 3 if vec else 1
-    nfields = ncomp * len(fields)
+    fields, ncomp, nfields, head = _real_fields(FFT, a_hat, b_hat)
     if range is None:
         m = real_moments(FFT, a_hat, b_hat, dealias, reduce=True)
         lo, hi = _range_of_moments(m, "field")
@@ -464,7 +466,7 @@ def real_histogram(FFT, a_hat, b_hat=None, dealias=None, bins=256, range=None, r
     out = np.zeros((nfields, int(bins) + 3), dtype=np.int64)
     count = ctypes.c_int64(0)
     dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
-    _nonlinear(FFT, "real_histogram", fields, dealias, head=(a_hat.ptr, b_hat.ptr if b_hat is not None else None, ncomp),
+    _nonlinear(FFT, "real_histogram", fields, dealias, head=head,
                tail=(lo.ctypes.data_as(dp), hi.ctypes.data_as(dp), int(bins), out.ctypes.data_as(ip), ctypes.byref(count)))
     n = count.value
     if reduce:
@@ -604,10 +606,8 @@ def real_joint_histogram(FFT, a_hat, b_hat, dealias=None, bins=64, range=None, r
     of ranks of a fused slab plan.  Synchronises the plan's stream; the inputs are preserved."""
     if b_hat is None:
         raise ValueError("a joint histogram counts pairs of fields: b_hat must be given")
-    cs = tuple(int(s) for s in FFT.complex_shape())
-    assert a_hat.shape in (cs, (3,) + cs) and b_hat.shape == a_hat.shape, (a_hat.shape, b_hat.shape, cs)
-    vec = len(a_hat.shape) == 4
-    ncomp = 3 if vec else 1
+    assert b_hat.shape == a_hat.shape, (a_hat.shape, b_hat.shape)
+    fields, ncomp, _, head = _real_fields(FFT, a_hat, b_hat)
     nba, nbb = _joint_bins(bins)
     if range is None:
         lo, hi = _range_of_moments(real_moments(FFT, a_hat, b_hat, dealias, reduce=True), "field")      # (a_0.., then b_0..)
@@ -617,7 +617,7 @@ def real_joint_histogram(FFT, a_hat, b_hat, dealias=None, bins=64, range=None, r
     out = np.zeros((ncomp, nba + 3, nbb + 3), dtype=np.int64)
     count = ctypes.c_int64(0)
     dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
-    _nonlinear(FFT, "real_joint_histogram", [(a_hat, vec), (b_hat, vec)], dealias, head=(a_hat.ptr, b_hat.ptr, ncomp),
+    _nonlinear(FFT, "real_joint_histogram", fields, dealias, head=head,
                tail=(lo.ctypes.data_as(dp), hi.ctypes.data_as(dp), nba, nbb, out.ctypes.data_as(ip), ctypes.byref(count)))
     return _joint_result(FFT, count.value, out, lo, hi, ncomp, nba, nbb, reduce)
 
@@ -718,12 +718,7 @@ def real_quadratic(FFT, a_hat, b_hat=None, dealias=None, weights=None, center=0.
     doubles.  q follows ONE rule on every route (`quad_rule`, fields in `quad_slot_order`).  A NaN or Inf in any field gives
     NaN statistics and counts in the non-finite slot.  With `reduce` over FFT.comm; bitwise reproducible.  Synchronises the
     plan's stream; the inputs are preserved."""
-    cs = tuple(int(s) for s in FFT.complex_shape())
-    assert a_hat.shape in (cs, (3,) + cs), (a_hat.shape, cs)
-    vec = len(a_hat.shape) == 4
-    fields = [(a_hat, vec)] + ([(b_hat, vec)] if b_hat is not None else [])
-    ncomp = 3 if vec else 1
-    nfields = ncomp * len(fields)
+    fields, ncomp, nfields, head = _real_fields(FFT, a_hat, b_hat)
     w, center, lo, hi = _quad_args(weights, nfields, center, bins, range)
     if int(bins) > 0 and range is None:
         lo, hi = _quad_range(real_quadratic(FFT, a_hat, b_hat, dealias, w, center, 0, None, True)[0])
@@ -731,7 +726,7 @@ def real_quadratic(FFT, a_hat, b_hat=None, dealias=None, weights=None, center=0.
     counts = np.zeros(int(bins) + 3, dtype=np.int64)
     count = ctypes.c_int64(0)
     dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
-    _nonlinear(FFT, "real_quadratic", fields, dealias, head=(a_hat.ptr, b_hat.ptr if b_hat is not None else None, ncomp),
+    _nonlinear(FFT, "real_quadratic", fields, dealias, head=head,
                tail=(w.ctypes.data_as(dp), center, lo, hi, int(bins), out6.ctypes.data_as(dp), counts.ctypes.data_as(ip), ctypes.byref(count)))
     return _quad_result(FFT, out6, counts, count.value, center, int(bins), lo, hi, reduce)
 
@@ -841,12 +836,7 @@ def real_increments(FFT, a_hat, b_hat=None, dealias=None, seps=None, reduce=True
     separations; a longer list is issued in chunks, and EACH CHUNK REPEATS THE TRANSFORMS.  Returns an `Increments`; with
     `reduce` the raw sums and the count are added over FFT.comm.  A NaN or Inf anywhere in a field gives NaN sums for that
     field; the values are bitwise reproducible.  Synchronises the plan's stream; the inputs are preserved."""
-    cs = tuple(int(s) for s in FFT.complex_shape())
-    assert a_hat.shape in (cs, (3,) + cs), (a_hat.shape, cs)
-    vec = len(a_hat.shape) == 4
-    fields = [(a_hat, vec)] + ([(b_hat, vec)] if b_hat is not None else [])
-    ncomp = 3 if vec else 1
-    nfields = ncomp * len(fields)
+    fields, ncomp, nfields, head = _real_fields(FFT, a_hat, b_hat)
     M = int(FFT.N[2]) * 3 // 2 if dealias == '3/2-rule' else int(FFT.N[2])
     seps, chunks = _incr_chunks(seps, M)
     count = ctypes.c_int64(0)
@@ -855,7 +845,7 @@ def real_increments(FFT, a_hat, b_hat=None, dealias=None, seps=None, reduce=True
     for ch in chunks:
         sv = np.ascontiguousarray(ch, dtype=np.int64)
         out = np.zeros(nfields * len(ch) * 3, dtype=np.float64)
-        _nonlinear(FFT, "real_increments", fields, dealias, head=(a_hat.ptr, b_hat.ptr if b_hat is not None else None, ncomp),
+        _nonlinear(FFT, "real_increments", fields, dealias, head=head,
                    tail=(sv.ctypes.data_as(ip), len(ch), out.ctypes.data_as(dp), ctypes.byref(count)))
         parts.append(out.reshape(nfields, len(ch), 3))
     return _incr_result(FFT, np.concatenate(parts, axis=1), count.value, seps, M, reduce)
