@@ -41,7 +41,7 @@ def _copy(FFT, dst, src):
 
 
 def solve(comm, N, U0_hat, theta0_hat, nu, kappa, dt, steps, dealias, one_op=True, g=0.0, precision="double", report=None,
-          timing=False, FFT=None, joint=False):
+          timing=False, FFT=None, joint=False, profiles=False):
     """Advance (U_hat, theta_hat) by `steps` RK4 steps and return them (DeviceArrays of (3,) + FFT.complex_shape() and
     FFT.complex_shape()); U0_hat and theta0_hat (DeviceArrays of the plan) are not modified.
     one_op=True: both nonlinear terms are ONE spectral.cross_dot_transform per stage.  one_op=False (--two-calls):
@@ -49,7 +49,10 @@ def solve(comm, N, U0_hat, theta0_hat, nu, kappa, dt, steps, dealias, one_op=Tru
     partner.  g: buoyancy, N_hat[2] += g theta_hat before the velocity's stage (0: the scalar is passive).
     joint=True: after every step report["joint"] gains the `spectral.JointHistogram` of (u_z, theta) in 64 x 64 bins over the
     fields' extremes, from ONE spectral.real_joint_histogram call on the two spectra (fused, the z kernel ends in the grid: no
-    real-space array); the timing then includes it."""
+    real-space array); the timing then includes it.
+    profiles=True: after every step report["profiles"] gains the pair (`spectral.Profiles` of (u_z, theta) from ONE
+    spectral.real_profiles call on the two spectra -- <theta>(z), <theta'^2>(z) and the heat flux <u_z theta>(z), no real-space
+    array --, the box value of <u_z theta> from the spectra by Parseval); the timing then includes both."""
     if FFT is None:
         FFT = make_plan(comm, N, precision)
     K = spectral.Wavenumbers(FFT)
@@ -98,6 +101,7 @@ def solve(comm, N, U0_hat, theta0_hat, nu, kappa, dt, steps, dealias, one_op=Tru
         FFT.enable_timing(True)
         FFT.reset_timing()
     t0 = time.perf_counter()
+    Kw = spectral.Wavenumbers(FFT) if profiles else None
     for _ in range(steps):
         _copy(FFT, th0, th)
         _copy(FFT, th1, th)
@@ -106,6 +110,9 @@ def solve(comm, N, U0_hat, theta0_hat, nu, kappa, dt, steps, dealias, one_op=Tru
         _copy(FFT, th, th1)
         if joint and report is not None:                 # (collective: a moments call for the ranges, then the joint histogram)
             report.setdefault("joint", []).append(spectral.real_joint_histogram(FFT, U_hat.component(2), th, dealias, bins=64))
+        if profiles and report is not None:              # (collective: the plane sums are added over the ranks)
+            report.setdefault("profiles", []).append((spectral.real_profiles(FFT, U_hat.component(2), th, dealias),
+                                                      float(spectral.transfer_spectrum(FFT, Kw, U_hat.component(2), th).sum())))
     FFT.sync()
     wall = time.perf_counter() - t0
     if report is not None:
@@ -151,12 +158,22 @@ def joint_summary(h):
     return float(corr), h.conditional_mean(0, of=0)[five], int(h.raw[0].sum())
 
 
+def profiles_summary(h):
+    """(<theta>, <theta'^2>, <u_z theta> at five heights, the mean over the planes of <u_z theta>) of pair 0 = (u_z, theta) of a
+    Profiles."""
+    five = np.linspace(0, h.M - 1, 7)[1:-1].astype(int)
+    flux = np.asarray(h.flux(0), dtype=np.float64)
+    return (np.asarray(h.mean(0)[1], dtype=np.float64)[five], np.asarray(h.variance(0)[1], dtype=np.float64)[five], flux[five], float(flux.mean()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--N", type=int, default=32, help="mesh edge")
     ap.add_argument("--M", type=int, default=0, help="mesh edge 2^M (overrides --N)")
     ap.add_argument("--joint", action="store_true", help="print per step the correlation coefficient of (u_z, theta), <u_z | theta> at five "
                     "theta bins and the counted total, from ONE spectral.real_joint_histogram call on the spectra (no real-space array)")
+    ap.add_argument("--profiles", action="store_true", help="print per step <theta>, <theta'^2> and the heat flux <u_z theta> at five heights z, "
+                    "and the plane-mean of <u_z theta> next to the box value, from ONE spectral.real_profiles call on the spectra (no real-space array)")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--dt", type=float, default=0.0, help="time step; default: inside the explicit scheme's stability bounds for this mesh")
     ap.add_argument("--nu", type=float, default=0.000625)
@@ -178,7 +195,7 @@ def main():
     U0, th0 = taylor_green_hat(FFT), random_scalar_hat(FFT)
     rep = {}
     U, th = solve(comm, args.N, U0, th0, args.nu, args.kappa, dt, args.steps, dealias, one_op=not args.two_calls, g=args.g,
-                  precision=args.precision, report=rep, timing=args.stages, FFT=FFT, joint=args.joint)
+                  precision=args.precision, report=rep, timing=args.stages, FFT=FFT, joint=args.joint, profiles=args.profiles)
     print("N = %d^3, %d RK4 steps of dt = %.3g, %.3f ms per step (%s; plan work buffers %.2f GB)"
           % (args.N, args.steps, dt, rep["ms_per_step"],
              "two calls per stage: cross_transform + dot_transform" if args.two_calls else
@@ -189,6 +206,11 @@ def main():
     for step, h in enumerate(rep.get("joint", [])):
         corr, cond, total = joint_summary(h)
         print("joint step %d: corr(u_z, theta) = %+.9e  <u_z | theta> = [%s]  total = %d" % (step + 1, corr, ", ".join("%+.6e" % c for c in cond), total))
+    for step, (h, box) in enumerate(rep.get("profiles", [])):
+        mean, var, flux, pm = profiles_summary(h)
+        fmt = lambda v: ", ".join("%+.6e" % c for c in v)
+        print("profiles step %d: <theta> = [%s]  <theta'^2> = [%s]  <u_z theta> = [%s]  plane-mean <u_z theta> = %+.12e  box <u_z theta> = %+.12e"
+              % (step + 1, fmt(mean), fmt(var), fmt(flux), pm, box))
     Kw = spectral.Wavenumbers(FFT)
     print("kinetic energy: %.15e -> %.15e" % (spectral.energy_spectrum(FFT, Kw, U0).sum(), spectral.energy_spectrum(FFT, Kw, U).sum()))
     print("mean of theta: %.15e -> %.15e" % (th0.get()[0, 0, 0].real, th.get()[0, 0, 0].real))

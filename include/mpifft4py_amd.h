@@ -364,6 +364,28 @@ MFFT_API int64_t mfft_nlz_quad_groups(int64_t nrows, int64_t n, int precision);
 MFFT_API int mfft_nlz_incr_rows(const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
                                 int64_t valid_in, int precision, const int64_t* seps, int nsep, double* out);
 MFFT_API int64_t mfft_nlz_incr_groups(int64_t nrows, int64_t n, int precision);
+/* Plane-averaged profiles along z: the rule that the fused kernel, the sweep, the emulator and the tests share.  For a pair of real
+ * fields (x, y), the centres (ca, cb) and every z index m of the real row of length M (N2 for dealias None and the 2/3-rule,
+ * 3 N2 / 2 for the 3/2-rule), over all rows -- a row is one (x, y) point, so over the plane z = m:
+ *     r    = (double)v * norm             the transform's value in the plan's precision, taken to double, then normalised (one
+ *                                         rounded product, as for the increments; a real array that is given as such: r = (double)x)
+ *     da = r_x - ca;   db = r_y - cb
+ *     sums[0] += da;  sums[1] += db;  sums[2] += da * da;  sums[3] += db * db;  sums[4] += da * db
+ * Products and sums in double in both precisions.  Per pair and z index the result is MFFT_PROFILE_STATS doubles.  No atomics:
+ * partial profiles go out by plain stores and are added in a fixed order, so the sums are bitwise reproducible run to run; they
+ * are sums of doubles, so they are NOT claimed identical for different numbers of ranks. */
+#define MFFT_PROFILE_STATS 5
+/* The z stage that ends in profiles (csrc/fft_nlz.h body_prof), synchronous: a and b are (ncomp, nrows, pitch) complex device arrays,
+ * ncomp = 1 or 3, pair p = (a_p, b_p); rows, valid and valid_in as mfft_nlz_moments_rows; center: 2 ncomp centres, a_0.., then
+ * b_0.. (NULL: zeros).  out[(p * 5 + s) * n + m] = sum s of pair p at position m of the rows irfft(row, n), without the real rows.
+ * A NaN or Inf bin of a field makes that field's two sums and the cross sum NaN at the positions of the thread that loaded it; the
+ * partner's own two sums keep the bytes of the run with that bin zero.  MFFT_ERR_INVALID for ncomp outside {1, 3}, a NULL b, a
+ * centre that is not finite and valid > n / 2 + 1; MFFT_ERR_UNSUPPORTED for lengths without a kernel; reported before anything is
+ * enqueued, out untouched.  The z stage of mfft_real_profiles on its own, for tests.
+ * mfft_nlz_profile_groups: the workgroups of that launch (it strides over the rows; 0: no kernel of that length). */
+MFFT_API int mfft_nlz_profile_rows(const void* a, const void* b, int ncomp, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
+                                   int64_t valid_in, int precision, const double* center, double* out);
+MFFT_API int64_t mfft_nlz_profile_groups(int64_t nrows, int64_t n, int precision);
 /* slab pack / unpack (slab.py:403; cython/maths.pyx:21-31 transpose_Uc) */
 MFFT_API int mfft_slab_pack(const void* uc_hatT, void* u_mpi, int P, int64_t np0, int64_t np1, int64_t nf, int precision);
 MFFT_API int mfft_slab_unpack(const void* u_mpi, void* uc_hatT, int P, int64_t np0, int64_t np1, int64_t nf, int precision);
@@ -543,6 +565,28 @@ MFFT_API int mfft_ew_increments(mfft_plan_t plan, const void* x, int ncomp, int6
  * reported before anything is enqueued.  The inputs are preserved.  Synchronises the plan's stream. */
 MFFT_API int mfft_real_increments(mfft_plan_t plan, const void* a_hat, const void* b_hat, int ncomp, int dealias, const int64_t* seps,
                                   int nsep, double* out, int64_t* count);
+
+/* out_host[(c * 5 + s) * n + m]: the five sums of the pairs (x[c, r, m], y[c, r, m]) over the nrows rows r of two real device
+ * arrays (ncomp, nrows, n) of equal shape, ncomp = 1 or 3, rows contiguous, in the plan's precision, by the rule above with norm
+ * = 1; center: 2 ncomp centres, x_0.., then y_0.. (NULL: zeros).  One sweep: threads run across z (coalesced loads), a workgroup
+ * takes a stripe of rows, partials by plain stores, one fold in fixed order, no atomics.  MFFT_ERR_INVALID for ncomp outside
+ * {1, 3}, no rows and a centre that is not finite.  The plan must not be null; synchronises the plan's stream. */
+MFFT_API int mfft_ew_profiles(mfft_plan_t plan, const void* x, const void* y, int ncomp, int64_t nrows, int64_t n, int precision,
+                              const double* center, double* out_host);
+
+/* Profiles of horizontal averages of fields that exist as spectra only: for the ncomp (1 or 3) components of a_hat and b_hat, pair
+ * p = (a_p, b_p), b_hat required (it may be a_hat), out[(p * 5 + s) * M + m] = sum s of (ifftn(a_p, dealias), ifftn(b_p, dealias))
+ * over the (x, y) plane z = m of THIS RANK's part of the real-space grid (as mfft_real_moments; z is whole on every rank of slabs
+ * and pencils alike), by the rule above about center (2 ncomp centres, a_0.., then b_0..; NULL: zeros); out holds ncomp * 5 * M
+ * host doubles, *count = the points per plane on this rank (sums / count, added over the ranks, are the plane averages).  Routes
+ * (mfft_plan_get_info "nonlinear_profiles_fused_3_2" / "_none" / "_2_3"): fused, a thread of the z kernel holds the same z
+ * positions for every row it meets, so the plane sums are its running sums (csrc/fft_nlz.h body_prof) and no real-space array
+ * exists; every other plan transforms a_p and b_p into TWO real work arrays and sweeps them (mfft_ew_profiles).  Bitwise
+ * reproducible run to run on one plan and device.  MFFT_ERR_INVALID for a NULL b_hat, ncomp outside {1, 3} and a centre that is not
+ * finite, reported before anything is enqueued, out and count untouched.  The inputs are preserved.  Synchronises the plan's
+ * stream. */
+MFFT_API int mfft_real_profiles(mfft_plan_t plan, const void* a_hat, const void* b_hat, int ncomp, int dealias, const double* center,
+                                double* out, int64_t* count);
 
 /* The nonlinear term of a pseudo-spectral step as ONE operation:
  *     out_hat = fftn(ifftn(a_hat) x ifftn(b_hat))        (cross product in real space, component by component)

@@ -335,8 +335,8 @@ int mfft_nlz_rows_absmax(const void* a, const void* b, void* out, int64_t nrows,
   return rc;
 }
 
-// The stages that end in a reduction (fft_nlz.h body_moments, body_hist, body_joint, body_quad, body_incr), synchronous; what their
-// five entry points share.  nfields = 1: a is (nrows, pitch); 2: a and b are; 3: a is (3, nrows, pitch); 6: a and b are.  `valid`
+// The stages that end in a reduction (fft_nlz.h body_moments, body_hist, body_joint, body_quad, body_incr, body_prof), synchronous; what
+// their six entry points share.  nfields = 1: a is (nrows, pitch); 2: a and b are; 3: a is (3, nrows, pitch); 6: a and b are.  `valid`
 // bins per row exist, the first valid_in of them are read (0: all of them).  Fields in the order a_0.., then b_0..; field f rides in
 // slot nls_slot(u, f), the plan's rule.  Everything is checked before the first launch; the outputs are written on success only.
 static int nlr_stage_args(Op kind, const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
@@ -420,6 +420,24 @@ int mfft_nlz_incr_rows(const void* a, const void* b, int nfields, int64_t nrows,
   return 0;
 }
 int64_t mfft_nlz_incr_groups(int64_t nrows, int64_t n, int precision) { return nlr_stage_groups(Op::Increments, nrows, n, precision); }
+
+// a, b: (ncomp, nrows, pitch), ncomp 1 or 3, pair p = (a_p, b_p); center: a_0.., then b_0.. (null: zeros)
+// out[(p * 5 + s) * n + m] = the sums over all rows of d_a, d_b, d_a^2, d_b^2, d_a d_b at position m of (irfft(a_p row, n), irfft(b_p row, n))
+int mfft_nlz_profile_rows(const void* a, const void* b, int ncomp, int64_t nrows, int64_t n, int64_t pitch, int64_t valid, int64_t valid_in,
+                          int precision, const double* center, double* out) {
+  if (!b || !out) return set_error(MFFT_ERR_INVALID, "bad argument");
+  if (ncomp != 1 && ncomp != 3) return set_error(MFFT_ERR_INVALID, "ncomp must be 1 or 3, not %d", ncomp);
+  NlFields u;
+  NlrArgs z;
+  MFFT_TRY(nlr_stage_args(Op::Profiles, a, b, 2 * ncomp, nrows, n, pitch, valid, valid_in, precision, &u, &z));
+  MFFT_TRY(prof_check(center, 2 * ncomp));
+  for (int f = 0; center && f < 2 * ncomp; ++f) z.call.center[nls_slot(u, f)] = center[f];
+  std::vector<double> host((size_t)ncomp * MFFT_PROFILE_STATS * (size_t)n);      // (the pairs lie in slot order already)
+  MFFT_TRY(nlr_stage_run(z, host.size() * sizeof(double), host.data(), 0, nullptr));
+  memcpy(out, host.data(), host.size() * sizeof(double));
+  return 0;
+}
+int64_t mfft_nlz_profile_groups(int64_t nrows, int64_t n, int precision) { return nlr_stage_groups(Op::Profiles, nrows, n, precision); }
 
 // out[f * (nbins + 3) + slot] = counts of irfft(row, n) over all rows
 int mfft_nlz_hist_rows(const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid, int64_t valid_in,

@@ -605,7 +605,7 @@ int launch_nlz(const NlzArgs& a, hipStream_t s) {
   });
 }
 
-// The stages that end in a reduction (fft_nlz.h body_moments, body_hist, body_joint, body_quad, body_incr: the table entries with
+// The stages that end in a reduction (fft_nlz.h body_moments, body_hist, body_joint, body_quad, body_incr, body_prof: the table entries with
 // nout == 0; NlrArgs of mfft_internal.h).  Their grid does not follow the rows: the workgroups that are resident at once, CUs x
 // min(what the runtime says fits, NLS_WG_PER_CU), asked once per device and kernel, and never more than there are pairs of rows to
 // start on.
@@ -713,6 +713,12 @@ static int launch_nlr_t(const KernelEntry* e, const NlrArgs& a, void* tw, hipStr
     P.nbins = c.nbins;
     return run(P);
   }
+  if (a.kind == Op::Profiles) {
+    auto P = nlr_params<T, NlpParams>(a, tw);
+    P.part = static_cast<double*>(a.part);
+    for (int i = 0; i < 2 * NLS_PAIRS; ++i) P.center[i] = c.center[i];
+    return run(P);
+  }
   auto P = nlr_params<T, NliParams>(a, tw);          // Op::Increments
   P.part = static_cast<double*>(a.part);
   for (int i = 0; i < NLI_MAXSEP; ++i) P.sep[i] = i < c.nsep ? c.sep[i] : 1;
@@ -743,6 +749,11 @@ int launch_nlr(const NlrArgs& a, hipStream_t s) {
     for (int i = 0; i < 2 * a.npairs; ++i)
       if (!std::isfinite(c.w[i])) return set_error(MFFT_ERR_INVALID, "a weight is not finite");
     if (c.nbins > 0 && !range_ok(0)) return set_error(MFFT_ERR_INVALID, "bad histogram range");
+  } else if (a.kind == Op::Profiles) {
+    for (int p = 0; p < a.npairs; ++p) {
+      if (!a.b[p]) return set_error(MFFT_ERR_INVALID, "null argument: a profile takes pairs of fields");
+      if (!std::isfinite(c.center[2 * p]) || !std::isfinite(c.center[2 * p + 1])) return set_error(MFFT_ERR_INVALID, "a centre is not finite");
+    }
   } else if (a.kind == Op::Increments) {
     if (c.nsep < 1 || c.nsep > NLI_MAXSEP) return set_error(MFFT_ERR_INVALID, "bad argument");
     for (int i = 0; i < c.nsep; ++i)               // (the kernel reads the row's exchange buffer at (position + sep) mod n)
@@ -761,6 +772,7 @@ size_t nlr_part_bytes(const NlrArgs& z, const NlrShape& shape) {
   if (z.kind == Op::Histogram) return hist_part_bytes(shape.ngroups, 2 * z.npairs, z.call.nbins);
   if (z.kind == Op::JointHistogram) return joint_part_bytes(shape.ngroups, z.npairs, z.call.nba, z.call.nbb);
   if (z.kind == Op::Quadratic) return quad_mpart_bytes(shape.waves) + quad_hpart_bytes(shape.ngroups, z.call.nbins);
+  if (z.kind == Op::Profiles) return prof_part_bytes(shape.ngroups, shape.tile, z.npairs, z.n);
   return (size_t)shape.waves * (z.kind == Op::Increments ? INCR_SLOTS : NLS_SLOTS) * sizeof(double);
 }
 // The ONE loop over the rows of a batch.  The kinds that sum doubles have no limit on the rows of a launch: one launch, one fold.
@@ -790,6 +802,9 @@ int nlr_rows(const NlrArgs& z0, void* acc, void* acc2, hipStream_t s) {
     } else if (z.kind == Op::Quadratic) {
       MFFT_TRY(moments_fold(static_cast<const double*>(z.part), waves, NLS_STATS, static_cast<double*>(acc), s));
       if (c.nbins > 0) MFFT_TRY(hist_fold(static_cast<const unsigned*>(z.part2), groups, 1, c.nbins, static_cast<int64_t*>(acc2), s));
+    } else if (z.kind == Op::Profiles) {            // one partial profile per row slot of the launch
+      MFFT_TRY(prof_fold(static_cast<const double*>(z.part), groups * (size_t)shape.tile, (size_t)z.npairs * NLP_STATS * (size_t)z.n,
+                         static_cast<double*>(acc), s));
     } else {
       MFFT_TRY(incr_fold(static_cast<const double*>(z.part), waves, INCR_SLOTS, static_cast<double*>(acc), s));
     }

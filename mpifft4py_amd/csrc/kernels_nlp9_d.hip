@@ -1,0 +1,7 @@
+// gfx950 instantiations: fused nonlinear z stage that ends in plane-averaged profiles along z (fft_nlz.h NlzProf), double precision
+#include "registry_nlz.h"
+#include "plans.h"
+namespace {
+#define MFFT_REG_NLP(N, ...) mfft::register_nlp<mfft::Spec<N, __VA_ARGS__>, double>("nlp n" #N "(" #__VA_ARGS__ ")double");
+mfft::PlanRegistrar registrar([] { MFFT_NLZPLANS_9(MFFT_REG_NLP) });
+}

@@ -160,6 +160,7 @@ constexpr NlProduct NL_PRODUCTS[] = {
     {Op::Quadratic, "quadratic", 6, 0, false, false, true},
     {Op::Increments, "increments", 6, 0, false, false},
     {Op::JointHistogram, "joint", 6, 0, false, false, true},       // (one or three PAIRS of fields: a_p with b_p)
+    {Op::Profiles, "profiles", 6, 0, false, false},                // (one or three PAIRS again; sums of doubles: no 2^32 limit)
 };
 inline const NlProduct& nl_product(Op op) {
   for (const NlProduct& q : NL_PRODUCTS)
@@ -194,12 +195,12 @@ bool nlz_supported(int64_t n, int prec, Op product = Op::Plain, bool absmax = fa
 int64_t nlz_absmax_waves(int64_t n, int prec, Op product, int64_t nrows);
 int launch_nlz(const NlzArgs& a, hipStream_t s);
 // The z stages that end in a REDUCTION instead of a product (the table entries with nout == 0; fft_nlz.h body_moments, body_hist,
-// body_joint, body_quad, body_incr), described ONCE: the launch, its shape, the loop over the rows and the routes of the plan read
+// body_joint, body_quad, body_incr, body_prof), described ONCE: the launch, its shape, the loop over the rows and the routes of the plan read
 // NlrArgs.  Pair p is the rows a[p] + i b[p] on one complex transform, p < npairs <= 3; b[p] may be null (an odd field count) except
-// in a joint histogram.  x = norm * (the un-normalised inverse transform).  Slots are [pair][a, b].
+// in a joint histogram and in a profile.  x = norm * (the un-normalised inverse transform).  Slots are [pair][a, b].
 // What a call of one kind adds to that -- the plan parks it between a call's begin and its batches (mfft_plan_s::nlcall):
 struct NlrCall {
-  double center[6] = {0, 0, 0, 0, 0, 0};   // Moments: S_p about center[slot]; Quadratic: about center[0]
+  double center[6] = {0, 0, 0, 0, 0, 0};   // Moments, Profiles: sums about center[slot]; Quadratic: about center[0]
   double lo[6] = {0, 0, 0, 0, 0, 0}, inv[6] = {1, 1, 1, 1, 1, 1};   // Histogram, JointHistogram: lower edge and bins / (hi - lo) per
                                                                     // slot; Quadratic: lo[0], inv[0] of q
   double w[6] = {0, 0, 0, 0, 0, 0};        // Quadratic: q = sum over the slots of w[slot] x^2
@@ -222,7 +223,8 @@ struct NlrArgs {
   int ngroups = 0;       // workgroups of the launch, from nlr_launch_shape(): nlr_rows sets it
   void* part = nullptr;  // the launch's partial results, nlr_part_bytes() of the shape of all rows: per wave NLS_SLOTS (Moments),
                          // INCR_SLOTS (Increments), NLS_STATS (Quadratic) doubles; per workgroup the unsigned counts (npairs, 2, nbins
-                         // + 3) (Histogram), (npairs, cells) (JointHistogram)
+                         // + 3) (Histogram), (npairs, cells) (JointHistogram); per ROW SLOT of a workgroup (npairs, 5, n) doubles
+                         // (Profiles: prof_part_bytes)
   void* part2 = nullptr; // Quadratic: per workgroup nbins + 3 unsigned counts of q, behind the doubles; nlr_rows sets it
   NlrCall call;
 };
@@ -265,6 +267,14 @@ constexpr int INCR_FIELD = MFFT_INCR_MAXSEP * 3, INCR_SLOTS = 6 * INCR_FIELD;
 int incr_fold(const double* part, size_t groups, int nvals, double* acc, hipStream_t s);
 // MFFT_ERR_INVALID for nsep outside 1 .. MFFT_INCR_MAXSEP or a separation outside 1 .. m - 1
 int incr_check(const int64_t* seps, int nsep, int64_t m);
+// Plane-averaged profiles along z (profiles.hip): per pair and position of the row the sums of d_a, d_b, d_a^2, d_b^2, d_a d_b over
+// all rows (fft_nlz.h prof_add).  acc: device doubles, (npairs, 5, n), pairs in slot order.
+// prof_fold: acc[v] += the nslots partial profiles part[g * nvals + v], added in a fixed order
+int prof_fold(const double* part, size_t nslots, size_t nvals, double* acc, hipStream_t s);
+// bytes of the partial profiles of a launch: one per row slot, ngroups x tile of them
+size_t prof_part_bytes(int ngroups, int tile, int npairs, int64_t n);
+// MFFT_ERR_INVALID for a centre that is not finite (center may be null: zeros)
+int prof_check(const double* center, int nfields);
 // max |x| reductions (absmax.hip): acc[s] = max(acc[s], scale * max_g part[g * period + s]), NaNs kept; `scratch` holds
 // absmax_fold_scratch_bytes(), `part` is in precision `prec`, acc in double
 size_t absmax_fold_scratch_bytes();

@@ -9,6 +9,7 @@ struct NlrShape {
   int ngroups = 0;        // workgroups of the launch: a workgroup takes 2 * tile rows per pass, then strides by the grid
   int64_t waves = 0;      // its waves (the kinds that sum doubles write one group of partial values per wave)
   int64_t max_rows = 0;   // rows ONE launch may take; a longer run of rows is split into launches of at most that many
+  int tile = 0;           // pairs of rows per workgroup = row slots of a workgroup (the profiles write one partial profile per row slot)
 };
 constexpr int64_t NLR_UNLIMITED = INT64_MAX;
 
@@ -18,6 +19,7 @@ constexpr int64_t NLR_UNLIMITED = INT64_MAX;
 // nothing wraps silently; a kind that sums doubles has no such limit.  false: one pass of a workgroup alone counts 2^32 values.
 inline bool nlr_shape(int tile, int threads, int64_t n, int cap, int64_t nrows, bool counts, NlrShape* out) {
   out->max_rows = NLR_UNLIMITED;
+  out->tile = tile;
   if (counts) {
     const int64_t per_pass = 2 * (int64_t)tile * n;                   // values per field of one workgroup's pass
     const int64_t passes = ((int64_t)1 << 32) / per_pass - 1;

@@ -9,7 +9,7 @@ using namespace mfft;
 #endif
 
 mfft_plan_s::~mfft_plan_s() {
-  for (Buf* b : {&work[0], &work[1], &work[2], &work3, &nlw[0], &nlw[1], &nlx, &nly, &nlr, &pcomp, &shl, &nlm, &nlmacc, &nlsacc, &nlhacc, &nlq, &nliacc, &nljacc, &nlr2})
+  for (Buf* b : {&work[0], &work[1], &work[2], &work3, &nlw[0], &nlw[1], &nlx, &nly, &nlr, &pcomp, &shl, &nlm, &nlmacc, &nlsacc, &nlhacc, &nlq, &nliacc, &nljacc, &nlr2, &nlpacc})
     if (b->p) (void)(b->arena ? wfree(b->p) : dev_free(b->p));
   if (mask) (void)hipFree(mask);
   if (band_tiles) (void)hipFree(band_tiles);
@@ -386,7 +386,7 @@ int mfft_plan_nonlinear_absmax(mfft_plan_t p, double out6[6]) {
   return p->nonlinear_absmax(out6);
 }
 
-// The five reductions: the plan on its device, a (and b, where given) of ncomp components, a known dealias mode -> the call's fields
+// The six reductions: the plan on its device, a (and b, where given) of ncomp components, a known dealias mode -> the call's fields
 static int reduce_fields(mfft_plan_t p, const void* a_hat, const void* b_hat, int ncomp, int dealias, NlFields* u) {
   MFFT_TRY(check_ready(p, a_hat, a_hat));
   if (ncomp != 1 && ncomp != 3) return set_error(MFFT_ERR_INVALID, "ncomp must be 1 or 3, not %d", ncomp);
@@ -445,6 +445,16 @@ int mfft_real_joint_histogram(mfft_plan_t p, const void* a_hat, const void* b_ha
   NlFields u;
   MFFT_TRY(reduce_fields(p, a_hat, b_hat, ncomp, dealias, &u));
   return p->real_joint_histogram(u, dealias, lo, hi, nba, nbb, out, count);
+}
+
+// per pair (ifftn(a_f), ifftn(b_f)) and per z index the five plane sums: see include/mpifft4py_amd.h
+int mfft_real_profiles(mfft_plan_t p, const void* a_hat, const void* b_hat, int ncomp, int dealias, const double* center, double* out,
+                       int64_t* count) {
+  if (!out || !count) return set_error(MFFT_ERR_INVALID, "null argument");
+  if (!b_hat) return set_error(MFFT_ERR_INVALID, "a profile takes pairs of fields: b_hat must not be NULL (it may be a_hat)");
+  NlFields u;
+  MFFT_TRY(reduce_fields(p, a_hat, b_hat, ncomp, dealias, &u));
+  return p->real_profiles(u, dealias, center, out, count);
 }
 
 int mfft_plan_sync(mfft_plan_t p) {

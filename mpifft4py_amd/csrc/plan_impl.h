@@ -133,6 +133,10 @@ struct mfft_plan_s {
   // mfft_real_increments / mfft_ew_increments (incr.hip): the sums in slot order, [slot][MFFT_INCR_MAXSEP][S2, S3, S4]; the partials
   // go to nlm.
   Buf nliacc{false, false};
+  // mfft_real_profiles / mfft_ew_profiles (profiles.hip): (npairs, 5, M) doubles, pairs in slot order, zeroed on the stream when a call
+  // starts; the partial profiles go to nlm -- one per row slot of the launch, (npairs, 5, M) doubles each, which the plan keeps as it
+  // keeps the joint grids.
+  Buf nlpacc{false, false};
   // The parameters of the reduction call that is running, in slot order (centres, ranges, weights, separations: whichever its kind
   // has), parked by its *_begin for the batches of the fused routes and the sweeps of the composed one.
   mfft::NlrCall nlcall;
@@ -579,6 +583,11 @@ struct mfft_plan_s {
   int incr_sweep(const void* x, int ncomp, int64_t nrows, int64_t n, int64_t pitch, double* acc);
   int incr_begin(const int64_t* seps, int nsep);
   int incr_end(double* host);
+  // profiles along z of one or three pairs, out: (npairs, 5, M).  center: 2 ncomp entries, a_0.., then b_0.. (null: zeros)
+  int real_profiles(const mfft::NlFields& u, int dealias, const double* center, double* out, int64_t* count);
+  int prof_sweep(const void* x, const void* y, int ncomp, int64_t nrows, int64_t n, const double* center, double* acc);
+  int prof_begin(const double center_slots[6], int npairs, int64_t n);
+  int prof_end(double* host, int npairs, int64_t n);
 };
 
 namespace mfft {

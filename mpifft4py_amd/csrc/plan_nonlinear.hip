@@ -22,7 +22,7 @@ extern "C" int mfft_ew_mul(mfft_plan_t plan, const void* a, const void* b, void*
 // 0..5 in place on the six inputs and 6..8 into three more fields of the batch, nine forward passes follow.
 // The routes read nin and nout from the table of products (mfft_internal.h NlProduct) and the caller's arrays through NlFields;
 // only the composed route, which chooses the element-wise products, names a product.
-// The REDUCTIONS are the table's entries with nout == 0 (moments, histograms, quadratic forms, increments, joint histograms): the
+// The REDUCTIONS are the table's entries with nout == 0 (moments, histograms, quadratic forms, increments, joint histograms, profiles): the
 // fused routes run their inverse passes and end the z stage in reduce_batch -- nothing forward is launched -- and a call is
 // real_reduce: mask, begin, fused or reduce_composed, end.  What a new kind supplies: its row of NL_PRODUCTS and its kernels'
 // registration; its members of NlrCall with their copy and checks in launch_nlr, its partials' size and its fold (core.hip); its
@@ -139,7 +139,7 @@ int mfft_plan_s::reduce_batch(Op kind, const NlFields& u, char* Y, size_t yelems
   MFFT_TRY(nlr_launch_shape(kind, L2, prec, nrows, &shape));
   MFFT_TRY(ensure(nlm, nlr_part_bytes(z, shape)));
   z.part = nlm.p;
-  Buf& acc = kind == Op::Histogram ? nlhacc : kind == Op::JointHistogram ? nljacc : kind == Op::Increments ? nliacc : nlsacc;
+  Buf& acc = kind == Op::Histogram ? nlhacc : kind == Op::JointHistogram ? nljacc : kind == Op::Increments ? nliacc : kind == Op::Profiles ? nlpacc : nlsacc;
   return nlr_rows(z, acc.p, nlhacc.p, stream);      // (the counts of a quadratic form: the second accumulator)
 }
 
@@ -419,9 +419,10 @@ int mfft_plan_s::real_reduce(const NlFields& u, int dealias, Op kind, int64_t* c
   return 0;
 }
 // Composed route: the statistics are per field, so ONE real work array serves the fields in turn -- inverse transform into nlr, the
-// kind's sweep, next field.  Two kinds keep a loop of their own: the quadratic form adds each field's term into the plan's ONE array
+// kind's sweep, next field.  Three kinds keep a loop of their own: the quadratic form adds each field's term into the plan's ONE array
 // of doubles, in slot order (the order the fused kernel adds in), and sweeps that once; the joint histogram needs a pair at a
-// time, a_p in nlr and b_p in nlr2 (two real work arrays, the least a pair can do with).
+// time, a_p in nlr and b_p in nlr2 (two real work arrays, the least a pair can do with); the profiles take the same two arrays and
+// sweep their rows along z (z is whole on every rank of a slab and of a pencil plan).
 int mfft_plan_s::reduce_composed(const NlFields& u, int dealias, Op kind) {
   const bool pad = dealias == MFFT_DEALIAS_3_2;
   const int64_t nr = local_real_count(pad), nc = local_complex_alloc(), M = pad ? M2 : N2;
@@ -437,6 +438,18 @@ int mfft_plan_s::reduce_composed(const NlFields& u, int dealias, Op kind) {
       MFFT_TRY(back(u.ncomp + p, nlr2));
       MFFT_TRY(stage("nl_joint", 2.0 * (double)nr * rs, [&] {
         return joint_sweep(nlr.p, nlr2.p, (size_t)nr, c.lo + 2 * p, c.inv + 2 * p, c.nba, c.nbb, acc + (size_t)p * joint_cells(c.nba, c.nbb));
+      }));
+    }
+    return 0;
+  }
+  if (kind == Op::Profiles) {
+    MFFT_TRY(ensure(nlr2, (size_t)nr * rs));
+    double* acc = static_cast<double*>(nlpacc.p);
+    for (int p = 0; p < u.ncomp; ++p) {
+      MFFT_TRY(back(p, nlr));
+      MFFT_TRY(back(u.ncomp + p, nlr2));
+      MFFT_TRY(stage("nl_profiles", 2.0 * (double)nr * rs, [&] {
+        return prof_sweep(nlr.p, nlr2.p, 1, nr / M, M, c.center + 2 * p, acc + (size_t)p * MFFT_PROFILE_STATS * (size_t)M);
       }));
     }
     return 0;
@@ -541,4 +554,21 @@ int mfft_plan_s::real_joint_histogram(const NlFields& u, int dealias, const doub
     l6[slot] = lo[f];
   }
   return real_reduce(u, dealias, Op::JointHistogram, count, [&] { return joint_begin(l6, i6, nba, nbb); }, [&] { return joint_end(out, u.ncomp); });
+}
+
+// per PAIR (x, y) = (ifftn(a_p), ifftn(b_p)) and per z index m the sums over the plane of d_x, d_y, d_x^2, d_y^2, d_x d_y, d = value -
+// centre (fft_nlz.h body_prof, prof_add); the pairs lie in slot order already
+int mfft_plan_s::real_profiles(const NlFields& u, int dealias, const double* center, double* out, int64_t* count) {
+  const bool pad = dealias == MFFT_DEALIAS_3_2;
+  const int64_t nr = local_real_count(pad), M = pad ? M2 : N2;
+  if (nr <= 0 || !r2c || M < 2 || nr % M != 0) return set_error(MFFT_ERR_UNSUPPORTED, "real_profiles needs a 3-D real-to-complex plan");
+  MFFT_TRY(prof_check(center, u.nfields));
+  double c6[6] = {0, 0, 0, 0, 0, 0};
+  for (int f = 0; center && f < u.nfields; ++f) c6[nls_slot(u, f)] = center[f];
+  std::vector<double> host((size_t)u.ncomp * MFFT_PROFILE_STATS * (size_t)M);      // (out is written on success only)
+  int64_t points = 0;
+  MFFT_TRY(real_reduce(u, dealias, Op::Profiles, &points, [&] { return prof_begin(c6, u.ncomp, M); }, [&] { return prof_end(host.data(), u.ncomp, M); }));
+  memcpy(out, host.data(), host.size() * sizeof(double));
+  *count = points / M;                             // points per plane on this rank
+  return 0;
 }

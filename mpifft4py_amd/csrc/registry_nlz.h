@@ -226,6 +226,20 @@ void register_nlj(const char* name) {
   reg.push_back(make_entry<K, NljParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::JointHistogram, Build::Default, R, name));
 }
 
+// Op::Profiles: the stage that ends in plane-averaged profiles along z (fft_nlz.h body_prof, NlpParams; kernels_nlp*.hip).  Rows,
+// twiddle placement, exchange, wave-synchronous build and the two-waves-per-SIMD cap are those of register_nls: the body inlines ONE
+// transform and holds ONE pair's accumulators across it, E x NLP_STATS doubles -- 40 for the 8-values plans, 60 for the 12-values
+// plans, where body_moments holds 36 and body_incr 48 --, and takes no LDS of its own (profiles/real_profiles_regs.tsv).  No other
+// cap was measured.
+template <class S, typename T>
+void register_nlp(const char* name) {
+  auto& reg = kernel_registry();
+  constexpr int R = nlz_rows<S, T>();
+  constexpr int W = MFFT_NLZ_OCC > 1 ? 16 + MFFT_NLZ_OCC : 0;
+  typedef NlzProf<NlzFft<S, T, R, nlz_twlds<S, T>(), nlz_split<S, T>(), nlz_wave<S, T>()>> K;
+  reg.push_back(make_entry<K, NlpParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::Profiles, Build::Default, R, name));
+}
+
 // ... and its pruned 3/2-rule flavour (Nlz3Fft: Build::Nlz3, entry.n = M = 3 L): three thread groups of SL::TPT threads per row
 template <class SL, typename T> constexpr int nlz3_rows() { return 256 / (3 * SL::TPT) > 0 ? 256 / (3 * SL::TPT) : 1; }
 template <class SL, typename T>

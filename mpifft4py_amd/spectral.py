@@ -873,6 +873,138 @@ def increments(FFT, u, seps=None, reduce=False):
     return _incr_result(FFT, np.concatenate(parts, axis=1), nrows * M, seps, M, reduce)
 
 
+PROFILE_STATS = 5       # sums per pair and z index (MFFT_PROFILE_STATS): d_a, d_b, d_a^2, d_b^2, d_a d_b
+
+
+def profile_rule(x, y, center=None):
+    """The rule of the profiles, in numpy float64 (include/mpifft4py_amd.h): x and y of shape (..., M) hold rows along their
+    last axis (normalised values, already double); with d_x = x - center[0], d_y = y - center[1] returns the five sums over all
+    rows [sum d_x, sum d_y, sum d_x^2, sum d_y^2, sum d_x d_y] per position, shape (5, M).  Products and sums in double."""
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    assert x.shape == y.shape, (x.shape, y.shape)
+    ca, cb = (0.0, 0.0) if center is None else (float(center[0]), float(center[1]))
+    M = x.shape[-1]
+    dx, dy = x.reshape(-1, M) - ca, y.reshape(-1, M) - cb
+    return np.stack([dx.sum(axis=0), dy.sum(axis=0), (dx * dx).sum(axis=0), (dy * dy).sum(axis=0), (dx * dy).sum(axis=0)])
+
+
+class Profiles(object):
+    """Raw plane sums along z of `npairs` pairs of real fields (x_p, y_p): `count` points per plane, `sums` of shape
+    (npairs, 5, M) with sums[p, :, m] = [sum d_x, sum d_y, sum d_x^2, sum d_y^2, sum d_x d_y] over the plane z = m,
+    d = value - center[p], and the `center` (npairs, 2) they were taken about.  The derived profiles are formed on the host in
+    np.longdouble from the raw sums, about the plane MEAN whatever the centre was."""
+
+    def __init__(self, count, sums, center):
+        self.count = int(count)
+        self.sums = np.asarray(sums, dtype=np.float64)
+        assert self.sums.ndim == 3 and self.sums.shape[1] == PROFILE_STATS, self.sums.shape
+        self.center = np.asarray(center, dtype=np.float64).reshape(self.sums.shape[0], 2)
+        self.M = int(self.sums.shape[2])
+
+    def _m(self, p):
+        return self.sums[p].astype(np.longdouble) / np.longdouble(self.count)
+
+    def mean(self, p=0):
+        """<x_p>(z), <y_p>(z): shape (2, M)."""
+        return self.center[p].astype(np.longdouble)[:, None] + self._m(p)[:2]
+
+    def variance(self, p=0):
+        """<x'^2>(z), <y'^2>(z) about the plane means: shape (2, M)."""
+        m = self._m(p)
+        return m[2:4] - m[:2] * m[:2]
+
+    def covariance(self, p=0):
+        """<x' y'>(z) about the plane means: shape (M,)."""
+        m = self._m(p)
+        return m[4] - m[0] * m[1]
+
+    def correlation(self, p=0):
+        """<x' y'> / sqrt(<x'^2> <y'^2>) per plane; nan where a variance is 0."""
+        v = self.variance(p)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where((v[0] > 0) & (v[1] > 0), self.covariance(p) / np.sqrt(np.abs(v[0] * v[1])), np.nan)
+
+    def flux(self, p=0):
+        """The raw <x y>(z), means included: the vertical heat flux <u_z theta>(z) of (u_z, theta)."""
+        m, (ca, cb) = self._m(p), self.center[p].astype(np.longdouble)
+        return m[4] + ca * m[1] + cb * m[0] + ca * cb
+
+    def z(self, FFT):
+        """The heights of the planes: m * L_z / M."""
+        return np.arange(self.M, dtype=np.float64) * float(FFT.L[2]) / self.M
+
+    @property
+    def finite(self):
+        """Per field (npairs, 2): all its own sums, sum d and sum d^2 at every z, are finite (the cross sum of a pair is finite
+        where both of its fields are)."""
+        f = np.isfinite(self.sums).all(axis=2)
+        return np.stack([f[:, 0] & f[:, 2], f[:, 1] & f[:, 3]], axis=1)
+
+
+def _profile_centers(center, ncomp):
+    """The centres in the order of the C interface, a_0.., then b_0..: `center` is None, (c_a, c_b) for all pairs, or of shape
+    (npairs, 2)."""
+    c = np.zeros((ncomp, 2), dtype=np.float64) if center is None else np.asarray(center, dtype=np.float64)
+    if c.shape == (2,):
+        c = np.tile(c, (ncomp, 1))
+    assert c.shape == (ncomp, 2), (c.shape, ncomp)
+    if not np.isfinite(c).all():
+        raise ValueError("the centres must be finite, not %r" % (c,))
+    return np.ascontiguousarray(c.T.ravel())
+
+
+def _profiles_result(FFT, sums, count, c, ncomp, reduce):
+    if reduce:      # sums and count: comm.allreduce adds in rank order, the same bits on every rank
+        tot = np.asarray(FFT.comm.allreduce(np.concatenate([sums.ravel(), [float(count)]])))
+        sums, count = tot[:-1].reshape(sums.shape), int(round(float(tot[-1])))
+    return Profiles(count, sums, c.reshape(2, ncomp).T)
+
+
+def real_profiles(FFT, a_hat, b_hat, dealias=None, center=None, reduce=True):
+    """Plane-averaged profiles along z of fields that exist as SPECTRA only (mfft_real_profiles): with x = ifftn(a_hat[p],
+    dealias), y = ifftn(b_hat[p], dealias), p over the 1 or 3 components, the five sums over every (x, y) plane of the real grid
+    [sum d_x, sum d_y, sum d_x^2, sum d_y^2, sum d_x d_y] for each of the M z indices (M = N[2], or 3 N[2] / 2 under the
+    3/2-rule) -- <theta>(z), <theta'^2>(z) and the heat flux <u_z theta>(z) of a stratified run, the mean profile and the
+    Reynolds stress of a Kolmogorov flow -- without a real array: on slab plans with radix kernels on every axis
+    (`FFT.plan_info("nonlinear_profiles_fused_3_2")`) a thread of the z kernel holds the same z positions for every row it meets,
+    so the plane sums are its running sums and need no exchange at all.  Elsewhere the plan transforms a_p and b_p into TWO real
+    work arrays and sweeps them.  z is whole on every rank.  b_hat may be a_hat.  `center`: None, (c_a, c_b) for all pairs or of
+    shape (npairs, 2); the sums are taken about it, and a centre near the mean keeps the digits of the variances.  Returns a
+    `Profiles`; with `reduce` the raw sums and the count are added over FFT.comm.  A NaN or Inf in a field gives sums of that
+    field that are not finite (`Profiles.finite`); the values are bitwise reproducible run to run, and are NOT claimed identical
+    for different numbers of ranks (they are sums of doubles).  Synchronises the plan's stream; the inputs are preserved."""
+    if b_hat is None:
+        raise ValueError("a profile takes pairs of fields: b_hat must be given (it may be a_hat)")
+    assert b_hat.shape == a_hat.shape, (a_hat.shape, b_hat.shape)
+    fields, ncomp, _, head = _real_fields(FFT, a_hat, b_hat)
+    c = _profile_centers(center, ncomp)
+    M = int(FFT.N[2]) * 3 // 2 if dealias == '3/2-rule' else int(FFT.N[2])
+    out = np.zeros((ncomp, PROFILE_STATS, M), dtype=np.float64)
+    count = ctypes.c_int64(0)
+    dp = ctypes.POINTER(ctypes.c_double)
+    _nonlinear(FFT, "real_profiles", fields, dealias, head=head, tail=(c.ctypes.data_as(dp), out.ctypes.data_as(dp), ctypes.byref(count)))
+    return _profiles_result(FFT, out, count.value, c, ncomp, reduce)
+
+
+def profiles(FFT, x, y, center=None, reduce=False):
+    """The same sums of two real DeviceArrays of the same shape along their LAST axis (mfft_ew_profiles, the companion of
+    `joint_histogram`): arrays of four axes are taken as (components, ..) with 1 or 3 components, pair p = (x[p], y[p]), any
+    other as one pair; M = x.shape[-1].  `center` as in `real_profiles`.  Returns a `Profiles`; with `reduce` over FFT.comm."""
+    if x.pitch is not None or y.pitch is not None:
+        raise ValueError("a profile of a pitched array would read the elements between its rows")
+    assert x.dtype == np.dtype(FFT.float) and y.dtype == x.dtype and x.shape == y.shape, (x.dtype, y.dtype, x.shape, y.shape)
+    ncomp = int(x.shape[0]) if len(x.shape) == 4 else 1
+    assert ncomp in (1, 3), ncomp
+    M = int(x.shape[-1])
+    nrows = x.size // (ncomp * M)
+    c = _profile_centers(center, ncomp)
+    FFT.comm.use_device()
+    out = np.zeros((ncomp, PROFILE_STATS, M), dtype=np.float64)
+    dp = ctypes.POINTER(ctypes.c_double)
+    _lib.call("mfft_ew_profiles", FFT._plan, x.ptr, y.ptr, ncomp, nrows, M, _prec(FFT), c.ctypes.data_as(dp), out.ctypes.data_as(dp))
+    return _profiles_result(FFT, out, nrows, c, ncomp, reduce)
+
+
 def strain_hat(FFT, K, U_hat, diag, off):
     """The strain-rate tensor S_ij = (du_i/dx_j + du_j/dx_i) / 2 of a vector field in spectral space (mfft_ew_strain_hat), U_hat
     read once: diag[f] = i K[f] U_hat[f] (S_00, S_11, S_22) and off = (S_01, S_02, S_12), S_ij = i (K[i] U_hat[j] + K[j] U_hat[i]) / 2.
