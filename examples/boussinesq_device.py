@@ -166,6 +166,17 @@ def profiles_summary(h):
     return (np.asarray(h.mean(0)[1], dtype=np.float64)[five], np.asarray(h.variance(0)[1], dtype=np.float64)[five], flux[five], float(flux.mean()))
 
 
+def print_spectrum2d(what, E, total):
+    """The two reduced spectra of E[k_perp, k_z], the share of the modes k_z = 0 (the 2-D, "vortical" ones) and the sum next to the
+    shell spectrum's."""
+    fmt = lambda v: ", ".join("%.6e" % c for c in v)
+    print("%s E(k_perp) = [%s]" % (what, fmt(E.sum(axis=1))))
+    print("%s E(k_z) = [%s]" % (what, fmt(E.sum(axis=0))))
+    print("%s share of k_z = 0: %.12f" % (what, E[:, 0].sum() / E.sum()))
+    ok = abs(E.sum() - total) <= 1e-12 * abs(total)
+    print("%s sum of E(k_perp, k_z) = %.15e: %s the sum of E(k) to 1e-12" % (what, E.sum(), "equals" if ok else "DIFFERS FROM"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--N", type=int, default=32, help="mesh edge")
@@ -174,6 +185,8 @@ def main():
                     "theta bins and the counted total, from ONE spectral.real_joint_histogram call on the spectra (no real-space array)")
     ap.add_argument("--profiles", action="store_true", help="print per step <theta>, <theta'^2> and the heat flux <u_z theta> at five heights z, "
                     "and the plane-mean of <u_z theta> next to the box value, from ONE spectral.real_profiles call on the spectra (no real-space array)")
+    ap.add_argument("--spectrum2d", action="store_true", help="print the final kinetic energy as E(k_perp) and E(k_z) -- gravity is along z --, the "
+                    "share of the modes k_z = 0 and the sum, from ONE spectral.energy_spectrum_2d call on the spectrum (no host copy of it)")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--dt", type=float, default=0.0, help="time step; default: inside the explicit scheme's stability bounds for this mesh")
     ap.add_argument("--nu", type=float, default=0.000625)
@@ -214,6 +227,8 @@ def main():
     Kw = spectral.Wavenumbers(FFT)
     print("kinetic energy: %.15e -> %.15e" % (spectral.energy_spectrum(FFT, Kw, U0).sum(), spectral.energy_spectrum(FFT, Kw, U).sum()))
     print("mean of theta: %.15e -> %.15e" % (th0.get()[0, 0, 0].real, th.get()[0, 0, 0].real))
+    if args.spectrum2d:
+        print_spectrum2d("kinetic energy", spectral.energy_spectrum_2d(FFT, Kw, U), spectral.energy_spectrum(FFT, Kw, U).sum())
 
 
 if __name__ == "__main__":

@@ -134,6 +134,8 @@ def main():
     ap.add_argument("--dealias", default="3/2-rule", choices=["3/2-rule", "2/3-rule", "None"])
     ap.add_argument("--precision", default="double")
     ap.add_argument("--composed", action="store_true", help="six ifftn, nine products and nine fftn per stage instead of one outer_transform")
+    ap.add_argument("--spectrum2d", action="store_true", help="print the final total energy as E(k_perp) and E(k_z) -- the mean field is along z --, "
+                    "the share of the modes k_z = 0 and the sum, from spectral.energy_spectrum_2d on the spectra (no host copy of them)")
     args = ap.parse_args()
     dealias = None if args.dealias == "None" else args.dealias
     # RK4 is explicit: nu |k|^2 dt and |z| |k| dt must stay inside its stability region (|z| <= 3.2 + B0 here)
@@ -145,7 +147,7 @@ def main():
     rep, trace = {}, []
     Kw = spectral.Wavenumbers(FFT)
     e0 = energies(FFT, Kw, Zp0, Zm0)
-    solve(comm, args.N, Zp0, Zm0, args.nu, args.eta, dt, args.steps, dealias, fused=not args.composed, precision=args.precision,
+    Zp, Zm = solve(comm, args.N, Zp0, Zm0, args.nu, args.eta, dt, args.steps, dealias, fused=not args.composed, precision=args.precision,
           report=rep, FFT=FFT, trace=trace)
     print("N = %d^3, %d RK4 steps of dt = %.3g, %.3f ms per step (%s; plan work buffers %.2f GB)"
           % (args.N, args.steps, dt, rep["ms_per_step"],
@@ -155,6 +157,15 @@ def main():
     print("step %4d  total energy %.15e  cross helicity %.15e" % ((0,) + e0))
     for i, (e, h) in enumerate(trace):
         print("step %4d  total energy %.15e  cross helicity %.15e" % (i + 1, e, h))
+    if args.spectrum2d:      # total energy = (<|z+|^2> + <|z-|^2>) / 4, as in energies()
+        E = 0.5 * (spectral.energy_spectrum_2d(FFT, Kw, Zp) + spectral.energy_spectrum_2d(FFT, Kw, Zm))
+        fmt = lambda v: ", ".join("%.6e" % c for c in v)
+        print("total energy E(k_perp) = [%s]" % fmt(E.sum(axis=1)))
+        print("total energy E(k_z) = [%s]" % fmt(E.sum(axis=0)))
+        print("total energy share of k_z = 0: %.12f" % (E[:, 0].sum() / E.sum()))
+        total = energies(FFT, Kw, Zp, Zm)[0]
+        ok = abs(E.sum() - total) <= 1e-12 * abs(total)
+        print("total energy sum of E(k_perp, k_z) = %.15e: %s the sum of E(k) to 1e-12" % (E.sum(), "equals" if ok else "DIFFERS FROM"))
 
 
 if __name__ == "__main__":

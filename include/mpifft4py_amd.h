@@ -684,6 +684,49 @@ MFFT_API int mfft_ew_shell_sums(mfft_plan_t plan, const void* a, const void* b, 
                                 const void* kz, int k2, const int64_t shape[3], int nshell, int precision,
                                 double* result_host);
 
+/* (k_perp, k_z) sums of device-resident spectra: cylindrical bins, for flows with one special direction (z: gravity, a mean
+ * field).  THE RULE, which the kernel, the Python layer and the tests quote: for a local spectral block of shape (s0, s1, s2),
+ * z contiguous and s2 the row length as it lies in memory (the pitch, where the spectrum is pitched),
+ *   R[p, q] = sum over the local modes k with  shell(kx^2 + ky^2) = p  and  |kz| = q
+ *             of  h(k) w(k) sum_c Re(conj(a_c[k]) b_c[k]),      0 <= p < nperp, 0 <= q < npar.
+ * shell is the integer rule of mfft_ew_shell_sums applied to m = kx^2 + ky^2 of the INTEGER wave numbers; |kz| is taken from
+ * ikz[z], which covers the half axis of the real transforms and the full axis of the complex slab plan, where kz and -kz share
+ * a bin; h = hz[z] is the Hermitian weight along z, and its 0 between pitched rows means "skip, whatever lies there";
+ * w = kx^2 + ky^2 + kz^2 of the scaled wave numbers, squared in double, with k2, else 1 (kx, ky, kz may then be null); ncomp is
+ * 1 or 3, components shape[0] * shape[1] * shape[2] elements apart; b may be a, which is then read once.  Products and sums are
+ * in double whatever `precision`.  For the global mesh nperp = shell((N0/2)^2 + (N1/2)^2) + 1 and npar = N2/2 + 1 (integer
+ * halves); the result is nperp x npar doubles, row-major; its sum is the Parseval sum, that of mfft_ew_shell_sums' result; its
+ * row sums are the k_perp spectrum and its column sums the k_z spectrum.
+ *
+ * The perp bin is constant along a memory row and the z bin is the position in the row, so R is a sum of rows grouped by a
+ * key the host knows (csrc/cylspec.hip): `rows` holds the local rows l * s1 + j sorted by (perp shell, l, j) and
+ * row_start[p] .. row_start[p + 1] are shell p's entries (nperp + 1 offsets; a shell without local rows is empty and its bins
+ * come back as 0.0).  Every list is cut into segments of at most seg_rows rows (0: MFFT_CYL_SEG_ROWS); a wave sums one
+ * (segment, run of z positions) in registers and stores it once; a second kernel adds the partial rows in fixed order.  No
+ * atomics on global memory; bitwise reproducible run to run for a given seg_rows.  Every lane loads 16 bytes; in single
+ * precision that needs every row to start at a multiple of 16 bytes (a, b 16-byte aligned and s2 even) -- otherwise, as for
+ * the compact rows of N2/2 + 1 elements with N2/2 even, the call is as correct and loads 8 bytes per lane.  The partial rows
+ * live in a buffer of the plan: segments * s2 + nperp * npar doubles. */
+#define MFFT_CYL_SEG_ROWS 256
+
+/* Host only, no device call: the lists of mfft_ew_cyl_sums for a block whose integer wave numbers along x and y are
+ * ikx_host[s0], iky_host[s1].  rows_out: s0 * s1 entries; row_start_out: nperp + 1.  MFFT_ERR_INVALID for null arguments, an
+ * empty block and a row whose shell is >= nperp. */
+MFFT_API int mfft_cyl_row_lists(const int32_t* ikx_host, const int32_t* iky_host, int64_t s0, int64_t s1, int nperp,
+                                int32_t* rows_out, int32_t* row_start_out);
+
+/* result_host receives THIS RANK's nperp * npar partial sums (the caller adds the ranks'); the call synchronises the plan's
+ * stream.  rows_dev is on the device, row_start_host on the host; ikz, hz, kx, ky, kz, shape as for mfft_ew_shell_sums.
+ * Reported before anything is enqueued, result_host untouched: MFFT_ERR_INVALID for null arguments (the plan included), ncomp
+ * not 1 or 3, an unknown precision, nperp or npar < 1, seg_rows < 0, an empty block, k2 without the scaled vectors, and a
+ * row_start that does not begin at 0, is not monotone or does not end at shape[0] * shape[1].  A mode with weight whose |kz| is
+ * >= npar, and an entry of rows_dev that is no row of the block, are found on the device (nothing is loaded or stored out of
+ * range) and reported as MFFT_ERR_INVALID, result_host untouched. */
+MFFT_API int mfft_ew_cyl_sums(mfft_plan_t plan, const void* a, const void* b, int ncomp, const int32_t* rows_dev,
+                              const int32_t* row_start_host, int nperp, const int32_t* ikz, const uint8_t* hz, const void* kx,
+                              const void* ky, const void* kz, int k2, const int64_t shape[3], int npar, int seg_rows,
+                              int precision, double* result_host);
+
 /* ---- HIP-event timers on the default stream (bench.py) ------------------ */
 typedef struct mfft_timer_s* mfft_timer_t;
 MFFT_API int mfft_timer_create(mfft_timer_t* t);

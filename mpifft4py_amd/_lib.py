@@ -6,7 +6,7 @@ the oracle, or torch.
 """
 import ctypes
 import os
-from ctypes import (POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_size_t,
+from ctypes import (POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t,
                     c_uint64, c_uint8, c_void_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -161,6 +161,9 @@ _SIGNATURES = {
                           POINTER(c_int64), c_int, POINTER(c_double)], c_int),
     "mfft_ew_shell_sums": ([c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_void_p, c_int, POINTER(c_int64), c_int, c_int, POINTER(c_double)], c_int),
+    "mfft_cyl_row_lists": ([POINTER(c_int32), POINTER(c_int32), c_int64, c_int64, c_int, POINTER(c_int32), POINTER(c_int32)], c_int),
+    "mfft_ew_cyl_sums": ([c_void_p, c_void_p, c_void_p, c_int, c_void_p, POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                          c_void_p, c_int, POINTER(c_int64), c_int, c_int, c_int, POINTER(c_double)], c_int),
     "mfft_timer_create": ([POINTER(c_void_p)], c_int),
     "mfft_timer_start": ([c_void_p], c_int),
     "mfft_timer_stop": ([c_void_p, POINTER(c_float)], c_int),

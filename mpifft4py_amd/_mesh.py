@@ -150,6 +150,24 @@ class Block(object):
         """Per axis the integer wave numbers of the block's spectral window as int32 (`mode_vectors`)."""
         return [np.ascontiguousarray(k, dtype=np.int32) for k in self.mode_vectors()]
 
+    # ---- (k_perp, k_z) spectra (spectral.cyl_sums) -----------------------------------------------------------------------
+    def perp_shell_count(self):
+        """Number of perp shells of the GLOBAL mesh, the corner rows included: shell((N0 // 2)^2 + (N1 // 2)^2) + 1."""
+        return int(self.shell_of((self.N[0] // 2) ** 2 + (self.N[1] // 2) ** 2)) + 1
+
+    def perp_row_lists(self):
+        """(rows, row_start) of the block's spectral window for mfft_ew_cyl_sums: `rows` holds the local rows l * s1 + j sorted by
+        (shell(kx^2 + ky^2), l, j), int32; row_start[p] .. row_start[p + 1] are the entries of shell p, int32 of
+        perp_shell_count() + 1 offsets.  A shell without a local row is empty."""
+        assert self.nd == 3
+        kx, ky = self.mode_vectors()[:2]
+        sh = self.shell_of(kx[:, None] ** 2 + ky[None, :] ** 2).reshape(-1)
+        nperp = self.perp_shell_count()
+        assert sh.size < 2 ** 31 and (sh.size == 0 or sh.max() < nperp)
+        rows = np.argsort(sh, kind="stable").astype(np.int32)        # stable: (l, j) order inside a shell
+        start = np.concatenate([[0], np.cumsum(np.bincount(sh, minlength=nperp))]).astype(np.int32)
+        return rows, start
+
     def hermitian_weights(self):
         """uint8 weights along the last axis of the block's spectral window: on the half axis of a real transform 1
         for k = 0 and for the Nyquist mode of an even axis, 2 for the modes whose conjugate partners are not stored;

@@ -13,7 +13,9 @@ from .device import DeviceArray
 
 class Wavenumbers(object):
     """Scaled local wavenumbers (2*pi/L * k) of an FFT object's complex layout; for the shell spectra (`shell_sums`) of
-    3-D plans also the integer ones (`idev`, int32), the Hermitian weights along z (`hdev`, uint8) and `nshell`."""
+    3-D plans also the integer ones (`idev`, int32), the Hermitian weights along z (`hdev`, uint8) and `nshell`.  For the
+    (k_perp, k_z) spectra (`cyl_sums`) `nperp`, `npar`, `perp_rows` (device, int32) and `perp_start` (host, int32) are built on
+    first use: the rows of the block sorted by perp shell (`_mesh.Block.perp_row_lists`)."""
 
     def __init__(self, FFT):
         K = FFT.get_local_wavenumbermesh(scaled=True)
@@ -38,6 +40,21 @@ class Wavenumbers(object):
             self.idev = [DeviceArray.from_numpy(v) for v in ivecs]
             self.hdev = DeviceArray.from_numpy(h)
             self.nshell = mesh.shell_count()
+        self._mesh = mesh if self.idev is not None else None
+        self._perp = None
+
+    def _perp_lists(self):
+        if self._perp is None:
+            if self._mesh is None:
+                raise NotImplementedError("(k_perp, k_z) spectra need a 3-D plan (slab or pencil)")
+            rows, start = self._mesh.perp_row_lists()
+            self._perp = (self._mesh.perp_shell_count(), self._mesh.N[2] // 2 + 1, DeviceArray.from_numpy(rows), start)
+        return self._perp
+
+    nperp = property(lambda self: self._perp_lists()[0])
+    npar = property(lambda self: self._perp_lists()[1])
+    perp_rows = property(lambda self: self._perp_lists()[2])
+    perp_start = property(lambda self: self._perp_lists()[3])
 
 
 def _prec(FFT):
@@ -1115,3 +1132,42 @@ def energy_spectrum(FFT, K, U_hat):
 def transfer_spectrum(FFT, K, U_hat, N_hat):
     """T[s] = shell_sums(U_hat, N_hat) / (N0 N1 N2)^2 = Re <U_hat*, N_hat> per shell."""
     return shell_sums(FFT, K, U_hat, N_hat) / _points(FFT) ** 2
+
+
+def cyl_sums(FFT, K, a_hat, b_hat=None, k2=False, reduce=True, seg_rows=0):
+    """(k_perp, k_z) sums of spectra on the device (mfft_ew_cyl_sums; the rule of include/mpifft4py_amd.h):
+        R[p, q] = sum over the modes k with shell(kx^2 + ky^2) = p and |kz| = q of  h(k) w(k) sum_c Re(conj(a_hat_c[k]) b_hat_c[k])
+    shell the integer rule of `shell_sums` applied to the two perpendicular integer wave numbers, h the Hermitian weight of the
+    half axis, w = |K|^2 of the scaled wave numbers with k2, else 1.  a_hat, b_hat (default a_hat, read once): DeviceArrays of
+    FFT.complex_shape() or (3,) + that.  Returns a float64 array of shape (K.nperp, K.npar), added over FFT.comm with `reduce`:
+    R.sum(axis=1) is the k_perp spectrum, R.sum(axis=0) the k_z spectrum (R[:, 0] the 2-D modes), R.sum() the Parseval sum,
+    shell_sums(...).sum().  Products and sums in double whatever the precision; bitwise reproducible run to run; synchronises
+    the plan's stream.  seg_rows: rows per partial sum, 0 for the library's default (tests)."""
+    if getattr(getattr(FFT, "_mesh", None), "nd", 0) != 3 or K is None or K.idev is None:
+        raise NotImplementedError("(k_perp, k_z) spectra need a 3-D plan (slab or pencil), not %s" % type(FFT).__name__)
+    if b_hat is None:
+        b_hat = a_hat
+    cs = tuple(int(x) for x in FFT.complex_shape())
+    assert a_hat.shape in (cs, (3,) + cs), (a_hat.shape, cs)
+    for x in (a_hat, b_hat):
+        assert x.shape == a_hat.shape and x.dtype == np.dtype(FFT.complex), (x.shape, x.dtype, a_hat.shape)
+        FFT._check_pitch(x, FFT.complex_pitch)
+    FFT.comm.use_device()
+    out = np.zeros((K.nperp, K.npar), dtype=np.float64)
+    _lib.call("mfft_ew_cyl_sums", FFT._plan, a_hat.ptr, b_hat.ptr, 3 if len(a_hat.shape) == 4 else 1, K.perp_rows.ptr,
+              K.perp_start.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), K.nperp, K.idev[2].ptr, K.hdev.ptr, K.dev[0].ptr,
+              K.dev[1].ptr, K.dev[2].ptr, 1 if k2 else 0, K.cshape, K.npar, int(seg_rows), _prec(FFT),
+              out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    return FFT.comm.allreduce(out) if reduce else out
+
+
+def energy_spectrum_2d(FFT, K, U_hat):
+    """E[p, q] = cyl_sums(U_hat, U_hat) / (2 (N0 N1 N2)^2), the normalisation of `energy_spectrum`: E.sum() is the mean kinetic
+    energy, E.sum(axis=1) the k_perp spectrum, E.sum(axis=0) the k_z spectrum, E[:, 0].sum() the energy of the modes k_z = 0."""
+    return cyl_sums(FFT, K, U_hat) / (2.0 * _points(FFT) ** 2)
+
+
+def transfer_spectrum_2d(FFT, K, U_hat, N_hat):
+    """T[p, q] = cyl_sums(U_hat, N_hat) / (N0 N1 N2)^2, the normalisation of `transfer_spectrum`: T.sum(axis=1) is the transfer
+    across k_perp, T.sum(axis=0) the transfer across k_z."""
+    return cyl_sums(FFT, K, U_hat, N_hat) / _points(FFT) ** 2

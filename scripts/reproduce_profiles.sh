@@ -139,6 +139,9 @@ run() {
       rocprofv3 --kernel-trace --stats --output-format csv -d out/shell_trace -- python scripts/shell_spectrum_ab.py --worker --cases 512:double,1024:double,1024:single
       rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d out/shell_pmc -- python scripts/shell_spectrum_ab.py --worker --cases 512:double
       python scripts/shell_spectrum_ab.py --out out/shell_spectrum_ab.txt --append-profiles out/shell_trace out/shell_pmc ;;
+    cyl_spectrum_ab.txt) python scripts/cyl_spectrum_ab.py --procs 3 --segs 64,128,256,512 --out out/cyl_spectrum_ab.txt
+      # its last section: the cyl_ and shell_ lines of the kernels' trace statistics, from a run of their own
+      rocprofv3 --kernel-trace --stats --output-format csv -d out/cyl_trace -- python scripts/cyl_spectrum_ab.py --worker --cases 512:double,1024:double ;;
     *) echo "no recipe for $1" >&2; return 1 ;;
   esac
 }
