@@ -30,7 +30,7 @@ def _zero(a):
 
 def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double", nu=0.000625, dt=0.01, steps=10,
           report=None, fused=True, timing=False, complex_pitch="default", edge=None, spectrum=False, cfl=None, dt_max=None,
-          stats=False, pdf=False, dissipation=False, structure=False):
+          stats=False, pdf=False, dissipation=False, structure=False, structure_pdf=False):
     """fused=True (round 6): the nonlinear term is ONE plan operation (spectral.cross_transform: no real-space work
     arrays, the z stages one kernel) and a Runge-Kutta stage's projection, viscous term, both updates and the next
     curl are ONE sweep (spectral.ns_rk_stage).  fused=False: the composition of rounds 3 - 5 (nine transforms, cross,
@@ -55,7 +55,11 @@ def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double
     default separations (the powers of two below M / 2, then M / 2) -- a two-point statistic of fields that exist as spectra only
     (spectral.real_increments: the z kernel reads the real row back shifted, no real-space array): report["structure"] lists the
     spectral.Increments and rank 0 prints S_2 of u_0 (transverse) and of u_2 (longitudinal: the increment runs along z) and the
-    skewness and flatness of the longitudinal increment."""
+    skewness and flatness of the longitudinal increment.
+    structure_pdf=True (fused loop): of the final state, the PDFs of the velocity increments along z at the same separations, 128 bins
+    over +-10 standard deviations of each (spectral.real_increment_histogram: the z kernel counts the shifted differences into LDS, no
+    real-space array): report["structure_pdf"] = (IncrementHistogram, Increments) and rank 0 prints, per separation, the flatness of
+    the longitudinal increment obtained from the PDF next to the one from the power sums of spectral.real_increments."""
     if complex_pitch == "default":       # the fused loop on ONE rank keeps its spectra pitched (rows a whole number of cache lines
         # apart: every pass runs on them); several ranks and the composition of rounds 3 - 5 keep compact rows
         complex_pitch = "auto" if (fused and comm.Get_size() == 1) else None
@@ -69,7 +73,7 @@ def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double
         raise ValueError("pdf needs the fused loop")
     if dissipation and not fused:
         raise ValueError("dissipation needs the fused loop")
-    if structure and not fused:
+    if (structure or structure_pdf) and not fused:
         raise ValueError("structure needs the fused loop")
     if decomposition == 'slab':
         FFT = Slab_R2C(N, L, comm, precision, complex_pitch=complex_pitch)
@@ -188,6 +192,18 @@ def solve(comm, M=5, dealias='3/2-rule', decomposition='slab', precision="double
             dissipation_report("final", bins=32 if pdf else 0)
         if structure:
             structure_report("final")
+        if structure_pdf:                                       # (collective: the sums for sigma, then the histograms)
+            inc = spectral.real_increments(FFT, U_hat, None, dealias)
+            ih = spectral.real_increment_histogram(FFT, U_hat, None, dealias, seps=list(inc.seps), bins=128, sigmas=10.0)
+            if report is not None:
+                report["structure_pdf"] = (ih, inc)
+            if comm.Get_rank() == 0:
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    fp = ih.moment(4)[2] / ih.moment(2)[2] ** 2
+                fs = inc.flatness()[2]
+                for i, sep in enumerate(inc.seps):
+                    print("structure-pdf s = %d  flatness from the PDF %.9f  from the sums %.9f  (outside the range: %.3e)"
+                          % (int(sep), float(fp[i]), float(fs[i]), float(ih.raw[2, i, [0, -2, -1]].sum()) / ih.count))
         for i in range(3):
             FFT.ifftn(U_hat.component(i), U.component(i))
         return FFT.comm.reduce(spectral.sumsq(FFT, U) / float(N[0]) / float(N[1]) / float(N[2]) / 2)
@@ -267,6 +283,9 @@ def main():
     ap.add_argument("--structure", action="store_true", help="print before every step and of the final state the structure functions along z "
                     "at the separations 1, 2, 4, .. M / 2: S_2 of u_0 and u_2 and the skewness and flatness of the longitudinal increment "
                     "of u_2, from the spectra (spectral.real_increments: no real-space array)")
+    ap.add_argument("--structure-pdf", action="store_true", help="print of the final state, per separation, the flatness of the longitudinal "
+                    "increment of u_2 from its PDF (128 bins over +-10 sigma) next to the one from the power sums, both from the spectra "
+                    "(spectral.real_increment_histogram, spectral.real_increments: no real-space array)")
     args = ap.parse_args()
     dealias = None if args.dealias == "None" else args.dealias
     from mpifft4py_amd import LocalGroup, SelfComm
@@ -275,11 +294,11 @@ def main():
         ks = LocalGroup(args.ranks).run(lambda c: solve(c, args.M, dealias, steps=args.steps, precision=args.precision,
                                                         report=rep if c.Get_rank() == 0 else None, fused=not args.composed,
                                                         timing=args.stages, complex_pitch=None if args.compact else "default",
-                                                        edge=args.N or None, spectrum=args.spectrum, cfl=args.cfl, dt_max=args.dt_max, stats=args.stats, pdf=args.pdf, dissipation=args.dissipation, structure=args.structure))
+                                                        edge=args.N or None, spectrum=args.spectrum, cfl=args.cfl, dt_max=args.dt_max, stats=args.stats, pdf=args.pdf, dissipation=args.dissipation, structure=args.structure, structure_pdf=args.structure_pdf))
     else:
         ks = [solve(SelfComm(), args.M, dealias, steps=args.steps, precision=args.precision, report=rep,
                     fused=not args.composed, timing=args.stages, complex_pitch=None if args.compact else "default",
-                    edge=args.N or None, spectrum=args.spectrum, cfl=args.cfl, dt_max=args.dt_max, stats=args.stats, pdf=args.pdf, dissipation=args.dissipation, structure=args.structure)]
+                    edge=args.N or None, spectrum=args.spectrum, cfl=args.cfl, dt_max=args.dt_max, stats=args.stats, pdf=args.pdf, dissipation=args.dissipation, structure=args.structure, structure_pdf=args.structure_pdf)]
     print("N = %d^3, %d RK4 steps, %.3f ms per step (%s, device-resident; plan work buffers %.2f GB)"
           % (args.N or 2 ** args.M, args.steps, rep.get("ms_per_step", float("nan")),
              "composed: 36 transforms + element-wise kernels" if args.composed else

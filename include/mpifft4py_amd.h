@@ -364,6 +364,30 @@ MFFT_API int64_t mfft_nlz_quad_groups(int64_t nrows, int64_t n, int precision);
 MFFT_API int mfft_nlz_incr_rows(const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
                                 int64_t valid_in, int precision, const int64_t* seps, int nsep, double* out);
 MFFT_API int64_t mfft_nlz_incr_groups(int64_t nrows, int64_t n, int precision);
+/* Increment PDFs along z: the ONE rule that the fused kernel, the sweep, the emulator, numpy (spectral.incr_hist_rule) and the tests
+ * share.  For a real z row of length M and a separation s, 1 <= s <= M - 1, periodic:
+ *     r(z) = (double)v(z) * norm          the increments' value rule above (one rounded product; a real array: r = (double)x)
+ *     d    = r((z + s) mod M) - r(z)      in double
+ *     slot = the histograms' unchanged slot rule applied to d with lo[f][i], inv[f][i] = nbins / (hi[f][i] - lo[f][i]):
+ *            d is NaN -> nbins + 2;  t = (d - lo) * inv;  t < 0 -> 0;  t >= nbins -> nbins + 1;  else 1 + (int)t
+ * Every field f and every separation i has its own lo < hi.  Per (field, separation) the result is nbins + 3 int64 counts: below lo,
+ * the nbins equal bins of [lo, hi), at or above hi, not finite; they always sum to the points.  1 <= nbins <=
+ * MFFT_INCR_HIST_MAXBINS, at most MFFT_INCR_MAXSEP separations per launch (duplicates allowed), increments along z only.  Counts
+ * are integers: the same bits run to run and for every number of ranks that computes the same values. */
+#define MFFT_INCR_HIST_MAXBINS 256
+/* The z stage that ends in increment histograms (csrc/fft_nlz.h body_incr_hist), synchronous: the counts of the increments of the
+ * real rows irfft(row, n) without the real rows.  Fields, rows, valid and valid_in as mfft_nlz_moments_rows; lo, hi: [(f * nsep + i)],
+ * fields in the order a_0.., then b_0..; out[(f * nsep + i) * (nbins + 3) + slot].  No global atomics: a workgroup counts in LDS,
+ * stores its rows by plain stores, one fold in fixed order into int64.  A thread whose load took a NaN or Inf bin out of a field
+ * counts its own increments of THAT field in slot nbins + 2; the partner on the same transform keeps its exact counts.
+ * MFFT_ERR_INVALID for nbins outside 1 .. MFFT_INCR_HIST_MAXBINS, nsep outside 1 .. MFFT_INCR_MAXSEP, any seps[i] < 1 or >= n, hi <=
+ * lo or a range that is not finite, valid > n / 2 + 1; MFFT_ERR_UNSUPPORTED for lengths without a kernel; reported before anything is
+ * enqueued, the outputs untouched.  The z stage of mfft_real_increment_histogram on its own, for tests.
+ * mfft_nlz_incr_hist_groups: the workgroups of that launch (it strides over the rows; 0: no kernel of that length). */
+MFFT_API int mfft_nlz_incr_hist_rows(const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
+                                     int64_t valid_in, int precision, const int64_t* seps, int nsep, const double* lo, const double* hi,
+                                     int nbins, int64_t* out);
+MFFT_API int64_t mfft_nlz_incr_hist_groups(int64_t nrows, int64_t n, int precision);
 /* Plane-averaged profiles along z: the rule that the fused kernel, the sweep, the emulator and the tests share.  For a pair of real
  * fields (x, y), the centres (ca, cb) and every z index m of the real row of length M (N2 for dealias None and the 2/3-rule,
  * 3 N2 / 2 for the 3/2-rule), over all rows -- a row is one (x, y) point, so over the plane z = m:
@@ -565,6 +589,30 @@ MFFT_API int mfft_ew_increments(mfft_plan_t plan, const void* x, int ncomp, int6
  * reported before anything is enqueued.  The inputs are preserved.  Synchronises the plan's stream. */
 MFFT_API int mfft_real_increments(mfft_plan_t plan, const void* a_hat, const void* b_hat, int ncomp, int dealias, const int64_t* seps,
                                   int nsep, double* out, int64_t* count);
+
+/* out_host[(c * nsep + i) * (nbins + 3) + slot]: the counts of the increments along the rows of a real device array of ncomp x
+ * nrows rows of n elements, row_pitch elements apart (>= n; component c starts c * nrows * row_pitch elements in), ncomp = 1, 2, 3
+ * or 6, in the plan's precision, by the rule of the increment PDFs above with norm = 1; lo, hi: [(c * nsep + i)].  One sweep: a
+ * workgroup takes a stripe of rows, stages each row in LDS, reads the shifted values from LDS and counts into an LDS histogram of its
+ * own -- every element is read from memory once, no 64-bit division per element; partial histograms by plain stores, one fold in
+ * fixed order, no global atomics.  Errors as mfft_nlz_incr_hist_rows (any n >= 2 is supported).  The plan must not be null;
+ * synchronises the plan's stream. */
+MFFT_API int mfft_ew_increment_histogram(mfft_plan_t plan, const void* x, int ncomp, int64_t nrows, int64_t n, int64_t row_pitch,
+                                         int precision, const int64_t* seps, int nsep, const double* lo, const double* hi, int nbins,
+                                         int64_t* out_host);
+
+/* Increment PDFs of fields that exist as spectra only: for the ncomp (1 or 3) components of a_hat and, where b_hat is not NULL, of
+ * b_hat -- 1, 2, 3 or 6 fields, in that order -- out[(f * nsep + i) * (nbins + 3) + slot] = the counts of the increments of x =
+ * ifftn(field f, dealias) along z at the separation seps[i] in nbins equal bins of [lo[f * nsep + i], hi[f * nsep + i]), by the rule
+ * above, over THIS RANK's part of the real-space grid (as mfft_real_increments: z is local to a rank, no halo), *count = the points
+ * per field.  Routes (mfft_plan_get_info "nonlinear_incr_hist_fused_3_2" / "_none" / "_2_3"): fused, the z kernel keeps the real row
+ * in its exchange buffer, reads it back shifted and counts into LDS (csrc/fft_nlz.h body_incr_hist), no real-space array exists;
+ * every other plan transforms one field at a time into ONE real work array and sweeps it (mfft_ew_increment_histogram).  The fused
+ * counts are the same for every number of ranks.  Errors as mfft_nlz_incr_hist_rows with n = M, reported before anything is
+ * enqueued, out and count untouched.  The inputs are preserved.  Synchronises the plan's stream. */
+MFFT_API int mfft_real_increment_histogram(mfft_plan_t plan, const void* a_hat, const void* b_hat, int ncomp, int dealias,
+                                           const int64_t* seps, int nsep, const double* lo, const double* hi, int nbins, int64_t* out,
+                                           int64_t* count);
 
 /* out_host[(c * 5 + s) * n + m]: the five sums of the pairs (x[c, r, m], y[c, r, m]) over the nrows rows r of two real device
  * arrays (ncomp, nrows, n) of equal shape, ncomp = 1 or 3, rows contiguous, in the plan's precision, by the rule above with norm

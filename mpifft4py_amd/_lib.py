@@ -109,6 +109,9 @@ _SIGNATURES = {
     "mfft_nlz_incr_rows": ([c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, POINTER(c_int64), c_int,
                             POINTER(c_double)], c_int),
     "mfft_nlz_incr_groups": ([c_int64, c_int64, c_int], c_int64),
+    "mfft_nlz_incr_hist_rows": ([c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, POINTER(c_int64), c_int,
+                                 POINTER(c_double), POINTER(c_double), c_int, POINTER(c_int64)], c_int),
+    "mfft_nlz_incr_hist_groups": ([c_int64, c_int64, c_int], c_int64),
     "mfft_nlz_profile_rows": ([c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, POINTER(c_double),
                                POINTER(c_double)], c_int),
     "mfft_nlz_profile_groups": ([c_int64, c_int64, c_int], c_int64),
@@ -155,6 +158,11 @@ _SIGNATURES = {
     "mfft_ew_strain_hat": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_int], c_int),
     "mfft_ew_increments": ([c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int, POINTER(c_int64), c_int, POINTER(c_double)], c_int),
     "mfft_real_increments": ([c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int64), c_int, POINTER(c_double), POINTER(c_int64)], c_int),
+    # increment PDFs (include/mpifft4py_amd.h: the rule; 1 .. 256 bins, 1 .. 8 separations per call, a range per field and separation)
+    "mfft_ew_increment_histogram": ([c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int, POINTER(c_int64), c_int, POINTER(c_double),
+                                     POINTER(c_double), c_int, POINTER(c_int64)], c_int),
+    "mfft_real_increment_histogram": ([c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int64), c_int, POINTER(c_double), POINTER(c_double),
+                                       c_int, POINTER(c_int64), POINTER(c_int64)], c_int),
     "mfft_ew_profiles": ([c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int, POINTER(c_double), POINTER(c_double)], c_int),
     "mfft_real_profiles": ([c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_double), POINTER(c_double), POINTER(c_int64)], c_int),
     "mfft_ew_dft_bins": ([c_void_p, c_void_p, c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), c_int, c_int,
@@ -173,7 +181,8 @@ _SIGNATURES = {
 # functions whose int result is a count, not a status
 _COUNT_RESULT = {"mfft_version", "mfft_length_supported", "mfft_length_route", "mfft_length_route_precision", "mfft_plan_timing_get",
                  "mfft_nlz_moments_groups", "mfft_nlz_hist_groups", "mfft_nlz_quad_groups",
-                 "mfft_nlz_incr_groups", "mfft_nlz_joint_groups", "mfft_nlz_profile_groups"}
+                 "mfft_nlz_incr_groups", "mfft_nlz_joint_groups", "mfft_nlz_profile_groups",
+                 "mfft_nlz_incr_hist_groups"}
 
 _lib = None
 

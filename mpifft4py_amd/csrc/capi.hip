@@ -335,8 +335,8 @@ int mfft_nlz_rows_absmax(const void* a, const void* b, void* out, int64_t nrows,
   return rc;
 }
 
-// The stages that end in a reduction (fft_nlz.h body_moments, body_hist, body_joint, body_quad, body_incr, body_prof), synchronous; what
-// their six entry points share.  nfields = 1: a is (nrows, pitch); 2: a and b are; 3: a is (3, nrows, pitch); 6: a and b are.  `valid`
+// The stages that end in a reduction (fft_nlz.h body_moments, body_hist, body_joint, body_quad, body_incr, body_incr_hist, body_prof), synchronous; what
+// their seven entry points share.  nfields = 1: a is (nrows, pitch); 2: a and b are; 3: a is (3, nrows, pitch); 6: a and b are.  `valid`
 // bins per row exist, the first valid_in of them are read (0: all of them).  Fields in the order a_0.., then b_0..; field f rides in
 // slot nls_slot(u, f), the plan's rule.  Everything is checked before the first launch; the outputs are written on success only.
 static int nlr_stage_args(Op kind, const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
@@ -420,6 +420,34 @@ int mfft_nlz_incr_rows(const void* a, const void* b, int nfields, int64_t nrows,
   return 0;
 }
 int64_t mfft_nlz_incr_groups(int64_t nrows, int64_t n, int precision) { return nlr_stage_groups(Op::Increments, nrows, n, precision); }
+
+// out[(f * nsep + i) * (nbins + 3) + slot] = counts of the increments of irfft(row, n) at seps[i] over all rows; lo, hi: [f * nsep + i]
+int mfft_nlz_incr_hist_rows(const void* a, const void* b, int nfields, int64_t nrows, int64_t n, int64_t pitch, int64_t valid, int64_t valid_in,
+                            int precision, const int64_t* seps, int nsep, const double* lo, const double* hi, int nbins, int64_t* out) {
+  if (!out || !seps || !lo || !hi) return set_error(MFFT_ERR_INVALID, "bad argument");
+  NlFields u;
+  NlrArgs z;
+  MFFT_TRY(nlr_stage_args(Op::IncrementHistogram, a, b, nfields, nrows, n, pitch, valid, valid_in, precision, &u, &z));
+  MFFT_TRY(incr_check(seps, nsep, n));
+  if (nbins < 1 || nbins > MFFT_INCR_HIST_MAXBINS) return set_error(MFFT_ERR_INVALID, "nbins must be 1 .. %d, not %d", MFFT_INCR_HIST_MAXBINS, nbins);
+  for (int f = 0; f < 6; ++f)
+    for (int i = 0; i < MFFT_INCR_MAXSEP; ++i) { z.call.ilo[f][i] = 0.0; z.call.iinv[f][i] = 1.0; }
+  for (int f = 0; f < nfields; ++f)
+    for (int i = 0; i < nsep; ++i) {
+      const int slot = nls_slot(u, f);
+      MFFT_TRY(incr_hist_range(lo[f * nsep + i], hi[f * nsep + i], nbins, &z.call.iinv[slot][i]));
+      z.call.ilo[slot][i] = lo[f * nsep + i];
+    }
+  for (int i = 0; i < nsep; ++i) z.call.sep[i] = (int)seps[i];
+  z.call.nsep = nsep;
+  z.call.nbins = nbins;
+  const size_t row = (size_t)nsep * (nbins + 3);
+  std::vector<int64_t> host((size_t)2 * z.npairs * row);
+  MFFT_TRY(nlr_stage_run(z, host.size() * sizeof(int64_t), host.data(), 0, nullptr));
+  for (int f = 0; f < nfields; ++f) memcpy(out + (size_t)f * row, host.data() + (size_t)nls_slot(u, f) * row, row * sizeof(int64_t));
+  return 0;
+}
+int64_t mfft_nlz_incr_hist_groups(int64_t nrows, int64_t n, int precision) { return nlr_stage_groups(Op::IncrementHistogram, nrows, n, precision); }
 
 // a, b: (ncomp, nrows, pitch), ncomp 1 or 3, pair p = (a_p, b_p); center: a_0.., then b_0.. (null: zeros)
 // out[(p * 5 + s) * n + m] = the sums over all rows of d_a, d_b, d_a^2, d_b^2, d_a d_b at position m of (irfft(a_p row, n), irfft(b_p row, n))

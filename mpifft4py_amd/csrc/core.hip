@@ -605,7 +605,7 @@ int launch_nlz(const NlzArgs& a, hipStream_t s) {
   });
 }
 
-// The stages that end in a reduction (fft_nlz.h body_moments, body_hist, body_joint, body_quad, body_incr, body_prof: the table entries with
+// The stages that end in a reduction (fft_nlz.h body_moments, body_hist, body_joint, body_quad, body_incr, body_incr_hist, body_prof: the table entries with
 // nout == 0; NlrArgs of mfft_internal.h).  Their grid does not follow the rows: the workgroups that are resident at once, CUs x
 // min(what the runtime says fits, NLS_WG_PER_CU), asked once per device and kernel, and never more than there are pairs of rows to
 // start on.
@@ -627,6 +627,7 @@ static int nls_resident(const KernelEntry* e, int* cap) {
   known.push_back(Key{dev, e->func, *cap});
   return 0;
 }
+static_assert(NLK_MAXBINS == MFFT_INCR_HIST_MAXBINS, "the public header states the kernels' limit");
 static_assert(NLI_MAXSEP == MFFT_INCR_MAXSEP && NLI_FIELD == INCR_FIELD && NLI_SLOTS == INCR_SLOTS, "one number of separations per launch");
 static int find_nlr(Op kind, int64_t n, int prec, const KernelEntry** e) {
   const NlProduct& q = nl_product(kind);
@@ -719,6 +720,19 @@ static int launch_nlr_t(const KernelEntry* e, const NlrArgs& a, void* tw, hipStr
     for (int i = 0; i < 2 * NLS_PAIRS; ++i) P.center[i] = c.center[i];
     return run(P);
   }
+  if (a.kind == Op::IncrementHistogram) {
+    auto P = nlr_params<T, NlkParams>(a, tw);
+    P.part = static_cast<unsigned*>(a.part);
+    for (int f = 0; f < 2 * NLS_PAIRS; ++f)
+      for (int i = 0; i < NLI_MAXSEP; ++i) {
+        P.lo[f][i] = i < c.nsep ? c.ilo[f][i] : 0.0;
+        P.inv[f][i] = i < c.nsep ? c.iinv[f][i] : 1.0;
+      }
+    for (int i = 0; i < NLI_MAXSEP; ++i) P.sep[i] = i < c.nsep ? c.sep[i] : 1;
+    P.nsep = c.nsep;
+    P.nbins = c.nbins;
+    return run(P);
+  }
   auto P = nlr_params<T, NliParams>(a, tw);          // Op::Increments
   P.part = static_cast<double*>(a.part);
   for (int i = 0; i < NLI_MAXSEP; ++i) P.sep[i] = i < c.nsep ? c.sep[i] : 1;
@@ -754,10 +768,16 @@ int launch_nlr(const NlrArgs& a, hipStream_t s) {
       if (!a.b[p]) return set_error(MFFT_ERR_INVALID, "null argument: a profile takes pairs of fields");
       if (!std::isfinite(c.center[2 * p]) || !std::isfinite(c.center[2 * p + 1])) return set_error(MFFT_ERR_INVALID, "a centre is not finite");
     }
-  } else if (a.kind == Op::Increments) {
+  } else if (a.kind == Op::Increments || a.kind == Op::IncrementHistogram) {
     if (c.nsep < 1 || c.nsep > NLI_MAXSEP) return set_error(MFFT_ERR_INVALID, "bad argument");
     for (int i = 0; i < c.nsep; ++i)               // (the kernel reads the row's exchange buffer at (position + sep) mod n)
       if (c.sep[i] < 1 || c.sep[i] >= a.n) return set_error(MFFT_ERR_INVALID, "separation %d outside 1 .. %d", c.sep[i], a.n - 1);
+    if (a.kind == Op::IncrementHistogram) {
+      if (c.nbins < 1 || c.nbins > NLK_MAXBINS) return set_error(MFFT_ERR_INVALID, "bad argument");
+      for (int f = 0; f < 2 * a.npairs; ++f)
+        for (int i = 0; i < c.nsep; ++i)
+          if (!(c.iinv[f][i] > 0.0) || !std::isfinite(c.iinv[f][i]) || !std::isfinite(c.ilo[f][i])) return set_error(MFFT_ERR_INVALID, "bad histogram range");
+    }
   }
   // what one workgroup counts per field stays below 2^32: passes x 2 x rows per workgroup x n
   if (nl_product(a.kind).counts && nlr_counted(e->tile, a.n, a.nrows, a.ngroups) >= ((int64_t)1 << 32))
@@ -773,6 +793,7 @@ size_t nlr_part_bytes(const NlrArgs& z, const NlrShape& shape) {
   if (z.kind == Op::JointHistogram) return joint_part_bytes(shape.ngroups, z.npairs, z.call.nba, z.call.nbb);
   if (z.kind == Op::Quadratic) return quad_mpart_bytes(shape.waves) + quad_hpart_bytes(shape.ngroups, z.call.nbins);
   if (z.kind == Op::Profiles) return prof_part_bytes(shape.ngroups, shape.tile, z.npairs, z.n);
+  if (z.kind == Op::IncrementHistogram) return incr_hist_part_bytes(shape.ngroups, 2 * z.npairs, z.call.nsep, z.call.nbins);
   return (size_t)shape.waves * (z.kind == Op::Increments ? INCR_SLOTS : NLS_SLOTS) * sizeof(double);
 }
 // The ONE loop over the rows of a batch.  The kinds that sum doubles have no limit on the rows of a launch: one launch, one fold.
@@ -802,6 +823,8 @@ int nlr_rows(const NlrArgs& z0, void* acc, void* acc2, hipStream_t s) {
     } else if (z.kind == Op::Quadratic) {
       MFFT_TRY(moments_fold(static_cast<const double*>(z.part), waves, NLS_STATS, static_cast<double*>(acc), s));
       if (c.nbins > 0) MFFT_TRY(hist_fold(static_cast<const unsigned*>(z.part2), groups, 1, c.nbins, static_cast<int64_t*>(acc2), s));
+    } else if (z.kind == Op::IncrementHistogram) {  // rows of nsep (nbins + 3) counts per slot: the histograms' fold
+      MFFT_TRY(hist_fold_slots(static_cast<const unsigned*>(z.part), groups, 2 * z.npairs, c.nsep * (c.nbins + 3), static_cast<int64_t*>(acc), s));
     } else if (z.kind == Op::Profiles) {            // one partial profile per row slot of the launch
       MFFT_TRY(prof_fold(static_cast<const double*>(z.part), groups * (size_t)shape.tile, (size_t)z.npairs * NLP_STATS * (size_t)z.n,
                          static_cast<double*>(acc), s));

@@ -1,0 +1,7 @@
+// gfx950 instantiations: fused nonlinear z stage that ends in increment histograms along z (fft_nlz.h NlzIncrHist), double precision
+#include "registry_nlz.h"
+#include "plans.h"
+namespace {
+#define MFFT_REG_NLK(N, ...) mfft::register_nlk<mfft::Spec<N, __VA_ARGS__>, double>("nlk n" #N "(" #__VA_ARGS__ ")double");
+mfft::PlanRegistrar registrar([] { MFFT_NLZPLANS_9(MFFT_REG_NLK) });
+}

@@ -161,6 +161,7 @@ constexpr NlProduct NL_PRODUCTS[] = {
     {Op::Increments, "increments", 6, 0, false, false},
     {Op::JointHistogram, "joint", 6, 0, false, false, true},       // (one or three PAIRS of fields: a_p with b_p)
     {Op::Profiles, "profiles", 6, 0, false, false},                // (one or three PAIRS again; sums of doubles: no 2^32 limit)
+    {Op::IncrementHistogram, "incr_hist", 6, 0, false, false, true},
 };
 inline const NlProduct& nl_product(Op op) {
   for (const NlProduct& q : NL_PRODUCTS)
@@ -208,6 +209,8 @@ struct NlrCall {
   int nba = 0, nbb = 0;                    // JointHistogram: 1 .. MFFT_JOINT_MAXBINS bins of the a fields / of the b fields
   int sep[MFFT_INCR_MAXSEP] = {0};         // Increments: 1 <= sep[i] < n, i < nsep
   int nsep = 0;                            // 1 .. MFFT_INCR_MAXSEP
+  // IncrementHistogram: sep, nsep as Increments, nbins 1 .. MFFT_INCR_HIST_MAXBINS, and a range per slot AND separation
+  double ilo[6][MFFT_INCR_MAXSEP] = {}, iinv[6][MFFT_INCR_MAXSEP] = {};
 };
 struct NlrArgs {
   Op kind = Op::Moments;
@@ -223,7 +226,8 @@ struct NlrArgs {
   int ngroups = 0;       // workgroups of the launch, from nlr_launch_shape(): nlr_rows sets it
   void* part = nullptr;  // the launch's partial results, nlr_part_bytes() of the shape of all rows: per wave NLS_SLOTS (Moments),
                          // INCR_SLOTS (Increments), NLS_STATS (Quadratic) doubles; per workgroup the unsigned counts (npairs, 2, nbins
-                         // + 3) (Histogram), (npairs, cells) (JointHistogram); per ROW SLOT of a workgroup (npairs, 5, n) doubles
+                         // + 3) (Histogram), (npairs, cells) (JointHistogram), (npairs, 2, nsep, nbins + 3) (IncrementHistogram); per ROW
+                         // SLOT of a workgroup (npairs, 5, n) doubles
                          // (Profiles: prof_part_bytes)
   void* part2 = nullptr; // Quadratic: per workgroup nbins + 3 unsigned counts of q, behind the doubles; nlr_rows sets it
   NlrCall call;
@@ -267,6 +271,12 @@ constexpr int INCR_FIELD = MFFT_INCR_MAXSEP * 3, INCR_SLOTS = 6 * INCR_FIELD;
 int incr_fold(const double* part, size_t groups, int nvals, double* acc, hipStream_t s);
 // MFFT_ERR_INVALID for nsep outside 1 .. MFFT_INCR_MAXSEP or a separation outside 1 .. m - 1
 int incr_check(const int64_t* seps, int nsep, int64_t m);
+// Histograms of the increments (incrhist.hip): per field and separation nbins + 3 counts of d = x(z + sep) - x(z) by hist_slot.  acc:
+// device int64, [slot][nsep][nbins + 3], six slots; the fold is hist_fold_slots over rows of nsep (nbins + 3) counts.
+size_t incr_hist_part_bytes(int ngroups, int nslots, int nsep, int nbins);
+// inv = nbins / (hi - lo) of a valid range; MFFT_ERR_INVALID for nbins outside 1 .. MFFT_INCR_HIST_MAXBINS, hi <= lo, a range that is
+// not finite
+int incr_hist_range(double lo, double hi, int nbins, double* inv);
 // Plane-averaged profiles along z (profiles.hip): per pair and position of the row the sums of d_a, d_b, d_a^2, d_b^2, d_a d_b over
 // all rows (fft_nlz.h prof_add).  acc: device doubles, (npairs, 5, n), pairs in slot order.
 // prof_fold: acc[v] += the nslots partial profiles part[g * nvals + v], added in a fixed order

@@ -9,7 +9,7 @@ using namespace mfft;
 #endif
 
 mfft_plan_s::~mfft_plan_s() {
-  for (Buf* b : {&work[0], &work[1], &work[2], &work3, &nlw[0], &nlw[1], &nlx, &nly, &nlr, &pcomp, &shl, &nlm, &nlmacc, &nlsacc, &nlhacc, &nlq, &nliacc, &nljacc, &nlr2, &nlpacc})
+  for (Buf* b : {&work[0], &work[1], &work[2], &work3, &nlw[0], &nlw[1], &nlx, &nly, &nlr, &pcomp, &shl, &nlm, &nlmacc, &nlsacc, &nlhacc, &nlq, &nliacc, &nljacc, &nlr2, &nlpacc, &nlkacc})
     if (b->p) (void)(b->arena ? wfree(b->p) : dev_free(b->p));
   if (mask) (void)hipFree(mask);
   if (band_tiles) (void)hipFree(band_tiles);
@@ -386,7 +386,7 @@ int mfft_plan_nonlinear_absmax(mfft_plan_t p, double out6[6]) {
   return p->nonlinear_absmax(out6);
 }
 
-// The six reductions: the plan on its device, a (and b, where given) of ncomp components, a known dealias mode -> the call's fields
+// The seven reductions: the plan on its device, a (and b, where given) of ncomp components, a known dealias mode -> the call's fields
 static int reduce_fields(mfft_plan_t p, const void* a_hat, const void* b_hat, int ncomp, int dealias, NlFields* u) {
   MFFT_TRY(check_ready(p, a_hat, a_hat));
   if (ncomp != 1 && ncomp != 3) return set_error(MFFT_ERR_INVALID, "ncomp must be 1 or 3, not %d", ncomp);
@@ -435,6 +435,15 @@ int mfft_real_increments(mfft_plan_t p, const void* a_hat, const void* b_hat, in
   NlFields u;
   MFFT_TRY(reduce_fields(p, a_hat, b_hat, ncomp, dealias, &u));
   return p->real_increments(u, dealias, seps, nsep, out, count);
+}
+
+// counts of the increments along z of ifftn(field f, dealias) in nbins equal bins per field and separation: see include/mpifft4py_amd.h
+int mfft_real_increment_histogram(mfft_plan_t p, const void* a_hat, const void* b_hat, int ncomp, int dealias, const int64_t* seps, int nsep,
+                                  const double* lo, const double* hi, int nbins, int64_t* out, int64_t* count) {
+  if (!out || !count || !seps || !lo || !hi) return set_error(MFFT_ERR_INVALID, "null argument");
+  NlFields u;
+  MFFT_TRY(reduce_fields(p, a_hat, b_hat, ncomp, dealias, &u));
+  return p->real_increment_histogram(u, dealias, seps, nsep, lo, hi, nbins, out, count);
 }
 
 // counts of the pairs (ifftn(a_f), ifftn(b_f)) in a grid of nba x nbb equal bins per pair: see include/mpifft4py_amd.h

@@ -133,6 +133,10 @@ struct mfft_plan_s {
   // mfft_real_increments / mfft_ew_increments (incr.hip): the sums in slot order, [slot][MFFT_INCR_MAXSEP][S2, S3, S4]; the partials
   // go to nlm.
   Buf nliacc{false, false};
+  // mfft_real_increment_histogram / mfft_ew_increment_histogram (incrhist.hip): 6 x MFFT_INCR_MAXSEP x (MFFT_INCR_HIST_MAXBINS + 3) int64
+  // counts in slot order, [slot][separation][nbins + 3] packed by the call's nsep and nbins, cleared on the stream when a call starts;
+  // the workgroups' partial histograms go to nlm.
+  Buf nlkacc{false, false};
   // mfft_real_profiles / mfft_ew_profiles (profiles.hip): (npairs, 5, M) doubles, pairs in slot order, zeroed on the stream when a call
   // starts; the partial profiles go to nlm -- one per row slot of the launch, (npairs, 5, M) doubles each, which the plan keeps as it
   // keeps the joint grids.
@@ -555,7 +559,7 @@ struct mfft_plan_s {
   int reduce_composed(const mfft::NlFields& u, int dealias, mfft::Op kind);
   int reduce_batch(mfft::Op kind, const mfft::NlFields& u, char* Y, size_t yelems, int64_t L2, int64_t Za, int64_t nrows, int valid_in);
   // What a kind supplies: its entry, begin / end around its accumulator, and its sweep (moments.hip, hist.hip, joint.hip, quad.hip,
-  // incr.hip).  [min, max, S1 .. S4] per field:
+  // incr.hip, incrhist.hip).  [min, max, S1 .. S4] per field:
   int real_moments(const mfft::NlFields& u, int dealias, const double* center, double* out, int64_t* count);
   int moments_sweep(const void* x, int ncomp, size_t n, const double* center, double* acc);
   int moments_begin(const double center_slots[6]);
@@ -583,6 +587,12 @@ struct mfft_plan_s {
   int incr_sweep(const void* x, int ncomp, int64_t nrows, int64_t n, int64_t pitch, double* acc);
   int incr_begin(const int64_t* seps, int nsep);
   int incr_end(double* host);
+  // increment PDFs along z, out: (nfields, nsep, nbins + 3).  lo, hi: [f * nsep + i]
+  int real_increment_histogram(const mfft::NlFields& u, int dealias, const int64_t* seps, int nsep, const double* lo, const double* hi, int nbins,
+                               int64_t* out, int64_t* count);
+  int incr_hist_sweep(const void* x, int ncomp, int64_t nrows, int64_t n, int64_t pitch, int slot0, int64_t* acc);
+  int incr_hist_begin(const int64_t* seps, int nsep, const double (*lo_slots)[MFFT_INCR_MAXSEP], const double (*inv_slots)[MFFT_INCR_MAXSEP], int nbins);
+  int incr_hist_end(int64_t* host, int nslots);
   // profiles along z of one or three pairs, out: (npairs, 5, M).  center: 2 ncomp entries, a_0.., then b_0.. (null: zeros)
   int real_profiles(const mfft::NlFields& u, int dealias, const double* center, double* out, int64_t* count);
   int prof_sweep(const void* x, const void* y, int ncomp, int64_t nrows, int64_t n, const double* center, double* acc);

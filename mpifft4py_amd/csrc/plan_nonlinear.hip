@@ -139,7 +139,7 @@ int mfft_plan_s::reduce_batch(Op kind, const NlFields& u, char* Y, size_t yelems
   MFFT_TRY(nlr_launch_shape(kind, L2, prec, nrows, &shape));
   MFFT_TRY(ensure(nlm, nlr_part_bytes(z, shape)));
   z.part = nlm.p;
-  Buf& acc = kind == Op::Histogram ? nlhacc : kind == Op::JointHistogram ? nljacc : kind == Op::Increments ? nliacc : kind == Op::Profiles ? nlpacc : nlsacc;
+  Buf& acc = kind == Op::Histogram ? nlhacc : kind == Op::JointHistogram ? nljacc : kind == Op::Increments ? nliacc : kind == Op::Profiles ? nlpacc : kind == Op::IncrementHistogram ? nlkacc : nlsacc;
   return nlr_rows(z, acc.p, nlhacc.p, stream);      // (the counts of a quadratic form: the second accumulator)
 }
 
@@ -479,6 +479,11 @@ int mfft_plan_s::reduce_composed(const NlFields& u, int dealias, Op kind) {
       MFFT_TRY(stage("nl_histogram", (double)nr * rs, [&] {
         return hist_sweep(nlr.p, 1, (size_t)nr, c.lo + slot, c.inv + slot, c.nbins, acc + (size_t)slot * (c.nbins + 3));
       }));
+    } else if (kind == Op::IncrementHistogram) {      // (z is whole on every rank, as for the increments below)
+      int64_t* acc = static_cast<int64_t*>(nlkacc.p);
+      MFFT_TRY(stage("nl_incr_hist", (double)nr * rs, [&] {
+        return incr_hist_sweep(nlr.p, 1, nr / M, M, M, slot, acc + (size_t)slot * c.nsep * (c.nbins + 3));
+      }));
     } else {      // Op::Increments: z is whole on every rank of a slab and of a pencil plan, so no halo is needed
       double* acc = static_cast<double*>(nliacc.p);
       MFFT_TRY(stage("nl_increments", (double)nr * rs, [&] { return incr_sweep(nlr.p, 1, nr / M, M, M, acc + slot * INCR_FIELD); }));
@@ -540,6 +545,33 @@ int mfft_plan_s::real_increments(const NlFields& u, int dealias, const int64_t* 
   for (int f = 0; f < u.nfields; ++f)
     for (int i = 0; i < nsep; ++i)
       for (int k = 0; k < 3; ++k) out[(f * nsep + i) * 3 + k] = host[(nls_slot(u, f) * MFFT_INCR_MAXSEP + i) * 3 + k];
+  return 0;
+}
+
+// per field and separation the nbins + 3 counts of d = x(z + s) - x(z) over [lo, hi) of that field and separation, rows periodic
+// (fft_nlz.h body_incr_hist)
+int mfft_plan_s::real_increment_histogram(const NlFields& u, int dealias, const int64_t* seps, int nsep, const double* lo, const double* hi,
+                                          int nbins, int64_t* out, int64_t* count) {
+  const bool pad = dealias == MFFT_DEALIAS_3_2;
+  const int64_t nr = local_real_count(pad), M = pad ? M2 : N2;
+  if (nr <= 0 || !r2c || M < 2 || nr % M != 0) return set_error(MFFT_ERR_UNSUPPORTED, "real_increment_histogram needs a 3-D real-to-complex plan");
+  MFFT_TRY(incr_check(seps, nsep, M));
+  double l6[6][MFFT_INCR_MAXSEP] = {}, i6[6][MFFT_INCR_MAXSEP];
+  for (int f = 0; f < 6; ++f)
+    for (int i = 0; i < MFFT_INCR_MAXSEP; ++i) i6[f][i] = 1.0;
+  if (nbins < 1 || nbins > MFFT_INCR_HIST_MAXBINS) return set_error(MFFT_ERR_INVALID, "nbins must be 1 .. %d, not %d", MFFT_INCR_HIST_MAXBINS, nbins);
+  for (int f = 0; f < u.nfields; ++f)
+    for (int i = 0; i < nsep; ++i) {
+      const int slot = nls_slot(u, f);
+      MFFT_TRY(incr_hist_range(lo[f * nsep + i], hi[f * nsep + i], nbins, &i6[slot][i]));
+      l6[slot][i] = lo[f * nsep + i];
+    }
+  const size_t row = (size_t)nsep * (nbins + 3);
+  const int nslots = 2 * ((u.nfields + 1) / 2);
+  std::vector<int64_t> host((size_t)nslots * row);      // (out is written on success only)
+  MFFT_TRY(real_reduce(u, dealias, Op::IncrementHistogram, count, [&] { return incr_hist_begin(seps, nsep, l6, i6, nbins); },
+                       [&] { return incr_hist_end(host.data(), nslots); }));
+  for (int f = 0; f < u.nfields; ++f) memcpy(out + (size_t)f * row, host.data() + (size_t)nls_slot(u, f) * row, row * sizeof(int64_t));
   return 0;
 }
 

@@ -43,7 +43,8 @@ enum class Op : unsigned {
   Outer = 10,       // all nine products a_i b_j: six rows in, NINE result rows (fft_nlz.h body_outer, NloParams); FAM_NLZ only
   Increments = 11,  // no result rows: power sums of the increments along z of the real rows (fft_nlz.h body_incr, NliParams); FAM_NLZ only
   JointHistogram = 12,  // no result rows: counts of the PAIRS of values of two real rows in a 2-D grid (fft_nlz.h body_joint, NljParams); FAM_NLZ only
-  Profiles = 13     // no result rows: per position of the row the sums over all rows of two real rows' values, squares and product (fft_nlz.h body_prof, NlpParams); FAM_NLZ only
+  Profiles = 13,    // no result rows: per position of the row the sums over all rows of two real rows' values, squares and product (fft_nlz.h body_prof, NlpParams); FAM_NLZ only
+  IncrementHistogram = 14  // no result rows: counts of the increments along z of the real rows in equal bins (fft_nlz.h body_incr_hist, NlkParams); FAM_NLZ only
 };
 constexpr Op operator|(Op a, Op b) { return (Op)((unsigned)a | (unsigned)b); }
 constexpr bool has(Op a, Op flag) { return ((unsigned)a & (unsigned)flag) != 0; }

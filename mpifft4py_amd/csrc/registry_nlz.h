@@ -226,6 +226,21 @@ void register_nlj(const char* name) {
   reg.push_back(make_entry<K, NljParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::JointHistogram, Build::Default, R, name));
 }
 
+// Op::IncrementHistogram: the stage that ends in increment histograms along z (fft_nlz.h body_incr_hist, NlkParams;
+// kernels_nlk*.hip).  Rows, twiddle placement, the two-waves-per-SIMD cap, the exchange and the wave build are those of
+// register_nlj, unchanged (nlj_split, nlj_wave): the pair's histograms take NLK_MAXCELLS x 4 = 16576 bytes behind the exchange
+// buffers, under the joint grid's 17956, so whatever the joint rule keeps resident stays resident here.  The body inlines ONE
+// transform and holds NO accumulators: a slot and an LDS add per increment (profiles/real_increment_histogram_regs.tsv).  No other
+// rule or cap was measured.
+template <class S, typename T>
+void register_nlk(const char* name) {
+  auto& reg = kernel_registry();
+  constexpr int R = nlz_rows<S, T>();
+  constexpr int W = MFFT_NLZ_OCC > 1 ? 16 + MFFT_NLZ_OCC : 0;
+  typedef NlzIncrHist<NlzFft<S, T, R, nlz_twlds<S, T>(), nlj_split<S, T>(), nlj_wave<S, T>()>> K;
+  reg.push_back(make_entry<K, NlkParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::IncrementHistogram, Build::Default, R, name));
+}
+
 // Op::Profiles: the stage that ends in plane-averaged profiles along z (fft_nlz.h body_prof, NlpParams; kernels_nlp*.hip).  Rows,
 // twiddle placement, exchange, wave-synchronous build and the two-waves-per-SIMD cap are those of register_nls: the body inlines ONE
 // transform and holds ONE pair's accumulators across it, E x NLP_STATS doubles -- 40 for the 8-values plans, 60 for the 12-values

@@ -890,6 +890,183 @@ def increments(FFT, u, seps=None, reduce=False):
     return _incr_result(FFT, np.concatenate(parts, axis=1), nrows * M, seps, M, reduce)
 
 
+INCR_HIST_MAXBINS = 256   # bins per field and separation of one call (MFFT_INCR_HIST_MAXBINS: 2 x 8 x 259 counts are a pair's share of LDS)
+
+
+def incr_hist_rule(r, seps, lo, hi, bins):
+    """The rule of the increment PDFs, in numpy float64 (include/mpifft4py_amd.h): r of shape (..., M) holds periodic rows along
+    its last axis (normalised values, already double); lo, hi broadcastable to (len(seps),).  Returns the int64 counts of
+    d = r[(z + seps[i]) mod M] - r[z] by the histograms' slot rule (`hist_slots`), shape (len(seps), bins + 3)."""
+    r = np.asarray(r, dtype=np.float64)
+    lo = np.broadcast_to(np.asarray(lo, dtype=np.float64), (len(seps),))
+    hi = np.broadcast_to(np.asarray(hi, dtype=np.float64), (len(seps),))
+    out = np.zeros((len(seps), int(bins) + 3), dtype=np.int64)
+    for i, s in enumerate(seps):
+        with np.errstate(invalid="ignore"):
+            d = np.roll(r, -int(s), axis=-1) - r
+        out[i] = np.bincount(hist_slots(d, lo[i], hi[i], int(bins)).ravel(), minlength=int(bins) + 3)
+    return out
+
+
+class IncrementHistogram(object):
+    """PDFs of the increments along z of `nfields` real fields over `count` points per field: `seps` (grid points of the z row of
+    `M` points), `raw` of shape (nfields, nsep, bins + 3), int64 -- per field and separation [below lo, the bins of [lo, hi), at or
+    above hi, not finite], summing to `count` -- and `lo`, `hi` of shape (nfields, nsep).  On a velocity field 2 is the
+    LONGITUDINAL increment (it runs along z), fields 0 and 1 the transverse ones."""
+
+    def __init__(self, count, seps, raw, lo, hi, M):
+        self.count = int(count)
+        self.seps = np.asarray(seps, dtype=np.int64).reshape(-1)
+        raw = np.asarray(raw, dtype=np.int64)
+        self.raw = raw.reshape(-1, self.seps.size, raw.shape[-1]).copy()
+        self.lo = np.asarray(lo, dtype=np.float64).reshape(self.raw.shape[:2]).copy()
+        self.hi = np.asarray(hi, dtype=np.float64).reshape(self.raw.shape[:2]).copy()
+        self.M = int(M)
+
+    @property
+    def nbins(self):
+        return int(self.raw.shape[2]) - 3
+
+    @property
+    def nfields(self):
+        return int(self.raw.shape[0])
+
+    def hist(self, i):
+        """The `Histogram` of separation i over the fields: pdf, cdf, quantile, below, above and nonfinite come with it."""
+        return Histogram(self.count, self.raw[:, i, :], self.lo[:, i], self.hi[:, i])
+
+    def centers(self, f, i):
+        return self.hist(i).centers(f)
+
+    def pdf(self, f, i):
+        """The density of the increments of field f at separation i over [lo, hi), normalised by ALL `count` points."""
+        return self.hist(i).pdf(f)
+
+    def _sigma(self, f, i):
+        c, w = self.centers(f, i), self.raw[f, i, 1:-2].astype(np.float64)
+        n = w.sum()
+        if not n > 0:
+            return np.nan
+        mean = (w * c).sum() / n
+        return float(np.sqrt((w * (c - mean) ** 2).sum() / n))
+
+    def standardized(self, f, i):
+        """(d / sigma, sigma * pdf): the PDF in units of its own standard deviation, sigma from the histogram's bins (bin centres,
+        the counts inside [lo, hi)).  It integrates to 1 minus the share outside the range, as `pdf` does."""
+        sg = self._sigma(f, i)
+        return self.centers(f, i) / sg, self.pdf(f, i) * sg
+
+    def moment(self, p, absolute=False):
+        """<d^p> (or <|d|^p>, any real p, with `absolute`) from the bin centres, shape (nfields, nsep); the counts outside [lo, hi)
+        contribute nothing, the divisor is `count`."""
+        out = np.zeros(self.raw.shape[:2], dtype=np.float64)
+        for f in range(self.nfields):
+            for i in range(self.seps.size):
+                c, w = self.centers(f, i), self.raw[f, i, 1:-2].astype(np.float64)
+                out[f, i] = (w * (np.abs(c) ** p if absolute else c ** p)).sum() / float(self.count)
+        return out
+
+    def r(self, FFT):
+        """The separations as lengths: s * L_z / M."""
+        return self.seps.astype(np.float64) * float(FFT.L[2]) / self.M
+
+
+def _incr_hist_ranges(rng, nfields, nsep):
+    r = np.asarray(rng, dtype=np.float64)
+    r = np.ascontiguousarray(np.broadcast_to(r, (nfields, nsep, 2)))
+    return np.ascontiguousarray(r[:, :, 0]), np.ascontiguousarray(r[:, :, 1])
+
+
+def _incr_hist_check(lo, hi, bins):
+    if not 1 <= int(bins) <= INCR_HIST_MAXBINS:
+        raise ValueError("bins must be 1 .. %d, not %r" % (INCR_HIST_MAXBINS, bins))
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo < hi)):
+        raise ValueError("every range needs finite lo < hi, not %r .. %r" % (lo, hi))
+
+
+def _range_of_increments(inc, sigmas):
+    """+-sigmas * sigma(f, s), sigma = sqrt(S2 / count) of an `Increments`; a field without increments (constant along z) gets
+    a range of width 1 about 0, as `_range_of_moments` gives a constant field."""
+    with np.errstate(invalid="ignore"):
+        sg = np.sqrt(inc.sums[:, :, 0] / float(inc.count))
+    if not np.all(np.isfinite(sg)):
+        raise ValueError("an increment variance is not finite (%r): give `range`" % (sg,))
+    hi = float(sigmas) * sg
+    hi[~(hi > 0)] = 0.5
+    return -hi, hi.copy()
+
+
+def _incr_hist_result(FFT, raw, count, seps, lo, hi, M, reduce):
+    if reduce:
+        raw, count = _add_over_ranks(FFT, raw), int(_add_over_ranks(FFT, [count])[0])
+    return IncrementHistogram(count, seps, raw, lo, hi, M)
+
+
+def real_increment_histogram(FFT, a_hat, b_hat=None, dealias=None, seps=None, bins=128, range=None, sigmas=10.0, reduce=True):
+    """PDFs of the increments along z of fields that exist as SPECTRA only (mfft_real_increment_histogram): for every field and
+    every separation s in `seps` the counts of ifftn(field, dealias)(z + s) - ifftn(field, dealias)(z) in `bins` equal bins of a
+    range of its own -- every order of structure function, |d|^p for any p, the tails and the asymmetry of the longitudinal PDF --
+    without a real array: on slab plans with radix kernels on every axis the z kernel keeps the real row in its exchange buffer,
+    reads it back shifted and counts into LDS (`FFT.plan_info("nonlinear_incr_hist_fused_3_2")`); elsewhere the plan transforms
+    one field at a time into ONE work array and sweeps it.  Fields, `seps`, M and the chunks as `real_increments` (at most
+    INCR_MAXSEP separations per call of the library, EACH CHUNK REPEATS THE TRANSFORMS); `bins` 1 .. INCR_HIST_MAXBINS; increments
+    along z only.  `range`: (lo, hi) for all, or an array broadcastable to (nfields, nsep, 2); None: one `real_increments` call on
+    the same separations gives sigma(f, s) = sqrt(S2 / count) over FFT.comm and the range is +-`sigmas` sigma (a field that is
+    constant along z: +-0.5).  Returns an `IncrementHistogram`; with `reduce` the int64 counts are added over FFT.comm.  Counts are
+    integers: the same bits run to run and for every number of ranks that computes the same values.  Synchronises the plan's
+    stream; the inputs are preserved."""
+    fields, ncomp, nfields, head = _real_fields(FFT, a_hat, b_hat)
+    M = int(FFT.N[2]) * 3 // 2 if dealias == '3/2-rule' else int(FFT.N[2])
+    seps, chunks = _incr_chunks(seps, M)
+    if range is None:
+        lo, hi = _range_of_increments(real_increments(FFT, a_hat, b_hat, dealias, seps=seps, reduce=True), sigmas)
+    else:
+        lo, hi = _incr_hist_ranges(range, nfields, len(seps))
+    _incr_hist_check(lo, hi, bins)
+    count = ctypes.c_int64(0)
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
+    parts, i0 = [], 0
+    for ch in chunks:
+        sv = np.ascontiguousarray(ch, dtype=np.int64)
+        l, h = np.ascontiguousarray(lo[:, i0:i0 + len(ch)]), np.ascontiguousarray(hi[:, i0:i0 + len(ch)])
+        out = np.zeros((nfields, len(ch), int(bins) + 3), dtype=np.int64)
+        _nonlinear(FFT, "real_increment_histogram", fields, dealias, head=head,
+                   tail=(sv.ctypes.data_as(ip), len(ch), l.ctypes.data_as(dp), h.ctypes.data_as(dp), int(bins), out.ctypes.data_as(ip),
+                         ctypes.byref(count)))
+        parts.append(out)
+        i0 += len(ch)
+    return _incr_hist_result(FFT, np.concatenate(parts, axis=1), count.value, seps, lo, hi, M, reduce)
+
+
+def increment_histogram(FFT, u, seps=None, bins=128, range=None, sigmas=10.0, reduce=False):
+    """The same counts of a real DeviceArray along its LAST axis (mfft_ew_increment_histogram, the companion of `increments`):
+    components, rows, M, pitch, `seps` and the chunks as `increments` (each chunk is one more sweep); `bins`, `range` and `sigmas`
+    as `real_increment_histogram`, the sigmas of `range=None` from `increments` (over FFT.comm with `reduce`).  Returns an
+    `IncrementHistogram`; with `reduce` over FFT.comm."""
+    assert u.dtype == np.dtype(FFT.float), (u.dtype, FFT.float)
+    ncomp = int(u.shape[0]) if len(u.shape) == 4 else 1
+    M = int(u.shape[-1])
+    nrows = u.size // (ncomp * M)
+    seps, chunks = _incr_chunks(seps, M)
+    if range is None:
+        lo, hi = _range_of_increments(increments(FFT, u, seps=seps, reduce=reduce), sigmas)
+    else:
+        lo, hi = _incr_hist_ranges(range, ncomp, len(seps))
+    _incr_hist_check(lo, hi, bins)
+    FFT.comm.use_device()
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
+    parts, i0 = [], 0
+    for ch in chunks:
+        sv = np.ascontiguousarray(ch, dtype=np.int64)
+        l, h = np.ascontiguousarray(lo[:, i0:i0 + len(ch)]), np.ascontiguousarray(hi[:, i0:i0 + len(ch)])
+        out = np.zeros((ncomp, len(ch), int(bins) + 3), dtype=np.int64)
+        _lib.call("mfft_ew_increment_histogram", FFT._plan, u.ptr, ncomp, nrows, M, M if u.pitch is None else int(u.pitch), _prec(FFT),
+                  sv.ctypes.data_as(ip), len(ch), l.ctypes.data_as(dp), h.ctypes.data_as(dp), int(bins), out.ctypes.data_as(ip))
+        parts.append(out)
+        i0 += len(ch)
+    return _incr_hist_result(FFT, np.concatenate(parts, axis=1), nrows * M, seps, lo, hi, M, reduce)
+
+
 PROFILE_STATS = 5       # sums per pair and z index (MFFT_PROFILE_STATS): d_a, d_b, d_a^2, d_b^2, d_a d_b
 
 

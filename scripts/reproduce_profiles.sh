@@ -131,6 +131,8 @@ run() {
       echo "(sections 3 - 5: bench.py --gpus 1 --steps 20 --warmup 3 --cpu-baseline off of the parent commit's build and of this one, alternating, 8 each; scripts/profile_cmd.sh and one more pass with --pmc TCP_UTCL1_TRANSLATION_MISS for both)" ;;
     real_profiles_regs.tsv) make -C mpifft4py_amd/csrc -j8 >/dev/null; python scripts/real_profiles_regs.py ;;
     real_profiles_ab.txt) python scripts/real_profiles_ab.py --procs 3 --out out/real_profiles_ab.txt ;;
+    real_increment_histogram_regs.tsv) make -C mpifft4py_amd/csrc -j8 >/dev/null; python scripts/real_increment_histogram_regs.py ;;
+    real_increment_histogram_ab.txt) python scripts/real_increment_histogram_ab.py --procs 3 --out out/real_increment_histogram_ab.txt ;;
     real_joint_regs.tsv) make -C mpifft4py_amd/csrc -j8 >/dev/null; python scripts/real_joint_regs.py ;;
     real_joint_ab.txt) make -C mpifft4py_amd/csrc -j8 nlj_variant >/dev/null      # the joint kernels with their twins' exchange, for section (3)
       python scripts/real_joint_ab.py --procs 3 --out out/real_joint_ab.txt ;;
