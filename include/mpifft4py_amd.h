@@ -267,7 +267,7 @@ MFFT_API int mfft_nlz_outer_rows(const void* a, const void* b, void* out, int64_
  * mfft_nonlinear_dot_absmax on its own, for tests. */
 MFFT_API int mfft_nlz_rows_absmax(const void* a, const void* b, void* out, int64_t nrows, int64_t n, int64_t pitch, int64_t valid,
                                   int precision, int dot, double out6[6]);
-/* The z stage that ends in a reduction (csrc/fft_nlz.h body_moments), synchronous: the one-point statistics of the real rows
+/* The z stage that ends in a reduction (csrc/nlz_moments.h NlzMoments::body), synchronous: the one-point statistics of the real rows
  * irfft(row, n) without the real rows.  nfields = 1: a is (nrows, pitch) complex; 2: a and b are; 3: a is (3, nrows, pitch), b
  * NULL; 6: a and b are.  `valid` bins per row exist, the first valid_in of them are read (0: all).  Per field, over all rows and
  * all n points (numpy's normalisation):  out[f * 6 + 0] = min, [1] = max, [2 + p - 1] = sum (x - center[f])^p, p = 1..4 (center
@@ -289,7 +289,7 @@ MFFT_API int64_t mfft_nlz_moments_groups(int64_t nrows, int64_t n, int precision
  *          :               1 + (int)t
  * A result is nbins + 3 int64 counts per field; they always sum to the number of points. */
 #define MFFT_HIST_MAXBINS 512
-/* The z stage that ends in a histogram (csrc/fft_nlz.h body_hist), synchronous: the histograms of the real rows irfft(row, n)
+/* The z stage that ends in a histogram (csrc/nlz_hist.h NlzHist::body), synchronous: the histograms of the real rows irfft(row, n)
  * without the real rows.  Fields, rows, valid and valid_in as mfft_nlz_moments_rows; lo[f], hi[f] per field, in the order a_0..,
  * then b_0..; out[f * (nbins + 3) + slot].  Counts are integers: bitwise reproducible, whatever the launch looks like.  A NaN or
  * Inf bin of a field puts at least one count into THAT field's slot nbins + 2, its slots still sum to nrows * n; every other
@@ -312,7 +312,7 @@ MFFT_API int64_t mfft_nlz_hist_groups(int64_t nrows, int64_t n, int precision);
  * is what a workgroup can hold next to its exchange buffers: (64 + 3)^2 x 4 = 17956 bytes of LDS.  A finer PDF is had by a second
  * call on a narrower range. */
 #define MFFT_JOINT_MAXBINS 64
-/* The z stage that ends in a joint histogram (csrc/fft_nlz.h body_joint), synchronous: a and b are (ncomp, nrows, pitch) complex
+/* The z stage that ends in a joint histogram (csrc/nlz_joint.h NlzJoint::body), synchronous: a and b are (ncomp, nrows, pitch) complex
  * rows, ncomp 1 or 3; pair p is (a_p, b_p), both ride ONE inverse transform.  Rows, valid and valid_in as mfft_nlz_hist_rows; lo
  * and hi have 2 ncomp entries in the order a_0.., then b_0..; out[p * cells + cell], cells = (nba + 3)(nbb + 3).  Integers: bitwise
  * reproducible, whatever the launch looks like.  MFFT_ERR_UNSUPPORTED for lengths without a kernel; MFFT_ERR_INVALID for a bin count
@@ -332,7 +332,7 @@ MFFT_API int64_t mfft_nlz_joint_groups(int64_t nrows, int64_t n, int precision);
  * Every product and every sum is rounded on its own, in double: nothing is contracted into a fused multiply-add, on the device
  * or on the host.  q is a double in both precisions; its statistics are the six of mfft_real_moments about one centre, its counts
  * follow the slot rule above with one lo < hi. */
-/* The z stage that ends in the statistics of a quadratic form (csrc/fft_nlz.h body_quad), synchronous: q over the real rows
+/* The z stage that ends in the statistics of a quadratic form (csrc/nlz_quad.h NlzQuad::body), synchronous: q over the real rows
  * irfft(row, n) of the fields without the real rows.  Fields, rows, valid and valid_in as mfft_nlz_moments_rows; weights[f] in the
  * order a_0.., then b_0..; out6 = [min, max, S1 .. S4] of q, S_p = sum (q - center)^p; counts[nbins + 3] by the slot rule (may be
  * NULL where nbins == 0).  A NaN or Inf bin in ANY field makes q NaN where that bin was loaded: NaN sums, NaN min and max, counts
@@ -354,7 +354,7 @@ MFFT_API int64_t mfft_nlz_quad_groups(int64_t nrows, int64_t n, int precision);
  * is not computed.  Per field and separation the result is three doubles, [S2, S3, S4].  One launch takes up to MFFT_INCR_MAXSEP
  * separations; duplicates are allowed. */
 #define MFFT_INCR_MAXSEP 8
-/* The z stage that ends in structure functions (csrc/fft_nlz.h body_incr), synchronous: the increment sums of the real rows
+/* The z stage that ends in structure functions (csrc/nlz_incr.h NlzIncr::body), synchronous: the increment sums of the real rows
  * irfft(row, n) without the real rows.  Fields, rows, valid and valid_in as mfft_nlz_moments_rows; out[(f * nsep + i) * 3 + {0, 1,
  * 2}] = S2, S3, S4 of field f at seps[i], fields in the order a_0.., then b_0...  No atomics: bitwise reproducible run to run.  A
  * NaN or Inf bin of a field makes all of THAT field's sums NaN; the partner on the same transform stays exact.
@@ -375,7 +375,7 @@ MFFT_API int64_t mfft_nlz_incr_groups(int64_t nrows, int64_t n, int precision);
  * MFFT_INCR_HIST_MAXBINS, at most MFFT_INCR_MAXSEP separations per launch (duplicates allowed), increments along z only.  Counts
  * are integers: the same bits run to run and for every number of ranks that computes the same values. */
 #define MFFT_INCR_HIST_MAXBINS 256
-/* The z stage that ends in increment histograms (csrc/fft_nlz.h body_incr_hist), synchronous: the counts of the increments of the
+/* The z stage that ends in increment histograms (csrc/nlz_incr_hist.h NlzIncrHist::body), synchronous: the counts of the increments of the
  * real rows irfft(row, n) without the real rows.  Fields, rows, valid and valid_in as mfft_nlz_moments_rows; lo, hi: [(f * nsep + i)],
  * fields in the order a_0.., then b_0..; out[(f * nsep + i) * (nbins + 3) + slot].  No global atomics: a workgroup counts in LDS,
  * stores its rows by plain stores, one fold in fixed order into int64.  A thread whose load took a NaN or Inf bin out of a field
@@ -399,7 +399,7 @@ MFFT_API int64_t mfft_nlz_incr_hist_groups(int64_t nrows, int64_t n, int precisi
  * partial profiles go out by plain stores and are added in a fixed order, so the sums are bitwise reproducible run to run; they
  * are sums of doubles, so they are NOT claimed identical for different numbers of ranks. */
 #define MFFT_PROFILE_STATS 5
-/* The z stage that ends in profiles (csrc/fft_nlz.h body_prof), synchronous: a and b are (ncomp, nrows, pitch) complex device arrays,
+/* The z stage that ends in profiles (csrc/nlz_prof.h NlzProf::body), synchronous: a and b are (ncomp, nrows, pitch) complex device arrays,
  * ncomp = 1 or 3, pair p = (a_p, b_p); rows, valid and valid_in as mfft_nlz_moments_rows; center: 2 ncomp centres, a_0.., then
  * b_0.. (NULL: zeros).  out[(p * 5 + s) * n + m] = sum s of pair p at position m of the rows irfft(row, n), without the real rows.
  * A NaN or Inf bin of a field makes that field's two sums and the cross sum NaN at the positions of the thread that loaded it; the
@@ -504,7 +504,7 @@ MFFT_API int mfft_ew_moments(mfft_plan_t plan, const void* x, int ncomp, size_t 
  * mfft_nonlinear_cross_absmax), *count = the points summed.  center NULL: zeros; a centre near the mean keeps the digits of the
  * central moments (about 0 they cancel as (mean / sigma)^p).  The routes are those of mfft_nonlinear_cross (mfft_plan_get_info
  * "nonlinear_moments_fused_3_2" / "_none" / "_2_3"): on slab R2C plans with radix kernels on every axis the inverse x and y passes
- * and ONE z kernel per batch of x planes that ends in a reduction (csrc/fft_nlz.h body_moments) -- no real-space array exists;
+ * and ONE z kernel per batch of x planes that ends in a reduction (csrc/nlz_moments.h NlzMoments::body) -- no real-space array exists;
  * every other plan transforms one field at a time into ONE real work array and sweeps it (mfft_ew_moments).  Powers and sums in
  * double in both precisions, no atomics: bitwise reproducible run to run on one plan and device.  A NaN or Inf bin gives NaN sums
  * and NaN / +-Inf extremes for its field.  The inputs are preserved.  Synchronises the plan's stream. */
@@ -522,7 +522,7 @@ MFFT_API int mfft_ew_histogram(mfft_plan_t plan, const void* x, int ncomp, size_
  * b_hat -- 1, 2, 3 or 6 fields, in that order -- out[f * (nbins + 3) + slot] = the counts of x = ifftn(field f, dealias) by the
  * slot rule above with lo[f], hi[f], over THIS RANK's part of the real-space grid (as mfft_real_moments), *count = the points
  * counted (every field's slots sum to it).  The routes are those of mfft_real_moments (mfft_plan_get_info
- * "nonlinear_histogram_fused_3_2" / "_none" / "_2_3"): fused, the z kernel ends in a histogram (csrc/fft_nlz.h body_hist) and no
+ * "nonlinear_histogram_fused_3_2" / "_none" / "_2_3"): fused, the z kernel ends in a histogram (csrc/nlz_hist.h NlzHist::body) and no
  * real-space array exists; every other plan transforms one field at a time into ONE real work array and sweeps it
  * (mfft_ew_histogram).  Integers: bitwise reproducible run to run, and the same on every device and for every number of ranks of
  * a fused slab plan.  The inputs are preserved.  Synchronises the plan's stream. */
@@ -540,8 +540,8 @@ MFFT_API int mfft_ew_joint_histogram(mfft_plan_t plan, const void* x, const void
  * out[p * cells + cell] = the counts of the points (ifftn(a_p, dealias), ifftn(b_p, dealias)) by the cell rule above, over THIS
  * RANK's part of the real-space grid (as mfft_real_histogram), *count = the points counted (every pair's cells sum to it).  lo, hi:
  * 2 ncomp entries, a_0.., then b_0...  b_hat must not be NULL; a_hat == b_hat is allowed; the inputs are read only.  Routes
- * (mfft_plan_get_info "nonlinear_joint_fused_3_2" / "_none" / "_2_3"): fused, the z kernel ends in a joint histogram (csrc/fft_nlz.h
- * body_joint; the pair rides one transform, so one thread holds both values) and no real-space array exists; every other plan
+ * (mfft_plan_get_info "nonlinear_joint_fused_3_2" / "_none" / "_2_3"): fused, the z kernel ends in a joint histogram (csrc/nlz_joint.h
+ * NlzJoint::body; the pair rides one transform, so one thread holds both values) and no real-space array exists; every other plan
  * transforms a_p and b_p into TWO real work arrays -- the least a pair can do with -- and sweeps them (mfft_ew_joint_histogram).
  * Integers: bitwise reproducible run to run, and the same for every number of ranks of a fused slab plan.  Errors
  * (MFFT_ERR_INVALID: bins outside 1 .. MFFT_JOINT_MAXBINS, hi <= lo, ranges not finite, NULL b_hat) are reported before anything
@@ -563,7 +563,7 @@ MFFT_API int mfft_ew_quadratic(mfft_plan_t plan, const void* x, int ncomp, size_
  * [min, max, S1 .. S4] of q about `center`, counts[nbins + 3] by the slot rule over [lo, hi) (nbins == 0: no histogram, counts may
  * be NULL, lo and hi are ignored), *count = the points.  Routes (mfft_plan_get_info "nonlinear_quadratic_fused_3_2" / "_none" /
  * "_2_3"): fused, the z kernel accumulates q in registers across the inverse transforms of a row and ends in the reductions
- * (csrc/fft_nlz.h body_quad), no real-space array exists; every other plan transforms one field at a time into ONE real work array,
+ * (csrc/nlz_quad.h NlzQuad::body), no real-space array exists; every other plan transforms one field at a time into ONE real work array,
  * adds its term into ONE array of doubles and sweeps that once.  Bitwise reproducible run to run; the counts of a fused slab plan
  * are the same for every number of ranks.  MFFT_ERR_INVALID as for mfft_nlz_quad_rows, the outputs untouched on error.  The
  * inputs are preserved.  Synchronises the plan's stream. */
@@ -583,7 +583,7 @@ MFFT_API int mfft_ew_increments(mfft_plan_t plan, const void* x, int ncomp, int6
  * increments of x = ifftn(field f, dealias) along z at the separation seps[i], by the rule above, over THIS RANK's part of the
  * real-space grid (as mfft_real_moments; z is local to a rank on slabs and pencils alike: no halo), *count = the points per field
  * (S_p / count is the structure function).  Routes (mfft_plan_get_info "nonlinear_increments_fused_3_2" / "_none" / "_2_3"):
- * fused, the z kernel keeps the real row in its exchange buffer and reads it back shifted (csrc/fft_nlz.h body_incr), no
+ * fused, the z kernel keeps the real row in its exchange buffer and reads it back shifted (csrc/nlz_incr.h NlzIncr::body), no
  * real-space array exists; every other plan transforms one field at a time into ONE real work array and sweeps it
  * (mfft_ew_increments).  Bitwise reproducible run to run on one plan and device.  Errors as mfft_nlz_incr_rows with n = M,
  * reported before anything is enqueued.  The inputs are preserved.  Synchronises the plan's stream. */
@@ -606,7 +606,7 @@ MFFT_API int mfft_ew_increment_histogram(mfft_plan_t plan, const void* x, int nc
  * ifftn(field f, dealias) along z at the separation seps[i] in nbins equal bins of [lo[f * nsep + i], hi[f * nsep + i]), by the rule
  * above, over THIS RANK's part of the real-space grid (as mfft_real_increments: z is local to a rank, no halo), *count = the points
  * per field.  Routes (mfft_plan_get_info "nonlinear_incr_hist_fused_3_2" / "_none" / "_2_3"): fused, the z kernel keeps the real row
- * in its exchange buffer, reads it back shifted and counts into LDS (csrc/fft_nlz.h body_incr_hist), no real-space array exists;
+ * in its exchange buffer, reads it back shifted and counts into LDS (csrc/nlz_incr_hist.h NlzIncrHist::body), no real-space array exists;
  * every other plan transforms one field at a time into ONE real work array and sweeps it (mfft_ew_increment_histogram).  The fused
  * counts are the same for every number of ranks.  Errors as mfft_nlz_incr_hist_rows with n = M, reported before anything is
  * enqueued, out and count untouched.  The inputs are preserved.  Synchronises the plan's stream. */
@@ -628,7 +628,7 @@ MFFT_API int mfft_ew_profiles(mfft_plan_t plan, const void* x, const void* y, in
  * and pencils alike), by the rule above about center (2 ncomp centres, a_0.., then b_0..; NULL: zeros); out holds ncomp * 5 * M
  * host doubles, *count = the points per plane on this rank (sums / count, added over the ranks, are the plane averages).  Routes
  * (mfft_plan_get_info "nonlinear_profiles_fused_3_2" / "_none" / "_2_3"): fused, a thread of the z kernel holds the same z
- * positions for every row it meets, so the plane sums are its running sums (csrc/fft_nlz.h body_prof) and no real-space array
+ * positions for every row it meets, so the plane sums are its running sums (csrc/nlz_prof.h NlzProf::body) and no real-space array
  * exists; every other plan transforms a_p and b_p into TWO real work arrays and sweeps them (mfft_ew_profiles).  Bitwise
  * reproducible run to run on one plan and device.  MFFT_ERR_INVALID for a NULL b_hat, ncomp outside {1, 3} and a centre that is not
  * finite, reported before anything is enqueued, out and count untouched.  The inputs are preserved.  Synchronises the plan's

@@ -6,6 +6,7 @@
 #include "comm.h"
 #include "mfft_internal.h"
 #include "fft_nlz.h"
+#include "nlz_moments.h"
 
 using namespace mfft;
 
@@ -335,7 +336,7 @@ int mfft_nlz_rows_absmax(const void* a, const void* b, void* out, int64_t nrows,
   return rc;
 }
 
-// The stages that end in a reduction (fft_nlz.h body_moments, body_hist, body_joint, body_quad, body_incr, body_incr_hist, body_prof), synchronous; what
+// The stages that end in a reduction (the body of NlzMoments, NlzHist, NlzJoint, NlzQuad, NlzIncr, NlzIncrHist, NlzProf: a header each, nlz_*.h), synchronous; what
 // their seven entry points share.  nfields = 1: a is (nrows, pitch); 2: a and b are; 3: a is (3, nrows, pitch); 6: a and b are.  `valid`
 // bins per row exist, the first valid_in of them are read (0: all of them).  Fields in the order a_0.., then b_0..; field f rides in
 // slot nls_slot(u, f), the plan's rule.  Everything is checked before the first launch; the outputs are written on success only.

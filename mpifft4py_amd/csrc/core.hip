@@ -12,6 +12,13 @@
 #include <tuple>
 #include "mfft_internal.h"
 #include "fft_nlz.h"
+#include "nlz_moments.h"
+#include "nlz_hist.h"
+#include "nlz_joint.h"
+#include "nlz_quad.h"
+#include "nlz_incr.h"
+#include "nlz_incr_hist.h"
+#include "nlz_prof.h"
 
 namespace mfft {
 
@@ -605,7 +612,7 @@ int launch_nlz(const NlzArgs& a, hipStream_t s) {
   });
 }
 
-// The stages that end in a reduction (fft_nlz.h body_moments, body_hist, body_joint, body_quad, body_incr, body_incr_hist, body_prof: the table entries with
+// The stages that end in a reduction (the body of NlzMoments, NlzHist, NlzJoint, NlzQuad, NlzIncr, NlzIncrHist, NlzProf, a header each, nlz_*.h: the table entries with
 // nout == 0; NlrArgs of mfft_internal.h).  Their grid does not follow the rows: the workgroups that are resident at once, CUs x
 // min(what the runtime says fits, NLS_WG_PER_CU), asked once per device and kernel, and never more than there are pairs of rows to
 // start on.

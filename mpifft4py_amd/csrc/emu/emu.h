@@ -1,4 +1,4 @@
-// emu.h -- host-side workgroup emulator for the kernel bodies of fft_kernels.h, fft_chirpz.h, fft_col3.h and fft_nlz.h
+// emu.h -- host-side workgroup emulator for the kernel bodies of fft_kernels.h, fft_chirpz.h, fft_col3.h, fft_nlz.h and nlz_*.h
 // (TEST INFRASTRUCTURE, built with g++, never part of the product library).  Each GPU thread of a workgroup is a ucontext
 // fibre; MFFT_BARRIER() yields to a round-robin scheduler, so the very same body code that hipcc compiles for gfx950 runs
 // here with real barrier semantics and a real shared "LDS" buffer.  The tests (test_col.h, test_row.h, test_nlz.h) check

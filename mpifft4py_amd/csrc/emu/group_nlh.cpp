@@ -1,4 +1,4 @@
-// emulator group nlh: the fused z stage that ends in a histogram (body_hist)
+// emulator group nlh: the fused z stage that ends in a histogram (NlzHist::body)
 #include "test_nlh.h"
 
 static void emu_group() {

@@ -1,4 +1,4 @@
-// emulator group nli: the fused z stage that ends in structure functions along z (body_incr)
+// emulator group nli: the fused z stage that ends in structure functions along z (NlzIncr::body)
 #include "test_incr.h"
 
 static void emu_group() {

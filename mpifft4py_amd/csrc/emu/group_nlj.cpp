@@ -1,4 +1,4 @@
-// emulator group nlj: the fused z stage that ends in a joint histogram (body_joint)
+// emulator group nlj: the fused z stage that ends in a joint histogram (NlzJoint::body)
 #include "test_nlj.h"
 
 static void emu_group() {

@@ -1,4 +1,4 @@
-// emulator group nlk: the fused z stage that ends in increment histograms along z (body_incr_hist)
+// emulator group nlk: the fused z stage that ends in increment histograms along z (NlzIncrHist::body)
 #include "test_nlk.h"
 
 static void emu_group() {

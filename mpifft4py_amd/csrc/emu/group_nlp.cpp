@@ -1,4 +1,4 @@
-// emulator group nlp: the fused z stage that ends in plane-averaged profiles along z (body_prof)
+// emulator group nlp: the fused z stage that ends in plane-averaged profiles along z (NlzProf::body)
 #include "test_nlp.h"
 
 static void emu_group() {

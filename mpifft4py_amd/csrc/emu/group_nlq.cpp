@@ -1,4 +1,4 @@
-// emulator group nlq: the fused z stage that ends in the statistics of a quadratic form (body_quad)
+// emulator group nlq: the fused z stage that ends in the statistics of a quadratic form (NlzQuad::body)
 #include "test_nlq.h"
 
 static void emu_group() {

@@ -1,4 +1,4 @@
-// emulator group nls: the fused z stage that ends in a reduction (body_moments)
+// emulator group nls: the fused z stage that ends in a reduction (NlzMoments::body)
 #include "test_nlz.h"
 
 static void emu_group() {

@@ -1,9 +1,10 @@
-// test_incr.h -- emulator tests of the fused z stage that ends in structure functions (fft_nlz.h body_incr, Op::Increments): per
+// test_incr.h -- emulator tests of the fused z stage that ends in structure functions (nlz_incr.h NlzIncr::body, Op::Increments): per
 // field and separation s the sums S2, S3, S4 of d = r(z + s) - r(z) over periodic rows, against long-double transforms of the
 // rows.  The bound is the moments' (test_nlz.h run_nls) with the factor 2 that a difference of two values brings:
 //     |S_p - ref| <= 2 tol p sqrt(sum d^(2 (p - 1)) sum x^2) + (cnt + 8) 2^-52 sum |d|^p
 // The launch has `ngroups` workgroups whatever the row count; the waves' slots are added up on the host in the order of the fold.
 #pragma once
+#include "nlz_incr.h"
 #include "test_nlz.h"
 
 struct NliCase {

@@ -1,4 +1,4 @@
-// test_nlh.h -- emulator tests of the fused z stage that ends in a histogram (fft_nlz.h body_hist, Op::Histogram): the counts of up
+// test_nlh.h -- emulator tests of the fused z stage that ends in a histogram (nlz_hist.h NlzHist::body, Op::Histogram): the counts of up
 // to six real fields in equal bins, against long-double transforms of the rows.  Counts cannot be compared with a tolerance, so
 // the test brackets them: the slot rule is monotone in x, hence with |x_kernel - x_ref| <= delta every CUMULATIVE count obeys
 //     C_j(x_ref + delta) <= C_j(kernel) <= C_j(x_ref - delta),   j = 0 .. nbins + 1,   C_j = points in slots 0 .. j,
@@ -6,6 +6,7 @@
 // 8 eps log2(M) sum_k h_k (|A_k| + |B_k|) / M over BOTH fields of the pair (they share the transform), h the Hermitian weights.
 // In the emulator the LDS add is a plain add (the threads are fibres of one host thread).
 #pragma once
+#include "nlz_hist.h"
 #include "test_nlz.h"
 
 struct NlhCase {

@@ -1,4 +1,4 @@
-// test_nlj.h -- emulator tests of the fused z stage that ends in a JOINT histogram (fft_nlz.h body_joint, Op::JointHistogram): the
+// test_nlj.h -- emulator tests of the fused z stage that ends in a JOINT histogram (nlz_joint.h NlzJoint::body, Op::JointHistogram): the
 // counts of the points (a_p, b_p) of one or three pairs of real fields in a grid of nba x nbb equal bins, against long-double
 // transforms of the rows.  Counts cannot be compared with a tolerance, so the test brackets them in two dimensions: the cell rule
 // is monotone in each argument, hence with |x_kernel - x_ref| <= delta on BOTH fields every cumulative count obeys
@@ -7,6 +7,7 @@
 // Both marginals EQUAL, count for count, what NlzHist of the same template parameters gives on the same inputs, ranges and bin
 // counts: in the emulator the two bodies run the same arithmetic.  In the emulator the LDS add is a plain add.
 #pragma once
+#include "nlz_joint.h"
 #include "test_nlh.h"
 
 struct NljCase {

@@ -1,4 +1,4 @@
-// test_nlk.h -- emulator tests of the fused z stage that ends in INCREMENT HISTOGRAMS (fft_nlz.h body_incr_hist,
+// test_nlk.h -- emulator tests of the fused z stage that ends in INCREMENT HISTOGRAMS (nlz_incr_hist.h NlzIncrHist::body,
 // Op::IncrementHistogram): per field and separation s the counts of d = r(z + s) - r(z) over periodic rows in nbins equal bins of a
 // range of its own, against long-double transforms of the rows THROUGH THE SAME RULE (hist_slot).  Counts cannot be compared with a
 // tolerance, so the test brackets them as test_nlh.h does: the slot rule is monotone in d, and with |x_kernel - x_ref| <= delta on
@@ -9,6 +9,7 @@
 // leaves every other field -- the partner on its transform among them -- with the counts of the run without it.  In the emulator
 // the LDS add is a plain add.
 #pragma once
+#include "nlz_incr_hist.h"
 #include "test_nlh.h"
 
 struct NlkCase {

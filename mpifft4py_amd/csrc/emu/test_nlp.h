@@ -1,4 +1,4 @@
-// test_nlp.h -- emulator tests of the fused z stage that ends in plane-averaged PROFILES (fft_nlz.h body_prof, Op::Profiles): per
+// test_nlp.h -- emulator tests of the fused z stage that ends in plane-averaged PROFILES (nlz_prof.h NlzProf::body, Op::Profiles): per
 // pair (a_p, b_p) of real fields and per position m of the row the five sums over all rows
 //     [ sum d_a, sum d_b, sum d_a^2, sum d_b^2, sum d_a d_b ],   d = value - centre,
 // against long-double transforms of the rows.  The bound is the moments' (test_nlz.h run_nls) applied per position: with R rows,
@@ -9,6 +9,7 @@
 // The launch has `ngroups` workgroups whatever the row count; the partial profiles are added up on the host in the order of the
 // fold.  Every slot of `part` is written (poison), the inputs are preserved.
 #pragma once
+#include "nlz_prof.h"
 #include "test_nlz.h"
 
 struct NlpCase {

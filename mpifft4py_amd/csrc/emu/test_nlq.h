@@ -1,4 +1,4 @@
-// test_nlq.h -- emulator tests of the fused z stage that ends in the statistics of a quadratic form (fft_nlz.h body_quad,
+// test_nlq.h -- emulator tests of the fused z stage that ends in the statistics of a quadratic form (nlz_quad.h NlzQuad::body,
 // Op::Quadratic): q = sum_f w_f r_f^2 over up to six real fields, its [min, max, S1 .. S4] and its counts in equal bins, against
 // long-double transforms of the rows.  With delta the worst-case error of a row of a PAIR (test_nlh.h: 8 eps log2(M) sum_k h_k
 // (|A_k| + |B_k|) / M over both fields of the transform) the pointwise bound of q is
@@ -6,6 +6,7 @@
 // and with d = q - c:  min and max within max dq;  |S_p - ref| <= sum p dq (|d| + dq)^(p - 1) + (cnt + 8) 2^-52 sum |d|^p;  the
 // cumulative counts bracketed by those of q_ref + dq and q_ref - dq (the slot rule is monotone).  A bound, not a measurement.
 #pragma once
+#include "nlz_quad.h"
 #include "test_nlz.h"
 
 struct NlqCase {

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include "emu.h"
 #include "fft_nlz.h"
+#include "nlz_moments.h"
 #include "plans.h"
 
 // The long-double reference the tests share.
@@ -397,7 +398,7 @@ template <class S> static void test_nlm_all() {
   }
 }
 
-// The stage that ends in a reduction (fft_nlz.h body_moments, Op::Moments): [min, max, S1 .. S4] of up to six real fields over all
+// The stage that ends in a reduction (nlz_moments.h NlzMoments::body, Op::Moments): [min, max, S1 .. S4] of up to six real fields over all
 // rows against long-double transforms of the rows.  The launch has `ngroups` workgroups whatever the row count, so the loop over
 // the rows iterates and ends unevenly; the waves' slots are added up on the host in the order of the fold kernel.
 struct NlsCase {

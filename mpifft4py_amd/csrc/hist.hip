@@ -1,13 +1,13 @@
 // hist.hip -- histograms on the device: per field nbins + 3 int64 counts, [0] below lo, [1 .. nbins] the equal bins of [lo, hi),
-// [nbins + 1] at or above hi, [nbins + 2] not finite (fft_nlz.h hist_slot: the one rule of host, sweep, fused kernel and tests).
-// The fold of the partial histograms that the fused z stage emits (fft_nlz.h body_hist) and the streaming sweep mfft_ew_histogram
+// [nbins + 1] at or above hi, [nbins + 2] not finite (nlz_reduce.h hist_slot: the one rule of host, sweep, fused kernel and tests).
+// The fold of the partial histograms that the fused z stage emits (nlz_hist.h NlzHist::body) and the streaming sweep mfft_ew_histogram
 // over real fields (the composed route of mfft_real_histogram, and the caller's own arrays), the companion of mfft_ew_moments.
 // No global atomics anywhere: a workgroup counts in LDS (unsigned), stores its histogram with plain stores, one small launch adds
 // the workgroups' rows in a FIXED order into int64.  Counts are integers, so the order would not matter anyway: the result is
 // the same bits run to run, device to device and for every number of ranks.
 #include <math.h>
 #include "plan_impl.h"
-#include "fft_nlz.h"
+#include "nlz_hist.h"
 
 using namespace mfft;
 

@@ -1,12 +1,12 @@
 // incr.hip -- structure functions along z on the device: per field and separation s the sums S2, S3, S4 of the increments
-// d = r(z + s) - r(z) over periodic rows (the rule: include/mpifft4py_amd.h, fft_nlz.h incr_value / incr_add).  The fold of the
-// partial sums that the fused z stage emits (fft_nlz.h body_incr), the streaming sweep mfft_ew_increments over real rows (the
+// d = r(z + s) - r(z) over periodic rows (the rule: include/mpifft4py_amd.h, nlz_reduce.h incr_value, nlz_incr.h incr_add).  The fold of the
+// partial sums that the fused z stage emits (nlz_incr.h NlzIncr::body), the streaming sweep mfft_ew_increments over real rows (the
 // composed route of mfft_real_increments, and the caller's own arrays) and the plan's accumulator.
 // No atomics anywhere: waves store their partials with plain stores, one small launch adds them in a FIXED order, so the sums are
 // bitwise reproducible run to run.  Powers and sums in double whatever the precision of the data.
 #include <math.h>
 #include "plan_impl.h"
-#include "fft_nlz.h"
+#include "nlz_incr.h"
 
 using namespace mfft;
 

@@ -1,14 +1,14 @@
 // incrhist.hip -- PDFs of the increments along z on the device: per field and separation s the nbins + 3 int64 counts of
 // d = r(z + s) - r(z) over periodic rows, each (field, separation) over a range of its own (the rule: include/mpifft4py_amd.h;
-// fft_nlz.h incr_value, incr_hist_slot, hist_slot).  The streaming sweep mfft_ew_increment_histogram over real rows (the composed
+// nlz_reduce.h incr_value and hist_slot, nlz_incr_hist.h incr_hist_slot).  The streaming sweep mfft_ew_increment_histogram over real rows (the composed
 // route of mfft_real_increment_histogram, and the caller's own arrays) and the plan's accumulator; the partial histograms that the
-// fused z stage emits (fft_nlz.h body_incr_hist) are rows of nsep (nbins + 3) counts per field and go through the histograms' fold
+// fused z stage emits (nlz_incr_hist.h NlzIncrHist::body) are rows of nsep (nbins + 3) counts per field and go through the histograms' fold
 // (hist.hip hist_fold_slots), as the sweep's do.
 // No global atomics anywhere: a workgroup counts in LDS (unsigned), stores its histograms with plain stores, one small launch adds the
 // workgroups' rows in a FIXED order into int64.
 #include <math.h>
 #include "plan_impl.h"
-#include "fft_nlz.h"
+#include "nlz_incr_hist.h"
 
 using namespace mfft;
 

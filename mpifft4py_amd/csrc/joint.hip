@@ -1,14 +1,14 @@
 // joint.hip -- joint histograms on the device: per PAIR of real fields (nba + 3)(nbb + 3) int64 counts,
 //     cell = sa * (nbb + 3) + sb,   sa = hist_slot(x_a, lo_a, inv_a, nba),   sb = hist_slot(x_b, lo_b, inv_b, nbb)
-// (fft_nlz.h hist_slot and joint_cell: the one rule of host, sweep, fused kernel and tests).  The plan's accumulator of the fused z
-// stage that ends in a joint histogram (fft_nlz.h body_joint; launches and fold: core.hip nlr_rows), and the streaming sweep
+// (nlz_reduce.h hist_slot and nlz_joint.h joint_cell: the one rule of host, sweep, fused kernel and tests).  The plan's accumulator of the fused z
+// stage that ends in a joint histogram (nlz_joint.h NlzJoint::body; launches and fold: core.hip nlr_rows), and the streaming sweep
 // mfft_ew_joint_histogram over two real arrays of equal length (the composed route of mfft_real_joint_histogram, and the caller's own arrays), the companion of
 // mfft_ew_histogram.  No global atomics anywhere: a workgroup counts in ONE LDS grid (unsigned), stores it with plain stores, the
 // fold of hist.hip adds the workgroups' rows in a FIXED order into int64.  Counts are integers: the same bits run to run, device
 // to device and for every number of ranks.
 #include <math.h>
 #include "plan_impl.h"
-#include "fft_nlz.h"
+#include "nlz_joint.h"
 
 using namespace mfft;
 

@@ -1,4 +1,4 @@
-// gfx950 instantiations: fused nonlinear z stage that ends in a histogram (fft_nlz.h NlzHist), double precision
+// gfx950 instantiations: fused nonlinear z stage that ends in a histogram (nlz_hist.h NlzHist), double precision
 #include "registry_nlz.h"
 #include "plans.h"
 namespace {

@@ -1,4 +1,4 @@
-// gfx950 instantiations: fused nonlinear z stage that ends in structure functions along z (fft_nlz.h NlzIncr), single precision
+// gfx950 instantiations: fused nonlinear z stage that ends in structure functions along z (nlz_incr.h NlzIncr), single precision
 #include "registry_nlz.h"
 #include "plans.h"
 namespace {

@@ -1,4 +1,4 @@
-// gfx950 instantiations: fused nonlinear z stage that ends in a joint histogram (fft_nlz.h NlzJoint), single precision
+// gfx950 instantiations: fused nonlinear z stage that ends in a joint histogram (nlz_joint.h NlzJoint), single precision
 #include "registry_nlz.h"
 #include "plans.h"
 namespace {

@@ -1,4 +1,4 @@
-// gfx950 instantiations: fused nonlinear z stage that ends in increment histograms along z (fft_nlz.h NlzIncrHist), single precision
+// gfx950 instantiations: fused nonlinear z stage that ends in increment histograms along z (nlz_incr_hist.h NlzIncrHist), single precision
 #include "registry_nlz.h"
 #include "plans.h"
 namespace {

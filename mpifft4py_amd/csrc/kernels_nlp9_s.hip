@@ -1,4 +1,4 @@
-// gfx950 instantiations: fused nonlinear z stage that ends in plane-averaged profiles along z (fft_nlz.h NlzProf), single precision
+// gfx950 instantiations: fused nonlinear z stage that ends in plane-averaged profiles along z (nlz_prof.h NlzProf), single precision
 #include "registry_nlz.h"
 #include "plans.h"
 namespace {

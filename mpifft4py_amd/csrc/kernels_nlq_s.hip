@@ -1,4 +1,4 @@
-// gfx950 instantiations: fused nonlinear z stage that ends in the statistics of a quadratic form (fft_nlz.h NlzQuad), single precision
+// gfx950 instantiations: fused nonlinear z stage that ends in the statistics of a quadratic form (nlz_quad.h NlzQuad), single precision
 #include "registry_nlz.h"
 #include "plans.h"
 namespace {

@@ -1,4 +1,4 @@
-// gfx950 instantiations: fused nonlinear z stage that ends in a reduction (fft_nlz.h NlzMoments), single precision
+// gfx950 instantiations: fused nonlinear z stage that ends in a reduction (nlz_moments.h NlzMoments), single precision
 #include "registry_nlz.h"
 #include "plans.h"
 namespace {

@@ -195,8 +195,8 @@ inline int nls_slot(const NlFields& u, int f) {
 bool nlz_supported(int64_t n, int prec, Op product = Op::Plain, bool absmax = false);
 int64_t nlz_absmax_waves(int64_t n, int prec, Op product, int64_t nrows);
 int launch_nlz(const NlzArgs& a, hipStream_t s);
-// The z stages that end in a REDUCTION instead of a product (the table entries with nout == 0; fft_nlz.h body_moments, body_hist,
-// body_joint, body_quad, body_incr, body_prof), described ONCE: the launch, its shape, the loop over the rows and the routes of the plan read
+// The z stages that end in a REDUCTION instead of a product (the table entries with nout == 0; a header each, nlz_*.h: the body of NlzMoments,
+// NlzHist, NlzJoint, NlzQuad, NlzIncr, NlzProf), described ONCE: the launch, its shape, the loop over the rows and the routes of the plan read
 // NlrArgs.  Pair p is the rows a[p] + i b[p] on one complex transform, p < npairs <= 3; b[p] may be null (an odd field count) except
 // in a joint histogram and in a profile.  x = norm * (the un-normalised inverse transform).  Slots are [pair][a, b].
 // What a call of one kind adds to that -- the plan parks it between a call's begin and its batches (mfft_plan_s::nlcall):
@@ -244,7 +244,7 @@ int nlr_rows(const NlrArgs& z, void* acc, void* acc2, hipStream_t s);
 // identity (+Inf, -Inf, zeros); moments_fold: acc[v] = merge(acc[v], the groups' part[g * nvals + v] in a fixed order), NaNs kept.
 int moments_clear(double* acc, int nvals, hipStream_t s);
 int moments_fold(const double* part, size_t groups, int nvals, double* acc, hipStream_t s);
-// Histograms (hist.hip): per field nbins + 3 counts -- below lo, the nbins bins of [lo, hi), at or above hi, not finite (fft_nlz.h
+// Histograms (hist.hip): per field nbins + 3 counts -- below lo, the nbins bins of [lo, hi), at or above hi, not finite (nlz_reduce.h
 // hist_slot).  acc: device int64, (nfields, nbins + 3).  hist_fold: acc[f][s] += sum over the groups g, in fixed order, of
 // part[(g * nfields + f) * (nbins + 3) + s]; nfields <= 6.
 size_t hist_part_bytes(int ngroups, int nslots, int nbins);
@@ -254,7 +254,7 @@ int hist_fold_slots(const unsigned* part, size_t groups, int nfields, int nslots
 // inv = nbins / (hi - lo) of a valid range; MFFT_ERR_INVALID for nbins outside 1 .. NLH_MAXBINS, hi <= lo, a range that is not finite
 int hist_range(double lo, double hi, int nbins, double* inv);
 int hist_max_bins();
-// Joint histograms (joint.hip): per pair (nba + 3)(nbb + 3) counts, cell = slot of a_p * (nbb + 3) + slot of b_p (fft_nlz.h joint_cell)
+// Joint histograms (joint.hip): per pair (nba + 3)(nbb + 3) counts, cell = slot of a_p * (nbb + 3) + slot of b_p (nlz_joint.h joint_cell)
 inline int joint_cells(int nba, int nbb) { return (nba + 3) * (nbb + 3); }
 size_t joint_part_bytes(int ngroups, int npairs, int nba, int nbb);
 // inv of a valid range; MFFT_ERR_INVALID for a bin count outside 1 .. MFFT_JOINT_MAXBINS, hi <= lo, a range that is not finite
@@ -265,7 +265,7 @@ size_t quad_hpart_bytes(int ngroups, int nbins);
 // finite weights, 0 <= nbins <= NLH_MAXBINS, and with nbins > 0 a valid range (hist_range); *inv = 1 where nbins == 0
 int quad_check(const double* weights, int nfields, double lo, double hi, int nbins, double* inv);
 // Sums of increment powers (incr.hip): per field and separation S2, S3, S4 of d = x(z + sep) - x(z), rows periodic.  acc: device
-// doubles, [slot][MFFT_INCR_MAXSEP][S2, S3, S4], six slots (fft_nlz.h NLI_SLOTS).
+// doubles, [slot][MFFT_INCR_MAXSEP][S2, S3, S4], six slots (nlz_incr.h NLI_SLOTS).
 // incr_fold: acc[v] += the groups' part[g * nvals + v] added in a fixed order, nvals = whole slots
 constexpr int INCR_FIELD = MFFT_INCR_MAXSEP * 3, INCR_SLOTS = 6 * INCR_FIELD;
 int incr_fold(const double* part, size_t groups, int nvals, double* acc, hipStream_t s);
@@ -278,7 +278,7 @@ size_t incr_hist_part_bytes(int ngroups, int nslots, int nsep, int nbins);
 // not finite
 int incr_hist_range(double lo, double hi, int nbins, double* inv);
 // Plane-averaged profiles along z (profiles.hip): per pair and position of the row the sums of d_a, d_b, d_a^2, d_b^2, d_a d_b over
-// all rows (fft_nlz.h prof_add).  acc: device doubles, (npairs, 5, n), pairs in slot order.
+// all rows (nlz_prof.h prof_add).  acc: device doubles, (npairs, 5, n), pairs in slot order.
 // prof_fold: acc[v] += the nslots partial profiles part[g * nvals + v], added in a fixed order
 int prof_fold(const double* part, size_t nslots, size_t nvals, double* acc, hipStream_t s);
 // bytes of the partial profiles of a launch: one per row slot, ngroups x tile of them

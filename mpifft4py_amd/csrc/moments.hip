@@ -1,5 +1,5 @@
 // moments.hip -- one-point statistics on the device: per field [min, max, S1, S2, S3, S4], S_p = sum (x - c)^p.  The fold of the
-// partial statistics that the fused z stage emits (fft_nlz.h body_moments) and the streaming sweep mfft_ew_moments over real
+// partial statistics that the fused z stage emits (nlz_moments.h NlzMoments::body) and the streaming sweep mfft_ew_moments over real
 // fields (the composed route of mfft_real_moments, and the caller's own arrays), the companion of mfft_ew_absmax.
 // No global atomics anywhere: waves store their partials with plain stores, one small launch adds them in a FIXED order, so the
 // sums are bitwise reproducible run to run.  Powers and sums in double whatever the precision of the data.
@@ -7,7 +7,7 @@
 // and NaN or Inf sums.
 #include <math.h>
 #include "plan_impl.h"
-#include "fft_nlz.h"
+#include "nlz_moments.h"
 
 using namespace mfft;
 
@@ -42,7 +42,7 @@ __global__ __launch_bounds__(MF_BLOCK) void moments_fold_kernel(const double* __
 }
 
 // One component of a real field per blockIdx.y: 16 bytes per lane, six doubles of accumulators per lane, one wave reduction at
-// the end (fft_nlz.h wave_moments_store), one plain store of six doubles per wave into part[(wave of the launch) * ncomp + component].
+// the end (nlz_moments.h wave_moments_store), one plain store of six doubles per wave into part[(wave of the launch) * ncomp + component].
 // A component need not start on 16 bytes (single precision, odd n): the elements before the first aligned one and after the last
 // whole vector are taken singly by the first lanes, as absmax.hip does.
 template <typename T>

@@ -2,6 +2,7 @@
 #include <cmath>
 #include "plan_impl.h"
 #include "fft_nlz.h"
+#include "nlz_moments.h"
 
 using namespace mfft;
 
@@ -24,7 +25,7 @@ extern "C" int mfft_ew_mul(mfft_plan_t plan, const void* a, const void* b, void*
 // only the composed route, which chooses the element-wise products, names a product.
 // The REDUCTIONS are the table's entries with nout == 0 (moments, histograms, quadratic forms, increments, joint histograms, profiles): the
 // fused routes run their inverse passes and end the z stage in reduce_batch -- nothing forward is launched -- and a call is
-// real_reduce: mask, begin, fused or reduce_composed, end.  What a new kind supplies: its row of NL_PRODUCTS and its kernels'
+// real_reduce: mask, begin, fused or reduce_composed, end.  What a new kind supplies: its header (nlz_*.h: parameters, rule, body), its row of NL_PRODUCTS and its kernels'
 // registration; its members of NlrCall with their copy and checks in launch_nlr, its partials' size and its fold (core.hip); its
 // sweep over a real array for reduce_composed; *_begin / *_end around its accumulator; its real_* entry.
 
@@ -502,7 +503,7 @@ int mfft_plan_s::real_moments(const NlFields& u, int dealias, const double* cent
   return 0;
 }
 
-// per field nbins + 3 counts: below lo, the nbins equal bins of [lo, hi), at or above hi, not finite (fft_nlz.h hist_slot).  Counts are
+// per field nbins + 3 counts: below lo, the nbins equal bins of [lo, hi), at or above hi, not finite (nlz_reduce.h hist_slot).  Counts are
 // integers: the same bits on every route that computes the same values.
 int mfft_plan_s::real_histogram(const NlFields& u, int dealias, const double* lo, const double* hi, int nbins, int64_t* out, int64_t* count) {
   double l6[6] = {0, 0, 0, 0, 0, 0}, i6[6] = {1, 1, 1, 1, 1, 1};
@@ -520,7 +521,7 @@ int mfft_plan_s::real_histogram(const NlFields& u, int dealias, const double* lo
 }
 
 // q(x) = sum_f w_f r_f(x)^2, r_f = ifftn(field f, dealias), by the one rule of include/mpifft4py_amd.h: [min, max, S1 .. S4] of q about
-// `center` and, nbins > 0, its nbins + 3 counts over [lo, hi) (fft_nlz.h body_quad)
+// `center` and, nbins > 0, its nbins + 3 counts over [lo, hi) (nlz_quad.h NlzQuad::body)
 int mfft_plan_s::real_quadratic(const NlFields& u, int dealias, const double* weights, double center, double lo, double hi, int nbins, double* out6,
                                 int64_t* counts, int64_t* count) {
   if (!std::isfinite(center)) return set_error(MFFT_ERR_INVALID, "the centre is not finite");
@@ -534,7 +535,7 @@ int mfft_plan_s::real_quadratic(const NlFields& u, int dealias, const double* we
   return real_reduce(u, dealias, Op::Quadratic, count, begin, [&] { return quad_end(out6, counts); });
 }
 
-// per field and separation the sums S2, S3, S4 of d = x(z + s) - x(z), rows periodic (fft_nlz.h body_incr)
+// per field and separation the sums S2, S3, S4 of d = x(z + s) - x(z), rows periodic (nlz_incr.h NlzIncr::body)
 int mfft_plan_s::real_increments(const NlFields& u, int dealias, const int64_t* seps, int nsep, double* out, int64_t* count) {
   const bool pad = dealias == MFFT_DEALIAS_3_2;
   const int64_t nr = local_real_count(pad), M = pad ? M2 : N2;
@@ -549,7 +550,7 @@ int mfft_plan_s::real_increments(const NlFields& u, int dealias, const int64_t* 
 }
 
 // per field and separation the nbins + 3 counts of d = x(z + s) - x(z) over [lo, hi) of that field and separation, rows periodic
-// (fft_nlz.h body_incr_hist)
+// (nlz_incr_hist.h NlzIncrHist::body)
 int mfft_plan_s::real_increment_histogram(const NlFields& u, int dealias, const int64_t* seps, int nsep, const double* lo, const double* hi,
                                           int nbins, int64_t* out, int64_t* count) {
   const bool pad = dealias == MFFT_DEALIAS_3_2;
@@ -575,7 +576,7 @@ int mfft_plan_s::real_increment_histogram(const NlFields& u, int dealias, const 
   return 0;
 }
 
-// per PAIR (x_a, x_b) = (ifftn(a_p), ifftn(b_p)) the (nba + 3)(nbb + 3) counts, cell = slot of x_a * (nbb + 3) + slot of x_b (fft_nlz.h
+// per PAIR (x_a, x_b) = (ifftn(a_p), ifftn(b_p)) the (nba + 3)(nbb + 3) counts, cell = slot of x_a * (nbb + 3) + slot of x_b (nlz_joint.h
 // joint_cell); the pairs lie in slot order already
 int mfft_plan_s::real_joint_histogram(const NlFields& u, int dealias, const double* lo, const double* hi, int nba, int nbb, int64_t* out,
                                       int64_t* count) {
@@ -589,7 +590,7 @@ int mfft_plan_s::real_joint_histogram(const NlFields& u, int dealias, const doub
 }
 
 // per PAIR (x, y) = (ifftn(a_p), ifftn(b_p)) and per z index m the sums over the plane of d_x, d_y, d_x^2, d_y^2, d_x d_y, d = value -
-// centre (fft_nlz.h body_prof, prof_add); the pairs lie in slot order already
+// centre (nlz_prof.h NlzProf::body, prof_add); the pairs lie in slot order already
 int mfft_plan_s::real_profiles(const NlFields& u, int dealias, const double* center, double* out, int64_t* count) {
   const bool pad = dealias == MFFT_DEALIAS_3_2;
   const int64_t nr = local_real_count(pad), M = pad ? M2 : N2;

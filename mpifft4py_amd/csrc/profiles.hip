@@ -1,14 +1,14 @@
 // profiles.hip -- plane-averaged profiles along z on the device: per PAIR of real fields (x, y) and per z index m the five sums
 //     [ sum (x - ca), sum (y - cb), sum (x - ca)^2, sum (y - cb)^2, sum (x - ca)(y - cb) ]
-// over the (x, y) plane at m (the rule: include/mpifft4py_amd.h, fft_nlz.h incr_value / prof_add) -- the first reduction whose
-// result is a vector in z.  The fold of the partial profiles that the fused z stage emits (fft_nlz.h body_prof; launches:
+// over the (x, y) plane at m (the rule: include/mpifft4py_amd.h, nlz_reduce.h incr_value, nlz_prof.h prof_add) -- the first reduction whose
+// result is a vector in z.  The fold of the partial profiles that the fused z stage emits (nlz_prof.h NlzProf::body; launches:
 // core.hip nlr_rows), the streaming sweep mfft_ew_profiles over two real arrays of rows (the composed route of mfft_real_profiles,
 // and the caller's own arrays) and the plan's accumulator.  No atomics anywhere: every partial profile goes out by plain stores,
 // one launch adds them in a FIXED order, so the sums are bitwise reproducible run to run.  Products and sums in double whatever the
 // precision of the data.
 #include <math.h>
 #include "plan_impl.h"
-#include "fft_nlz.h"
+#include "nlz_prof.h"
 
 using namespace mfft;
 

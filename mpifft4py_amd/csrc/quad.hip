@@ -1,14 +1,14 @@
 // quad.hip -- statistics of a quadratic form q = sum_f w_f r_f^2 of up to six real fields: [min, max, S1 .. S4] of q about a
-// centre and, with nbins > 0, its nbins + 3 counts (fft_nlz.h hist_slot).  The plan's accumulators of the fused z stage that
-// ends in them (fft_nlz.h body_quad; launches and folds: core.hip nlr_rows), the streaming sweep mfft_ew_quadratic over real fields -- q is formed on the fly, there is
+// centre and, with nbins > 0, its nbins + 3 counts (nlz_reduce.h hist_slot).  The plan's accumulators of the fused z stage that
+// ends in them (nlz_quad.h NlzQuad::body; launches and folds: core.hip nlr_rows), the streaming sweep mfft_ew_quadratic over real fields -- q is formed on the fly, there is
 // no q array --, and the two small kernels of the composed route of mfft_real_quadratic: add one field's (w r) r into the plan's
-// array of doubles, sweep that array once.  ONE evaluation rule (include/mpifft4py_amd.h; fft_nlz.h quad_term): q = 0, then per
+// array of doubles, sweep that array once.  ONE evaluation rule (include/mpifft4py_amd.h; nlz_quad.h quad_term): q = 0, then per
 // field in slot order q = q + (w r) r, every product and sum rounded on its own, in double.
 // No global atomics: waves store their partial statistics and workgroups their LDS histograms with plain stores, the folds of
 // moments.hip and hist.hip add them in a FIXED order.  Bitwise reproducible.
 #include <math.h>
 #include "plan_impl.h"
-#include "fft_nlz.h"
+#include "nlz_quad.h"
 
 using namespace mfft;
 

@@ -37,14 +37,14 @@ enum class Op : unsigned {
   // FAM_NLZ (a value no other family uses, and no combination of the flags above):
   Dot = 5,          // the dot product sum_f a_f b_f instead of the cross product: one result row (fft_nlz.h body_dot)
   CrossDot = 6,     // a x b AND sum_f a_f c_f of a third field: four result rows (fft_nlz.h body_cross_dot, NlcParams)
-  Moments = 7,      // no product and no result rows: min, max and power sums of the real rows (fft_nlz.h body_moments, NlsParams)
-  Histogram = 8,    // ... nor here: counts of the real rows' values in equal bins (fft_nlz.h body_hist, NlhParams); FAM_NLZ only
-  Quadratic = 9,    // ... nor here: moments and counts of q = sum_f w_f r_f^2 over the real rows (fft_nlz.h body_quad, NlqParams); FAM_NLZ only
+  Moments = 7,      // no product and no result rows: min, max and power sums of the real rows (nlz_moments.h NlzMoments::body, NlsParams)
+  Histogram = 8,    // ... nor here: counts of the real rows' values in equal bins (nlz_hist.h NlzHist::body, NlhParams); FAM_NLZ only
+  Quadratic = 9,    // ... nor here: moments and counts of q = sum_f w_f r_f^2 over the real rows (nlz_quad.h NlzQuad::body, NlqParams); FAM_NLZ only
   Outer = 10,       // all nine products a_i b_j: six rows in, NINE result rows (fft_nlz.h body_outer, NloParams); FAM_NLZ only
-  Increments = 11,  // no result rows: power sums of the increments along z of the real rows (fft_nlz.h body_incr, NliParams); FAM_NLZ only
-  JointHistogram = 12,  // no result rows: counts of the PAIRS of values of two real rows in a 2-D grid (fft_nlz.h body_joint, NljParams); FAM_NLZ only
-  Profiles = 13,    // no result rows: per position of the row the sums over all rows of two real rows' values, squares and product (fft_nlz.h body_prof, NlpParams); FAM_NLZ only
-  IncrementHistogram = 14  // no result rows: counts of the increments along z of the real rows in equal bins (fft_nlz.h body_incr_hist, NlkParams); FAM_NLZ only
+  Increments = 11,  // no result rows: power sums of the increments along z of the real rows (nlz_incr.h NlzIncr::body, NliParams); FAM_NLZ only
+  JointHistogram = 12,  // no result rows: counts of the PAIRS of values of two real rows in a 2-D grid (nlz_joint.h NlzJoint::body, NljParams); FAM_NLZ only
+  Profiles = 13,    // no result rows: per position of the row the sums over all rows of two real rows' values, squares and product (nlz_prof.h NlzProf::body, NlpParams); FAM_NLZ only
+  IncrementHistogram = 14  // no result rows: counts of the increments along z of the real rows in equal bins (nlz_incr_hist.h NlzIncrHist::body, NlkParams); FAM_NLZ only
 };
 constexpr Op operator|(Op a, Op b) { return (Op)((unsigned)a | (unsigned)b); }
 constexpr bool has(Op a, Op flag) { return ((unsigned)a & (unsigned)flag) != 0; }

@@ -3,6 +3,13 @@
 #pragma once
 #include "registry.h"
 #include "fft_nlz.h"
+#include "nlz_moments.h"
+#include "nlz_hist.h"
+#include "nlz_joint.h"
+#include "nlz_quad.h"
+#include "nlz_incr.h"
+#include "nlz_incr_hist.h"
+#include "nlz_prof.h"
 
 namespace mfft {
 
@@ -133,7 +140,7 @@ void register_nlo(const char* name) {
   reg.push_back(make_entry<K, NloParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::Outer, Build::Default, R, name));
 }
 
-// Op::Moments: the stage that ends in a reduction (fft_nlz.h body_moments, NlsParams; kernels_nls*.hip).  Rows, twiddle placement,
+// Op::Moments: the stage that ends in a reduction (nlz_moments.h NlzMoments::body, NlsParams; kernels_nls*.hip).  Rows, twiddle placement,
 // exchange, wave-synchronous build and the two-waves-per-SIMD cap are the cross kernels': the body inlines ONE transform where
 // the cross body inlines five and parks no row, but holds 36 doubles of accumulators for the whole launch: no scratch in single
 // precision, 36 - 196 bytes in the double-precision 12-values plans from 192 on (profiles/real_moments_regs.tsv).  No other cap
@@ -147,11 +154,11 @@ void register_nls(const char* name) {
   reg.push_back(make_entry<K, NlsParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::Moments, Build::Default, R, name));
 }
 
-// Op::Histogram: the stage that ends in a histogram (fft_nlz.h body_hist, NlhParams; kernels_nlh*.hip).  Rows, twiddle placement,
+// Op::Histogram: the stage that ends in a histogram (nlz_hist.h NlzHist::body, NlhParams; kernels_nlh*.hip).  Rows, twiddle placement,
 // exchange, wave-synchronous build and the two-waves-per-SIMD cap are the cross kernels', as the moments kernels' are: the body
 // inlines ONE transform and keeps its counts in LDS, 2 x (NLH_MAXBINS + 3) x 4 = 4120 bytes behind the exchange buffers
 // (DESIGN.md 7 has the table of LDS bytes and resident workgroups per plan).
-// MFFT_NLH_MERGE=1 builds the variant that merges runs of equal slot inside the wave before the add (fft_nlz.h lds_count_runs;
+// MFFT_NLH_MERGE=1 builds the variant that merges runs of equal slot inside the wave before the add (nlz_hist.h lds_count_runs;
 // `make nlh_variant`): measured against the plain add, profiles/real_histogram_ab.txt, and not shipped.
 #ifndef MFFT_NLH_MERGE
 #define MFFT_NLH_MERGE 0
@@ -165,9 +172,9 @@ void register_nlh(const char* name) {
   reg.push_back(make_entry<K, NlhParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::Histogram, Build::Default, R, name));
 }
 
-// Op::Quadratic: the stage that ends in the statistics of a quadratic form of its fields (fft_nlz.h body_quad, NlqParams;
+// Op::Quadratic: the stage that ends in the statistics of a quadratic form of its fields (nlz_quad.h NlzQuad::body, NlqParams;
 // kernels_nlq*.hip).  Rows, twiddle placement, exchange, wave-synchronous build and the two-waves-per-SIMD cap are those of
-// register_nls: the body inlines ONE transform, holds E doubles of running sum and 6 accumulators across it where body_moments holds
+// register_nls: the body inlines ONE transform, holds E doubles of running sum and 6 accumulators across it where NlzMoments::body holds
 // 36, and keeps ONE histogram in LDS, (NLH_MAXBINS + 3) x 4 = 2060 bytes behind the exchange buffers (DESIGN.md 7:
 // profiles/real_quadratic_regs.tsv, and the table of LDS bytes and resident workgroups).  No other cap was measured.
 template <class S, typename T>
@@ -179,9 +186,9 @@ void register_nlq(const char* name) {
   reg.push_back(make_entry<K, NlqParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::Quadratic, Build::Default, R, name));
 }
 
-// Op::Increments: the stage that ends in structure functions along z (fft_nlz.h body_incr, NliParams; kernels_nli*.hip).  Rows,
+// Op::Increments: the stage that ends in structure functions along z (nlz_incr.h NlzIncr::body, NliParams; kernels_nli*.hip).  Rows,
 // twiddle placement, exchange, wave-synchronous build and the two-waves-per-SIMD cap are those of register_nls: the body inlines ONE
-// transform and holds ONE pair's accumulators across it, 2 x NLI_MAXSEP x 3 = 48 doubles where body_moments holds 36, and takes no
+// transform and holds ONE pair's accumulators across it, 2 x NLI_MAXSEP x 3 = 48 doubles where NlzMoments::body holds 36, and takes no
 // LDS of its own (profiles/real_increments_regs.tsv).  No other cap was measured.
 template <class S, typename T>
 void register_nli(const char* name) {
@@ -192,9 +199,9 @@ void register_nli(const char* name) {
   reg.push_back(make_entry<K, NliParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::Increments, Build::Default, R, name));
 }
 
-// Op::JointHistogram: the stage that ends in a joint histogram (fft_nlz.h body_joint, NljParams; kernels_nlj*.hip).  Rows, twiddle
+// Op::JointHistogram: the stage that ends in a joint histogram (nlz_joint.h NlzJoint::body, NljParams; kernels_nlj*.hip).  Rows, twiddle
 // placement and the two-waves-per-SIMD cap are those of register_nlh: the body inlines ONE transform, computes the two slots that
-// body_hist computes and issues one LDS add where it issues two.  What differs is the LDS: the grid takes NLJ_MAXCELLS x 4 = 17956
+// NlzHist::body computes and issues one LDS add where it issues two.  What differs is the LDS: the grid takes NLJ_MAXCELLS x 4 = 17956
 // bytes behind the exchange buffers where the histograms take 4120, so the exchange has a rule of its own (nlj_split): whole complex
 // values where twiddles + exchange + grid stay within the 81920 bytes that keep two workgroups on a CU, real and imaginary halves
 // in turn beyond.  Every kernel whose twin has TWO resident workgroups by LDS keeps them, but for 3072 points in double precision,
@@ -226,7 +233,7 @@ void register_nlj(const char* name) {
   reg.push_back(make_entry<K, NljParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::JointHistogram, Build::Default, R, name));
 }
 
-// Op::IncrementHistogram: the stage that ends in increment histograms along z (fft_nlz.h body_incr_hist, NlkParams;
+// Op::IncrementHistogram: the stage that ends in increment histograms along z (nlz_incr_hist.h NlzIncrHist::body, NlkParams;
 // kernels_nlk*.hip).  Rows, twiddle placement, the two-waves-per-SIMD cap, the exchange and the wave build are those of
 // register_nlj, unchanged (nlj_split, nlj_wave): the pair's histograms take NLK_MAXCELLS x 4 = 16576 bytes behind the exchange
 // buffers, under the joint grid's 17956, so whatever the joint rule keeps resident stays resident here.  The body inlines ONE
@@ -241,10 +248,10 @@ void register_nlk(const char* name) {
   reg.push_back(make_entry<K, NlkParams<T>, S, T, W>(FAM_NLZ, S::N, 0, Op::IncrementHistogram, Build::Default, R, name));
 }
 
-// Op::Profiles: the stage that ends in plane-averaged profiles along z (fft_nlz.h body_prof, NlpParams; kernels_nlp*.hip).  Rows,
+// Op::Profiles: the stage that ends in plane-averaged profiles along z (nlz_prof.h NlzProf::body, NlpParams; kernels_nlp*.hip).  Rows,
 // twiddle placement, exchange, wave-synchronous build and the two-waves-per-SIMD cap are those of register_nls: the body inlines ONE
 // transform and holds ONE pair's accumulators across it, E x NLP_STATS doubles -- 40 for the 8-values plans, 60 for the 12-values
-// plans, where body_moments holds 36 and body_incr 48 --, and takes no LDS of its own (profiles/real_profiles_regs.tsv).  No other
+// plans, where NlzMoments::body holds 36 and NlzIncr::body 48 --, and takes no LDS of its own (profiles/real_profiles_regs.tsv).  No other
 // cap was measured.
 template <class S, typename T>
 void register_nlp(const char* name) {

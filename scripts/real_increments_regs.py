@@ -42,7 +42,7 @@ def main():
     build = os.path.join(CSRC, "build")
     rows = table([os.path.join(build, "kernels_%s_%s.o" % (u, p)) for u in ("nls", "nls9", "nli", "nli9") for p in "ds"])
     lds = lds_table()
-    header = open(os.path.join(CSRC, "fft_nlz.h")).read()
+    header = open(os.path.join(CSRC, "nlz_incr.h")).read()
     maxsep = int(re.search(r"NLI_MAXSEP = (\d+)", header).group(1))
     kinds = ("moments", "incr")
     print("# NlzFft kernels, gfx950: moments (kernels_nls*.hip) | increments (kernels_nli*.hip), NLI_MAXSEP = %d: one pair's 2 x %d x 3 = %d doubles of" % (maxsep, maxsep, 6 * maxsep))

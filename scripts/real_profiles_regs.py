@@ -42,7 +42,7 @@ def main():
     build = os.path.join(CSRC, "build")
     rows = table([os.path.join(build, "kernels_%s_%s.o" % (u, p)) for u in ("nls", "nls9", "nlp", "nlp9") for p in "ds"])
     lds = lds_table()
-    header = open(os.path.join(CSRC, "fft_nlz.h")).read()
+    header = open(os.path.join(CSRC, "nlz_prof.h")).read()
     stats = int(re.search(r"NLP_STATS = (\d+)", header).group(1))
     kinds = ("moments", "prof")
     print("# NlzFft kernels, gfx950: moments (kernels_nls*.hip) | profiles (kernels_nlp*.hip), NLP_STATS = %d: one pair's E x %d doubles of accumulators" % (stats, stats))

@@ -1,5 +1,5 @@
 """GPU: histograms of spectral fields without the real-space arrays (mfft_real_histogram, mfft_nlz_hist_rows, mfft_ew_histogram;
-csrc/fft_nlz.h body_hist, csrc/hist.hip) -- the sweep against numpy exactly, the z stage on known answers exactly and on random
+csrc/nlz_hist.h NlzHist::body, csrc/hist.hip) -- the sweep against numpy exactly, the z stage on known answers exactly and on random
 spectra by brackets, the plan operation on every route (fused on one rank and several, batches, composed, pencils, pitched),
 `range=None`, the Taylor-Green known answer and the example's --pdf.
 

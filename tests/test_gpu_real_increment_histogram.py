@@ -1,5 +1,5 @@
 """GPU: PDFs of the increments along z of spectral fields without the real-space arrays (mfft_real_increment_histogram,
-mfft_nlz_incr_hist_rows, mfft_ew_increment_histogram; csrc/fft_nlz.h body_incr_hist, csrc/incrhist.hip) -- the sweep against numpy
+mfft_nlz_incr_hist_rows, mfft_ew_increment_histogram; csrc/nlz_incr_hist.h NlzIncrHist::body, csrc/incrhist.hip) -- the sweep against numpy
 exactly, the z stage on known answers exactly and on random spectra by brackets, its consistency with mfft_nlz_incr_rows, non-finite
 bins and every error code, the plan operation on every route (fused on one rank and several, chunks, composed, pencils, pitched),
 `range=None`, the Taylor-Green known answer and the example's --structure-pdf.

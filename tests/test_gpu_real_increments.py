@@ -1,5 +1,5 @@
 """GPU: structure functions along z of spectral fields without the real-space arrays (mfft_real_increments, mfft_nlz_incr_rows,
-mfft_ew_increments; csrc/fft_nlz.h body_incr, csrc/incr.hip) -- the z stage on its own against numpy (np.roll), the plan operation
+mfft_ew_increments; csrc/nlz_incr.h NlzIncr::body, csrc/incr.hip) -- the z stage on its own against numpy (np.roll), the plan operation
 against the ORACLE's backward transforms of the same spectra on every route (fused on one rank and several, composed, pencils,
 pitched), spectral.increments, S_2 against the spectrum of the rows, the Taylor-Green known answer, and the example's --structure.
 

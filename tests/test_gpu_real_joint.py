@@ -1,5 +1,5 @@
 """GPU: joint histograms of two spectral fields without the real-space arrays (mfft_real_joint_histogram, mfft_nlz_joint_rows,
-mfft_ew_joint_histogram; csrc/fft_nlz.h body_joint, csrc/joint.hip) -- the sweep against numpy exactly, the z stage on known
+mfft_ew_joint_histogram; csrc/nlz_joint.h NlzJoint::body, csrc/joint.hip) -- the sweep against numpy exactly, the z stage on known
 answers exactly and on random spectra by brackets, the plan operation on every route (fused on one rank and several, batches,
 composed, pencils, pitched), `range=None`, `a_hat is b_hat`, the marginals against `real_histogram` and the example's --joint.
 

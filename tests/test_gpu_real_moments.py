@@ -1,5 +1,5 @@
 """GPU: one-point statistics of spectral fields without the real-space arrays (mfft_real_moments, mfft_nlz_moments_rows,
-mfft_ew_moments, mfft_ew_diag_grad_hat; csrc/fft_nlz.h body_moments, csrc/moments.hip) -- the z stage on its own against numpy,
+mfft_ew_moments, mfft_ew_diag_grad_hat; csrc/nlz_moments.h NlzMoments::body, csrc/moments.hip) -- the z stage on its own against numpy,
 the plan operation against the ORACLE's backward transforms of the same spectra on every route (fused on one rank and several,
 batches, composed, pencils, pitched), spectral.moments, the Taylor-Green known answer, `center`, and the example's --stats.
 

@@ -1,5 +1,5 @@
 """GPU: plane-averaged profiles along z of spectral fields without the real-space arrays (mfft_real_profiles,
-mfft_nlz_profile_rows, mfft_ew_profiles; csrc/fft_nlz.h body_prof, csrc/profiles.hip) -- the sweep against the numpy rule, the z
+mfft_nlz_profile_rows, mfft_ew_profiles; csrc/nlz_prof.h NlzProf::body, csrc/profiles.hip) -- the sweep against the numpy rule, the z
 stage on its own against numpy, the plan operation against the ORACLE's backward transforms of the same spectra on every route
 (fused on one rank and several, batches, composed, pencils, pitched), `a_hat is b_hat`, `center`, known answers, the consistency
 with `real_moments` and the example's --profiles.

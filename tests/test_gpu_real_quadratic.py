@@ -1,5 +1,5 @@
 """GPU: moments and PDFs of quadratic forms q = sum_f w_f ifftn(field f)^2 without the real-space arrays (mfft_real_quadratic,
-mfft_nlz_quad_rows, mfft_ew_quadratic, mfft_ew_strain_hat; csrc/fft_nlz.h body_quad, csrc/quad.hip) -- the sweep against numpy
+mfft_nlz_quad_rows, mfft_ew_quadratic, mfft_ew_strain_hat; csrc/nlz_quad.h NlzQuad::body, csrc/quad.hip) -- the sweep against numpy
 (counts exactly), the z stage on known answers exactly and on random spectra by bounds, the plan operation on every route (fused
 on one rank and several, batches, composed, pencils, pitched), `range=None`, Taylor-Green known answers, the strain tensor, the
 identity with the enstrophy spectrum and the example's --dissipation.

@@ -1,4 +1,4 @@
-"""CPU: the body of the fused z stage that ends in a histogram (csrc/fft_nlz.h body_hist, Op::Histogram) runs in the workgroup
+"""CPU: the body of the fused z stage that ends in a histogram (csrc/nlz_hist.h NlzHist::body, Op::Histogram) runs in the workgroup
 emulator (`make emu_nlh`): every plan of MFFT_NLZPLANS_P2 / _3 / _9, both precisions, wave-synchronous and barrier builds,
 whole-complex and split exchanges, with and without LDS twiddles, field counts 1, 2, 3 and 6, one row, odd row counts and row
 counts of several passes of the launch's workgroups plus a ragged rest, `valid` = n/2+1 and n/3+1, pruned `valid_in`, bin counts

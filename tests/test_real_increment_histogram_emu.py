@@ -1,4 +1,4 @@
-"""CPU: the body of the fused z stage that ends in increment histograms (csrc/fft_nlz.h body_incr_hist, Op::IncrementHistogram) runs
+"""CPU: the body of the fused z stage that ends in increment histograms (csrc/nlz_incr_hist.h NlzIncrHist::body, Op::IncrementHistogram) runs
 in the workgroup emulator (`make emu_nlk`): every plan of MFFT_NLZPLANS_P2 / _3 / _9, both precisions, wave-synchronous and barrier
 builds, whole-complex and split exchanges, with and without LDS twiddles, field counts 1, 2, 3 and 6, one row, odd row counts and
 row counts of several passes of the launch's workgroups plus a ragged rest, `valid` = n/2+1 and n/3+1, pruned `valid_in`, bin counts
@@ -68,12 +68,12 @@ def test_new_entry_points_in_header_binding_and_library():
 def test_limits_are_one_number():
     from mpifft4py_amd import spectral
     header = open(os.path.join(ROOT, "include", "mpifft4py_amd.h")).read()
-    kernel = open(os.path.join(ROOT, "mpifft4py_amd", "csrc", "fft_nlz.h")).read()
+    kernel = open(os.path.join(ROOT, "mpifft4py_amd", "csrc", "nlz_incr_hist.h")).read()
     h = int(re.search(r"#define MFFT_INCR_HIST_MAXBINS (\d+)", header).group(1))
     k = int(re.search(r"NLK_MAXBINS = (\d+)", kernel).group(1))
     assert h == k == spectral.INCR_HIST_MAXBINS == 256
     assert int(re.search(r"#define MFFT_INCR_MAXSEP (\d+)", header).group(1)) == spectral.INCR_MAXSEP == 8
     # a pair's histograms fit under the joint grid, whose exchange rule the kernels take
     cells = 2 * 8 * (k + 3)
-    joint = int(re.search(r"NLJ_MAXBINS = (\d+)", kernel).group(1))
+    joint = int(re.search(r"NLJ_MAXBINS = (\d+)", open(os.path.join(ROOT, "mpifft4py_amd", "csrc", "nlz_joint.h")).read()).group(1))
     assert cells == 4144 and cells <= (joint + 3) ** 2

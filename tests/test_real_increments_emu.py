@@ -1,4 +1,4 @@
-"""CPU: the body of the fused z stage that ends in structure functions (csrc/fft_nlz.h body_incr, Op::Increments) runs in the
+"""CPU: the body of the fused z stage that ends in structure functions (csrc/nlz_incr.h NlzIncr::body, Op::Increments) runs in the
 workgroup emulator (`make emu_nli`): every plan of MFFT_NLZPLANS_P2 / _3 / _9, both precisions, wave-synchronous and barrier
 builds, whole-complex and split exchanges, with and without LDS twiddles, field counts 1, 2, 3 and 6, one row, odd row counts and
 row counts of several passes of the launch's workgroups plus a ragged rest, `valid` = n/2+1 and n/3+1, pruned `valid_in`, a NaN
@@ -68,7 +68,7 @@ def test_maxsep_is_one_number():
     import os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     header = open(os.path.join(root, "include", "mpifft4py_amd.h")).read()
-    kernel = open(os.path.join(root, "mpifft4py_amd", "csrc", "fft_nlz.h")).read()
+    kernel = open(os.path.join(root, "mpifft4py_amd", "csrc", "nlz_incr.h")).read()
     h = int(re.search(r"#define MFFT_INCR_MAXSEP (\d+)", header).group(1))
     k = int(re.search(r"NLI_MAXSEP = (\d+)", kernel).group(1))
     assert h == k == spectral.INCR_MAXSEP and h >= 8

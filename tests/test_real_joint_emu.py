@@ -1,4 +1,4 @@
-"""CPU: the body of the fused z stage that ends in a JOINT histogram (csrc/fft_nlz.h body_joint, Op::JointHistogram) runs in the
+"""CPU: the body of the fused z stage that ends in a JOINT histogram (csrc/nlz_joint.h NlzJoint::body, Op::JointHistogram) runs in the
 workgroup emulator (`make emu_nlj`): every plan of MFFT_NLZPLANS_P2 / _3 / _9, both precisions, wave-synchronous and barrier
 builds, whole-complex and split exchanges, with and without LDS twiddles, 2 and 6 fields, one row, odd row counts and row counts
 of several passes of the launch's workgroups plus a ragged rest, `valid` = n/2+1 and n/3+1, pruned `valid_in`, the bin pairs

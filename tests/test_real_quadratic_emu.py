@@ -1,4 +1,4 @@
-"""CPU: the body of the fused z stage that ends in the statistics of a quadratic form (csrc/fft_nlz.h body_quad, Op::Quadratic)
+"""CPU: the body of the fused z stage that ends in the statistics of a quadratic form (csrc/nlz_quad.h NlzQuad::body, Op::Quadratic)
 runs in the workgroup emulator (`make emu_nlq`): every plan of MFFT_NLZPLANS_P2 / _3 / _9, both precisions, wave-synchronous and
 barrier builds, whole-complex and split exchanges, with and without LDS twiddles, field counts 1, 2, 3 and 6, one row, odd row
 counts and row counts of several passes of the launch's workgroups plus a ragged rest, `valid` = n/2+1 and n/3+1, pruned
